@@ -10,11 +10,19 @@ GeographicGrid (kernel 'ewh') on MI355X; beside it one leg per remaining BASELIN
     smoother     config 5   3650 daily d/o-40 epochs (d = 1681), block-tridiagonal normal equations: solution and covariance
                             blocks from one factorisation (fp64 MFMA); epochs sharded over the ranks, all_gather of separators
 
-    python bench.py --gpus N --steps K --warmup W [--legs synthesis,covariance,analysis,filters,smoother]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W --full [--legs synthesis,covariance,analysis,filters,smoother] [--dump-outputs DIR]
 
 One "step" of the headline = one pass of the hot path over one batch: 240 coefficient sets already resident in HBM ->
 240 grids in HBM (shg_synthesis through the C ABI).  `value` is measured exactly as the contract says: W warm-up steps, then K
-timed steps between barrier + synchronize pairs, max over ranks.  Leg order (also in `config.leg_order`): synthesis setup, the timed
+timed steps between barrier + synchronize pairs, max over ranks.
+
+A plain run (no --full) does only what the headline needs: the synthesis setup, SETTLE_LAUNCHES untimed steps, the W warm-up and K
+timed steps, --dump-outputs, and a line of the contract fields.  The untimed steps take the place of the legs that run in front of the
+contract pass of a full run (below): behind an idle setup the kernel runs up to 13 % slower until the card has settled on the load.
+--dump-outputs DIR writes what the last timed step computed (rank 0's grids, a fixed sample within 64 MB) as DIR/<name>.npy.
+
+--full adds everything else, as follows.  Leg order (also in `config.leg_order`): synthesis setup, the timed
 repeats of the covariance leg, the timed steps of the filters leg (block form, then the dense form: config 3's full-matrix products), THEN
 the synthesis contract pass.  Why: behind an idle period -- or behind work that loads only the MFMA units or only the HBM -- launches
 6 .. 25 of the synthesis kernel run 4 .. 13 % slower than its steady state (the card's power management settling on the new load;
@@ -69,6 +77,9 @@ ANA_DEGREE, ANA_GRID_STEP = 96, 0.5
 DDK_DEGREE, DDK_LEVEL_SCALE = 120, 1e11          # config 3: DDK5 weights 1e11 n^4 (grates/filter.py:334-349)
 SMOOTHER_DIM, SMOOTHER_EPOCHS = 1681, 3650       # config 5: d/o 40 state, ten years of daily solutions
 LEGS = ('synthesis', 'covariance', 'analysis', 'filters', 'smoother')
+SETTLE_LAUNCHES = 300            # untimed steps in front of the warm-up of a plain run (tools/ramp_probe.py: settled after ~100)
+DUMP_LIMIT_BYTES = 64_000_000    # --dump-outputs: all arrays together
+DUMP_SAMPLE, DUMP_SEED = 1 << 22, 2024
 FORBIDDEN_ENVIRONMENT = ('SHG_LIBRARY', 'SHG_DEBUG', 'SHG_TIMELINE_PTR', 'SHG_STAGGER', 'SHG_STAGGER2')
 
 
@@ -97,7 +108,12 @@ def parse_args(argv=None):
     ap.add_argument('--smoother-cpu-epochs', type=int, default=12, help='epochs of the short chain the CPU oracle solves (baseline + spot check)')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for N > 1 ('nccl' = RCCL; 'gloo' only to rehearse on one GPU)")
     ap.add_argument('--same-device', action='store_true', help='rehearsal: map every rank to cuda:0 (with --backend gloo)')
+    ap.add_argument('--full', action='store_true', help='run the other legs, the extra synthesis passes, the oracle checks and the CPU baselines '
+                                                         'as well (without it: the headline alone; the options above that tune them need --full)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed synthesis step computed (rank 0) as DIR/<name>.npy')
     args = ap.parse_args(argv)
+    if args.legs != 'all' and not args.full:
+        ap.error('--legs selects legs of the full run: add --full')
     wanted = LEGS if args.legs == 'all' else tuple(x.strip() for x in args.legs.split(',') if x.strip())
     unknown = [x for x in wanted if x not in LEGS]
     if unknown:
@@ -246,6 +262,16 @@ class GpuWorkload:
 
     def synthesis_step(self):
         self.plan.synthesis(self.batch, out=self.out)
+
+    def outputs(self):
+        """The grids the last synthesis step returned (self.out, 2 GB at full size) within DUMP_LIMIT_BYTES: the whole grids of the first,
+        middle and last epoch, and DUMP_SAMPLE values at seeded positions over the whole batch."""
+        import numpy as np
+        B = self.out.shape[0]
+        flat = self.out.view(-1)
+        where = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_SAMPLE))
+        return {'grids_first_middle_last_epoch': self.out[sorted({0, B // 2, B - 1})].cpu().numpy(),
+                'grid_values_seeded_sample': flat[self.torch.from_numpy(where).to(flat.device)].cpu().numpy()}
 
     def set_stage_limit(self, limit):
         self.plan.set_stage_limit(limit)
@@ -1033,6 +1059,12 @@ def run_rank(args, workload_factory=GpuWorkload, emit=print):
     # own leg -- runs between the synthesis setup and the synthesis passes, so that the contract pass starts on a card whose clocks
     # have ramped (r03: 0.60 against 0.53 ms per launch when the headline was timed straight after an idle setup).
     wl.setup_synthesis()
+    if not args.full:
+        line = headline_run(args, wl, ctx)
+        if rank == 0:
+            emit(json.dumps(line, separators=(',', ':')))
+        leave_process_group(dist)
+        return line
     B = args.epochs
     leg_order = ['synthesis setup']
     # the contract pass straight behind the (idle) setup, before any other leg: reported as `roofline.value_idle_start`, so that what the
@@ -1060,6 +1092,8 @@ def run_rank(args, workload_factory=GpuWorkload, emit=print):
     leg_order += ['synthesis contract pass', 'synthesis pass behind {0} more launches'.format(args.ramp), 'synthesis check + CPU baseline']
     barrier()
     elapsed, prof = timed_steps(args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.outputs())
     for _ in range(args.ramp):
         wl.synthesis_step()
     barrier()
@@ -1091,31 +1125,13 @@ def run_rank(args, workload_factory=GpuWorkload, emit=print):
         limit_achieved, limit_avg_ms, _ = kernel_rate(limit_prof) if limit_prof is not None else (None, None, None)
         traffic, traffic_source = pmc_traffic('synthesis', [wl.kernel_name])
         kernels = {k: {'ms_total': round(v[0], 4), 'launches': int(v[1]), 'avg_us': round(1e3 * v[0] / max(v[1], 1), 3)} for k, v in prof.items()}
-        config = {'workload': 'batch of {0} monthly solutions d/o {1} -> {2} deg GeographicGrid ({3}x{4}), kernel {5}, per GPU'.format(
-            B, MAX_DEGREE, GRID_STEP, wl.nlat, wl.nlon, KERNEL),
-            'max_degree': MAX_DEGREE, 'epochs_per_gpu': B, 'grid': [wl.nlat, wl.nlon],
-            'parallelism': 'epochs sharded over {0} GPU(s), no collective'.format(world),
+        line = contract_fields(args, wl, world, elapsed, dist)
+        line['config'].update({
             'legs': sorted(args.leg_set), 'ramp_launches_before_value_after_ramp': args.ramp,
             'leg_order': leg_order + (['covariance extensions + CPU baseline'] if cov_state is not None else []) +
                          (['filters checks + CPU baselines'] if flt_state is not None else []) +
-                         [n for n in ('analysis', 'filters', 'smoother') if n in args.leg_set and not (n == 'filters' and flt_state is not None)]}
-        config.update(wl.config)
-        if dist.is_initialized():
-            config['process_group'] = {'backend': dist.get_backend(), 'world': dist.get_world_size()}
-        line = {
-            'metric': METRIC,
-            'value': world * B * args.steps / elapsed,
-            'unit': 'solutions/s',
-            'n_gpus': world,
-            'steps': args.steps,
-            'warmup': args.warmup,
-            'ms_per_step': 1e3 * elapsed / args.steps,
-            'higher_is_better': True,
-            'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': 'f64',
-            'data': 'synthetic',
-            'config': config,
+                         [n for n in ('analysis', 'filters', 'smoother') if n in args.leg_set and not (n == 'filters' and flt_state is not None)]})
+        line.update({
             'value_after_ramp': world * B * args.steps / ramp_elapsed,
             'ms_per_step_after_ramp': 1e3 * ramp_elapsed / args.steps,
             'roofline': {
@@ -1139,7 +1155,7 @@ def run_rank(args, workload_factory=GpuWorkload, emit=print):
             },
             'api_chain': chain,
             'kernels': kernels,
-        }
+        })
         sample = min(args.cpu_sample, B) if world == 1 else min(args.cpu_sample, 1)
         if sample > 0:
             line['check'], line['cpu_baseline'] = wl.synthesis_check(sample, timed=world == 1)
@@ -1168,10 +1184,54 @@ def run_rank(args, workload_factory=GpuWorkload, emit=print):
         line['all_checks_ok'] = all(c.get('ok', True) for c in checks if isinstance(c, dict))
         line = compact_line(summarise(line))
         emit(json.dumps(line, separators=(',', ':')))
+    leave_process_group(dist)
+    return line
+
+
+def leave_process_group(dist):
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
+
+
+def contract_fields(args, wl, world, elapsed, dist):
+    """The contract fields of the line and the headline's `config`, from the K timed steps that took `elapsed` seconds (max over ranks)."""
+    B = args.epochs
+    config = {'workload': 'batch of {0} monthly solutions d/o {1} -> {2} deg GeographicGrid ({3}x{4}), kernel {5}, per GPU'.format(
+        B, MAX_DEGREE, GRID_STEP, wl.nlat, wl.nlon, KERNEL),
+        'max_degree': MAX_DEGREE, 'epochs_per_gpu': B, 'grid': [wl.nlat, wl.nlon],
+        'parallelism': 'epochs sharded over {0} GPU(s), no collective'.format(world)}
+    config.update(wl.config)
+    if dist.is_initialized():
+        config['process_group'] = {'backend': dist.get_backend(), 'world': dist.get_world_size()}
+    return {'metric': METRIC, 'value': world * B * args.steps / elapsed, 'unit': 'solutions/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'dtype': 'f64', 'data': 'synthetic', 'config': config}
+
+
+def headline_run(args, wl, ctx):
+    """The plain run on a set-up synthesis workload: SETTLE_LAUNCHES untimed steps, then W warm-up and K timed steps between barrier +
+    synchronize pairs, max over ranks; --dump-outputs.  -> the line on rank 0, None elsewhere."""
+    elapsed, _, _ = ctx.timed(wl.synthesis_step, SETTLE_LAUNCHES + args.warmup, args.steps)
+    if ctx.rank != 0:
+        return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl.outputs())
+    line = contract_fields(args, wl, ctx.world, elapsed, ctx.dist)
+    line['config']['settle_launches'] = SETTLE_LAUNCHES
     return line
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array of `arrays` (float32 / float64, DUMP_LIMIT_BYTES in all) as DIRECTORY/<name>.npy."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES or any(a.dtype not in (np.float32, np.float64) for a in arrays.values()):
+        raise ValueError('--dump-outputs takes float32 / float64 arrays of at most {0} bytes in all, got {1}'.format(
+            DUMP_LIMIT_BYTES, {k: (str(a.dtype), a.nbytes) for k, a in arrays.items()}))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
 
 
 def covariance_leg(args, wl, rank, world, barrier, max_over_ranks, gd):

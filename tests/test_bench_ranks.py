@@ -43,6 +43,9 @@ class StubWorkload:
         self.x = self.x * 1.0000001
         self.steps_done += 1
 
+    def outputs(self):
+        return {'x': self.x.numpy().copy(), 'steps_done_rank': np.array([self.steps_done, self.rank], dtype=np.float64)}
+
     def profile(self, enable):
         self.profiling = enable
         self.mark = self.steps_done
@@ -108,7 +111,7 @@ def _free_port():
 
 def _rank(rank, world, port, out_dir):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    args = bench.parse_args(['--gpus', str(world), '--steps', '4', '--warmup', '2', '--ramp', '3', '--epochs', '6', '--backend', 'gloo',
+    args = bench.parse_args(['--full', '--gpus', str(world), '--steps', '4', '--warmup', '2', '--ramp', '3', '--epochs', '6', '--backend', 'gloo',
                              '--cov-repeats', '2', '--smoother-epochs', '11'])
     lines = []
     result = bench.run_rank(args, workload_factory=StubWorkload, emit=lines.append)
@@ -176,7 +179,7 @@ def test_rank_function_gloo(world, tmp_path):
 def test_rank_function_single_process(monkeypatch):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         monkeypatch.delenv(k, raising=False)
-    args = bench.parse_args(['--steps', '3', '--warmup', '1', '--ramp', '0', '--epochs', '5', '--cov-repeats', '3'])
+    args = bench.parse_args(['--full', '--steps', '3', '--warmup', '1', '--ramp', '0', '--epochs', '5', '--cov-repeats', '3'])
     lines = []
     line = bench.run_rank(args, workload_factory=StubWorkload, emit=lines.append)
     assert json.loads(lines[0]) == json.loads(json.dumps(line))
@@ -185,6 +188,72 @@ def test_rank_function_single_process(monkeypatch):
     assert line['smoother']['epochs_per_rank'] == [bench.SMOOTHER_EPOCHS] and line['all_checks_ok']
     assert line['covariance']['sigma_checksum'] == pytest.approx(_expected_sigma().sum(), rel=0, abs=1e-12)
     assert line['covariance']['seconds_min'] <= line['covariance']['seconds_median']
+
+
+CONTRACT_KEYS = {'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data',
+                 'config'}
+
+
+def test_plain_run_is_the_headline_alone(monkeypatch, tmp_path):
+    """Without --full: SETTLE_LAUNCHES untimed, W warm-up and K timed synthesis steps and nothing else (no other leg, pass, check or CPU
+    baseline), the outputs of the last timed step under --dump-outputs, a line of the contract fields."""
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        monkeypatch.delenv(k, raising=False)
+    made = []
+    args = bench.parse_args(['--steps', '7', '--warmup', '2', '--epochs', '5', '--dump-outputs', str(tmp_path / 'out')])
+    lines = []
+    line = bench.run_rank(args, workload_factory=lambda *a: made.append(StubWorkload(*a)) or made[-1], emit=lines.append)
+    wl = made[0]
+    assert json.loads(lines[0]) == json.loads(json.dumps(line)) and set(line) == CONTRACT_KEYS
+    assert wl.steps_done == bench.SETTLE_LAUNCHES + 2 + 7 and not hasattr(wl, 'cov_calls')
+    assert line['metric'] == bench.METRIC and line['unit'] == 'solutions/s' and line['higher_is_better'] is True and line['dtype'] == 'f64'
+    assert line['steps'] == 7 and line['warmup'] == 2 and line['n_gpus'] == 1 and line['config']['settle_launches'] == bench.SETTLE_LAUNCHES
+    assert line['value'] == pytest.approx(5 * 7 / (line['ms_per_step'] * 7e-3))
+    assert sorted(os.listdir(tmp_path / 'out')) == ['steps_done_rank.npy', 'x.npy']
+    x = np.load(tmp_path / 'out' / 'x.npy')
+    assert x.dtype == np.float64 and np.array_equal(x, wl.x.numpy())
+    assert np.load(tmp_path / 'out' / 'steps_done_rank.npy').tolist() == [wl.steps_done, 0]
+
+
+def test_full_run_dumps_the_outputs_of_the_contract_pass(monkeypatch, tmp_path):
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        monkeypatch.delenv(k, raising=False)
+    args = bench.parse_args(['--full', '--steps', '3', '--warmup', '1', '--ramp', '4', '--epochs', '5', '--legs', 'synthesis',
+                             '--dump-outputs', str(tmp_path)])
+    line = bench.run_rank(args, workload_factory=StubWorkload, emit=lambda text: None)
+    assert line['all_checks_ok'] and line['steps'] == 3
+    # the idle pass and the contract pass, 1 + 3 steps each: the ramp and the passes behind it come later
+    assert np.load(tmp_path / 'steps_done_rank.npy').tolist() == [8, 0]
+
+
+def test_legs_need_full_and_dump_limits(tmp_path):
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--legs', 'analysis'])
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'big'), {'a': np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'int'), {'a': np.zeros(4, dtype=np.int64)})
+    assert not os.listdir(tmp_path)
+
+
+def _rank_plain(rank, world, port, out_dir):
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    args = bench.parse_args(['--gpus', str(world), '--steps', '4', '--warmup', '1', '--epochs', '6', '--backend', 'gloo',
+                             '--dump-outputs', os.path.join(out_dir, 'dump')])
+    lines = []
+    result = bench.run_rank(args, workload_factory=StubWorkload, emit=lines.append)
+    assert (result is not None) == (rank == 0) and len(lines) == (1 if rank == 0 else 0)
+    if rank == 0:
+        with open(os.path.join(out_dir, 'line.json'), 'w') as f:
+            f.write(lines[0])
+
+
+def test_plain_run_gloo_world2(tmp_path):
+    mp.spawn(_rank_plain, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    line = json.loads(open(tmp_path / 'line.json').read())
+    assert set(line) == CONTRACT_KEYS and line['n_gpus'] == 2 and line['config']['process_group'] == {'backend': 'gloo', 'world': 2}
+    assert line['value'] == pytest.approx(2 * 6 * 4 / (line['ms_per_step'] * 4e-3))        # whole-job aggregate over all ranks
+    assert np.load(tmp_path / 'dump' / 'steps_done_rank.npy').tolist() == [bench.SETTLE_LAUNCHES + 1 + 4, 0]     # rank 0 writes
 
 
 def test_bare_multi_gpu_invocation_launches_ranks(monkeypatch):
@@ -217,7 +286,7 @@ def test_bare_multi_gpu_invocation_launches_ranks(monkeypatch):
 
 def _rank_world_of_one(rank, port, out_dir):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK='0', WORLD_SIZE='1', LOCAL_RANK='0')
-    args = bench.parse_args(['--gpus', '1', '--steps', '2', '--warmup', '1', '--ramp', '0', '--epochs', '4', '--backend', 'gloo',
+    args = bench.parse_args(['--full', '--gpus', '1', '--steps', '2', '--warmup', '1', '--ramp', '0', '--epochs', '4', '--backend', 'gloo',
                              '--cov-repeats', '1', '--smoother-epochs', '9'])
     import torch.distributed as dist
     seen = []

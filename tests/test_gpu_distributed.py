@@ -365,7 +365,7 @@ def test_bench_rehearsal_world2_and_world4_real_shard_sizes():
         pytest.skip('four replicas of the d/o-180 covariance matrix and a 512-epoch chain need ~150 GB of free device memory')
     torch.cuda.empty_cache()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = [sys.executable, os.path.join(root, 'bench.py'), '--legs', 'covariance,smoother', '--smoother-epochs', '512', '--smoother-repeats', '1',
+    common = [sys.executable, os.path.join(root, 'bench.py'), '--full', '--legs', 'covariance,smoother', '--smoother-epochs', '512', '--smoother-repeats', '1',
               '--cpu-sample', '0', '--cov-repeats', '1', '--cov-extensions', '0', '--steps', '2', '--warmup', '1', '--ramp', '0', '--epochs', '8']
     lines = {}
     for world in (1, 2, 4):

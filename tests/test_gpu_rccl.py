@@ -93,7 +93,7 @@ def test_bench_rank_function_over_rccl():
     smoother's separator gathers, at reduced sizes; the line certifies itself like the N = 1 line."""
     root = os.path.dirname(HERE)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
-           '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '1', '--backend', 'nccl', '--steps', '2', '--warmup', '1',
+           '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--full', '--gpus', '1', '--backend', 'nccl', '--steps', '2', '--warmup', '1',
            '--ramp', '0', '--epochs', '8', '--cpu-sample', '1', '--cov-parallels', '3', '--cov-repeats', '1', '--cov-extensions', '0',
            '--smoother-epochs', '24', '--smoother-cpu-epochs', '3', '--smoother-repeats', '1', '--legs', 'synthesis,covariance,smoother']
     done = subprocess.run(cmd, env=_launcher_env(), capture_output=True, text=True, timeout=900)

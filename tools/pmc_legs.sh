@@ -16,10 +16,10 @@ pass() {   # leg, counter, bench arguments...
   rm -rf $d
 }
 for c in FETCH_SIZE WRITE_SIZE; do
-  pass synthesis $c --legs synthesis --cpu-sample 0 --steps 10 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
-  pass analysis $c --legs analysis --cpu-sample 0 --steps 10 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
-  pass filters $c --legs filters --cpu-sample 0 --steps 10 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
-  pass covariance $c --legs covariance --cpu-sample 0 --steps 2 --warmup 1 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0 --cov-repeats 1 --cov-extensions 0 --cov-parallels 8
-  pass smoother $c --legs smoother --cpu-sample 0 --steps 2 --warmup 1 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0 --smoother-epochs 64 --smoother-repeats 1
+  pass synthesis $c --full --legs synthesis --cpu-sample 0 --steps 10 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
+  pass analysis $c --full --legs analysis --cpu-sample 0 --steps 10 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
+  pass filters $c --full --legs filters --cpu-sample 0 --steps 10 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
+  pass covariance $c --full --legs covariance --cpu-sample 0 --steps 2 --warmup 1 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0 --cov-repeats 1 --cov-extensions 0 --cov-parallels 8
+  pass smoother $c --full --legs smoother --cpu-sample 0 --steps 2 --warmup 1 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0 --smoother-epochs 64 --smoother-repeats 1
 done
 python3 $GRAFT_REPO_ROOT/tools/pmc_legs_summary.py $out $tag

@@ -4,7 +4,7 @@
 # Run on a GPU box from the repository root: writes gpurun_out/r03_kernel_stats.csv and gpurun_out/r03_pmc_traffic.json.
 out=$GRAFT_REPO_ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-args="--legs synthesis --cpu-sample 0 --steps 20 --warmup 5 --ramp 300"
+args="--full --legs synthesis --cpu-sample 0 --steps 20 --warmup 5 --ramp 300"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_r03 -o run -- python3 $GRAFT_REPO_ROOT/bench.py $args > $out/prof_r03.log 2>&1
 cp $(find $out/prof_r03 -name "*kernel_stats.csv" | head -1) $out/r03_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do

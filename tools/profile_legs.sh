@@ -14,8 +14,8 @@ run_leg() {   # leg-name, bench arguments...
   if [ -n "$f" ]; then cp $f $out/${tag}_${leg}_kernel_stats.csv; echo "$leg: $(wc -l < $f) kernels"; else echo "$leg: no kernel stats"; fi
   rm -rf $d
 }
-run_leg synthesis --legs synthesis --cpu-sample 0 --steps 20 --warmup 5 --ramp 300 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
-run_leg analysis --legs analysis --cpu-sample 0 --steps 20 --warmup 5 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
-run_leg filters --legs filters --cpu-sample 0 --steps 20 --warmup 5 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
-run_leg covariance --legs covariance --cpu-sample 0 --steps 5 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0 --cov-repeats 1 --cov-extensions 0
-run_leg smoother --legs smoother --cpu-sample 0 --steps 5 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0 --smoother-epochs 256 --smoother-repeats 1
+run_leg synthesis --full --legs synthesis --cpu-sample 0 --steps 20 --warmup 5 --ramp 300 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
+run_leg analysis --full --legs analysis --cpu-sample 0 --steps 20 --warmup 5 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
+run_leg filters --full --legs filters --cpu-sample 0 --steps 20 --warmup 5 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0
+run_leg covariance --full --legs covariance --cpu-sample 0 --steps 5 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0 --cov-repeats 1 --cov-extensions 0
+run_leg smoother --full --legs smoother --cpu-sample 0 --steps 5 --warmup 2 --ramp 0 --idle-pass 0 --api-chain 0 --stage-limit-pass 0 --smoother-epochs 256 --smoother-repeats 1
