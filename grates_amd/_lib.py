@@ -83,6 +83,13 @@ PROTOTYPES = {
     'shg_block_inverse': [ctypes.c_int] + [ctypes.c_void_p] * 6,
     'shg_block_multiply': [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p],
     'shg_congruence': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
+    'shg_basin_pip': [ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_longlong, c_double_p, ctypes.c_int, c_double_p,
+                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    'shg_basin_buffer': [ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_longlong, c_double_p, ctypes.c_int, c_double_p,
+                         ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    'shg_winding_number': [ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p],
+    'shg_mask_pack': [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p],
+    'shg_basin_statistics': [c_double_p, ctypes.c_int, ctypes.c_longlong, c_double_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
 }
 STRING_GETTERS = ('shg_last_error', 'shg_version')
 

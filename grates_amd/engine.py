@@ -619,6 +619,62 @@ def epoch_rms(values, acc=None, count=0):
     return acc
 
 
+def polygon_mask(points, polygons, buffers=(), buffer_value=True):
+    """Point-in-polygon mask on the device (shg_basin_pip / shg_basin_buffer): a bool tensor [n] that holds the parity of the
+    polygons containing a point, then `buffer_value` where a point lies in one of the buffers.  `points` is either the pair of
+    per-axis tables (lat_tab [2, nlat], lon_tab [2, nlon]) of a regular grid or the host coordinates xyz [n, 3]; `polygons` and
+    `buffers` are lists of (host frame, host edge table) as grates_amd.grid builds them."""
+    torch = require_gpu()
+    if isinstance(points, tuple):
+        lat_tab, lon_tab = to_device(points[0]), to_device(points[1])
+        nlat, nlon, xyz = lat_tab.shape[1], lon_tab.shape[1], None
+        n = nlat * nlon
+        args = (nlat, _ptr(lat_tab), nlon, _ptr(lon_tab), None)
+    else:
+        xyz = to_device(points)
+        n = xyz.shape[0]
+        args = (0, None, 0, None, _ptr(xyz))
+    mask = torch.zeros((n,), dtype=torch.bool, device=device())
+    if n == 0:
+        return mask
+    work = torch.empty((n + 1,), dtype=torch.int64, device=mask.device)
+    for name, tables, last in (('shg_basin_pip', polygons, None), ('shg_basin_buffer', buffers, int(bool(buffer_value)))):
+        for k, (frame, edges) in enumerate(tables):
+            frame = np.ascontiguousarray(frame, dtype=np.float64)
+            e = to_device(edges)
+            _lib.call(name, *args, n, _host_ptr(frame), e.shape[0], _ptr(e), int(k == 0) if last is None else last, _ptr(work), _ptr(mask),
+                      _stream())
+    return mask
+
+
+def winding_mask(edges, x, y):
+    """winding number != 0 of the points (x, y) [n] for the closed polygon's edge table [k, 5] (shg_winding_number)."""
+    torch = require_gpu()
+    e, px, py = to_device(edges), to_device(x), to_device(y)
+    mask = torch.empty((px.numel(),), dtype=torch.bool, device=px.device)
+    _lib.call('shg_winding_number', e.shape[0], _ptr(e), _ptr(px), _ptr(py), px.numel(), _ptr(mask), _stream())
+    return mask
+
+
+def pack_masks(masks):
+    """uint64 mask bits [P] (as int64) of a bool tensor [B, P], B <= 64 (shg_mask_pack)."""
+    torch = require_gpu()
+    m = masks.contiguous()
+    bits = torch.empty((m.shape[1],), dtype=torch.int64, device=m.device)
+    _lib.call('shg_mask_pack', _ptr(m), m.shape[0], m.shape[1], _ptr(bits), _stream())
+    return bits
+
+
+def basin_statistics(values, weights, bits, count):
+    """[3, T, count] = area-weighted mean, rms and std of values [T, P] (fp64, contiguous, device) over each of the `count` masks whose
+    bits pack_masks gave, with the weights [P] (shg_basin_statistics)."""
+    torch = require_gpu()
+    T, P = values.shape
+    out = torch.empty((3, T, count), dtype=torch.float64, device=values.device)
+    _lib.call('shg_basin_statistics', _ptr(values), T, P, _ptr(weights), _ptr(bits), int(count), _ptr(out), _stream())
+    return out
+
+
 class OrderMajorSeries:
     """A time series of coefficient sets that stays on the device between operators (the batching of TimeSeries.to_array,
     grates/gravityfield.py:964-980, in the layout the order-wise operators work on): `data` [(N+1)^2, Bpad] with the epochs fastest

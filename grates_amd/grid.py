@@ -1,12 +1,13 @@
 """
 Point distributions on the ellipsoid with the interface of ``grates.grid``: the ``Grid`` base class with
 its area-weighted statistics (grates/grid.py:92-507), ``RegularGrid`` (:510-839), ``IrregularGrid``
-(:842-1120), ``GeographicGrid`` (:1123-1162) and ``GaussGrid`` (:1165-1204), plus the coordinate helpers the
-kernels need.  Reuter / geodesic / mascon grids, basins and point-in-polygon tests are host-side geometry
-and out of scope.
+(:842-1120), ``GeographicGrid`` (:1123-1162) and ``GaussGrid`` (:1165-1204), the basins and point-in-polygon
+tests (``Basin``, ``spherical_pip``, ``spherical_pib``, ``winding_number``, ``Grid.create_mask``: :262-281, :1617-1890),
+plus the coordinate helpers the kernels need.  Geodesic / spiral / mascon grids are out of scope.
 
 Heavy operators -- ``to_potential_coefficients`` (analysis), ``covariance_propagation``,
-``synthesis_matrix`` / ``analysis_matrix`` -- run on the GPU through libshg.
+``synthesis_matrix`` / ``analysis_matrix``, the polygon masks and ``basin_statistics`` (mean / rms / std of a device
+series of grids over up to 64 masks) -- run on the GPU through libshg.
 """
 
 import abc
@@ -18,6 +19,8 @@ from . import gravityfield as _gravityfield
 
 _GM = 3.9860044150e+14
 _R = 6.3781363000e+06
+_A = 6378137.0                  # default ellipsoid of the point-in-polygon tests
+_F = 298.2572221010**-1
 
 
 class Grid(metaclass=abc.ABCMeta):
@@ -67,6 +70,64 @@ class Grid(metaclass=abc.ABCMeta):
         mask, w = self.__weights(mask)
         centred = self.values[mask] - self.mean(mask)
         return np.sqrt(np.sum(w * centred ** 2) / np.sum(w))
+
+    # ---- basins (grates/grid.py:262-281) ------------------------------------------------------------------------------
+    def _mask_points(self):
+        """the points as the mask kernels take them: host xyz [n, 3] on the default ellipsoid (the reference's create_mask tests
+        the grid's longitude / latitude with the defaults of spherical_pip)"""
+        return geodetic2cartesian(self.longitude, self.latitude, h=0, a=_A, f=_F)
+
+    def create_mask(self, basin, buffer=None, as_tensor=False):
+        """
+        Boolean mask of the grid points inside `basin` (a Basin or a list of polygons, lon / lat in radians), optionally
+        enlarged (buffer > 0) or shrunk (buffer < 0) by a buffer in meters around the polygon edges.  Returns a host bool
+        array [point_count], or with as_tensor=True a device torch.bool tensor [point_count].
+        """
+        if not isinstance(basin, Basin):
+            basin = Basin(basin)
+        mask = basin._device_mask(self._mask_points(), buffer)
+        return mask if as_tensor else engine.to_host(mask)
+
+    def basin_statistics(self, values, masks=None):
+        """
+        Area-weighted mean, rms and standard deviation of every epoch of a device series of grids over every mask: entry (t, b)
+        is what ``mean(mask_b)``, ``rms(mask_b)`` and ``std(mask_b)`` give for a grid holding epoch t (grates/grid.py:174-260).
+
+        values : torch.Tensor [T, point_count] or [T, nlat, nlon] (a RegularGrid's layout), float64, contiguous, on the GPU --
+                 e.g. ``to_grid(grid, as_tensor=True)`` of a filtered series
+        masks  : None (all points), one mask [point_count] or a stack [B, point_count] (B <= 64) of bool tensors or host arrays
+
+        Returns (mean, rms, std), float64 device tensors [T, B].  Weights are the area elements (equal weights for a grid without
+        areas); an empty mask gives NaN.  The sums run in a fixed order: repeated calls give bitwise equal results.
+        """
+        torch = engine.require_gpu()
+        P = self.point_count
+        if not isinstance(values, torch.Tensor) or values.device.type != 'cuda':
+            raise ValueError('values must be a torch tensor on the GPU')
+        if values.dtype != torch.float64:
+            raise ValueError('values must be float64, got {0}'.format(values.dtype))
+        if not values.is_contiguous():
+            raise ValueError('values must be contiguous')
+        grid_shape = (self.parallels.size, self.meridians.size) if isinstance(self, RegularGrid) else (P,)
+        if tuple(values.shape[1:]) not in (grid_shape, (P,)):
+            raise ValueError('values of shape {0} do not fit a grid of {1} points: expected [T, {1}] or [T, {2}]'.format(
+                tuple(values.shape), P, ', '.join(str(n) for n in grid_shape)))
+        if masks is None:
+            m = torch.ones((1, P), dtype=torch.bool, device=values.device)
+        else:
+            m = torch.as_tensor(masks, device=values.device)
+            if m.dtype != torch.bool:
+                raise ValueError('masks must be boolean, got {0}'.format(m.dtype))
+            if m.dim() == 1:
+                m = m[None, :]
+            if m.dim() != 2 or m.shape[1] != P:
+                raise ValueError('masks of shape {0} do not fit a grid of {1} points'.format(tuple(m.shape), P))
+            if not 1 <= m.shape[0] <= 64:
+                raise ValueError('{0} masks: 1 to 64 masks are supported'.format(m.shape[0]))
+        areas = self.area
+        w = torch.ones((P,), dtype=torch.float64, device=values.device) if areas is None else engine.to_device(areas, values.device)
+        out = engine.basin_statistics(values.reshape(values.shape[0], P), w, engine.pack_masks(m), m.shape[0])
+        return out[0], out[1], out[2]
 
     def distance_matrix(self):
         """Spherical distance [rad] between all pairs of grid points."""
@@ -209,6 +270,15 @@ class RegularGrid(Grid):
         self.value_array = np.reshape(val, (self.parallels.size, self.meridians.size))
 
     values = property(__get_values, __set_values)
+
+    def _mask_points(self):
+        """per-axis tables of the mask kernels: x = ((N + h) cos phi) cos lambda as geodetic2cartesian forms it, the factors of
+        a parallel and of a meridian from the host (default ellipsoid, like the reference's create_mask)"""
+        lat = self.parallels
+        e2 = 2 * _F - _F ** 2
+        nu = _A / np.sqrt(1 - e2 * np.sin(lat) ** 2)
+        rows = np.vstack(((nu + 0) * np.cos(lat), ((1 - e2) * nu + 0) * np.sin(lat)))
+        return rows, np.vstack((np.cos(self.meridians), np.sin(self.meridians)))
 
     # ---- tables ----------------------------------------------------------------------------------------------------
     def _parallel_tables(self, kernel, max_degree, GM, R):
@@ -426,6 +496,121 @@ class GaussGrid(RegularGrid):
             grid.values = self.values.copy()
         grid.epoch = self.epoch
         return grid
+
+
+# -------------------------------------------------------------------------------------------------------
+# basins and point-in-polygon tests (grates/grid.py:1617-1890): the host builds the O(k) tables of a polygon with the
+# reference's NumPy operations, the per-point work runs on the device (grates_amd/csrc/basin.hip)
+# -------------------------------------------------------------------------------------------------------
+
+def _unit_polygon(polygon, a, f):
+    """unit vertices (closed by repeating vertex 0), the antipode of their mean and the cap bound min_k(-v_k . antipode)"""
+    vertices = geodetic2cartesian(polygon[:, 0], polygon[:, 1], h=0, a=a, f=f)
+    vertices /= np.sqrt(np.sum(vertices ** 2, axis=1))[:, np.newaxis]
+    antipode = -np.mean(vertices, axis=0)
+    antipode /= np.sqrt(np.sum(antipode ** 2))
+    min_cos_angle = np.min(-vertices @ antipode[:, np.newaxis], axis=0)
+    return np.append(vertices, vertices[0][np.newaxis, :], axis=0), antipode, min_cos_angle
+
+
+def _pip_tables(polygon, a, f):
+    """frame (antipode, cap bound) and edge table [k, 9] = (q, b0 x q, b1 x q), b0 = vertex e + 1, b1 = vertex e"""
+    closed, antipode, min_cos_angle = _unit_polygon(np.asarray(polygon, dtype=float), a, f)
+    b0, b1 = closed[1:], closed[:-1]
+    q = np.cross(b0, b1)
+    return np.concatenate((antipode, min_cos_angle)), np.hstack((q, np.cross(b0, q), np.cross(b1, q)))
+
+
+def _pib_tables(polygon, buffer, a, f):
+    """frame (antipode, buffered cap bound, cos(buffer / a)) and edge table [k, 16] = (b0, b1, n, b0 x b1, b1 x b0, valid)"""
+    closed, antipode, min_cos_angle = _unit_polygon(np.asarray(polygon, dtype=float), a, f)
+    bound = np.cos(np.arccos(min_cos_angle) + buffer / a)
+    b0, b1 = closed[1:], closed[:-1]
+    normal = np.cross(b0, b1)
+    norm = np.sqrt(np.sum(normal ** 2, axis=1))
+    valid = norm != 0.0
+    n = normal / np.where(valid, norm, 1.0)[:, np.newaxis]
+    edges = np.hstack((b0, b1, n, normal, np.cross(b1, b0), valid[:, np.newaxis].astype(float)))
+    return np.concatenate((antipode, bound, [np.cos(buffer / a)])), edges
+
+
+def _points_xyz(lon, lat, a, f):
+    """host coordinates [n, 3] of the points (lon, lat) as spherical_pip forms them, and the shape of the result"""
+    lon, lat = np.atleast_1d(lon), np.atleast_1d(lat)
+    shape = lon.shape if lat.size == 1 else lat.shape
+    lon, lat = (np.array(np.broadcast_to(v, shape), dtype=float).ravel() for v in (lon, lat))
+    return geodetic2cartesian(lon, lat, h=0, a=a, f=f), shape
+
+
+class Basin:
+    """
+    An area enclosed by polygon boundaries, potentially with holes (grates/grid.py:1617-1712).  Edges are great-circle
+    segments; counts of several polygons combine by parity.
+
+    polygons : ndarray(k, 2) or list of ndarray(k, 2) with longitude / latitude [rad] in the columns
+    """
+
+    def __init__(self, polygons):
+        if isinstance(polygons, np.ndarray):
+            self.__polygons = polygons,
+        else:
+            self.__polygons = polygons
+
+    def bounding_box(self):
+        """(lon_min, lat_min, lon_max, lat_max) of all vertices [rad]."""
+        lons = np.concatenate([p[:, 0] for p in self.__polygons])
+        lats = np.concatenate([p[:, 1] for p in self.__polygons])
+        return np.min(lons), np.min(lats), np.max(lons), np.max(lats)
+
+    def _device_mask(self, points, buffer):
+        pip = [_pip_tables(p, _A, _F) for p in self.__polygons]
+        pib = [] if buffer is None else [_pib_tables(p, np.abs(buffer), _A, _F) for p in self.__polygons]
+        return engine.polygon_mask(points, pip, pib, buffer is not None and buffer > 0)
+
+    def contains_points(self, lon, lat, buffer=None):
+        """
+        Host bool array: which of the points (lon, lat) [rad] lie in the basin; a buffer of b meters sets every point within |b|
+        of a polygon edge to b > 0.  Scalars and arrays are accepted; a scalar latitude applies to every longitude.
+        """
+        xyz, shape = _points_xyz(lon, lat, _A, _F)
+        return engine.to_host(self._device_mask(xyz, buffer)).reshape(shape)
+
+    @staticmethod
+    def from_extent(lon_min, lat_min, lon_max, lat_max):
+        """Basin of the box with lower left corner (lon_min, lat_min) and upper right corner (lon_max, lat_max) [rad]."""
+        poly = np.empty((4, 2))
+        poly[0, :] = (lon_min, lat_min)
+        poly[1, :] = (lon_min, lat_max)
+        poly[2, :] = (lon_max, lat_max)
+        poly[3, :] = (lon_max, lat_min)
+        return Basin(poly)
+
+
+def winding_number(polygon, x, y):
+    """Planar winding-number test of the points (x, y) against the polygon [k, 2] (grates/grid.py:1715-1748); a host bool array
+    of the shape of x (scalar y) or of y."""
+    x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+    coords = np.asarray(polygon, dtype=float)
+    if np.any(coords[0] != coords[-1]):
+        coords = np.append(coords, coords[0][np.newaxis, :], axis=0)
+    shape = x.shape if y.size == 1 else y.shape
+    xb, yb = (np.array(np.broadcast_to(v, shape)).ravel() for v in (x, y))
+    p0, p1 = coords[:-1], coords[1:]
+    edges = np.stack((p0[:, 0], p0[:, 1], p1[:, 1], p1[:, 0] - p0[:, 0], p1[:, 1] - p0[:, 1]), axis=1)
+    return engine.to_host(engine.winding_mask(edges, xb, yb)).reshape(shape)
+
+
+def spherical_pip(polygon, lon, lat, a=6378137.0, f=298.2572221010**-1):
+    """Point-in-polygon test on the sphere (grates/grid.py:1751-1824): host bool array [m], computed on the device."""
+    xyz, _ = _points_xyz(lon, lat, a, f)
+    return engine.to_host(engine.polygon_mask(xyz, [_pip_tables(polygon, a, f)]))
+
+
+def spherical_pib(polygon, lon, lat, buffer, a=6378137.0, f=298.2572221010**-1):
+    """Which points lie within `buffer` meters of the polygon's edges (grates/grid.py:1827-1890): host bool array [m], computed on
+    the device."""
+    xyz, _ = _points_xyz(lon, lat, a, f)
+    return engine.to_host(engine.polygon_mask(xyz, [], [_pib_tables(polygon, buffer, a, f)], True))
 
 
 # -------------------------------------------------------------------------------------------------------

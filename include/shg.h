@@ -324,6 +324,36 @@ int shg_synthesis_matrix(int N, int nmin, const double* colat, const double* lon
 int shg_analysis_matrix(shg_plan* plan, const double* area, int nmin, double* F, void* stream);
 int shg_congruence(int n, int k, const double* W, int ldw, const double* S, int lds, double* C, int ldc, double* work, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Basins: point-in-polygon masks and masked statistics of grid series
+ *   Points of the mask calls: a regular grid (xyz == NULL, npts = nlat * nlon, point i = parallel i / nlon, meridian i % nlon)
+ *   given by lat_tab [2][nlat] = ((N + h) cos phi, ((1 - e^2) N + h) sin phi) and lon_tab [2][nlon] = (cos lambda, sin lambda),
+ *   or a point list xyz [npts][3] = geodetic2cartesian(lon, lat) (grates/grid.py:1920-1950); both are normalised to unit
+ *   vectors on the device.  mask [npts] bytes (0 / 1); work [npts + 1] scratch (the compacted list of the cap test).
+ *   shg_basin_pip       mask ^= inside one polygon (first != 0: mask = inside), the per-point part of spherical_pip
+ *                       (grates/grid.py:1751-1824).  frame_h [4] HOST = (antipode a, min_k(-v_k . a)); edges [nedges][9] =
+ *                       (q = b0 x b1, b0 x q, b1 x q) for b0 = vertex k + 1, b1 = vertex k of the closed unit polygon
+ *   shg_basin_buffer    mask = value where a point lies within the buffer of one polygon, the per-point part of spherical_pib
+ *                       (grates/grid.py:1827-1890).  frame_h [5] HOST = (a, cos(acos(min_k(-v_k . a)) + buffer / a_e),
+ *                       cos(buffer / a_e)); edges [nedges][16] = (b0, b1, n = (b0 x b1) / |b0 x b1|, b0 x b1, b1 x b0,
+ *                       |b0 x b1| != 0); value 0 or 1
+ *   shg_winding_number  mask = winding number != 0 (grates/grid.py:1715-1748).  edges [nedges][5] = (x0, y0, y1, x1 - x0,
+ *                       y1 - y0) of the closed polygon; x, y [npts]
+ *   shg_mask_pack       bits [P] = sum_b (masks[b][p] != 0) << b for masks [B][P] bytes, B <= 64
+ *   shg_basin_statistics  out [3][T][B] = the area-weighted mean, rms and std of values [T][P] over the points of each mask
+ *                       (Grid.mean / rms / std, grates/grid.py:174-260); w [P] weights, bits [P] from shg_mask_pack,
+ *                       1 <= B <= 64.  std is the two-pass sum w (v - mean)^2; an empty mask gives NaN.  Sums over fixed
+ *                       tiles, reduced in a fixed order: bitwise reproducible.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_basin_pip(int nlat, const double* lat_tab, int nlon, const double* lon_tab, const double* xyz, long long npts, const double* frame_h,
+                  int nedges, const double* edges, int first, unsigned long long* work, unsigned char* mask, void* stream);
+int shg_basin_buffer(int nlat, const double* lat_tab, int nlon, const double* lon_tab, const double* xyz, long long npts, const double* frame_h,
+                     int nedges, const double* edges, int value, unsigned long long* work, unsigned char* mask, void* stream);
+int shg_winding_number(int nedges, const double* edges, const double* x, const double* y, long long npts, unsigned char* mask, void* stream);
+int shg_mask_pack(const unsigned char* masks, int B, long long P, unsigned long long* bits, void* stream);
+int shg_basin_statistics(const double* values, int T, long long P, const double* w, const unsigned long long* bits, int B, double* out,
+                         void* stream);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
