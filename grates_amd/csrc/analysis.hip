@@ -16,8 +16,6 @@
 
 namespace shg {
 
-int covprop_build_cs_table(shg_plan* p, hipStream_t stream);   // gemm.hip
-
 constexpr int kAnaEpochChunk = 256;   // epochs per pass: one pass for the usual batches (workspace 0.65 GB at 0.5 degree); 64 measured 1.98 ms per 240 epochs
 
 __global__ __launch_bounds__(256) void weight_transpose_kernel(int nb, int nlat, int nlon, const double* __restrict__ v,
@@ -303,14 +301,6 @@ __global__ __launch_bounds__(256) void weight_squares_kernel(int S, int nlat, in
         if (s < S) w2[(size_t)s * nlat + i] = acc;
     }
 }
-
-// blas.hip
-int gemm_ex(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
-            long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, hipStream_t stream);
-int factor_invert_batched(int n, double* A, int lda, long long strideA, double* X, int ldx, long long strideX, int batch, int* info,
-                          hipStream_t stream);
-int potrf_upper(int n, double* A, int lda, double* work, int* info, hipStream_t stream);
-int trtri_upper(int n, const double* U, int ldu, double* X, int ldx, double* work, hipStream_t stream);
 
 // Per slot s = (m, cos | sin) the least-squares solution is x_s = H_s g_s with the operator
 //   H_s = (PK_m W2_s PK_m^T)^-1 PK_m      [d_s][nlat],   d_s = N + 1 - max(m, nmin) degrees,
@@ -671,15 +661,15 @@ static int build_parity_operator(shg_plan* p, int nmin, hipStream_t stream) {
     p->ana_parity_defect = -1.0;
     if (!p->sym_ns || nlat % 4 != 0 || R > kOpRows) return SHG_OK;
     const size_t count = (size_t)S * 2 * RE * (nlat / 2);
-    if (!p->ana_Hp && hipMalloc((void**)&p->ana_Hp, count * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "analysis operator allocation failed");
-    double* norms = nullptr;
-    if (workspace_alloc((void**)&norms, 2 * sizeof(double), stream) != hipSuccess) return fail(SHG_ERR_NOMEM, "shg_analysis: workspace allocation failed");
+    if (p->ana_Hp.ensure(count) != hipSuccess) return fail(SHG_ERR_NOMEM, "analysis operator allocation failed");
+    Workspace ws = Workspace::pooled(stream);
+    double* norms;
+    if (!ws.alloc(norms, 2)) return fail(SHG_ERR_NOMEM, "shg_analysis: workspace allocation failed");
     SHG_HIP(hipMemsetAsync(norms, 0, 2 * sizeof(double), stream));
-    hipLaunchKernelGGL(analysis_parity_kernel, dim3(2 * RE, S), dim3(256), 0, stream, N, nmin, nlat, p->ana_H, p->ana_Hp, norms);
+    hipLaunchKernelGGL(analysis_parity_kernel, dim3(2 * RE, S), dim3(256), 0, stream, N, nmin, nlat, p->ana_H.get(), p->ana_Hp.get(), norms);
     double host[2] = {0.0, 0.0};
     SHG_HIP(hipMemcpyAsync(host, norms, sizeof(host), hipMemcpyDeviceToHost, stream));
     SHG_HIP(hipStreamSynchronize(stream));
-    (void)hipFreeAsync(norms, stream);
     p->ana_parity_defect = host[0] > 0.0 ? host[1] / host[0] : 0.0;
     p->ana_parity = p->ana_parity_defect <= kParityDefectMax;
     return SHG_OK;
@@ -689,48 +679,38 @@ static int build_parity_operator(shg_plan* p, int nmin, hipStream_t stream) {
 static int build_analysis_operator(shg_plan* p, const double* w2, int nmin, hipStream_t stream) {
     const int N = p->N, S = 2 * N + 1, nlat = p->nlat, R = N + 1;
     const size_t slab = (size_t)S * R * nlat;
-    if (!p->ana_H && hipMalloc((void**)&p->ana_H, slab * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "analysis operator allocation failed");
-    double *pks = nullptr, *pkw = nullptr, *nmat = nullptr, *uinv = nullptr, *work = nullptr;
-    int* info = nullptr;
-    if (workspace_alloc((void**)&pks, slab * sizeof(double), stream) != hipSuccess || workspace_alloc((void**)&pkw, slab * sizeof(double), stream) != hipSuccess ||
-        workspace_alloc((void**)&nmat, (size_t)S * R * R * sizeof(double), stream) != hipSuccess ||
-        workspace_alloc((void**)&uinv, (size_t)S * R * R * sizeof(double), stream) != hipSuccess ||
-        workspace_alloc((void**)&work, ((size_t)R * R + 128 * 128) * sizeof(double), stream) != hipSuccess ||
-        workspace_alloc((void**)&info, sizeof(int), stream) != hipSuccess) {
-        for (void* q : {(void*)pks, (void*)pkw, (void*)nmat, (void*)uinv, (void*)work, (void*)info})
-            if (q) (void)hipFreeAsync(q, stream);
-        return fail(SHG_ERR_NOMEM, "analysis operator workspace allocation failed");
-    }
-    if (zero_fill(info, stream) != SHG_OK) return SHG_ERR_HIP;
-    hipLaunchKernelGGL(analysis_gather_kernel, dim3(ceil_div(nlat, 128), R, S), dim3(128), 0, stream, N, nmin, nlat, p->ldlat, p->pk, w2, pks, pkw);
-    // normal matrices N_s = PKw_s PKs_s^T
-    int rc = gemm_ex(false, true, R, R, nlat, 1.0, pkw, nlat, (long long)R * nlat, pks, nlat, (long long)R * nlat, 0.0, nmat, R, (long long)R * R, S,
+    if (p->ana_H.ensure(slab) != hipSuccess) return fail(SHG_ERR_NOMEM, "analysis operator allocation failed");
+    int bad = 0, rc;
+    {
+        Workspace ws = Workspace::pooled(stream);
+        double *pks, *pkw, *nmat, *uinv, *work;
+        int* info;
+        if (!ws.alloc(pks, slab, pkw, slab, nmat, (size_t)S * R * R, uinv, (size_t)S * R * R, work, (size_t)R * R + 128 * 128, info, 1))
+            return fail(SHG_ERR_NOMEM, "analysis operator workspace allocation failed");
+        if (zero_fill(info, stream) != SHG_OK) return SHG_ERR_HIP;
+        hipLaunchKernelGGL(analysis_gather_kernel, dim3(ceil_div(nlat, 128), R, S), dim3(128), 0, stream, N, nmin, nlat, p->ldlat, p->pk.get(), w2, pks, pkw);
+        // normal matrices N_s = PKw_s PKs_s^T
+        rc = gemm_ex(false, true, R, R, nlat, 1.0, pkw, nlat, (long long)R * nlat, pks, nlat, (long long)R * nlat, 0.0, nmat, R, (long long)R * R, S,
                      false, stream);
-    if (!rc) {
-        hipLaunchKernelGGL(analysis_pad_kernel, dim3(S), dim3(std::max(64, round_up(R, 64))), 0, stream, N, nmin, nmat);
-        if (R <= 128) {
-            rc = factor_invert_batched(R, nmat, R, (long long)R * R, uinv, R, (long long)R * R, S, info, stream);
-        } else {
-            for (int s = 0; s < S && !rc; ++s) {
-                rc = potrf_upper(R, nmat + (size_t)s * R * R, R, work + (size_t)R * R, info, stream);
-                if (!rc) rc = trtri_upper(R, nmat + (size_t)s * R * R, R, uinv + (size_t)s * R * R, R, work, stream);
+        if (!rc) {
+            hipLaunchKernelGGL(analysis_pad_kernel, dim3(S), dim3(std::max(64, round_up(R, 64))), 0, stream, N, nmin, nmat);
+            if (R <= 128) {
+                rc = factor_invert_batched(R, nmat, R, (long long)R * R, uinv, R, (long long)R * R, S, info, stream);
+            } else {
+                for (int s = 0; s < S && !rc; ++s) {
+                    rc = potrf_upper(R, nmat + (size_t)s * R * R, R, work + (size_t)R * R, info, stream);
+                    if (!rc) rc = trtri_upper(R, nmat + (size_t)s * R * R, R, uinv + (size_t)s * R * R, R, work, stream);
+                }
             }
         }
+        // H_s = U_s^-1 (U_s^-T PKs_s)
+        if (!rc) rc = gemm_ex(true, false, R, nlat, R, 1.0, uinv, R, (long long)R * R, pks, nlat, (long long)R * nlat, 0.0, pkw, nlat, (long long)R * nlat, S, false, stream);
+        if (!rc) rc = gemm_ex(false, false, R, nlat, R, 1.0, uinv, R, (long long)R * R, pkw, nlat, (long long)R * nlat, 0.0, p->ana_H.get(), nlat, (long long)R * nlat, S, false, stream);
+        if (!rc) {
+            SHG_HIP(hipMemcpyAsync(&bad, info, sizeof(int), hipMemcpyDeviceToHost, stream));
+            SHG_HIP(hipStreamSynchronize(stream));
+        }
     }
-    // H_s = U_s^-1 (U_s^-T PKs_s)
-    if (!rc) rc = gemm_ex(true, false, R, nlat, R, 1.0, uinv, R, (long long)R * R, pks, nlat, (long long)R * nlat, 0.0, pkw, nlat, (long long)R * nlat, S, false, stream);
-    if (!rc) rc = gemm_ex(false, false, R, nlat, R, 1.0, uinv, R, (long long)R * R, pkw, nlat, (long long)R * nlat, 0.0, p->ana_H, nlat, (long long)R * nlat, S, false, stream);
-    int bad = 0;
-    if (!rc) {
-        SHG_HIP(hipMemcpyAsync(&bad, info, sizeof(int), hipMemcpyDeviceToHost, stream));
-        SHG_HIP(hipStreamSynchronize(stream));
-    }
-    (void)hipFreeAsync(pks, stream);
-    (void)hipFreeAsync(pkw, stream);
-    (void)hipFreeAsync(nmat, stream);
-    (void)hipFreeAsync(uinv, stream);
-    (void)hipFreeAsync(work, stream);
-    (void)hipFreeAsync(info, stream);
     if (rc) return rc;
     if (bad) return fail(SHG_ERR_INVALID, "shg_analysis: a normal matrix is not positive definite (grid does not resolve the requested degrees)");
     return build_parity_operator(p, nmin, stream);
@@ -753,14 +733,17 @@ static int rebuild_analysis_operator(shg_plan* p, const double* area, int nmin, 
     const int N = p->N, S = 2 * N + 1, nlat = p->nlat, nlon = p->nlon;
     const size_t na = (size_t)nlat * nlon;
     p->ana_nmin = -1;
-    if (!p->ana_area && hipMalloc((void**)&p->ana_area, na * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "analysis weight copy allocation failed");
-    double* w2 = nullptr;
-    if (workspace_alloc((void**)&w2, (size_t)S * nlat * sizeof(double), stream) != hipSuccess) return fail(SHG_ERR_NOMEM, "shg_analysis: workspace allocation failed");
-    hipLaunchKernelGGL(weight_squares_kernel, dim3(nlat), dim3(256), 0, stream, S, nlat, nlon, area, p->cs_slot, w2);
-    int rc = build_analysis_operator(p, w2, nmin, stream);
-    (void)hipFreeAsync(w2, stream);
+    if (p->ana_area.ensure(na) != hipSuccess) return fail(SHG_ERR_NOMEM, "analysis weight copy allocation failed");
+    int rc;
+    {
+        Workspace ws = Workspace::pooled(stream);
+        double* w2;
+        if (!ws.alloc(w2, (size_t)S * nlat)) return fail(SHG_ERR_NOMEM, "shg_analysis: workspace allocation failed");
+        hipLaunchKernelGGL(weight_squares_kernel, dim3(nlat), dim3(256), 0, stream, S, nlat, nlon, area, p->cs_slot.get(), w2);
+        rc = build_analysis_operator(p, w2, nmin, stream);
+    }
     if (rc) return rc;
-    SHG_HIP(hipMemcpyAsync(p->ana_area, area, na * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    SHG_HIP(hipMemcpyAsync(p->ana_area.get(), area, na * sizeof(double), hipMemcpyDeviceToDevice, stream));
     {   // weights that are constant along every parallel (geographic and Gauss grids) need not be streamed by the transform kernel
         ScratchLease lease(stream);
         int* varies = (int*)lease.get(kScratchAnaFlag, sizeof(int));
@@ -779,7 +762,7 @@ static int rebuild_analysis_operator(shg_plan* p, const double* area, int nmin, 
 // *diff (device, zeroed here) becomes non-zero when `area` is not the set of weights the cached operator was built for
 static int launch_weight_compare(shg_plan* p, const double* area, int* diff, hipStream_t stream) {
     if (zero_fill(diff, stream) != SHG_OK) return SHG_ERR_HIP;
-    hipLaunchKernelGGL(analysis_compare_kernel, dim3(256), dim3(256), 0, stream, (long long)p->nlat * p->nlon, area, p->ana_area, diff);
+    hipLaunchKernelGGL(analysis_compare_kernel, dim3(256), dim3(256), 0, stream, (long long)p->nlat * p->nlon, area, p->ana_area.get(), diff);
     SHG_HIP(hipGetLastError());
     return SHG_OK;
 }
@@ -788,13 +771,13 @@ static int ensure_analysis_operator(shg_plan* p, const double* area, int nmin, h
     int rc = analysis_tables(p, stream);
     if (rc) return rc;
     if (analysis_operator_cached(p, nmin)) {
-        int* diff = nullptr;
-        if (workspace_alloc((void**)&diff, sizeof(int), stream) != hipSuccess) return fail(SHG_ERR_NOMEM, "shg_analysis: workspace allocation failed");
+        Workspace ws = Workspace::pooled(stream);           // (freed before the rebuild below)
+        int* diff;
+        if (!ws.alloc(diff, 1)) return fail(SHG_ERR_NOMEM, "shg_analysis: workspace allocation failed");
         int host = 0;
         rc = launch_weight_compare(p, area, diff, stream);
         hipError_t e = rc ? hipSuccess : hipMemcpyAsync(&host, diff, sizeof(int), hipMemcpyDeviceToHost, stream);
         if (!rc && e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFreeAsync(diff, stream);
         if (rc) return rc;
         if (e != hipSuccess) return fail(SHG_ERR_HIP, "shg_analysis: weight comparison failed: %s", hipGetErrorString(e));
         if (host == 0) return SHG_OK;
@@ -818,8 +801,8 @@ extern "C" int shg_analysis_matrix(shg_plan* p, const double* area, int nmin, do
     const int rc = ensure_analysis_operator(p, area, nmin, stream);
     if (rc) return rc;
     const int N = p->N;
-    hipLaunchKernelGGL(analysis_matrix_kernel, dim3(p->nlat, N + 1, 2 * N + 1), dim3(256), 0, stream, N, nmin, p->nlat, p->nlon, p->ana_H, area,
-                       p->cs_slot, F);
+    hipLaunchKernelGGL(analysis_matrix_kernel, dim3(p->nlat, N + 1, 2 * N + 1), dim3(256), 0, stream, N, nmin, p->nlat, p->nlon, p->ana_H.get(), area,
+                       p->cs_slot.get(), F);
     SHG_HIP(hipGetLastError());
     return SHG_OK;
 }
@@ -829,13 +812,9 @@ static int ensure_transform_table(shg_plan* p, int mt, hipStream_t stream) {
     if (p->ana_trig && p->ana_trig_mt == mt) return SHG_OK;
     const int TR = 4 * mt * 16;
     const int ncol = ceil_div(p->nlon / 4, kAtKC) * kAtKC;
-    if (p->ana_trig) {
-        SHG_HIP(hipStreamSynchronize(stream));
-        (void)hipFree(p->ana_trig);
-        p->ana_trig = nullptr;
-    }
-    if (hipMalloc((void**)&p->ana_trig, (size_t)ncol * TR * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "analysis trig table allocation failed");
-    hipLaunchKernelGGL(analysis_trig_kernel, dim3(ceil_div(TR, 128), ncol), dim3(128), 0, stream, p->N, p->nlon, mt, p->cs_slot, p->ana_trig);
+    if (p->ana_trig) SHG_HIP(hipStreamSynchronize(stream));
+    if (p->ana_trig.assign((size_t)ncol * TR) != hipSuccess) return fail(SHG_ERR_NOMEM, "analysis trig table allocation failed");
+    hipLaunchKernelGGL(analysis_trig_kernel, dim3(ceil_div(TR, 128), ncol), dim3(128), 0, stream, p->N, p->nlon, mt, p->cs_slot.get(), p->ana_trig.get());
     SHG_HIP(hipGetLastError());
     p->ana_trig_mt = mt;
     return SHG_OK;
@@ -854,7 +833,7 @@ static int folded_transform(shg_plan* p, const double* grid, const double* area,
                nlon, grid, area, wvt);
     ProfileScope ps(p, 4, stream);
     int rc;
-    const double* quarter = p->cs_slot + nlon / 2;
+    const double* quarter = p->cs_slot.get() + nlon / 2;
     rc = gemm_ex(false, false, 1, (int)rows, nq, 1.0, quarter, nlon, 0, wvt + 2 * plane, (int)rows, 0, 0.0, gt, (int)rows, 0, 1, false, stream);
     const int odd = (N + 1) / 2, even = N / 2;    // orders 1, 3, ... / 2, 4, ...
     if (!rc && odd)
@@ -874,7 +853,7 @@ static int launch_fused_transform(shg_plan* p, const double* values, const doubl
     const int rc = ensure_transform_table(p, mt, stream);
     if (rc) return rc;
 #define SHG_ANA_LAUNCH(MT_, RW_)                                                                                                       \
-    hipLaunchKernelGGL((analysis_transform_kernel<MT_, RW_>), dim3(blocks), dim3(256), 0, stream, nb, nlat, nlon, N, values, area, p->ana_trig, gt)
+    hipLaunchKernelGGL((analysis_transform_kernel<MT_, RW_>), dim3(blocks), dim3(256), 0, stream, nb, nlat, nlon, N, values, area, p->ana_trig.get(), gt)
     if (p->ana_rowconst) {
         if (mt == 2) SHG_ANA_LAUNCH(2, true); else if (mt == 3) SHG_ANA_LAUNCH(3, true); else SHG_ANA_LAUNCH(4, true);
     } else {
@@ -911,19 +890,19 @@ static int analysis_pass(shg_plan* p, const double* grid, const double* area, in
             hipLaunchKernelGGL(weight_transpose_kernel, dim3(ceil_div(nlon, 32), (unsigned)ceil_div64(rows, 32)), dim3(256), 0, stream, nb,
                                nlat, nlon, grid + (size_t)b0 * nlat * nlon, area, wvt);
             ProfileScope ps(p, 4, stream);
-            rc = shg_dgemm(S, (int)rows, nlon, p->cs_slot, nlon, wvt, (int)rows, gt, (int)rows, stream);
+            rc = shg_dgemm(S, (int)rows, nlon, p->cs_slot.get(), nlon, wvt, (int)rows, gt, (int)rows, stream);
         }
         if (rc) return rc;
         ProfileScope ps(p, 5, stream);
         if (p->ana_parity && SHG_ANA_PARITY) {
             hipLaunchKernelGGL(analysis_operator_parity_kernel, dim3((unsigned)(8 * ceil_div(S, 8) * ceil_div(nb, kOpCols))), dim3(256), 0, stream, N, nmin, nlat, nb, b0,
-                               ceil_div(nb, kOpCols), p->ana_Hp, gt, anm);
+                               ceil_div(nb, kOpCols), p->ana_Hp.get(), gt, anm);
         } else if (R <= kOpRows && nlat % 2 == 0) {
             hipLaunchKernelGGL(analysis_operator_kernel, dim3((unsigned)(8 * ceil_div(S, 8) * ceil_div(nb, kOpCols))), dim3(256), 0, stream, N, nmin, nlat, nb, b0,
-                               ceil_div(nb, kOpCols), p->ana_H, gt, anm);
+                               ceil_div(nb, kOpCols), p->ana_H.get(), gt, anm);
         } else {
             // X_s [R][nb] = H_s [R][nlat] gt_s^T   (gt_s is [nb][nlat])
-            rc = gemm_ex(false, true, R, nb, nlat, 1.0, p->ana_H, nlat, (long long)R * nlat, gt, nlat, rows, 0.0, X, nb, (long long)R * nb, S, false, stream);
+            rc = gemm_ex(false, true, R, nb, nlat, 1.0, p->ana_H.get(), nlat, (long long)R * nlat, gt, nlat, rows, 0.0, X, nb, (long long)R * nb, S, false, stream);
             if (rc) return rc;
             hipLaunchKernelGGL(analysis_scatter_kernel, dim3(ceil_div(nb, 64), R, S), dim3(64), 0, stream, N, nmin, nb, b0, X, anm);
         }
@@ -943,7 +922,7 @@ extern "C" int shg_analysis(shg_plan* p, const double* grid, const double* area,
     const bool trusted = area == nullptr;               // the weights of the previous call: the plan's own copy, nothing to compare
     if (trusted) {
         SHG_REQUIRE(analysis_operator_cached(p, nmin), "shg_analysis: area == NULL, but the plan holds no operators for min_degree %d", nmin);
-        area = p->ana_area;
+        area = p->ana_area.get();
     }
     const int N = p->N, S = 2 * N + 1, nlat = p->nlat, nlon = p->nlon;
     int rc = analysis_tables(p, stream);

@@ -392,9 +392,9 @@ int basin_statistics(const double* V, int T, long long P, const double* w, const
     SHG_REQUIRE(ntiles <= 0x7fffffff, "shg_basin_statistics: too many points");
     const size_t n_partial = (size_t)ntiles * (T + 1) * NB * 2;
     const size_t n_keep = (size_t)T * NB + NB;
-    double* work = nullptr;
-    if (workspace_alloc((void**)&work, (n_partial + n_keep) * sizeof(double), stream) != hipSuccess)
-        return fail(SHG_ERR_NOMEM, "shg_basin_statistics: workspace allocation failed");
+    Workspace ws = Workspace::pooled(stream);
+    double* work;
+    if (!ws.alloc(work, n_partial + n_keep)) return fail(SHG_ERR_NOMEM, "shg_basin_statistics: workspace allocation failed");
     double* partial = work;
     double* keep = work + n_partial;
     const unsigned red_blocks = (unsigned)((T * NB + 3) / 4);
@@ -404,9 +404,7 @@ int basin_statistics(const double* V, int T, long long P, const double* w, const
     hipLaunchKernelGGL((stats_kernel<NB, 2>), dim3((unsigned)ntiles, (unsigned)((T + kStatRows - 1) / kStatRows)), dim3(256), 0, stream, V, T, P,
                        w, bits, tile, (const double*)keep, partial);
     hipLaunchKernelGGL((stats_reduce_kernel<NB, 2>), dim3(red_blocks), dim3(256), 0, stream, T, B, (int)ntiles, (const double*)partial, keep, out);
-    const hipError_t err = hipGetLastError();
-    (void)hipFreeAsync(work, stream);
-    SHG_HIP(err);
+    SHG_HIP(hipGetLastError());
     return SHG_OK;
 }
 

@@ -534,9 +534,6 @@ static int panel_gemm(bool ta, int M, int N, int K, double alpha, const double* 
     return SHG_OK;
 }
 
-int gemm_ex_tri(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
-                long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, int tri, hipStream_t stream);
-
 int gemm_ex(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
             long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, hipStream_t stream) {
     return gemm_ex_tri(ta, tb, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch, upper_only, 0, stream);
@@ -1318,13 +1315,11 @@ extern "C" int shg_potrf(int n, double* A, int lda, int* info, void* stream_) {
     if (n == 0) return SHG_OK;
     SHG_REQUIRE(A != nullptr && lda >= n, "shg_potrf: bad matrix");
     hipStream_t stream = (hipStream_t)stream_;
-    double* work = nullptr;
-    if (workspace_alloc((void**)&work, (size_t)LEAF * LEAF * sizeof(double), stream) != hipSuccess)
-        return fail(SHG_ERR_NOMEM, "shg_potrf: workspace allocation failed");
+    Workspace ws = Workspace::pooled(stream);
+    double* work;
+    if (!ws.alloc(work, (size_t)LEAF * LEAF)) return fail(SHG_ERR_NOMEM, "shg_potrf: workspace allocation failed");
     if (info && (zero_fill(info, stream) != SHG_OK)) return SHG_ERR_HIP;
-    const int rc = potrf_upper(n, A, lda, work, info, stream);
-    (void)hipFreeAsync(work, stream);
-    return rc;
+    return potrf_upper(n, A, lda, work, info, stream);
 }
 
 extern "C" int shg_trtri(int n, const double* U, int ldu, double* X, int ldx, void* stream_) {
@@ -1333,12 +1328,10 @@ extern "C" int shg_trtri(int n, const double* U, int ldu, double* X, int ldx, vo
     SHG_REQUIRE(U && X && ldu >= n && ldx >= n, "shg_trtri: bad matrix");
     SHG_REQUIRE(U != X, "shg_trtri: in-place inversion is not supported");
     hipStream_t stream = (hipStream_t)stream_;
-    double* work = nullptr;
-    if (workspace_alloc((void**)&work, (size_t)n * n / 2 * sizeof(double) + 1024, stream) != hipSuccess)
-        return fail(SHG_ERR_NOMEM, "shg_trtri: workspace allocation failed");
-    const int rc = trtri_upper(n, U, ldu, X, ldx, work, stream);
-    (void)hipFreeAsync(work, stream);
-    return rc;
+    Workspace ws = Workspace::pooled(stream);
+    double* work;
+    if (!ws.alloc(work, (size_t)n * n / 2 + 128)) return fail(SHG_ERR_NOMEM, "shg_trtri: workspace allocation failed");
+    return trtri_upper(n, U, ldu, X, ldx, work, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -27,17 +27,6 @@
 
 namespace shg {
 
-int gemm_ex(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
-            long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, hipStream_t stream);
-int gemm_ex_tri(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
-                long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, int tri, hipStream_t stream);
-int potrf_inverse_batch(int n, double* A, int lda, long long strideA, double* X, int ldx, long long strideX, double* work, long long strideW,
-                        int* info, int info_stride, int batch, const Coupling* cp, hipStream_t stream);
-bool potrf_inverse_carries_coupling(int n, hipStream_t stream);
-void potrf_inverse_set_lookahead(int mode);
-int potrf_inverse_lookahead_mode();
-size_t potrf_inverse_work(int n);
-
 namespace {
 
 struct BlockView {

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstdint>
@@ -61,6 +62,35 @@ bool gemm_tall_shape(bool ta, bool tb, int M, int N, int K, int batch, bool uppe
                      const double* C);
 int gemm_tall(int M, int N, int K, double alpha, const double* A, int lda, const double* B, int ldb, double beta, double* C, int ldc, hipStream_t stream);
 
+// blas.hip: batched C = alpha op(A) op(B) + beta C; tri: triangular structure of the operands (see GemmExParams::tri)
+int gemm_ex(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
+            long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, hipStream_t stream);
+int gemm_ex_tri(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
+                long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, int tri, hipStream_t stream);
+// blas.hip: Cholesky factors U (A = U^T U, in place) and their inverses
+int factor_invert_batched(int n, double* A, int lda, long long strideA, double* X, int ldx, long long strideX, int batch, int* info,
+                          hipStream_t stream);
+int potrf_upper(int n, double* A, int lda, double* work, int* info, hipStream_t stream);
+int trtri_upper(int n, const double* U, int ldu, double* X, int ldx, double* work, hipStream_t stream);
+int potrf_inverse_batch(int n, double* A, int lda, long long strideA, double* X, int ldx, long long strideX, double* work, long long strideW,
+                        int* info, int info_stride, int batch, const Coupling* cp, hipStream_t stream);
+bool potrf_inverse_carries_coupling(int n, hipStream_t stream);
+void potrf_inverse_set_lookahead(int mode);
+int potrf_inverse_lookahead_mode();
+size_t potrf_inverse_work(int n);
+
+// gemm.hip / covprop.hip: products whose A entries are generated from per-point or per-plan tables
+int covprop_build_cs_table(shg_plan* p, hipStream_t stream);
+int covprop_rows(shg_plan* p, const double* cov, int Pn, int p_off, int lat0, int lat1, double* partial, hipStream_t stream);
+int synth_generic(const double* pkd, int ldp, const double* csr, int ldcs, const int* rslot, long long idiv, long long jmod, int M,
+                  const double* X, int K, int N, double* C, hipStream_t stream);
+int covprop_generic(const double* pkd, int ldp, const double* csr, int ldcs, const int* rslot, long long idiv, long long jmod,
+                    long long row0, int M, const double* cov, int Pn, int p_off, double* partial, double* sigma, shg_plan* prof,
+                    hipStream_t stream, bool symmetric, bool transposed_table, const unsigned* csoff = nullptr, int pk_rows = 0, int ldcov = 0);
+
+// plan.hip: recursion factors a_nm / b_nm in packed order-major layout (the reference's expression order)
+void recursion_tables(int N, std::vector<double>& a, std::vector<double>& b);
+
 void stream_scratch_release();
 hipError_t workspace_alloc(void** ptr, size_t bytes, hipStream_t stream);    // hipMallocAsync from a pool that keeps freed memory cached
 
@@ -76,6 +106,72 @@ hipError_t workspace_alloc(void** ptr, size_t bytes, hipStream_t stream);    // 
     do {                                                                                           \
         if (!(cond)) return shg::fail(SHG_ERR_INVALID, __VA_ARGS__);                               \
     } while (0)
+
+// Device array that lives as long as its owner (a plan table): hipMalloc / hipFree.  ensure(n) keeps a buffer of at least n
+// elements (grow-only workspaces), assign(n) replaces it by one of exactly n (tables rebuilt when their key changes); after a
+// failed allocation the array is empty.
+template <typename T>
+class DeviceArray {
+public:
+    DeviceArray() = default;
+    DeviceArray(DeviceArray&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    DeviceArray& operator=(DeviceArray&& o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); return *this; }
+    ~DeviceArray() { reset(); }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    hipError_t ensure(size_t n) { return n <= n_ ? hipSuccess : assign(n); }
+    hipError_t assign(size_t n) {
+        reset();
+        const hipError_t e = hipMalloc((void**)&p_, n * sizeof(T));
+        if (e == hipSuccess) n_ = n; else p_ = nullptr;
+        return e;
+    }
+private:
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// a table of at least one element filled from the host
+template <typename T>
+int upload(DeviceArray<T>& dst, const std::vector<T>& src) {
+    SHG_HIP(dst.assign(std::max<size_t>(src.size(), 1)));
+    if (!src.empty()) SHG_HIP(hipMemcpy(dst.get(), src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return SHG_OK;
+}
+
+// Device buffers of one call, allocated on a stream and given back with hipFreeAsync on that stream, in the order of their
+// allocation, when the workspace goes out of scope.  pooled(): workspace_alloc; plain(): hipMallocAsync from the pool as it is.
+class Workspace {
+public:
+    static Workspace pooled(hipStream_t stream) { return Workspace(stream, true); }
+    static Workspace plain(hipStream_t stream) { return Workspace(stream, false); }
+    Workspace(Workspace&& o) noexcept : stream_(o.stream_), pooled_(o.pooled_), bufs_(std::move(o.bufs_)) { o.bufs_.clear(); }
+    Workspace& operator=(Workspace&&) = delete;
+    ~Workspace() {
+        for (void* q : bufs_) (void)hipFreeAsync(q, stream_);
+    }
+    // alloc(a, na, b, nb, ...): na elements for a, then nb for b, ...; false when one of them fails (the others stay owned)
+    template <typename T, typename... More>
+    bool alloc(T*& p, size_t n, More&&... more) {
+        void* q = nullptr;
+        if ((pooled_ ? workspace_alloc(&q, n * sizeof(T), stream_) : hipMallocAsync(&q, n * sizeof(T), stream_)) != hipSuccess) return false;
+        bufs_.push_back(q);
+        p = static_cast<T*>(q);
+        if constexpr (sizeof...(More) > 0) return alloc(std::forward<More>(more)...);
+        return true;
+    }
+private:
+    Workspace(hipStream_t stream, bool pooled) : stream_(stream), pooled_(pooled) {}
+    hipStream_t stream_;
+    bool pooled_;
+    std::vector<void*> bufs_;
+};
 
 // Knock-out switches for timing experiments (results are wrong with any of them on) exist in -DSHG_EXPERIMENT builds only
 // (`make timeline` -> libshg_timeline.so, never loaded by the package): the shipping library reads no environment variable.
@@ -164,7 +260,7 @@ struct shg_plan {
     bool sym4 = false;      // 4-fold longitude symmetry path
     int rotR = 0;           // rotations of the meridian set used by the rotation-folded kernel (synthesis_rot.hip): 10, 9, 6, 3 or 0 = not applicable
     std::vector<double> lon_host;   // meridians as given (the trig stream of that kernel is rebuilt when shg_plan_set_rotations changes R)
-    double* rot_trig = nullptr; // [column tiles][k-steps][64 lanes][2] cos / signed sin stream of that kernel
+    shg::DeviceArray<double> rot_trig; // [column tiles][k-steps][64 lanes][2] cos / signed sin stream of that kernel
     bool sym_ns = false;    // parallels (colatitude and kn rows) symmetric about the equator
     int ngroups = 1;        // 4 (sym4) or 1
     int goff[5] = {0, 0, 0, 0, 0};   // first K slot of each group (multiples of 4), goff[ngroups] = K
@@ -174,71 +270,68 @@ struct shg_plan {
     int chunk = 16;         // epochs per pass
 
     // device tables
-    double* ct = nullptr;       // [ldlat] cos(colat)
-    double* st = nullptr;       // [ldlat] sin(colat)
-    double* pmm = nullptr;      // [N+1][ldlat] sectorial seeds P_mm(theta_i)
-    double* knT = nullptr;      // [N+1][ldlat] kn transposed
-    double* arec = nullptr;     // [packed] recursion factor a_nm
-    double* brec = nullptr;     // [packed] recursion factor b_nm
-    double* trig = nullptr;     // [ncoltiles][K][16] cos/sin table, column-tile major
+    shg::DeviceArray<double> ct;   // [ldlat] cos(colat)
+    shg::DeviceArray<double> st;   // [ldlat] sin(colat)
+    shg::DeviceArray<double> pmm;  // [N+1][ldlat] sectorial seeds P_mm(theta_i)
+    shg::DeviceArray<double> knT;  // [N+1][ldlat] kn transposed
+    shg::DeviceArray<double> arec; // [packed] recursion factor a_nm
+    shg::DeviceArray<double> brec; // [packed] recursion factor b_nm
+    shg::DeviceArray<double> trig; // [ncoltiles][K][16] cos/sin table, column-tile major
     // 64-row fused kernel: order 0 (constant along a parallel) leaves the K loop and becomes the start value of the cosine /
     // even-order accumulators, when that saves a body of 16 slots (d/o 96: 13 -> 12 bodies).  Slot K_f of the panel holds it.
     bool fold0 = false;
     int goff_f[5] = {0, 0, 0, 0, 0};
     int K_f = 0;
-    double* trig_f = nullptr;   // [ncoltiles][K_f][16]
-    double* lon = nullptr;      // [nlon]
-    double* colat = nullptr;    // [nlat]
+    shg::DeviceArray<double> trig_f; // [ncoltiles][K_f][16]
+    shg::DeviceArray<double> lon;    // [nlon]
+    shg::DeviceArray<double> colat;  // [nlat]
     // covariance-propagation tables (built lazily)
-    double* pk_deg = nullptr;   // [nlat][Pfull] kn-scaled P_nm in degree-wise order (nmin = 0)
-    double* cs_slot = nullptr;  // [2N+1][nlon] cos/sin per slot (0, 1c, 1s, 2c, 2s, ...)
-    int* rslot = nullptr;       // [Pfull] rank inside its degree of every degree-wise index
-    double* cov_partial = nullptr;   // [column blocks][band rows] partial row sums of the covariance kernel
-    size_t cov_partial_size = 0;
-    double* cov_pad = nullptr;       // covariance matrix copied to rows of even length (16-byte aligned rows for the LDS copy of the kernel)
-    size_t cov_pad_size = 0;
+    shg::DeviceArray<double> pk_deg;      // [nlat][Pfull] kn-scaled P_nm in degree-wise order (nmin = 0)
+    shg::DeviceArray<double> cs_slot;     // [2N+1][nlon] cos/sin per slot (0, 1c, 1s, 2c, 2s, ...)
+    shg::DeviceArray<int> rslot;          // [Pfull] rank inside its degree of every degree-wise index
+    shg::DeviceArray<double> cov_partial; // [column blocks][band rows] partial row sums of the covariance kernel
+    shg::DeviceArray<double> cov_pad;     // covariance matrix copied to rows of even length (16-byte aligned rows for the LDS copy of the kernel)
     // workspace
-    double* cpk = nullptr;      // [packed][2][chunk_pad] repacked coefficients of one pass
-    double* F = nullptr;        // [chunk][K][ldlat] output of the Legendre stage
+    shg::DeviceArray<double> cpk; // [packed][2][chunk_pad] repacked coefficients of one pass
+    shg::DeviceArray<double> F;   // [chunk][K][ldlat] output of the Legendre stage
     int chunk_alloc = 0;
     // fused synthesis path (synthesis_fused.hip)
-    double* pk = nullptr;       // [packed + 4][ldlat] kn-scaled Legendre table (two-kernel variant), built on first use
-    double* pkf = nullptr;      // [nit][Qtot][64 lanes][2] the same table in MFMA-fragment order (fused kernel), built on first use
-    int* qoff = nullptr;        // [N+2] first row-octet of every order in the fragment-ordered tables; qoff[N+1] = Qtot
+    shg::DeviceArray<double> pk;  // [packed + 4][ldlat] kn-scaled Legendre table (two-kernel variant), built on first use
+    shg::DeviceArray<double> pkf; // [nit][Qtot][64 lanes][2] the same table in MFMA-fragment order (fused kernel), built on first use
+    shg::DeviceArray<int> qoff;   // [N+2] first row-octet of every order in the fragment-ordered tables; qoff[N+1] = Qtot
     int Qtot = 0;
     std::vector<int> ns_badmap; // per block of 8 northern parallels: -1, or rank among the blocks whose mirrored parallels get their own table
     int ns_nbad = 0;
-    int* badmap_d = nullptr;
-    int* octinfo_d = nullptr;   // [Qtot] order | octet-in-order << 8 of every octet of the fragment-ordered tables
-    int* itemtab_d = nullptr;   // work items of the fused kernel's Legendre stage, [8 waves][nrec][4]
+    shg::DeviceArray<int> badmap_d;
+    shg::DeviceArray<int> octinfo_d; // [Qtot] order | octet-in-order << 8 of every octet of the fragment-ordered tables
+    shg::DeviceArray<int> itemtab_d; // work items of the fused kernel's Legendre stage, [8 waves][nrec][4]
     int itemtab_nrec = 0, itemtab_ntrip = 0;
     int itemtab_rot = -1;       // panel slot convention of the work items: 0 = 4-fold kernel, R = rotation-folded kernel
     const double* om_src = nullptr;   // set for the duration of shg_synthesis_om: the coefficient repack reads this order-major series
     int om_N = 0, om_Bpad = 0;
-    int* sem_d = nullptr;       // token counter of the rotation-folded kernel's Legendre stage (synthesis_rot.hip), allocated by rot_set_stage_limit
+    shg::DeviceArray<int> sem_d; // token counter of the rotation-folded kernel's Legendre stage (synthesis_rot.hip), allocated by rot_set_stage_limit
     int stage_limit = 0;        // workgroups that may run their Legendre stage at once (0 = no limit, the default)
-    int* blockmap_d = nullptr;  // XCD-aware (epoch tile, parallel tile) order of the fused kernel's workgroups
+    shg::DeviceArray<int> blockmap_d; // XCD-aware (epoch tile, parallel tile) order of the fused kernel's workgroups
     int blockmap_nbt = 0, blockmap_nit = 0;
     std::vector<char> ns_badrow;    // per northern parallel: mirror image deviates too much to share the northern table
     // two-workgroup fused synthesis (synthesis_fused32.hip): blocks of 4 northern parallels
-    double* pkf32 = nullptr;
-    int* qoff32 = nullptr;
-    int* badmap32_d = nullptr;
+    shg::DeviceArray<double> pkf32;
+    shg::DeviceArray<int> qoff32;
+    shg::DeviceArray<int> badmap32_d;
     int Qtot32 = 0, nbad32 = 0;
     int pkf_variant = 0;        // 1 plain fragment order, 2 north-south symmetric fragment order
-    double* cpk4 = nullptr;     // repacked coefficients of the whole batch: [ceil(B/4)][Qtot][32][2] (fused) or [ceil(B/8)][packed][2][8]
-    size_t cpk4_size = 0;
+    shg::DeviceArray<double> cpk4; // repacked coefficients of the whole batch: [ceil(B/4)][Qtot][32][2] (fused) or [ceil(B/8)][packed][2][8]
     int cpk4_variant = 0;       // layout the workspace was last zero-initialised for
     size_t cpk4_zeroed = 0;
     // analysis operator cache (analysis.hip): H[S][N+1][nlat] for the area weights ana_area and min degree ana_nmin
-    double* ana_H = nullptr;
-    double* ana_Hp = nullptr;   // north-south parity form of the operator [S][2 ceil((N+1)/2)][nlat/2] (analysis.hip), valid when ana_parity
+    shg::DeviceArray<double> ana_H;
+    shg::DeviceArray<double> ana_Hp; // north-south parity form of the operator [S][2 ceil((N+1)/2)][nlat/2] (analysis.hip), valid when ana_parity
     bool ana_parity = false;
     double ana_parity_defect = -1.0;   // largest dropped entry / largest entry of H when ana_Hp was formed (-1: not formed)
-    double* ana_area = nullptr; // [nlat][nlon] copy of the area weights the operator was built for (compared on the device per call)
+    shg::DeviceArray<double> ana_area; // [nlat][nlon] copy of the area weights the operator was built for (compared on the device per call)
     int ana_nmin = -1;
     bool ana_rowconst = false;  // the weights of the cached operator are constant along every parallel (geographic and Gauss grids)
-    double* ana_trig = nullptr; // trig table of the fused transform kernel in chunk order [chunk][8 columns][4 groups x MT x 16 orders], zero padded
+    shg::DeviceArray<double> ana_trig; // trig table of the fused transform kernel in chunk order [chunk][8 columns][4 groups x MT x 16 orders], zero padded
     int ana_trig_mt = 0;
     int path = 0;               // 0 auto, 1 three-kernel path, 2 fused 4-fold kernel, 5 fused kernel with 32-row panels (two workgroups per CU), 6 rotation-folded fused kernel
 
@@ -270,6 +363,7 @@ int rot_choose(int nlon, const double* lon_h, int N);
 int rot_applicable(const shg_plan* p);
 int build_rot_trig(shg_plan* p, const double* lon_h);
 int synthesis_rot(shg_plan* p, const double* anm, int B, double* grid, hipStream_t stream);
+int rot_kernel_waves();           // waves per workgroup of the rotation-folded kernel
 int rot_set_stage_limit(shg_plan* p, int limit);
 int fused32_applicable(const shg_plan* p);
 int synthesis_fused32(shg_plan* p, const double* anm, int B, double* grid, hipStream_t stream);

@@ -180,8 +180,8 @@ int covprop_rows(shg_plan* p, const double* cov, int Pn, int p_off, int lat0, in
     C.tiles_per_parallel = ceil_div(p->nlon, CT);
     C.M = (lat1 - lat0) * p->nlon;
     C.cov = cov;
-    C.pkd = p->pk_deg;
-    C.csr = p->cs_slot;
+    C.pkd = p->pk_deg.get();
+    C.csr = p->cs_slot.get();
     C.partial = partial;
     const size_t lds = (size_t)4 * CK * CLD * sizeof(double);            // 73.7 KB: two workgroups per CU
     SHG_HIP(hipFuncSetAttribute((const void*)covprop_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -17,10 +17,6 @@
 
 namespace shg {
 
-int gemm_ex(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
-            long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, hipStream_t stream);   // blas.hip
-int covprop_build_cs_table(shg_plan* p, hipStream_t stream);   // gemm.hip
-
 constexpr int kSepSlotChunk = 32;      // slots whose G matrices are alive at one time
 
 constexpr int kPermSegment = 8192;     // doubles of a source row staged in LDS at one time (64 KB: two workgroups per CU)
@@ -150,61 +146,50 @@ static int covprop_diag_separable(shg_plan* p, const double* cov, int nmin, int 
             pairs[(size_t)fill[k]++] = make_int2(b, perm[b] - k * kPermSegment);
         }
     }
-    int *soff_d = nullptr, *perm_d = nullptr, *pair_off_d = nullptr;
-    int2* pairs_d = nullptr;
-    double *Sp = nullptr, *G = nullptr, *Bm = nullptr, *Y = nullptr;
-    if (workspace_alloc((void**)&soff_d, soff.size() * sizeof(int), stream) != hipSuccess ||
-        workspace_alloc((void**)&perm_d, perm.size() * sizeof(int), stream) != hipSuccess ||
-        workspace_alloc((void**)&pairs_d, pairs.size() * sizeof(int2), stream) != hipSuccess ||
-        workspace_alloc((void**)&pair_off_d, pair_off.size() * sizeof(int), stream) != hipSuccess ||
-        workspace_alloc((void**)&Sp, (size_t)Pn * Pn * sizeof(double), stream) != hipSuccess ||
-        workspace_alloc((void**)&G, (size_t)kSepSlotChunk * Pn * nb * sizeof(double), stream) != hipSuccess ||
-        workspace_alloc((void**)&Bm, (size_t)nb * S * S * sizeof(double), stream) != hipSuccess ||
-        workspace_alloc((void**)&Y, (size_t)nb * S * nlon * sizeof(double), stream) != hipSuccess)
-        return fail(SHG_ERR_NOMEM, "shg_covprop_diag_separable: workspace allocation failed (%.1f GB)",
-                    ((double)Pn * Pn + (double)kSepSlotChunk * Pn * nb + (double)nb * S * S + (double)nb * S * nlon) * 8e-9);
-    SHG_HIP(hipMemcpyAsync(soff_d, soff.data(), soff.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    SHG_HIP(hipMemcpyAsync(perm_d, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    SHG_HIP(hipMemcpyAsync(pairs_d, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice, stream));
-    SHG_HIP(hipMemcpyAsync(pair_off_d, pair_off.data(), pair_off.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    SHG_HIP(hipStreamSynchronize(stream));                              // the host vectors go out of scope at return
-    hipLaunchKernelGGL(covsep_permute_kernel, dim3(Pn), dim3(1024), 0, stream, Pn, perm_d, pairs_d, pair_off_d, cov, Sp);
-
     {
-        ProfileScope ps(p, 3, stream);
-        for (int sc0 = 0; sc0 < S && rc == SHG_OK; sc0 += kSepSlotChunk) {
-            const int nsc = std::min(kSepSlotChunk, S - sc0);
-            for (int c = 0; c < nsc && rc == SHG_OK;) {
-                const int s = sc0 + c, m = (s + 1) >> 1, n0 = std::max(m, nmin), ns = N - n0 + 1;
-                // the cosine and the sine slot of an order have the same coefficients count and the same PK rows: one batched launch
-                const int pair = (s >= 1 && (s & 1) == 1 && c + 1 < nsc) ? 2 : 1;
-                double* Gc = G + (size_t)c * Pn * nb;
-                const int row0 = half ? soff[s] : 0;                      // symmetric Sigma: only the rows of this slot and the later ones
-                if (ns <= 0)
-                    SHG_HIP(hipMemsetAsync(Gc, 0, (size_t)pair * Pn * nb * sizeof(double), stream));
-                else
-                    rc = gemm_ex(false, false, Pn - row0, nb, ns, 1.0, Sp + (size_t)row0 * Pn + soff[s], Pn, ns,
-                                 p->pk + (size_t)(order_offset(N, m) + n0 - m) * p->ldlat + lat0, p->ldlat, 0, 0.0, Gc + (size_t)row0 * nb, nb,
-                                 (long long)Pn * nb, pair, false, stream);
-                c += pair;
+        Workspace ws = Workspace::pooled(stream);
+        int *soff_d, *perm_d, *pair_off_d;
+        int2* pairs_d;
+        double *Sp, *G, *Bm, *Y;
+        if (!ws.alloc(soff_d, soff.size(), perm_d, perm.size(), pairs_d, pairs.size(), pair_off_d, pair_off.size(), Sp, (size_t)Pn * Pn,
+                      G, (size_t)kSepSlotChunk * Pn * nb, Bm, (size_t)nb * S * S, Y, (size_t)nb * S * nlon))
+            return fail(SHG_ERR_NOMEM, "shg_covprop_diag_separable: workspace allocation failed (%.1f GB)",
+                        ((double)Pn * Pn + (double)kSepSlotChunk * Pn * nb + (double)nb * S * S + (double)nb * S * nlon) * 8e-9);
+        SHG_HIP(hipMemcpyAsync(soff_d, soff.data(), soff.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(perm_d, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(pairs_d, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(pair_off_d, pair_off.data(), pair_off.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipStreamSynchronize(stream));                              // the host vectors go out of scope at return
+        hipLaunchKernelGGL(covsep_permute_kernel, dim3(Pn), dim3(1024), 0, stream, Pn, perm_d, pairs_d, pair_off_d, cov, Sp);
+
+        {
+            ProfileScope ps(p, 3, stream);
+            for (int sc0 = 0; sc0 < S && rc == SHG_OK; sc0 += kSepSlotChunk) {
+                const int nsc = std::min(kSepSlotChunk, S - sc0);
+                for (int c = 0; c < nsc && rc == SHG_OK;) {
+                    const int s = sc0 + c, m = (s + 1) >> 1, n0 = std::max(m, nmin), ns = N - n0 + 1;
+                    // the cosine and the sine slot of an order have the same coefficients count and the same PK rows: one batched launch
+                    const int pair = (s >= 1 && (s & 1) == 1 && c + 1 < nsc) ? 2 : 1;
+                    double* Gc = G + (size_t)c * Pn * nb;
+                    const int row0 = half ? soff[s] : 0;                      // symmetric Sigma: only the rows of this slot and the later ones
+                    if (ns <= 0)
+                        SHG_HIP(hipMemsetAsync(Gc, 0, (size_t)pair * Pn * nb * sizeof(double), stream));
+                    else
+                        rc = gemm_ex(false, false, Pn - row0, nb, ns, 1.0, Sp + (size_t)row0 * Pn + soff[s], Pn, ns,
+                                     p->pk.get() + (size_t)(order_offset(N, m) + n0 - m) * p->ldlat + lat0, p->ldlat, 0, 0.0, Gc + (size_t)row0 * nb, nb,
+                                     (long long)Pn * nb, pair, false, stream);
+                    c += pair;
+                }
+                if (rc) break;
+                hipLaunchKernelGGL(covsep_contract_kernel, dim3(ceil_div(nb, 32), S, ceil_div(nsc, 32)), dim3(256), 0, stream, N, nmin, Pn, nb, p->ldlat,
+                                   lat0, S, sc0, nsc, half ? 1 : 0, soff_d, p->pk.get(), G, Bm);
             }
-            if (rc) break;
-            hipLaunchKernelGGL(covsep_contract_kernel, dim3(ceil_div(nb, 32), S, ceil_div(nsc, 32)), dim3(256), 0, stream, N, nmin, Pn, nb, p->ldlat,
-                               lat0, S, sc0, nsc, half ? 1 : 0, soff_d, p->pk, G, Bm);
+            if (rc == SHG_OK)
+                rc = gemm_ex(false, false, S, nlon, S, 1.0, Bm, S, (long long)S * S, p->cs_slot.get(), nlon, 0, 0.0, Y, nlon, (long long)S * nlon, nb, false, stream);
+            if (rc == SHG_OK)
+                hipLaunchKernelGGL(covsep_reduce_kernel, dim3(ceil_div(nlon, 256), nb), dim3(256), 0, stream, S, nlon, nb, p->cs_slot.get(), Y, sigma);
         }
-        if (rc == SHG_OK)
-            rc = gemm_ex(false, false, S, nlon, S, 1.0, Bm, S, (long long)S * S, p->cs_slot, nlon, 0, 0.0, Y, nlon, (long long)S * nlon, nb, false, stream);
-        if (rc == SHG_OK)
-            hipLaunchKernelGGL(covsep_reduce_kernel, dim3(ceil_div(nlon, 256), nb), dim3(256), 0, stream, S, nlon, nb, p->cs_slot, Y, sigma);
     }
-    (void)hipFreeAsync(soff_d, stream);
-    (void)hipFreeAsync(perm_d, stream);
-    (void)hipFreeAsync(pairs_d, stream);
-    (void)hipFreeAsync(pair_off_d, stream);
-    (void)hipFreeAsync(Sp, stream);
-    (void)hipFreeAsync(G, stream);
-    (void)hipFreeAsync(Bm, stream);
-    (void)hipFreeAsync(Y, stream);
     if (rc) return rc;
     SHG_HIP(hipGetLastError());
     return SHG_OK;

@@ -668,11 +668,12 @@ extern "C" int shg_spd_solve(const double* A, int n, const double* Bm, int k, do
     SHG_REQUIRE(A && Bm && X, "shg_spd_solve: NULL pointer");
     hipStream_t stream = (hipStream_t)stream_;
     const int nblocks = ceil_div(k, 256);
-    double* work = nullptr;
-    if (hipMallocAsync((void**)&work, (size_t)nblocks * n * n * sizeof(double), stream) != hipSuccess)
-        return fail(SHG_ERR_NOMEM, "shg_spd_solve: workspace allocation failed");
-    hipLaunchKernelGGL(shg::spd_solve_kernel, dim3(nblocks), dim3(256), 0, stream, n, k, A, Bm, work, X);
-    (void)hipFreeAsync(work, stream);
+    {
+        Workspace ws = Workspace::plain(stream);
+        double* work;
+        if (!ws.alloc(work, (size_t)nblocks * n * n)) return fail(SHG_ERR_NOMEM, "shg_spd_solve: workspace allocation failed");
+        hipLaunchKernelGGL(shg::spd_solve_kernel, dim3(nblocks), dim3(256), 0, stream, n, k, A, Bm, work, X);
+    }
     SHG_HIP(hipGetLastError());
     return SHG_OK;
 }

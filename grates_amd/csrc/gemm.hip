@@ -672,8 +672,8 @@ __global__ void cs_table_kernel(int N, int nlon, const double* __restrict__ lon,
 int covprop_build_cs_table(shg_plan* p, hipStream_t stream) {
     if (p->cs_slot) return SHG_OK;
     const long long n = (long long)(2 * p->N + 1) * p->nlon;
-    if (hipMalloc((void**)&p->cs_slot, (size_t)n * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "cos/sin table allocation failed");
-    hipLaunchKernelGGL(cs_table_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, stream, p->N, p->nlon, p->lon, p->cs_slot);
+    if (p->cs_slot.assign((size_t)n) != hipSuccess) return fail(SHG_ERR_NOMEM, "cos/sin table allocation failed");
+    hipLaunchKernelGGL(cs_table_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, stream, p->N, p->nlon, p->lon.get(), p->cs_slot.get());
     SHG_HIP(hipGetLastError());
     return SHG_OK;
 }
@@ -784,12 +784,6 @@ int covprop_generic(const double* pkd, int ldp, const double* csr, int ldcs, con
 
 }  // namespace shg
 
-namespace shg {
-int gemm_ex(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
-            long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, hipStream_t stream);   // blas.hip
-int covprop_rows(shg_plan* p, const double* cov, int Pn, int p_off, int lat0, int lat1, double* partial, hipStream_t stream);
-}
-
 using namespace shg;
 
 extern "C" int shg_dgemm(int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc, void* stream_) {
@@ -895,27 +889,21 @@ static int covprop_diag_impl(shg_plan* p, const double* cov, int nmin, int lat0,
     rc = covprop_build_cs_table(p, stream);
     if (rc) return rc;
     if (!p->pk_deg) {
-        if (hipMalloc((void**)&p->pk_deg, ((size_t)p->nlat * Pfull + 64) * sizeof(double)) != hipSuccess ||      // + padding: scalar loads run a tile ahead
-            hipMalloc((void**)&p->rslot, ((size_t)2 * Pfull + 48) * sizeof(int)) != hipSuccess)      // ranks | cos/sin row offsets + 48 entries of padding
+        if (p->pk_deg.assign((size_t)p->nlat * Pfull + 64) != hipSuccess ||      // + padding: scalar loads run a tile ahead
+            p->rslot.assign((size_t)2 * Pfull + 48) != hipSuccess) {              // ranks | cos/sin row offsets + 48 entries of padding
+            p->pk_deg.reset();                                                    // (the next call starts over)
             return fail(SHG_ERR_NOMEM, "covariance propagation tables: allocation failed");
-        SHG_HIP(hipMemsetAsync(p->rslot, 0, ((size_t)2 * Pfull + 48) * sizeof(int), stream));
-        SHG_HIP(hipMemsetAsync(p->pk_deg + (size_t)p->nlat * Pfull, 0, 64 * sizeof(double), stream));
+        }
+        SHG_HIP(hipMemsetAsync(p->rslot.get(), 0, ((size_t)2 * Pfull + 48) * sizeof(int), stream));
+        SHG_HIP(hipMemsetAsync(p->pk_deg.get() + (size_t)p->nlat * Pfull, 0, 64 * sizeof(double), stream));
         hipLaunchKernelGGL(covprop_pkd_kernel, dim3((unsigned)ceil_div64((long long)p->nlat * Pfull, 256)), dim3(256), 0, stream, p->N,
-                           p->nlat, p->ldlat, p->nlon, p->pk, p->pk_deg, p->rslot, reinterpret_cast<unsigned*>(p->rslot + Pfull));
+                           p->nlat, p->ldlat, p->nlon, p->pk.get(), p->pk_deg.get(), p->rslot.get(), reinterpret_cast<unsigned*>(p->rslot.get() + Pfull));
         SHG_HIP(hipGetLastError());
     }
     const int ncolblocks = std::max(1, ceil_div(Pn, BN));
     const size_t need = (size_t)ncolblocks * M;
-    if (need > p->cov_partial_size) {
-        if (p->cov_partial) {
-            SHG_HIP(hipStreamSynchronize(stream));
-            (void)hipFree(p->cov_partial);
-            p->cov_partial = nullptr;
-            p->cov_partial_size = 0;                 // a failed grow must not leave the old size behind
-        }
-        if (hipMalloc((void**)&p->cov_partial, need * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "covariance propagation workspace (%zu doubles)", need);
-        p->cov_partial_size = need;
-    }
+    if (need > p->cov_partial.size() && p->cov_partial) SHG_HIP(hipStreamSynchronize(stream));
+    if (p->cov_partial.ensure(need) != hipSuccess) return fail(SHG_ERR_NOMEM, "covariance propagation workspace (%zu doubles)", need);
     if (Pn == 0) {
         SHG_HIP(hipMemsetAsync(sigma, 0, M * sizeof(double), stream));
         return SHG_OK;
@@ -924,9 +912,9 @@ static int covprop_diag_impl(shg_plan* p, const double* cov, int nmin, int lat0,
     // pads every parallel to a multiple of 128 meridians; the general kernel generates A element-wise and wastes nothing.
     const int padded = round_up(p->nlon, 128);
     if (!symmetric && (padded - p->nlon) * 25 <= p->nlon) {   // padding waste <= 4 %
-        rc = covprop_rows(p, cov, Pn, nmin * nmin, lat0, lat1, p->cov_partial, stream);
+        rc = covprop_rows(p, cov, Pn, nmin * nmin, lat0, lat1, p->cov_partial.get(), stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(covprop_reduce_kernel, dim3(ceil_div((int)M, 256)), dim3(256), 0, stream, (int)M, ncolblocks, p->cov_partial, sigma);
+        hipLaunchKernelGGL(covprop_reduce_kernel, dim3(ceil_div((int)M, 256)), dim3(256), 0, stream, (int)M, ncolblocks, p->cov_partial.get(), sigma);
         SHG_HIP(hipGetLastError());
         return SHG_OK;
     }
@@ -939,24 +927,16 @@ static int covprop_diag_impl(shg_plan* p, const double* cov, int nmin, int lat0,
     if (!symmetric && !aligned && (double)M * Pn * Pn > 1e12) {
         const int ld_pad = Pn + (Pn & 1) + ((Pn + (Pn & 1)) % 512 == 0 ? 2 : 0);        // even, not a multiple of 4 KB
         const size_t need_pad = (size_t)Pn * ld_pad;
-        if (need_pad > p->cov_pad_size) {
-            if (p->cov_pad) {
-                SHG_HIP(hipStreamSynchronize(stream));
-                (void)hipFree(p->cov_pad);
-                p->cov_pad = nullptr;
-                p->cov_pad_size = 0;
-            }
-            if (hipMalloc((void**)&p->cov_pad, need_pad * sizeof(double)) == hipSuccess) p->cov_pad_size = need_pad;
-            else (void)hipGetLastError();                                                // no room for the copy: register path
-        }
+        if (need_pad > p->cov_pad.size() && p->cov_pad) SHG_HIP(hipStreamSynchronize(stream));
+        if (p->cov_pad.ensure(need_pad) != hipSuccess) (void)hipGetLastError();         // no room for the copy: register path
         if (p->cov_pad) {
-            SHG_HIP(hipMemcpy2DAsync(p->cov_pad, (size_t)ld_pad * sizeof(double), cov, (size_t)Pn * sizeof(double), (size_t)Pn * sizeof(double), Pn,
+            SHG_HIP(hipMemcpy2DAsync(p->cov_pad.get(), (size_t)ld_pad * sizeof(double), cov, (size_t)Pn * sizeof(double), (size_t)Pn * sizeof(double), Pn,
                                      hipMemcpyDeviceToDevice, stream));
-            sigma_in = p->cov_pad;
+            sigma_in = p->cov_pad.get();
             ld_in = ld_pad;
         }
     }
-    return covprop_generic(p->pk_deg, Pfull, p->cs_slot, p->nlon, p->rslot, p->nlon, p->nlon, (long long)lat0 * p->nlon, (int)M, sigma_in, Pn,
-                           nmin * nmin, p->cov_partial, sigma, p, stream, symmetric, false, reinterpret_cast<const unsigned*>(p->rslot + Pfull), p->nlat,
+    return covprop_generic(p->pk_deg.get(), Pfull, p->cs_slot.get(), p->nlon, p->rslot.get(), p->nlon, p->nlon, (long long)lat0 * p->nlon, (int)M, sigma_in, Pn,
+                           nmin * nmin, p->cov_partial.get(), sigma, p, stream, symmetric, false, reinterpret_cast<const unsigned*>(p->rslot.get() + Pfull), p->nlat,
                            ld_in);
 }

@@ -75,26 +75,23 @@ int zero_fill(int* p, hipStream_t stream) {
 // being enqueued, so that two threads that feed the same stream cannot interleave their use of one buffer; leases nest
 // inside a thread (shg_analysis holds one while gemm_ex takes its own).  shg_scratch_release() gives the buffers back.
 namespace {
-struct ScratchBuffer {
-    void* ptr = nullptr;
-    size_t size = 0;
-};
 struct StreamScratch {
     std::recursive_mutex mtx;
     int device = 0;
     hipStream_t stream = nullptr;
-    std::map<int, ScratchBuffer> slots;
+    std::map<int, DeviceArray<char>> slots;
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t to_side = nullptr, from_side[2] = {nullptr, nullptr};
     hipEvent_t more[8] = {};
     int side_apart = 0;              // how many of the side streams run on hardware queues of their own (found by experiment)
 };
 // Keyed by (device, stream): the default stream is the null handle on every device, and a buffer allocated on one device must
-// never be handed to a kernel of another.  Entries are created once and never erased, so a pointer to one stays valid.
+// never be handed to a kernel of another.  Entries are created once and never erased, so a pointer to one stays valid; the
+// map itself is never destroyed either (its buffers would otherwise be freed at exit, after the HIP runtime may be gone).
 // Lock order: g_scratch_mutex is only ever held for the map lookup itself and never while a stream mutex is taken -- a nested
 // lease (shg_analysis -> gemm_ex) and a concurrent shg_scratch_release() can then not wait for each other in a cycle.
 std::mutex g_scratch_mutex;
-std::map<std::pair<int, hipStream_t>, std::unique_ptr<StreamScratch>> g_scratch;
+auto& g_scratch = *new std::map<std::pair<int, hipStream_t>, std::unique_ptr<StreamScratch>>;
 }  // namespace
 
 ScratchLease::ScratchLease(hipStream_t stream) {
@@ -116,20 +113,13 @@ ScratchLease::ScratchLease(hipStream_t stream) {
 ScratchLease::~ScratchLease() { static_cast<StreamScratch*>(owner_)->mtx.unlock(); }
 
 void* ScratchLease::get(int slot, size_t bytes) {
-    ScratchBuffer& e = static_cast<StreamScratch*>(owner_)->slots[slot];
-    if (e.size < bytes) {
-        if (e.ptr) (void)hipFree(e.ptr);             // waits for the device: whatever still used the old buffer is done
-        e.ptr = nullptr;
-        e.size = 0;
-        const size_t want = std::max(bytes + bytes / 4, (size_t)1 << 20);
-        if (hipMalloc(&e.ptr, want) != hipSuccess) {
-            e.ptr = nullptr;
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        e.size = want;
+    DeviceArray<char>& e = static_cast<StreamScratch*>(owner_)->slots[slot];
+    // (hipFree of the old buffer waits for the device: whatever still used it is done)
+    if (e.size() < bytes && e.assign(std::max(bytes + bytes / 4, (size_t)1 << 20)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
     }
-    return e.ptr;
+    return e.get();
 }
 
 // Side streams that really run beside the leased stream.  The runtime spreads its streams over a few hardware queues (four by
@@ -162,15 +152,16 @@ static bool queues_apart(hipStream_t a, hipStream_t b, long long* probe) {
 int ScratchLease::side(hipStream_t streams[2], hipEvent_t* to_side, hipEvent_t from_side[2]) {
     StreamScratch* e = static_cast<StreamScratch*>(owner_);
     if (!e->to_side) {
-        long long* probe = nullptr;
-        SHG_HIP(hipMalloc((void**)&probe, 2 * sizeof(long long)));
+        DeviceArray<long long> probe;
+        SHG_HIP(probe.assign(2));
         hipStream_t found[2] = {nullptr, nullptr};
         int nfound = 0;
         std::vector<hipStream_t> rejected;
         for (int attempt = 0; attempt < 12 && nfound < 2; ++attempt) {
             hipStream_t s = nullptr;
             if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) break;
-            const bool ok = queues_apart(e->stream, s, probe) && (nfound == 0 || (queues_apart(found[0], s, probe) && queues_apart(s, found[0], probe)));
+            const bool ok = queues_apart(e->stream, s, probe.get()) &&
+                            (nfound == 0 || (queues_apart(found[0], s, probe.get()) && queues_apart(s, found[0], probe.get())));
             if (ok)
                 found[nfound++] = s;
             else
@@ -178,15 +169,12 @@ int ScratchLease::side(hipStream_t streams[2], hipEvent_t* to_side, hipEvent_t f
         }
         // (fewer than two such streams: the result is the same, the streams just take turns)
         for (int i = nfound; i < 2; ++i) {
-            if (rejected.empty()) {
-                (void)hipFree(probe);
-                return fail(SHG_ERR_HIP, "side streams could not be created");
-            }
+            if (rejected.empty()) return fail(SHG_ERR_HIP, "side streams could not be created");
             found[i] = rejected.back();
             rejected.pop_back();
         }
         for (hipStream_t s : rejected) (void)hipStreamDestroy(s);
-        (void)hipFree(probe);
+        probe.reset();
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
         bool created = true;
         for (int i = 0; i < 3 && created; ++i) created = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
@@ -234,8 +222,6 @@ void stream_scratch_release() {
         std::lock_guard<std::recursive_mutex> hold(e->mtx);
         if (e->slots.empty() && !e->to_side) continue;
         (void)hipSetDevice(e->device);
-        for (auto& b : e->slots)
-            if (b.second.ptr) (void)hipFree(b.second.ptr);
         e->slots.clear();
         // the side streams of the look-ahead and every event of the entry (the caller has drained the device): the next
         // factorisation on this stream repeats the queue experiment
@@ -276,12 +262,6 @@ void recursion_tables(int N, std::vector<double>& a, std::vector<double>& b) {
             }
         }
     }
-}
-
-static int upload(double** dst, const std::vector<double>& src) {
-    SHG_HIP(hipMalloc((void**)dst, std::max<size_t>(src.size(), 1) * sizeof(double)));
-    if (!src.empty()) SHG_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice));
-    return SHG_OK;
 }
 
 // True when meridians obey lon[nlon-1-j] = -lon[j], lon[nlon/2-1-j] = -pi - lon[j], lon[nlon/2+j] = lon[j] + pi
@@ -333,18 +313,16 @@ static bool has_north_south_symmetry(int N, int nlat, const double* colat, const
 
 int plan_alloc_workspace(shg_plan* p) {
     if (p->chunk_alloc == p->chunk && p->F) return SHG_OK;
-    if (p->cpk) (void)hipFree(p->cpk);
-    if (p->F) (void)hipFree(p->F);
-    p->cpk = p->F = nullptr;
+    p->cpk.reset();
+    p->F.reset();
     const int chunk_pad = round_up(p->chunk, kEpochTile);
     const size_t ncpk = (size_t)packed_count(p->N) * 2 * chunk_pad;
     const size_t nF = (size_t)chunk_pad * p->K * p->ldlat;
-    if (hipMalloc((void**)&p->cpk, ncpk * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&p->F, nF * sizeof(double)) != hipSuccess)
+    if (p->cpk.assign(ncpk) != hipSuccess || p->F.assign(nF) != hipSuccess)
         return fail(SHG_ERR_NOMEM, "workspace allocation failed (%zu + %zu doubles)", ncpk, nF);
     // padding slots / padding epochs must hold finite numbers: they meet zero table rows in the MFMA
-    SHG_HIP(hipMemset(p->cpk, 0, ncpk * sizeof(double)));
-    SHG_HIP(hipMemset(p->F, 0, nF * sizeof(double)));
+    SHG_HIP(hipMemset(p->cpk.get(), 0, ncpk * sizeof(double)));
+    SHG_HIP(hipMemset(p->F.get(), 0, nF * sizeof(double)));
     p->chunk_alloc = p->chunk;
     return SHG_OK;
 }
@@ -515,11 +493,11 @@ extern "C" int shg_plan_create(shg_plan** out, int N, int nlat, const double* co
     }
 
     int rc = SHG_OK;
-    if ((p->fold0 && (rc = upload(&p->trig_f, trig_f))) || (rc = upload(&p->ct, ct)) || (rc = upload(&p->st, st)) || (rc = upload(&p->pmm, pmm)) ||
-        (rc = upload(&p->knT, knT)) || (rc = upload(&p->arec, a)) || (rc = upload(&p->brec, b)) ||
-        (rc = upload(&p->trig, trig)) ||
-        (rc = upload(&p->lon, std::vector<double>(lon_h, lon_h + nlon))) ||
-        (rc = upload(&p->colat, std::vector<double>(colat_h, colat_h + nlat)))) {
+    if ((p->fold0 && (rc = upload(p->trig_f, trig_f))) || (rc = upload(p->ct, ct)) || (rc = upload(p->st, st)) || (rc = upload(p->pmm, pmm)) ||
+        (rc = upload(p->knT, knT)) || (rc = upload(p->arec, a)) || (rc = upload(p->brec, b)) ||
+        (rc = upload(p->trig, trig)) ||
+        (rc = upload(p->lon, std::vector<double>(lon_h, lon_h + nlon))) ||
+        (rc = upload(p->colat, std::vector<double>(colat_h, colat_h + nlat)))) {
         shg_plan_destroy(p);
         return rc;
     }
@@ -533,19 +511,6 @@ extern "C" int shg_plan_create(shg_plan** out, int N, int nlat, const double* co
 
 extern "C" int shg_plan_destroy(shg_plan* p) {
     if (!p) return SHG_OK;
-    double* ptrs[] = {p->ct, p->st, p->pmm, p->knT, p->arec, p->brec, p->trig, p->trig_f, p->lon, p->colat,
-                      p->pk_deg, p->cs_slot, p->cpk, p->F, p->pk, p->pkf, p->pkf32, p->cpk4, p->cov_partial, p->cov_pad, p->ana_H, p->ana_Hp, p->ana_area, p->ana_trig, p->rot_trig};
-    if (p->rslot) (void)hipFree(p->rslot);
-    if (p->qoff) (void)hipFree(p->qoff);
-    if (p->badmap_d) (void)hipFree(p->badmap_d);
-    if (p->blockmap_d) (void)hipFree(p->blockmap_d);
-    if (p->sem_d) (void)hipFree(p->sem_d);
-    if (p->itemtab_d) (void)hipFree(p->itemtab_d);
-    if (p->octinfo_d) (void)hipFree(p->octinfo_d);
-    if (p->qoff32) (void)hipFree(p->qoff32);
-    if (p->badmap32_d) (void)hipFree(p->badmap32_d);
-    for (double* q : ptrs)
-        if (q) (void)hipFree(q);
     for (hipEvent_t e : p->prof_events) (void)hipEventDestroy(e);
     if (p->order_event) (void)hipEventDestroy(p->order_event);
     delete p;

@@ -7,8 +7,6 @@
 
 namespace shg {
 
-void recursion_tables(int N, std::vector<double>& a, std::vector<double>& b);   // plan.hip
-
 constexpr int kPtEpochs = 16;
 
 // dst[c][r] = src[r][c] through 32 x 32 LDS tiles (coalesced on both sides).  Used for knT[n][pt] = kn[pt][n] -- inside the
@@ -167,13 +165,6 @@ __global__ __launch_bounds__(256) void synthesis_matrix_kernel(int npts, int Pn,
     }
 }
 
-int synth_generic(const double* pkd, int ldp, const double* csr, int ldcs, const int* rslot, long long idiv, long long jmod, int M,
-                  const double* X, int K, int N, double* C, hipStream_t stream);      // gemm.hip
-
-int covprop_generic(const double* pkd, int ldp, const double* csr, int ldcs, const int* rslot, long long idiv, long long jmod,
-                    long long row0, int M, const double* cov, int Pn, int p_off, double* partial, double* sigma, shg_plan* prof,
-                    hipStream_t stream, bool symmetric, bool transposed_table, const unsigned* csoff = nullptr, int pk_rows = 0, int ldcov = 0);
-
 }  // namespace shg
 
 using namespace shg;
@@ -184,63 +175,63 @@ static int point_chunk(int npts, int Pfull) {
     return (int)std::min<long long>(std::min<long long>(npts, 65535LL * 32), by_memory);
 }
 
+// The recursion factors a | b of degree N (host-built like the plans', in the reference's expression order) in one table of ws;
+// b starts at tab + packed_count(N).  Synchronous: the host vectors go out of scope.
+static int upload_recursion_tables(Workspace& ws, int N, double*& tab, hipStream_t stream) {
+    std::vector<double> a, b;
+    recursion_tables(N, a, b);
+    if (!ws.alloc(tab, 2 * a.size())) return fail(SHG_ERR_NOMEM, "recursion table allocation failed");
+    SHG_HIP(hipMemcpyAsync(tab, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    SHG_HIP(hipMemcpyAsync(tab + a.size(), b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    SHG_HIP(hipStreamSynchronize(stream));
+    return SHG_OK;
+}
+
 extern "C" int shg_synthesis_points(int N, const double* colat, const double* lon, const double* kn, int npts, const double* anm,
                                     int B, double* values, void* stream_) {
     SHG_REQUIRE(N >= 0 && npts >= 0 && B >= 0, "shg_synthesis_points: negative size");
     if (npts == 0 || B == 0) return SHG_OK;
     SHG_REQUIRE(colat && lon && kn && anm && values, "shg_synthesis_points: NULL pointer");
     hipStream_t stream = (hipStream_t)stream_;
-    std::vector<double> a, b;
-    recursion_tables(N, a, b);                       // same host-built factors as the plans (reference expression order)
-    double* tab = nullptr;
-    if (hipMallocAsync((void**)&tab, 2 * a.size() * sizeof(double), stream) != hipSuccess) return fail(SHG_ERR_NOMEM, "shg_synthesis_points: table allocation failed");
-    SHG_HIP(hipMemcpyAsync(tab, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    SHG_HIP(hipMemcpyAsync(tab + a.size(), b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    SHG_HIP(hipStreamSynchronize(stream));           // the host vectors go out of scope
-    double* knT = nullptr;
-    if (hipMallocAsync((void**)&knT, (size_t)(N + 1) * npts * sizeof(double), stream) != hipSuccess) {
-        (void)hipFreeAsync(tab, stream);
-        return fail(SHG_ERR_NOMEM, "shg_synthesis_points: table allocation failed");
-    }
-    hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(npts, 32), ceil_div(N + 1, 32)), dim3(256), 0, stream, npts, N + 1, kn, (size_t)(N + 1), knT, (size_t)npts);
-    // Many epochs: values = Y X as one fp64 MFMA GEMM per chunk of points, with the rows of the spherical harmonic matrix
-    // Y[pt][p] = PK[p][pt] cs[rank(p)][pt] generated inside the kernel from per-point tables (MODE_SYNTH of gemm.hip): the
-    // recursion runs once per point instead of once per point and group of 16 epochs.
-    if (B >= 48) {
-        const int Pfull = (N + 1) * (N + 1);
-        const int chunk = point_chunk(npts, Pfull);
-        double *X = nullptr, *xr = nullptr, *pkT = nullptr, *csr = nullptr, *Cc = nullptr;
-        int* rslot = nullptr;
-        int rc = SHG_OK;
-        if (hipMallocAsync((void**)&xr, (size_t)B * Pfull * sizeof(double), stream) != hipSuccess ||
-            hipMallocAsync((void**)&X, (size_t)B * Pfull * sizeof(double), stream) != hipSuccess ||
-            hipMallocAsync((void**)&pkT, (size_t)chunk * Pfull * sizeof(double), stream) != hipSuccess ||
-            hipMallocAsync((void**)&csr, (size_t)(2 * N + 1) * chunk * sizeof(double), stream) != hipSuccess ||
-            hipMallocAsync((void**)&Cc, (size_t)chunk * B * sizeof(double), stream) != hipSuccess ||
-            hipMallocAsync((void**)&rslot, (size_t)Pfull * sizeof(int), stream) != hipSuccess)
-            rc = fail(SHG_ERR_NOMEM, "shg_synthesis_points: workspace allocation failed");
-        if (rc == SHG_OK) rc = shg_ravel(anm, B, N, 0, N, xr, stream);
-        if (rc == SHG_OK) {
-            hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(B, 32), ceil_div(Pfull, 32)), dim3(256), 0, stream, B, Pfull, xr, (size_t)Pfull, X, (size_t)B);
-            for (int c0 = 0; c0 < npts && rc == SHG_OK; c0 += chunk) {
-                const int nc = std::min(chunk, npts - c0);
-                hipLaunchKernelGGL(synth_point_tables_kernel, dim3(ceil_div(nc, 64)), dim3(64), 0, stream, N, nc, colat + c0, lon + c0, knT + c0,
-                                   (size_t)npts, tab, tab + a.size(), pkT, csr, rslot);
-                rc = synth_generic(pkT, nc, csr, nc, rslot, 1, (long long)1 << 40, nc, X, Pfull, B, Cc, stream);
-                if (rc) break;
-                hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(nc, 32), ceil_div(B, 32)), dim3(256), 0, stream, nc, B, Cc, (size_t)B, values + c0, (size_t)npts);
+    int rc = SHG_OK;
+    {   // (workspaces are freed in the reverse order of their scopes: the chunk buffers, knT, the recursion table)
+        Workspace tables = Workspace::plain(stream);
+        double* tab;
+        if ((rc = upload_recursion_tables(tables, N, tab, stream))) return rc;
+        Workspace kn_table = Workspace::plain(stream);
+        double* knT;
+        if (!kn_table.alloc(knT, (size_t)(N + 1) * npts)) return fail(SHG_ERR_NOMEM, "shg_synthesis_points: table allocation failed");
+        hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(npts, 32), ceil_div(N + 1, 32)), dim3(256), 0, stream, npts, N + 1, kn, (size_t)(N + 1), knT, (size_t)npts);
+        // Many epochs: values = Y X as one fp64 MFMA GEMM per chunk of points, with the rows of the spherical harmonic matrix
+        // Y[pt][p] = PK[p][pt] cs[rank(p)][pt] generated inside the kernel from per-point tables (MODE_SYNTH of gemm.hip): the
+        // recursion runs once per point instead of once per point and group of 16 epochs.
+        if (B >= 48) {
+            const int Pfull = (N + 1) * (N + 1);
+            const int chunk = point_chunk(npts, Pfull);
+            Workspace ws = Workspace::plain(stream);
+            double *X, *xr, *pkT, *csr, *Cc;
+            int* rslot;
+            if (!ws.alloc(X, (size_t)B * Pfull, xr, (size_t)B * Pfull, pkT, (size_t)chunk * Pfull, csr, (size_t)(2 * N + 1) * chunk, Cc, (size_t)chunk * B,
+                          rslot, (size_t)Pfull))
+                return fail(SHG_ERR_NOMEM, "shg_synthesis_points: workspace allocation failed");
+            rc = shg_ravel(anm, B, N, 0, N, xr, stream);
+            if (rc == SHG_OK) {
+                hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(B, 32), ceil_div(Pfull, 32)), dim3(256), 0, stream, B, Pfull, xr, (size_t)Pfull, X, (size_t)B);
+                for (int c0 = 0; c0 < npts && rc == SHG_OK; c0 += chunk) {
+                    const int nc = std::min(chunk, npts - c0);
+                    hipLaunchKernelGGL(synth_point_tables_kernel, dim3(ceil_div(nc, 64)), dim3(64), 0, stream, N, nc, colat + c0, lon + c0, knT + c0,
+                                       (size_t)npts, tab, tab + packed_count(N), pkT, csr, rslot);
+                    rc = synth_generic(pkT, nc, csr, nc, rslot, 1, (long long)1 << 40, nc, X, Pfull, B, Cc, stream);
+                    if (rc) break;
+                    hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(nc, 32), ceil_div(B, 32)), dim3(256), 0, stream, nc, B, Cc, (size_t)B, values + c0, (size_t)npts);
+                }
             }
+        } else {
+            hipLaunchKernelGGL(synthesis_points_kernel, dim3(ceil_div(npts, 64), ceil_div(B, kPtEpochs)), dim3(64), (size_t)(N + 1) * 2 * kPtEpochs * sizeof(double), stream, N, npts, B, colat, lon,
+                               knT, tab, tab + packed_count(N), anm, values);
         }
-        for (void* q : {(void*)X, (void*)xr, (void*)pkT, (void*)csr, (void*)Cc, (void*)rslot, (void*)knT, (void*)tab})
-            if (q) (void)hipFreeAsync(q, stream);
-        if (rc) return rc;
-        SHG_HIP(hipGetLastError());
-        return SHG_OK;
     }
-    hipLaunchKernelGGL(synthesis_points_kernel, dim3(ceil_div(npts, 64), ceil_div(B, kPtEpochs)), dim3(64), (size_t)(N + 1) * 2 * kPtEpochs * sizeof(double), stream, N, npts, B, colat, lon,
-                       knT, tab, tab + a.size(), anm, values);
-    (void)hipFreeAsync(knT, stream);
-    (void)hipFreeAsync(tab, stream);
+    if (rc) return rc;
     SHG_HIP(hipGetLastError());
     return SHG_OK;
 }
@@ -260,26 +251,21 @@ extern "C" int shg_covprop_points(int N, const double* colat, const double* lon,
     SHG_REQUIRE(cov != nullptr, "shg_covprop_points: NULL covariance");
     // per-point tables, Legendre table transposed (pkT[p][point]): consecutive lanes of the generated-operand kernel are
     // consecutive points (43 -> 55 TFLOP/s against the point-major table)
-    std::vector<double> a, b;
-    recursion_tables(N, a, b);
-    double *pkT = nullptr, *csr = nullptr, *partial = nullptr, *knT = nullptr, *tab = nullptr;
-    int* rslot = nullptr;
     const int ncolblocks = ceil_div(Pn, 128);
-    if (hipMallocAsync((void**)&pkT, (size_t)npts * Pfull * sizeof(double), stream) != hipSuccess ||
-        hipMallocAsync((void**)&csr, (size_t)(2 * N + 1) * npts * sizeof(double), stream) != hipSuccess ||
-        hipMallocAsync((void**)&rslot, (size_t)Pfull * sizeof(int), stream) != hipSuccess ||
-        hipMallocAsync((void**)&partial, (size_t)ncolblocks * npts * sizeof(double), stream) != hipSuccess ||
-        hipMallocAsync((void**)&knT, (size_t)(N + 1) * npts * sizeof(double), stream) != hipSuccess ||
-        hipMallocAsync((void**)&tab, 2 * a.size() * sizeof(double), stream) != hipSuccess)
-        return fail(SHG_ERR_NOMEM, "shg_covprop_points: workspace allocation failed");
-    SHG_HIP(hipMemcpyAsync(tab, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    SHG_HIP(hipMemcpyAsync(tab + a.size(), b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-    SHG_HIP(hipStreamSynchronize(stream));           // the host vectors go out of scope
-    hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(npts, 32), ceil_div(N + 1, 32)), dim3(256), 0, stream, npts, N + 1, kn, (size_t)(N + 1), knT, (size_t)npts);
-    hipLaunchKernelGGL(synth_point_tables_kernel, dim3(ceil_div(npts, 64)), dim3(64), 0, stream, N, npts, colat, lon, knT, (size_t)npts, tab,
-                       tab + a.size(), pkT, csr, rslot);
-    int rc = covprop_generic(pkT, npts, csr, npts, rslot, 1, (long long)1 << 40, 0, npts, cov, Pn, nmin * nmin, partial, sigma, nullptr, stream, false, true);
-    for (void* q : {(void*)pkT, (void*)csr, (void*)rslot, (void*)partial, (void*)knT, (void*)tab}) (void)hipFreeAsync(q, stream);
+    int rc;
+    {
+        Workspace ws = Workspace::plain(stream);
+        double *pkT, *csr, *partial, *knT, *tab;
+        int* rslot;
+        if (!ws.alloc(pkT, (size_t)npts * Pfull, csr, (size_t)(2 * N + 1) * npts, rslot, (size_t)Pfull, partial, (size_t)ncolblocks * npts,
+                      knT, (size_t)(N + 1) * npts))
+            return fail(SHG_ERR_NOMEM, "shg_covprop_points: workspace allocation failed");
+        if ((rc = upload_recursion_tables(ws, N, tab, stream))) return rc;
+        hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(npts, 32), ceil_div(N + 1, 32)), dim3(256), 0, stream, npts, N + 1, kn, (size_t)(N + 1), knT, (size_t)npts);
+        hipLaunchKernelGGL(synth_point_tables_kernel, dim3(ceil_div(npts, 64)), dim3(64), 0, stream, N, npts, colat, lon, knT, (size_t)npts, tab,
+                           tab + packed_count(N), pkT, csr, rslot);
+        rc = covprop_generic(pkT, npts, csr, npts, rslot, 1, (long long)1 << 40, 0, npts, cov, Pn, nmin * nmin, partial, sigma, nullptr, stream, false, true);
+    }
     if (rc) return rc;
     SHG_HIP(hipGetLastError());
     return SHG_OK;
@@ -294,37 +280,23 @@ extern "C" int shg_synthesis_matrix(int N, int nmin, const double* colat, const 
     if (npts == 0 || Pn == 0) return SHG_OK;
     SHG_REQUIRE(colat && lon && kn && A, "shg_synthesis_matrix: NULL pointer");
     hipStream_t stream = (hipStream_t)stream_;
-    std::vector<double> a, b;
-    recursion_tables(N, a, b);
     const int chunk = point_chunk(npts, Pfull);
-    double *pkT = nullptr, *csr = nullptr, *knT = nullptr, *tab = nullptr;
-    int* rslot = nullptr;
-    int rc = SHG_OK;
-    if (hipMallocAsync((void**)&pkT, (size_t)chunk * Pfull * sizeof(double), stream) != hipSuccess ||
-        hipMallocAsync((void**)&csr, (size_t)(2 * N + 1) * chunk * sizeof(double), stream) != hipSuccess ||
-        hipMallocAsync((void**)&rslot, (size_t)Pfull * sizeof(int), stream) != hipSuccess ||
-        hipMallocAsync((void**)&knT, (size_t)(N + 1) * npts * sizeof(double), stream) != hipSuccess ||
-        hipMallocAsync((void**)&tab, 2 * a.size() * sizeof(double), stream) != hipSuccess)
-        rc = fail(SHG_ERR_NOMEM, "shg_synthesis_matrix: workspace allocation failed");
-    if (rc == SHG_OK) {
-        hipError_t e = hipMemcpyAsync(tab, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(tab + a.size(), b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);           // the host vectors go out of scope
-        if (e != hipSuccess) rc = fail(SHG_ERR_HIP, "shg_synthesis_matrix: table upload failed: %s", hipGetErrorString(e));
-    }
-    if (rc == SHG_OK) {
+    {
+        Workspace ws = Workspace::plain(stream);
+        double *pkT, *csr, *knT, *tab;
+        int* rslot;
+        if (!ws.alloc(pkT, (size_t)chunk * Pfull, csr, (size_t)(2 * N + 1) * chunk, rslot, (size_t)Pfull, knT, (size_t)(N + 1) * npts))
+            return fail(SHG_ERR_NOMEM, "shg_synthesis_matrix: workspace allocation failed");
+        if (int rc = upload_recursion_tables(ws, N, tab, stream)) return rc;
         hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(npts, 32), ceil_div(N + 1, 32)), dim3(256), 0, stream, npts, N + 1, kn, (size_t)(N + 1), knT, (size_t)npts);
         for (int c0 = 0; c0 < npts; c0 += chunk) {
             const int nc = std::min(chunk, npts - c0);
             hipLaunchKernelGGL(synth_point_tables_kernel, dim3(ceil_div(nc, 64)), dim3(64), 0, stream, N, nc, colat + c0, lon + c0, knT + c0,
-                               (size_t)npts, tab, tab + a.size(), pkT, csr, rslot);
+                               (size_t)npts, tab, tab + packed_count(N), pkT, csr, rslot);
             hipLaunchKernelGGL(synthesis_matrix_kernel, dim3(ceil_div(Pn, 32), ceil_div(nc, 32)), dim3(256), 0, stream, nc, Pn, nmin * nmin, pkT, csr,
                                rslot, A + (size_t)c0 * Pn, (size_t)Pn);
         }
     }
-    for (void* q : {(void*)pkT, (void*)csr, (void*)rslot, (void*)knT, (void*)tab})
-        if (q) (void)hipFreeAsync(q, stream);
-    if (rc) return rc;
     SHG_HIP(hipGetLastError());
     return SHG_OK;
 }

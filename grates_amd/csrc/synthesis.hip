@@ -279,12 +279,12 @@ static int synthesis_dispatch(shg_plan* p, const double* anm, int B, double* gri
         {
             ProfileScope ps(p, 0, stream);
             hipLaunchKernelGGL(pack_coefficients_kernel, dim3(ceil_div(E, 256), nbt), dim3(256), 0, stream, N, nb, Bpad,
-                               anm + (size_t)c0 * E, p->cpk);
+                               anm + (size_t)c0 * E, p->cpk.get());
         }
         {
             ProfileScope ps(p, 1, stream);
             hipLaunchKernelGGL(legendre_stage_kernel, dim3(p->ldlat / kLatTile, N + 1, nbt), dim3(64), 0, stream, N, p->ldlat,
-                               p->K, Bpad, map, p->ct, p->pmm, p->knT, p->arec, p->brec, p->cpk, p->F);
+                               p->K, Bpad, map, p->ct.get(), p->pmm.get(), p->knT.get(), p->arec.get(), p->brec.get(), p->cpk.get(), p->F.get());
         }
         LonParams L;
         L.nlat = p->nlat;
@@ -295,8 +295,8 @@ static int synthesis_dispatch(shg_plan* p, const double* anm, int B, double* gri
         L.nrt = ceil_div(p->nlat, 16);
         L.total_rt = nb * L.nrt;
         for (int g = 0; g < 5; ++g) L.goff[g] = p->goff[g];
-        L.F = p->F;
-        L.trig = p->trig;
+        L.F = p->F.get();
+        L.trig = p->trig.get();
         L.G = grid + (size_t)c0 * p->nlat * p->nlon;
         dim3 grid_dim(ceil_div(L.total_rt, 4), ceil_div(p->ncoltiles, 4));
         ProfileScope ps(p, 2, stream);

@@ -596,17 +596,16 @@ int fused_chunk_for(const shg_plan* p) {
 int build_pk_table(shg_plan* p, hipStream_t stream) {
     if (p->pk) return SHG_OK;
     const size_t n = ((size_t)packed_count(p->N) + 4) * p->ldlat;
-    if (hipMalloc((void**)&p->pk, n * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "PK table allocation failed (%zu doubles)", n);
-    SHG_HIP(hipMemsetAsync(p->pk, 0, n * sizeof(double), stream));
-    hipLaunchKernelGGL(pk_table_kernel, dim3(p->ldlat / 64, p->N + 1), dim3(64), 0, stream, p->N, p->ldlat, p->ct, p->pmm, p->knT,
-                       p->arec, p->brec, p->pk);
+    if (p->pk.assign(n) != hipSuccess) return fail(SHG_ERR_NOMEM, "PK table allocation failed (%zu doubles)", n);
+    SHG_HIP(hipMemsetAsync(p->pk.get(), 0, n * sizeof(double), stream));
+    hipLaunchKernelGGL(pk_table_kernel, dim3(p->ldlat / 64, p->N + 1), dim3(64), 0, stream, p->N, p->ldlat, p->ct.get(), p->pmm.get(), p->knT.get(),
+                       p->arec.get(), p->brec.get(), p->pk.get());
     SHG_HIP(hipGetLastError());
     return SHG_OK;
 }
 
 // fragment-ordered table of the fused kernel (and the octet offsets both fragment-ordered tables share)
 static int build_item_table(shg_plan* p, int od, const std::vector<int>& qoff, int rotR, hipStream_t stream);
-int rot_kernel_waves();          // synthesis_rot.hip: waves per workgroup of the rotation-folded kernel
 
 // rotR != 0: the work items carry the panel slots of the rotation-folded kernel (synthesis_rot.hip) instead of those of the 4-fold one
 int build_pkf_table(shg_plan* p, bool ns, int rotR, hipStream_t stream) {
@@ -614,8 +613,7 @@ int build_pkf_table(shg_plan* p, bool ns, int rotR, hipStream_t stream) {
     if (p->pkf && p->pkf_variant == variant && p->itemtab_rot == rotR) return SHG_OK;
     if (p->pkf) {                                       // the other layout was built before (explicit path switch)
         SHG_HIP(hipDeviceSynchronize());
-        (void)hipFree(p->pkf);
-        p->pkf = nullptr;
+        p->pkf.reset();
     }
     const int N = p->N;
     const int od = ns ? 16 : 8;                         // degrees per octet
@@ -628,22 +626,22 @@ int build_pkf_table(shg_plan* p, bool ns, int rotR, hipStream_t stream) {
     }
     qoff[N + 1] = q;
     p->Qtot = q;
-    if (!p->qoff && hipMalloc((void**)&p->qoff, qoff.size() * sizeof(int)) != hipSuccess) return fail(SHG_ERR_NOMEM, "octet table allocation failed");
-    SHG_HIP(hipMemcpy(p->qoff, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (p->qoff.ensure(qoff.size()) != hipSuccess) return fail(SHG_ERR_NOMEM, "octet table allocation failed");
+    SHG_HIP(hipMemcpy(p->qoff.get(), qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice));
     const size_t n = (size_t)(nit + (ns ? p->ns_nbad : 0)) * q * 128;
-    if (hipMalloc((void**)&p->pkf, n * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "PK table allocation failed (%zu doubles)", n);
-    SHG_HIP(hipMemsetAsync(p->pkf, 0, n * sizeof(double), stream));
+    if (p->pkf.assign(n) != hipSuccess) return fail(SHG_ERR_NOMEM, "PK table allocation failed (%zu doubles)", n);
+    SHG_HIP(hipMemsetAsync(p->pkf.get(), 0, n * sizeof(double), stream));
     if (ns) {
         if (!p->badmap_d) {
-            if (hipMalloc((void**)&p->badmap_d, p->ns_badmap.size() * sizeof(int)) != hipSuccess) return fail(SHG_ERR_NOMEM, "block map allocation failed");
-            SHG_HIP(hipMemcpy(p->badmap_d, p->ns_badmap.data(), p->ns_badmap.size() * sizeof(int), hipMemcpyHostToDevice));
+            if (p->badmap_d.assign(p->ns_badmap.size()) != hipSuccess) return fail(SHG_ERR_NOMEM, "block map allocation failed");
+            SHG_HIP(hipMemcpy(p->badmap_d.get(), p->ns_badmap.data(), p->ns_badmap.size() * sizeof(int), hipMemcpyHostToDevice));
         }
         hipLaunchKernelGGL(pkf_ns_table_kernel, dim3(ceil_div(p->nlat / 2, 64), N + 1, 2), dim3(64), 0, stream, N, p->nlat, p->ldlat, p->nlat / 2, nit, q,
-                           p->qoff, p->badmap_d, p->ct, p->pmm, p->knT, p->arec, p->brec, p->pkf);
+                           p->qoff.get(), p->badmap_d.get(), p->ct.get(), p->pmm.get(), p->knT.get(), p->arec.get(), p->brec.get(), p->pkf.get());
     }
     else
-        hipLaunchKernelGGL(pkf_table_kernel, dim3(p->ldlat / 64, N + 1), dim3(64), 0, stream, N, p->ldlat, nit, q, p->qoff, p->ct, p->pmm,
-                           p->knT, p->arec, p->brec, p->pkf);
+        hipLaunchKernelGGL(pkf_table_kernel, dim3(p->ldlat / 64, N + 1), dim3(64), 0, stream, N, p->ldlat, nit, q, p->qoff.get(), p->ct.get(), p->pmm.get(),
+                           p->knT.get(), p->arec.get(), p->brec.get(), p->pkf.get());
     SHG_HIP(hipGetLastError());
     const int rc_items = build_item_table(p, od, qoff, rotR, stream);
     if (rc_items) return rc_items;
@@ -691,13 +689,9 @@ static int build_item_table(shg_plan* p, int od, const std::vector<int>& qoff, i
     std::vector<int> octinfo((size_t)qoff[N + 1], 0);
     for (int m = 0; m <= N; ++m)
         for (int o = qoff[m]; o < qoff[m + 1]; ++o) octinfo[o] = m | ((o - qoff[m]) << 8);
-    if (p->octinfo_d) {
-        SHG_HIP(hipDeviceSynchronize());
-        (void)hipFree(p->octinfo_d);
-        p->octinfo_d = nullptr;
-    }
-    if (hipMalloc((void**)&p->octinfo_d, std::max<size_t>(octinfo.size(), 1) * sizeof(int)) != hipSuccess) return fail(SHG_ERR_NOMEM, "octet table allocation failed");
-    SHG_HIP(hipMemcpy(p->octinfo_d, octinfo.data(), octinfo.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (p->octinfo_d) SHG_HIP(hipDeviceSynchronize());
+    if (p->octinfo_d.assign(std::max<size_t>(octinfo.size(), 1)) != hipSuccess) return fail(SHG_ERR_NOMEM, "octet table allocation failed");
+    SHG_HIP(hipMemcpy(p->octinfo_d.get(), octinfo.data(), octinfo.size() * sizeof(int), hipMemcpyHostToDevice));
     const int ntrip = (int)((longest + 3) / 4), nrec = 4 * ntrip + 8;
     std::vector<int> table((size_t)nw * nrec * 4, 0);
     for (int w = 0; w < nw; ++w) {
@@ -708,13 +702,9 @@ static int build_item_table(shg_plan* p, int od, const std::vector<int>& qoff, i
                 table[((size_t)w * nrec + t) * 4 + c] = src < rec[w].size() ? rec[w][src] : (c < 2 ? pad : 0);
             }
     }
-    if (p->itemtab_d) {
-        SHG_HIP(hipDeviceSynchronize());
-        (void)hipFree(p->itemtab_d);
-        p->itemtab_d = nullptr;
-    }
-    if (hipMalloc((void**)&p->itemtab_d, table.size() * sizeof(int)) != hipSuccess) return fail(SHG_ERR_NOMEM, "work item table allocation failed");
-    SHG_HIP(hipMemcpyAsync(p->itemtab_d, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    if (p->itemtab_d) SHG_HIP(hipDeviceSynchronize());
+    if (p->itemtab_d.assign(table.size()) != hipSuccess) return fail(SHG_ERR_NOMEM, "work item table allocation failed");
+    SHG_HIP(hipMemcpyAsync(p->itemtab_d.get(), table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     SHG_HIP(hipStreamSynchronize(stream));                             // the host vector goes out of scope
     p->itemtab_nrec = nrec;
     p->itemtab_rot = rotR;
@@ -749,13 +739,9 @@ int build_blockmap(shg_plan* p, int nbt, int nit, hipStream_t stream) {
         map[2 * (size_t)b + 1] = per_xcd[k][next[k] + 1];
         next[k] += 2;
     }
-    if (p->blockmap_d) {
-        SHG_HIP(hipStreamSynchronize(stream));
-        (void)hipFree(p->blockmap_d);
-        p->blockmap_d = nullptr;
-    }
-    if (hipMalloc((void**)&p->blockmap_d, map.size() * sizeof(int)) != hipSuccess) return fail(SHG_ERR_NOMEM, "block map allocation failed");
-    SHG_HIP(hipMemcpy(p->blockmap_d, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (p->blockmap_d) SHG_HIP(hipStreamSynchronize(stream));
+    if (p->blockmap_d.assign(map.size()) != hipSuccess) return fail(SHG_ERR_NOMEM, "block map allocation failed");
+    SHG_HIP(hipMemcpy(p->blockmap_d.get(), map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
     p->blockmap_nbt = nbt;
     p->blockmap_nit = nit;
     return SHG_OK;
@@ -767,36 +753,30 @@ int pack_coefficients_fused(shg_plan* p, bool ns, int rotR, const double* anm, i
     const int nbt = ceil_div(B, 4);
     const int variant = ns ? 4 : 2;
     const size_t need = (size_t)nbt * p->Qtot * (ns ? 128 : 64);
-    if (need > p->cpk4_size) {
-        if (p->cpk4) {
-            SHG_HIP(hipStreamSynchronize(stream));
-            (void)hipFree(p->cpk4);
-            p->cpk4 = nullptr;
-            p->cpk4_size = 0;
-            p->cpk4_zeroed = 0;
-        }
-        if (hipMalloc((void**)&p->cpk4, need * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "coefficient workspace allocation failed");
-        p->cpk4_size = need;
+    if (need > p->cpk4.size()) {
+        if (p->cpk4) SHG_HIP(hipStreamSynchronize(stream));
+        p->cpk4_zeroed = 0;
+        if (p->cpk4.ensure(need) != hipSuccess) return fail(SHG_ERR_NOMEM, "coefficient workspace allocation failed");
     }
     // sine slots of order 0 and the padding rows of the octets are never written by the scatter kernel and must read as
     // zero (layouts differ per variant)
     if (need > 0 && (p->cpk4_variant != variant || p->cpk4_zeroed < need)) {
-        SHG_HIP(hipMemsetAsync(p->cpk4, 0, p->cpk4_size * sizeof(double), stream));
+        SHG_HIP(hipMemsetAsync(p->cpk4.get(), 0, p->cpk4.size() * sizeof(double), stream));
         p->cpk4_variant = variant;
-        p->cpk4_zeroed = p->cpk4_size;
+        p->cpk4_zeroed = p->cpk4.size();
     }
     const int E = (p->N + 1) * (p->N + 1);
     ProfileScope ps(p, 0, stream);
     if (p->om_src) {
         if (!ns) return fail(SHG_ERR_UNSUPPORTED, "synthesis from an order-major series needs parallels symmetric about the equator (the gather repack)");
         hipLaunchKernelGGL(pack_coefficients4_ns_gather_om_kernel, dim3((unsigned)(8 * ceil_div(nbt, 8) * ceil_div(p->Qtot * 64, 256))), dim3(256), 0, stream, p->N, B,
-                           p->Qtot, rotR, nbt, p->octinfo_d, p->om_src, p->om_N, p->om_Bpad, p->cpk4);
+                           p->Qtot, rotR, nbt, p->octinfo_d.get(), p->om_src, p->om_N, p->om_Bpad, p->cpk4.get());
     } else if (ns)
         hipLaunchKernelGGL(pack_coefficients4_ns_gather_kernel, dim3((unsigned)(8 * ceil_div(nbt, 8) * ceil_div(p->Qtot * 64, 256))), dim3(256), 0, stream, p->N, B,
-                           p->Qtot, rotR, nbt, p->octinfo_d, anm, p->cpk4);
+                           p->Qtot, rotR, nbt, p->octinfo_d.get(), anm, p->cpk4.get());
     else
-        hipLaunchKernelGGL(pack_coefficients4_kernel, dim3(ceil_div(E, 256), nbt), dim3(256), 0, stream, p->N, B, p->Qtot, rotR, p->qoff, anm,
-                           p->cpk4);
+        hipLaunchKernelGGL(pack_coefficients4_kernel, dim3(ceil_div(E, 256), nbt), dim3(256), 0, stream, p->N, B, p->Qtot, rotR, p->qoff.get(), anm,
+                           p->cpk4.get());
     SHG_HIP(hipGetLastError());
     return SHG_OK;
 }
@@ -833,20 +813,20 @@ int synthesis_fused(shg_plan* p, const double* anm, int B, double* grid, hipStre
     P.dbg = experiment_switches();
 #endif
     P.Qtot = p->Qtot;
-    P.qoff = p->qoff;
-    P.cpk4 = p->cpk4;
-    P.pkf = p->pkf;
-    P.badmap = p->badmap_d;
-    P.itemtab = reinterpret_cast<const int4*>(p->itemtab_d);
+    P.qoff = p->qoff.get();
+    P.cpk4 = p->cpk4.get();
+    P.pkf = p->pkf.get();
+    P.badmap = p->badmap_d.get();
+    P.itemtab = reinterpret_cast<const int4*>(p->itemtab_d.get());
     P.nrec = p->itemtab_nrec;
     P.ntrip = p->itemtab_ntrip;
     P.blockmap = nullptr;
     if (!SHG_DBG(P, 2048)) {                             // SHG_DEBUG bit 11: plain block order (experiment switch)
         rc = build_blockmap(p, nbt, nit, stream);
         if (rc) return rc;
-        P.blockmap = p->blockmap_d;
+        P.blockmap = p->blockmap_d.get();
     }
-    P.trig = fold ? p->trig_f : p->trig;
+    P.trig = fold ? p->trig_f.get() : p->trig.get();
     P.G = grid;
 #ifdef SHG_TIMELINE
     P.tl = getenv("SHG_TIMELINE_PTR") ? (unsigned long long*)strtoull(getenv("SHG_TIMELINE_PTR"), nullptr, 0) : nullptr;

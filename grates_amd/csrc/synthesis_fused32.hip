@@ -352,17 +352,17 @@ int build_pkf32_table(shg_plan* p, hipStream_t stream) {
     int nbad = 0;
     for (int i = 0; i < nh; ++i)
         if (p->ns_badrow[i] && badmap[i >> 2] < 0) badmap[i >> 2] = nbad++;
-    if (hipMalloc((void**)&p->qoff32, qoff.size() * sizeof(int)) != hipSuccess || hipMalloc((void**)&p->badmap32_d, badmap.size() * sizeof(int)) != hipSuccess)
+    if (p->qoff32.assign(qoff.size()) != hipSuccess || p->badmap32_d.assign(badmap.size()) != hipSuccess)
         return fail(SHG_ERR_NOMEM, "octet / block map allocation failed");
-    SHG_HIP(hipMemcpy(p->qoff32, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice));
-    SHG_HIP(hipMemcpy(p->badmap32_d, badmap.data(), badmap.size() * sizeof(int), hipMemcpyHostToDevice));
+    SHG_HIP(hipMemcpy(p->qoff32.get(), qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice));
+    SHG_HIP(hipMemcpy(p->badmap32_d.get(), badmap.data(), badmap.size() * sizeof(int), hipMemcpyHostToDevice));
     p->Qtot32 = q;
     p->nbad32 = nbad;
     const size_t n = (size_t)(nit + nbad) * q * 128;
-    if (hipMalloc((void**)&p->pkf32, n * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "PK table allocation failed (%zu doubles)", n);
-    SHG_HIP(hipMemsetAsync(p->pkf32, 0, n * sizeof(double), stream));
-    hipLaunchKernelGGL(pkf32_table_kernel, dim3(ceil_div(nh, 64), N + 1, 2), dim3(64), 0, stream, N, p->nlat, p->ldlat, nh, nit, q, p->qoff32, p->badmap32_d,
-                       p->ct, p->pmm, p->knT, p->arec, p->brec, p->pkf32);
+    if (p->pkf32.assign(n) != hipSuccess) return fail(SHG_ERR_NOMEM, "PK table allocation failed (%zu doubles)", n);
+    SHG_HIP(hipMemsetAsync(p->pkf32.get(), 0, n * sizeof(double), stream));
+    hipLaunchKernelGGL(pkf32_table_kernel, dim3(ceil_div(nh, 64), N + 1, 2), dim3(64), 0, stream, N, p->nlat, p->ldlat, nh, nit, q, p->qoff32.get(), p->badmap32_d.get(),
+                       p->ct.get(), p->pmm.get(), p->knT.get(), p->arec.get(), p->brec.get(), p->pkf32.get());
     SHG_HIP(hipGetLastError());
     return SHG_OK;
 }
@@ -375,21 +375,15 @@ int synthesis_fused32(shg_plan* p, const double* anm, int B, double* grid, hipSt
     const int N = p->N;
     const int nh = p->nlat / 2, nit = ceil_div(nh, 4);
     const size_t need = (size_t)nbt * p->Qtot32 * 128;
-    if (need > p->cpk4_size) {
-        if (p->cpk4) {
-            SHG_HIP(hipStreamSynchronize(stream));
-            (void)hipFree(p->cpk4);
-            p->cpk4 = nullptr;
-            p->cpk4_size = 0;                        // a failed grow must not leave the old size behind
-            p->cpk4_zeroed = 0;
-        }
-        if (hipMalloc((void**)&p->cpk4, need * sizeof(double)) != hipSuccess) return fail(SHG_ERR_NOMEM, "coefficient workspace allocation failed");
-        p->cpk4_size = need;
+    if (need > p->cpk4.size()) {
+        if (p->cpk4) SHG_HIP(hipStreamSynchronize(stream));
+        p->cpk4_zeroed = 0;
+        if (p->cpk4.ensure(need) != hipSuccess) return fail(SHG_ERR_NOMEM, "coefficient workspace allocation failed");
     }
     if (need > 0 && (p->cpk4_variant != 4 || p->cpk4_zeroed < need)) {      // same coefficient layout as the NS variant of synthesis_fused.hip
-        SHG_HIP(hipMemsetAsync(p->cpk4, 0, p->cpk4_size * sizeof(double), stream));
+        SHG_HIP(hipMemsetAsync(p->cpk4.get(), 0, p->cpk4.size() * sizeof(double), stream));
         p->cpk4_variant = 4;
-        p->cpk4_zeroed = p->cpk4_size;
+        p->cpk4_zeroed = p->cpk4.size();
     }
     Fused32Params P;
     P.N = N;
@@ -408,16 +402,16 @@ int synthesis_fused32(shg_plan* p, const double* anm, int B, double* grid, hipSt
 #ifdef SHG_EXPERIMENT
     P.dbg = experiment_switches();
 #endif
-    P.qoff = p->qoff32;
-    P.badmap = p->badmap32_d;
-    P.cpk4 = p->cpk4;
-    P.pkf = p->pkf32;
-    P.trig = p->trig;
+    P.qoff = p->qoff32.get();
+    P.badmap = p->badmap32_d.get();
+    P.cpk4 = p->cpk4.get();
+    P.pkf = p->pkf32.get();
+    P.trig = p->trig.get();
     P.G = grid;
     const int E = (N + 1) * (N + 1);
     {
         ProfileScope ps(p, 0, stream);
-        hipLaunchKernelGGL(pack_coefficients4_ns_kernel, dim3(ceil_div(E, 256), nbt), dim3(256), 0, stream, N, B, p->Qtot32, p->qoff32, anm, p->cpk4);
+        hipLaunchKernelGGL(pack_coefficients4_ns_kernel, dim3(ceil_div(E, 256), nbt), dim3(256), 0, stream, N, B, p->Qtot32, p->qoff32.get(), anm, p->cpk4.get());
     }
     const size_t lds = fused32_lds_bytes(p->K);
     ProfileScope ps(p, 2, stream);

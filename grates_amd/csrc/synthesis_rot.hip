@@ -853,10 +853,6 @@ int rot_choose(int nlon, const double* lon_h, int N) {
 
 // trig stream [nct][npieces][64][2] (+ one spare piece), built on the host like the other cos/sin tables (grates/utilities.py:272-273)
 int build_rot_trig(shg_plan* p, const double* lon_h) {
-    if (p->rot_trig) {
-        (void)hipFree(p->rot_trig);
-        p->rot_trig = nullptr;
-    }
     const int R = p->rotR, N = p->N, nlon = p->nlon, nd = nlon / (2 * R), nct = ceil_div(nd, 16);
     int nk[kMaxClasses], cnt[kMaxClasses];
     std::vector<int> order_slot;
@@ -877,9 +873,7 @@ int build_rot_trig(shg_plan* p, const double* lon_h) {
                 dst[0] = std::cos(arg);
                 dst[1] = sg * std::sin(arg);
             }
-    SHG_HIP(hipMalloc((void**)&p->rot_trig, tab.size() * sizeof(double)));
-    SHG_HIP(hipMemcpy(p->rot_trig, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-    return SHG_OK;
+    return upload(p->rot_trig, tab);
 }
 
 template <int R>
@@ -921,24 +915,24 @@ int synthesis_rot(shg_plan* p, const double* anm, int B, double* grid, hipStream
     P.stagger2 = getenv("SHG_STAGGER2") ? atoi(getenv("SHG_STAGGER2")) : 0;
 #endif
     P.Qtot = p->Qtot;
-    P.cpk4 = p->cpk4;
-    P.pkf = p->pkf;
-    P.itemtab = reinterpret_cast<const int4*>(p->itemtab_d);
+    P.cpk4 = p->cpk4.get();
+    P.pkf = p->pkf.get();
+    P.itemtab = reinterpret_cast<const int4*>(p->itemtab_d.get());
     P.nrec = p->itemtab_nrec;
     P.ntrip = p->itemtab_ntrip;
-    P.sem = p->sem_d;                         // allocated and zeroed by rot_set_stage_limit; 0 again whenever a grid has drained
+    P.sem = p->sem_d.get();                         // allocated and zeroed by rot_set_stage_limit; 0 again whenever a grid has drained
     P.sem_limit = p->sem_d ? p->stage_limit : 0;
 #ifdef SHG_EXPERIMENT
     if (getenv("SHG_SEM") && p->sem_d) P.sem_limit = atoi(getenv("SHG_SEM"));
 #endif
-    P.badmap = p->badmap_d;
+    P.badmap = p->badmap_d.get();
     P.blockmap = nullptr;
     if (!SHG_DBG(P, 2048)) {
         rc = build_blockmap(p, nbt, nit, stream);
         if (rc) return rc;
-        P.blockmap = p->blockmap_d;
+        P.blockmap = p->blockmap_d.get();
     }
-    P.trig = p->rot_trig;
+    P.trig = p->rot_trig.get();
     P.G = grid;
 #ifdef SHG_TIMELINE
     P.tl = getenv("SHG_TIMELINE_PTR") ? (unsigned long long*)strtoull(getenv("SHG_TIMELINE_PTR"), nullptr, 0) : nullptr;
@@ -970,8 +964,8 @@ int rot_set_stage_limit(shg_plan* p, int limit) {
         limit = std::max(1, cus * -limit / 16);
     }
     if (limit > 0 && !p->sem_d) {
-        if (hipMalloc((void**)&p->sem_d, 256) != hipSuccess) return fail(SHG_ERR_NOMEM, "token counter allocation failed");
-        SHG_HIP(hipMemset(p->sem_d, 0, 256));
+        if (p->sem_d.assign(64) != hipSuccess) return fail(SHG_ERR_NOMEM, "token counter allocation failed");
+        SHG_HIP(hipMemset(p->sem_d.get(), 0, 256));
         SHG_HIP(hipDeviceSynchronize());
     }
     p->stage_limit = limit;

@@ -225,14 +225,13 @@ extern "C" int shg_synthesis_matrix_order(int N, int m, int nmin, const double* 
     SHG_REQUIRE(colat && kn && out_cos && (m == 0 || (lon && out_sin)), "shg_synthesis_matrix_order: NULL pointer");
     SHG_REQUIRE(rows * cnt < (1LL << 31) * 256, "shg_synthesis_matrix_order: problem too large");
     hipStream_t stream = (hipStream_t)stream_;
-    double* pm = nullptr;
-    if (workspace_alloc((void**)&pm, (size_t)nlat * (N + 1 - m) * sizeof(double), stream) != hipSuccess)
-        return fail(SHG_ERR_NOMEM, "shg_synthesis_matrix_order: workspace allocation failed");
+    Workspace ws = Workspace::pooled(stream);
+    double* pm;
+    if (!ws.alloc(pm, (size_t)nlat * (N + 1 - m))) return fail(SHG_ERR_NOMEM, "shg_synthesis_matrix_order: workspace allocation failed");
     hipLaunchKernelGGL(legendre_order_kernel, dim3(ceil_div(nlat, 64)), dim3(64), 0, stream, N, m, nlat, colat, pm);
     hipLaunchKernelGGL(order_block_kernel, dim3((unsigned)ceil_div64(rows * cnt, 256)), dim3(256), 0, stream, N, m, c0, cnt, nlat, nlon, pointwise,
                        pm, kn, lon, out_cos, out_sin);
     const hipError_t e = hipGetLastError();
-    (void)hipFreeAsync(pm, stream);
     if (e != hipSuccess) return fail(SHG_ERR_HIP, "shg_synthesis_matrix_order: launch failed: %s", hipGetErrorString(e));
     return SHG_OK;
 }

@@ -128,3 +128,39 @@ def test_block_calls_reject_null_inverse_table():
     for name, tail in (('shg_block_solve', (0, None, 1, 1, None)), ('shg_block_sparse_inverse', (None,)), ('shg_block_inverse', (None,))):
         status = getattr(lib, name)(1, as_p(bounds), as_p(rowptr), as_p(colidx), as_p(blocks), None, *tail)
         assert status == -1 and b'inverses' in lib.shg_last_error(), name
+
+
+# The only code that allocates or frees device memory by hand: the owner types of common.h and workspace_alloc's pool set-up.
+DEVICE_MEMORY_OWNERS = {'common.h': ('class DeviceArray', 'class Workspace'), 'plan.hip': ('hipError_t workspace_alloc(',)}
+
+
+def strip_c_comments(text):
+    text = re.sub(r'/\*.*?\*/', lambda m: '\n' * m.group(0).count('\n'), text, flags=re.S)
+    return re.sub(r'//[^\n]*', '', text)
+
+
+def braced_span(text, start):
+    """[start, end) of the declaration at `start` up to the brace that closes its body."""
+    depth = 0
+    for i in range(text.index('{', start), len(text)):
+        depth += {'{': 1, '}': -1}.get(text[i], 0)
+        if depth == 0:
+            return start, i + 1
+    raise AssertionError('unbalanced braces after ' + text[start:start + 40])
+
+
+def test_device_memory_only_through_owner_types():
+    """Every hipMalloc / hipMallocAsync / hipFree / hipFreeAsync of libshg sits inside DeviceArray or Workspace (or the one
+    workspace_alloc): buffers are freed by their owner on every return path."""
+    csrc = os.path.join(ROOT, 'grates_amd', 'csrc')
+    seen = 0
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith(('.hip', '.h', '.cpp')):
+            continue
+        text = strip_c_comments(open(os.path.join(csrc, fn)).read())
+        spans = [braced_span(text, text.index(owner)) for owner in DEVICE_MEMORY_OWNERS.get(fn, ())]
+        for m in re.finditer(r'\b(hipMalloc|hipMallocAsync|hipFree|hipFreeAsync)\s*\(', text):
+            line = text.count('\n', 0, m.start()) + 1
+            assert any(a <= m.start() < b for a, b in spans), '{0}:{1}: {2} outside the owner types of common.h'.format(fn, line, m.group(1))
+            seen += 1
+    assert seen >= 5
