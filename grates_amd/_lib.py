@@ -90,6 +90,8 @@ PROTOTYPES = {
     'shg_winding_number': [ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p],
     'shg_mask_pack': [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p],
     'shg_basin_statistics': [c_double_p, ctypes.c_int, ctypes.c_longlong, c_double_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
+    'shg_basin_functionals': [c_plan_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
+    'shg_basin_covariance': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
 }
 STRING_GETTERS = ('shg_last_error', 'shg_version')
 

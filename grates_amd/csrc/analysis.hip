@@ -846,7 +846,8 @@ static int folded_transform(shg_plan* p, const double* grid, const double* area,
 }
 
 // The fused transform kernel for `nb` epochs starting at `values` -> gt [S][nb][nlat] (degrees up to 126, four-fold meridian symmetry)
-static int launch_fused_transform(shg_plan* p, const double* values, const double* area, int nb, double* gt, hipStream_t stream) {
+// rowconst: the weights are constant along every parallel (read once per row)
+static int launch_fused_transform(shg_plan* p, const double* values, const double* area, int nb, bool rowconst, double* gt, hipStream_t stream) {
     const int N = p->N, nlat = p->nlat, nlon = p->nlon;
     const unsigned blocks = (unsigned)ceil_div64((long long)nb * nlat, kAtRows);
     const int mt = N <= 64 ? 2 : (N <= 96 ? 3 : 4);           // (N + 1) / 2 orders per group at most: 32 | 48 | 64
@@ -854,13 +855,35 @@ static int launch_fused_transform(shg_plan* p, const double* values, const doubl
     if (rc) return rc;
 #define SHG_ANA_LAUNCH(MT_, RW_)                                                                                                       \
     hipLaunchKernelGGL((analysis_transform_kernel<MT_, RW_>), dim3(blocks), dim3(256), 0, stream, nb, nlat, nlon, N, values, area, p->ana_trig.get(), gt)
-    if (p->ana_rowconst) {
+    if (rowconst) {
         if (mt == 2) SHG_ANA_LAUNCH(2, true); else if (mt == 3) SHG_ANA_LAUNCH(3, true); else SHG_ANA_LAUNCH(4, true);
     } else {
         if (mt == 2) SHG_ANA_LAUNCH(2, false); else if (mt == 3) SHG_ANA_LAUNCH(3, false); else SHG_ANA_LAUNCH(4, false);
     }
 #undef SHG_ANA_LAUNCH
     return SHG_OK;
+}
+
+// gt [S][nb][nlat] = sum_j area[i][j] T_s(lon_j) values[b][i][j] for `nb` grids: the fused kernel (degrees up to 126) or fold + GEMMs on
+// grids with the four-fold meridian symmetry (`folded`), weight transpose + one GEMM otherwise (wvt [nlon][nb * nlat] unless fused)
+static int longitude_transform(shg_plan* p, const double* values, const double* area, int nb, bool folded, bool rowconst, double* wvt, double* gt,
+                               hipStream_t stream) {
+    const int N = p->N, S = 2 * N + 1, nlat = p->nlat, nlon = p->nlon;
+    const long long rows = (long long)nb * nlat;
+    if (folded) {
+        // slots in gt: 0 = order 0, 2m-1 = cos m, 2m = sin m.  Per parity and cos | sin the slots are 4 apart, so each
+        // group is a GEMM on strided rows of the trig table (columns nlon/2 ... of cs_slot = the quarter domain) whose
+        // output rows land in slot order; the two groups of a parity differ by one slot and form one batched call.
+        if (N <= 126) {
+            ProfileScope ps(p, 4, stream);
+            return launch_fused_transform(p, values, area, nb, rowconst, gt, stream);
+        }
+        return folded_transform(p, values, area, nb, wvt, gt, stream);
+    }
+    hipLaunchKernelGGL(weight_transpose_kernel, dim3(ceil_div(nlon, 32), (unsigned)ceil_div64(rows, 32)), dim3(256), 0, stream, nb, nlat, nlon,
+                       values, area, wvt);
+    ProfileScope ps(p, 4, stream);
+    return shg_dgemm(S, (int)rows, nlon, p->cs_slot.get(), nlon, wvt, (int)rows, gt, (int)rows, stream);
 }
 
 // one pass over all epochs with the operator in p->ana_H (workspaces sized for `chunk` epochs)
@@ -875,23 +898,7 @@ static int analysis_pass(shg_plan* p, const double* grid, const double* area, in
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = std::min(chunk, B - b0);
         const long long rows = (long long)nb * nlat;
-        int rc;
-        if (folded) {
-            // slots in gt: 0 = order 0, 2m-1 = cos m, 2m = sin m.  Per parity and cos | sin the slots are 4 apart, so each
-            // group is a GEMM on strided rows of the trig table (columns nlon/2 ... of cs_slot = the quarter domain) whose
-            // output rows land in slot order; the two groups of a parity differ by one slot and form one batched call.
-            if (N <= 126) {
-                ProfileScope ps(p, 4, stream);
-                rc = launch_fused_transform(p, grid + (size_t)b0 * nlat * nlon, area, nb, gt, stream);
-            } else {
-                rc = folded_transform(p, grid + (size_t)b0 * nlat * nlon, area, nb, wvt, gt, stream);
-            }
-        } else {
-            hipLaunchKernelGGL(weight_transpose_kernel, dim3(ceil_div(nlon, 32), (unsigned)ceil_div64(rows, 32)), dim3(256), 0, stream, nb,
-                               nlat, nlon, grid + (size_t)b0 * nlat * nlon, area, wvt);
-            ProfileScope ps(p, 4, stream);
-            rc = shg_dgemm(S, (int)rows, nlon, p->cs_slot.get(), nlon, wvt, (int)rows, gt, (int)rows, stream);
-        }
+        int rc = longitude_transform(p, grid + (size_t)b0 * nlat * nlon, area, nb, folded, p->ana_rowconst, wvt, gt, stream);
         if (rc) return rc;
         ProfileScope ps(p, 5, stream);
         if (p->ana_parity && SHG_ANA_PARITY) {
@@ -957,4 +964,105 @@ extern "C" int shg_analysis(shg_plan* p, const double* grid, const double* area,
         }
     }
     return rc;
+}
+
+// ---- Basin functionals.  The area-weighted mean over mask b of the synthesised grid is a linear functional of the
+// coefficients,
+//   F_b[(n, m, cs)] = sum_i PK_m[n][i] g_{b,s}[i] / S_b,   g_{b,s}[i] = sum_j area[i][j] m_b[i][j] T_s(lon_j),   S_b = sum_i g_{b,0}[i],
+// so it needs the analysis' longitude transform of the masks (expanded from their bits into 0 / 1 grids) and one product per slot with
+// the plain operator PK_m = kn P_nm -- no least-squares inverse.
+namespace shg {
+
+// values[b][p] = bit b of bits[p] (0 / 1) for the B masks
+__global__ __launch_bounds__(256) void mask_expand_kernel(long long P, int B, const unsigned long long* __restrict__ bits, double* __restrict__ values) {
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long long)gridDim.x * 256) {
+        const unsigned long long w = bits[p];
+        for (int b = 0; b < B; ++b) values[(size_t)b * P + p] = (double)((w >> b) & 1ull);
+    }
+}
+
+// sums[b] = S_b = sum of the order-0 slot gt[0][b][i] over the parallels, in ascending order
+__global__ __launch_bounds__(64) void functional_sums_kernel(int B, int nlat, const double* __restrict__ gt, double* __restrict__ sums) {
+    const int b = threadIdx.x;
+    if (b >= B) return;
+    double acc = 0.0;
+    for (int i = 0; i < nlat; ++i) acc += gt[(size_t)b * nlat + i];
+    sums[b] = acc;
+}
+
+// F[b][col(n, m, cs)] = sum_i PK[(m, n)][i] gt[s][b][i] / S_b for the rows a0 .. a0 + 31 of slot s (degrees n = max(m, nmin) + a).
+// Thread (a, b-group): 8 masks b = tid / 32 + 8 k; chunks of 32 parallels through LDS; the sums over i run in ascending order.
+constexpr int kFnKC = 32, kFnRows = 32;
+__global__ __launch_bounds__(256) void functional_product_kernel(int N, int nmin, int nlat, int ldlat, int B, const double* __restrict__ pk,
+                                                                 const double* __restrict__ gt, const double* __restrict__ sums, double* __restrict__ F) {
+    __shared__ double PL[kFnRows][kFnKC + 1];
+    __shared__ double GL[64][kFnKC + 1];
+    const int s = blockIdx.y, a0 = blockIdx.x * kFnRows;
+    const int m = (s + 1) >> 1;
+    const bool sine = s > 0 && (s & 1) == 0;
+    const int n0 = max(m, nmin), d = N + 1 - n0;
+    if (a0 >= d) return;
+    const int tid = threadIdx.x, la = tid & (kFnRows - 1), bg = tid / kFnRows;
+    const long long rows = (long long)B * nlat;
+    double acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.0;
+    const double* pkrow = pk + (size_t)(order_offset(N, m) + n0 - m) * ldlat;
+    const double* gslot = gt + (size_t)s * rows;
+    for (int i0 = 0; i0 < nlat; i0 += kFnKC) {
+        __syncthreads();
+        for (int e = tid; e < kFnRows * kFnKC; e += 256) {
+            const int r = e / kFnKC, c = e % kFnKC, i = i0 + c;
+            PL[r][c] = (a0 + r < d && i < nlat) ? pkrow[(size_t)(a0 + r) * ldlat + i] : 0.0;
+        }
+        for (int e = tid; e < B * kFnKC; e += 256) {
+            const int r = e / kFnKC, c = e % kFnKC, i = i0 + c;
+            GL[r][c] = i < nlat ? gslot[(size_t)r * nlat + i] : 0.0;
+        }
+        __syncthreads();
+        for (int c = 0; c < kFnKC; ++c) {
+            const double p = PL[la][c];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[k] = fma(p, GL[bg + 8 * k][c], acc[k]);
+        }
+    }
+    const int a = a0 + la;
+    if (a >= d) return;
+    const int n = n0 + a;
+    const size_t P = (size_t)(N + 1) * (N + 1) - (size_t)nmin * nmin;
+    const size_t col = (size_t)n * n - (size_t)nmin * nmin + (m == 0 ? 0 : 2 * m - 1 + (sine ? 1 : 0));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int b = bg + 8 * k;
+        if (b < B) F[(size_t)b * P + col] = acc[k] / sums[b];
+    }
+}
+
+}  // namespace shg
+
+extern "C" int shg_basin_functionals(shg_plan* p, const unsigned long long* bits, int B, const double* area, int nmin, double* F, void* stream_) {
+    SHG_REQUIRE(B >= 1 && B <= 64, "shg_basin_functionals: %d masks, 1 to 64 are supported", B);
+    SHG_REQUIRE(p != nullptr && bits != nullptr && area != nullptr && F != nullptr, "shg_basin_functionals: NULL pointer");
+    SHG_REQUIRE(nmin >= 0 && nmin <= p->N, "shg_basin_functionals: min_degree %d out of range", nmin);
+    hipStream_t stream = (hipStream_t)stream_;
+    PlanGuard guard(p, stream);
+    int rc = analysis_tables(p, stream);
+    if (rc) return rc;
+    const int N = p->N, S = 2 * N + 1, nlat = p->nlat, nlon = p->nlon;
+    const long long P = (long long)nlat * nlon, rows = (long long)B * nlat;
+    const bool folded = p->sym4 && 4LL * rows < (1LL << 29);
+    const bool fused = folded && N <= 126;
+    Workspace ws = Workspace::pooled(stream);
+    double *values, *gt, *sums, *wvt = nullptr;
+    if (!ws.alloc(values, (size_t)B * P, gt, (size_t)S * rows, sums, 64) || (!fused && !ws.alloc(wvt, (size_t)nlon * rows)))
+        return fail(SHG_ERR_NOMEM, "shg_basin_functionals: workspace allocation failed");
+    hipLaunchKernelGGL(mask_expand_kernel, dim3((unsigned)std::min<long long>(ceil_div64(P, 256), 8192)), dim3(256), 0, stream, P, B, bits, values);
+    // the weights are streamed with the values: the transform does not rely on p->ana_rowconst, which belongs to the analysis' weights
+    rc = longitude_transform(p, values, area, B, folded, false, wvt, gt, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(functional_sums_kernel, dim3(1), dim3(64), 0, stream, B, nlat, (const double*)gt, sums);
+    hipLaunchKernelGGL(functional_product_kernel, dim3(ceil_div(N + 1, kFnRows), S), dim3(256), 0, stream, N, nmin, nlat, p->ldlat, B, p->pk.get(), gt,
+                       (const double*)sums, F);
+    SHG_HIP(hipGetLastError());
+    return SHG_OK;
 }

@@ -675,6 +675,32 @@ def basin_statistics(values, weights, bits, count):
     return out
 
 
+def basin_functionals(plan, bits, count, area, min_degree):
+    """F [count, (N+1)^2 - min_degree^2] (device): the area-weighted mean over each of the `count` masks whose bits pack_masks gave, of
+    the plan's synthesis, as row vectors on the degree-wise coefficients (shg_basin_functionals); `area` [nlat, nlon]."""
+    torch = require_gpu()
+    a = to_device(area, plan.device).reshape(plan.nlat, plan.nlon)
+    P = (plan.max_degree + 1) ** 2 - min_degree ** 2
+    out = torch.empty((count, P), dtype=torch.float64, device=plan.device)
+    with torch.cuda.device(plan.device):
+        _lib.call('shg_basin_functionals', plan._handle, _ptr(bits), int(count), _ptr(a), int(min_degree), _ptr(out), _stream())
+    return out
+
+
+def basin_covariance(F, S):
+    """F S F^T [B, B] (device) for F [B, n], B <= 64, from the upper triangle of S [n, n] only (shg_basin_covariance): exactly
+    symmetric, bitwise reproducible."""
+    torch = require_gpu()
+    F = F if isinstance(F, torch.Tensor) and F.is_cuda and F.dtype == torch.float64 and F.is_contiguous() else to_device(F)
+    S = S if isinstance(S, torch.Tensor) and S.is_cuda and S.dtype == torch.float64 and S.is_contiguous() else to_device(S)
+    if F.dim() != 2 or S.dim() != 2 or S.shape[0] != S.shape[1] or F.shape[1] != S.shape[0]:
+        raise ValueError('basin_covariance: F [B, n] and a square S [n, n] expected, got {0} and {1}'.format(tuple(F.shape), tuple(S.shape)))
+    B, n = F.shape
+    out = torch.empty((B, B), dtype=torch.float64, device=F.device)
+    _lib.call('shg_basin_covariance', int(B), int(n), _ptr(F), max(int(n), 1), _ptr(S), max(int(n), 1), _ptr(out), _stream())
+    return out
+
+
 class OrderMajorSeries:
     """A time series of coefficient sets that stays on the device between operators (the batching of TimeSeries.to_array,
     grates/gravityfield.py:964-980, in the layout the order-wise operators work on): `data` [(N+1)^2, Bpad] with the epochs fastest

@@ -344,6 +344,16 @@ int shg_congruence(int n, int k, const double* W, int ldw, const double* S, int 
  *                       (Grid.mean / rms / std, grates/grid.py:174-260); w [P] weights, bits [P] from shg_mask_pack,
  *                       1 <= B <= 64.  std is the two-pass sum w (v - mean)^2; an empty mask gives NaN.  Sums over fixed
  *                       tiles, reduced in a fixed order: bitwise reproducible.
+ *   shg_basin_functionals  F [B][Pn] (Pn = (N+1)^2 - nmin^2, degree-wise columns as shg_ravel orders them) with F[b] . x = the
+ *                       mean over mask b, weighted by area [nlat][nlon], of the plan's synthesis of the degree-wise vector x
+ *                       (degrees nmin .. N, kernel factors of the plan): sum_i kn[i][n] P_nm(theta_i) g_{b,s}[i] / S_b with the
+ *                       longitude transform g of shg_analysis applied to the masks and S_b = sum of area over mask b.  bits [nlat * nlon]
+ *                       from shg_mask_pack, 1 <= B <= 64; an empty mask gives a row of NaN.  Bitwise reproducible; the plan's
+ *                       analysis operators are not touched.
+ *   shg_basin_covariance  C [B][B] (row-major, ld B) = F S F^T for F [B][n] (ld ldf) and a symmetric S [n][n] (ld lds) of which
+ *                       ONLY THE UPPER TRIANGLE is read (LAPACK 'U'; nothing below the diagonal is loaded).  1 <= B <= 64,
+ *                       ldf, lds >= n.  fp64 MFMA, partial sums reduced in a fixed order: C is exactly symmetric and repeated
+ *                       calls are bitwise equal.
  * ------------------------------------------------------------------------------------------------ */
 int shg_basin_pip(int nlat, const double* lat_tab, int nlon, const double* lon_tab, const double* xyz, long long npts, const double* frame_h,
                   int nedges, const double* edges, int first, unsigned long long* work, unsigned char* mask, void* stream);
@@ -353,6 +363,8 @@ int shg_winding_number(int nedges, const double* edges, const double* x, const d
 int shg_mask_pack(const unsigned char* masks, int B, long long P, unsigned long long* bits, void* stream);
 int shg_basin_statistics(const double* values, int T, long long P, const double* w, const unsigned long long* bits, int B, double* out,
                          void* stream);
+int shg_basin_functionals(shg_plan* plan, const unsigned long long* bits, int B, const double* area, int nmin, double* F, void* stream);
+int shg_basin_covariance(int B, int n, const double* F, int ldf, const double* S, int lds, double* C, void* stream);
 
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
