@@ -92,6 +92,10 @@ PROTOTYPES = {
     'shg_basin_statistics': [c_double_p, ctypes.c_int, ctypes.c_longlong, c_double_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
     'shg_basin_functionals': [c_plan_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
     'shg_basin_covariance': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
+    'shg_acceleration_points': [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                c_double_p, ctypes.c_void_p],
+    'shg_acceleration_points_om': [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                   ctypes.c_double, c_double_p, ctypes.c_void_p],
 }
 STRING_GETTERS = ('shg_last_error', 'shg_version')
 

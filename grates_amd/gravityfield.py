@@ -225,12 +225,17 @@ class PotentialCoefficients:
         else:
             raise ValueError("grid values must be either None or " + str(np.ndarray))
 
-    def gravitational_acceleration(self, xyz):
+    def gravitational_acceleration(self, xyz, as_tensor=False):
         """
-        Gravitational acceleration [m/s^2] at cartesian positions xyz (m, 3).  Host-side helper (needed for the
-        GRS80 normal gravity of the geoid / obp / deformation kernels); per-order formulation of
-        grates/gravityfield.py:437-481.
+        Gravitational acceleration [m/s^2] at cartesian positions xyz (m, 3).  The default is the host computation (needed for the
+        GRS80 normal gravity of the geoid / obp / deformation kernels; per-order formulation of grates/gravityfield.py:437-481).
+        With as_tensor=True the GPU kernel (shg_acceleration_points) computes it and the result is a float64 device tensor [m, 3];
+        xyz may then be a device tensor too.
         """
+        if as_tensor:
+            if len(xyz.shape) != 2 or xyz.shape[1] != 3:
+                raise ValueError('positions must have shape (M, 3), got {0}'.format(tuple(xyz.shape)))
+            return engine.acceleration_points(self.max_degree, xyz, self.anm[np.newaxis, :, :], self.GM, self.R)[0]
         from . import grid as _grid
         r, colat, lon = _grid.cartesian2spherical(xyz)
         N = self.max_degree
@@ -548,6 +553,27 @@ class TimeSeries:
             g.epoch = epoch
             out.append(g)
         return out
+
+    def gravitational_acceleration(self, xyz, as_tensor=False):
+        """
+        Gravitational acceleration [m/s^2] of every epoch, [T, M, 3], at the positions xyz: [M, 3] for all epochs (a grid at altitude)
+        or [T, M, 3] (points of their own per epoch, e.g. orbit arcs, padded by the caller).  One GPU call for all epochs
+        (shg_acceleration_points); a device series is read in its own order-major layout and never leaves the device.  Fields with
+        different GM or R take one call each.  Returns an ndarray, or the float64 device tensor with as_tensor=True.
+        """
+        per_epoch = engine.check_acceleration_points(xyz, len(self))
+        if self.__series is not None:
+            GM, R = self._constants()
+            g = engine.acceleration_points(self.__series.max_degree, xyz, self.__series, GM, R)
+        else:
+            fields = self.__data
+            if all(d.GM == fields[0].GM and d.R == fields[0].R for d in fields):
+                batch = self.to_coefficient_batch()
+                g = engine.acceleration_points(batch.shape[-1] - 1, xyz, batch, fields[0].GM, fields[0].R)
+            else:
+                import torch
+                g = torch.stack([d.gravitational_acceleration(xyz[k] if per_epoch else xyz, as_tensor=True) for k, d in enumerate(fields)])
+        return g if as_tensor else engine.to_host(g)
 
     def detrend(self, basis_functions):
         """

@@ -366,6 +366,24 @@ int shg_basin_statistics(const double* values, int T, long long P, const double*
 int shg_basin_functionals(shg_plan* plan, const unsigned long long* bits, int B, const double* area, int nmin, double* F, void* stream);
 int shg_basin_covariance(int B, int n, const double* F, int ldf, const double* S, int lds, double* C, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Gravitational acceleration at points (PotentialCoefficients.gravitational_acceleration, grates/gravityfield.py:423-481)
+ *   g [B][M][3] (m/s^2) of the fields anm [B][N+1][N+1] (one GM and R for all) at the Cartesian positions xyz:
+ *     layout SHG_POINTS_SHARED     xyz [M][3], the same points for every field
+ *     layout SHG_POINTS_PER_EPOCH  xyz [B][M][3], points of their own for every field
+ *   Regrouped by the Legendre function (n', k) of degree n' <= N + 1, each component is a point synthesis of degree N + 1: one
+ *   column recursion per point and (n', k) serves the three components of all epochs of a pass.  No atomics: a field's result does
+ *   not depend on the other fields of the call or on the layout, and repeated calls are bitwise equal.  Points at the poles and
+ *   below R are fine; r = 0 is not.
+ *   shg_acceleration_points_om  the same from an order-major series om [(N+1)^2][Bpad] (shg_order_major_pack), Bpad >= B.
+ *   Arguments are checked before the first HIP call.
+ * ------------------------------------------------------------------------------------------------ */
+enum { SHG_POINTS_SHARED = 0, SHG_POINTS_PER_EPOCH = 1 };
+int shg_acceleration_points(int N, const double* xyz, int M, int layout, const double* anm, int B, double GM, double R, double* g,
+                            void* stream);
+int shg_acceleration_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM, double R,
+                               double* g, void* stream);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
