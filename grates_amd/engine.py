@@ -738,6 +738,33 @@ def acceleration_points(max_degree, xyz, coefficients, GM, R):
     return out
 
 
+def gravitational_gradients_points(max_degree, xyz, coefficients, GM, R):
+    """Gravitational gradient tensor T [B, M, 3, 3] (device, s^-2), T[b, m, c, d] = d g_c / d x_d, of the fields `coefficients` -- a
+    batch [B, N+1, N+1] or an OrderMajorSeries, read in its own layout -- with constants GM and R at the positions xyz [M, 3] (shared
+    by all fields) or [B, M, 3] (per field) (shg_gravitational_gradients_points / shg_gravitational_gradients_points_om)."""
+    torch = require_gpu()
+    om = isinstance(coefficients, OrderMajorSeries)
+    if not om:
+        coefficients = to_device(coefficients)
+        if coefficients.dim() != 3 or coefficients.shape[1] != coefficients.shape[2] or coefficients.shape[1] != max_degree + 1:
+            raise ValueError('coefficient batch must have shape (B, {0}, {0}), got {1}'.format(max_degree + 1, tuple(coefficients.shape)))
+    elif coefficients.max_degree != max_degree:
+        raise ValueError('the series holds degrees up to {0}, not {1}'.format(coefficients.max_degree, max_degree))
+    B = coefficients.epochs if om else int(coefficients.shape[0])
+    per_epoch = check_acceleration_points(xyz, B)
+    x = to_device(xyz, coefficients.data.device if om else coefficients.device)
+    M = int(x.shape[-2])
+    out = torch.empty((B, M, 3, 3), dtype=torch.float64, device=x.device)
+    layout = 1 if per_epoch else 0
+    if om:
+        _lib.call('shg_gravitational_gradients_points_om', int(max_degree), _ptr(x), M, layout, _ptr(coefficients.data), B,
+                  coefficients.padded_epochs, float(GM), float(R), _ptr(out), _stream())
+    else:
+        _lib.call('shg_gravitational_gradients_points', int(max_degree), _ptr(x), M, layout, _ptr(coefficients), B, float(GM), float(R),
+                  _ptr(out), _stream())
+    return out
+
+
 class OrderMajorSeries:
     """A time series of coefficient sets that stays on the device between operators (the batching of TimeSeries.to_array,
     grates/gravityfield.py:964-980, in the layout the order-wise operators work on): `data` [(N+1)^2, Bpad] with the epochs fastest

@@ -275,6 +275,18 @@ class PotentialCoefficients:
             g[:, 2] += -2 * C_zero @ cnm - 2 * S_zero @ snm
         return g * self.GM / (2 * self.R ** 2)
 
+    def gravitational_gradients(self, xyz, as_tensor=False):
+        """
+        Gravitational gradient tensor d^2 V / dx_i dx_j [s^-2; 1 E = 1e-9 s^-2] at cartesian positions xyz (m, 3), in their Earth-fixed
+        frame: [m, 3, 3], the Jacobian of gravitational_acceleration, T[k, c, d] = d g_c / d x_d.  There is no host implementation:
+        the GPU kernel (shg_gravitational_gradients_points) always computes it.  Returns an ndarray, or the float64 device tensor with
+        as_tensor=True; xyz may be an ndarray or a device tensor.
+        """
+        if len(xyz.shape) != 2 or xyz.shape[1] != 3:
+            raise ValueError('positions must have shape (M, 3), got {0}'.format(tuple(xyz.shape)))
+        T = engine.gravitational_gradients_points(self.max_degree, xyz, self.anm[np.newaxis, :, :], self.GM, self.R)[0]
+        return T if as_tensor else engine.to_host(T)
+
 
 def _host_legendre_per_order(max_degree, order, colat):
     """Host NumPy per-order Legendre recursion (formulas of grates/utilities.py:62-115, 138-151) for the few
@@ -574,6 +586,28 @@ class TimeSeries:
                 import torch
                 g = torch.stack([d.gravitational_acceleration(xyz[k] if per_epoch else xyz, as_tensor=True) for k, d in enumerate(fields)])
         return g if as_tensor else engine.to_host(g)
+
+    def gravitational_gradients(self, xyz, as_tensor=False):
+        """
+        Gravitational gradient tensor [s^-2] of every epoch, [T, M, 3, 3] with T[t, k, c, d] = d g_c / d x_d, at the positions xyz:
+        [M, 3] for all epochs or [T, M, 3] (points of their own per epoch).  Branches as gravitational_acceleration does: one GPU call
+        for all epochs (shg_gravitational_gradients_points); a device series is read in its own order-major layout and never leaves the
+        device; fields with different GM or R take one call each.  There is no host implementation.  Returns an ndarray, or the float64
+        device tensor with as_tensor=True.
+        """
+        per_epoch = engine.check_acceleration_points(xyz, len(self))
+        if self.__series is not None:
+            GM, R = self._constants()
+            T = engine.gravitational_gradients_points(self.__series.max_degree, xyz, self.__series, GM, R)
+        else:
+            fields = self.__data
+            if all(d.GM == fields[0].GM and d.R == fields[0].R for d in fields):
+                batch = self.to_coefficient_batch()
+                T = engine.gravitational_gradients_points(batch.shape[-1] - 1, xyz, batch, fields[0].GM, fields[0].R)
+            else:
+                import torch
+                T = torch.stack([d.gravitational_gradients(xyz[k] if per_epoch else xyz, as_tensor=True) for k, d in enumerate(fields)])
+        return T if as_tensor else engine.to_host(T)
 
     def detrend(self, basis_functions):
         """

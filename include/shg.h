@@ -384,6 +384,26 @@ int shg_acceleration_points(int N, const double* xyz, int M, int layout, const d
 int shg_acceleration_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM, double R,
                                double* g, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Gravitational gradient tensor at points (the Jacobian of shg_acceleration_points; no reference counterpart)
+ *   T [B][M][3][3] (s^-2; 1 E = 1e-9 s^-2), T[b][m][c][d] = d g_c / d x_d = d^2 V / dx_c dx_d, of the fields anm [B][N+1][N+1]
+ *   (one GM and R for all) at the Cartesian positions xyz, in their Earth-fixed frame:
+ *     layout SHG_POINTS_SHARED     xyz [M][3], the same points for every field
+ *     layout SHG_POINTS_PER_EPOCH  xyz [B][M][3], points of their own for every field
+ *   Each component is a point synthesis of degree N + 2 whose coefficients are the acceleration's first-derivative map applied
+ *   twice: one column recursion per point and (n'', k) serves the six components of all epochs of a pass.  Each off-diagonal value is
+ *   computed once and stored twice (T[..][c][d] == T[..][d][c] bitwise); xx, yy and zz are computed independently.  No atomics: a
+ *   field's result does not depend on the other fields of the call or on the layout, and repeated calls are bitwise equal.  Points at
+ *   the poles and below R are fine; r = 0 is not.
+ *   shg_gravitational_gradients_points_om  the same from an order-major series om [(N+1)^2][Bpad] (shg_order_major_pack), Bpad >= B.
+ *   Arguments are checked before the first HIP call (the rules of shg_acceleration_points, and N small enough that one pass of the
+ *   combined coefficients, 48 (N+3)(N+4)/2 values, is indexable by int); nothing to do (M = 0 or B = 0) returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_gravitational_gradients_points(int N, const double* xyz, int M, int layout, const double* anm, int B, double GM, double R,
+                                       double* T, void* stream);
+int shg_gravitational_gradients_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM,
+                                          double R, double* T, void* stream);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
