@@ -63,6 +63,12 @@ PROTOTYPES = {
     'shg_dgemm': [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p],
     'shg_gemm': [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
                  ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_void_p],
+    'shg_gemm_ex': [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_longlong,
+                    c_double_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                    ctypes.c_void_p],
+    'shg_gemm_route': [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_longlong,
+                       c_double_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                       ctypes.POINTER(ctypes.c_int64)],
     'shg_axpby': [ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_void_p],
     'shg_transpose_in_place': [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p],
     'shg_potrf': [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p],

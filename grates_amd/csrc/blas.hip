@@ -539,21 +539,106 @@ int gemm_ex(bool ta, bool tb, int M, int N, int K, double alpha, const double* A
     return gemm_ex_tri(ta, tb, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch, upper_only, 0, stream);
 }
 
-// tri: triangular structure of the operands (see GemmExParams::tri); entries on the zero side are not read
-int gemm_ex_tri(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
-                long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, int tri, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || batch <= 0) return SHG_OK;
-    if (SHG_GEMM_TALL && K > 0 && gemm_tall_shape(ta, tb, M, N, K, batch, upper_only, tri, A, lda, B, ldb, C))
-        return gemm_tall(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, stream);
-    // Tall products in 64-tiles whose last round of workgroups would be mostly empty (W [14637^2] X [14637 x 240]: 916 tiles on 768 workgroup
-    // slots -- the card works for four tiles per CU where 3.6 are needed): the rows of the whole rounds first, the remaining rows as a product of
-    // their own, which the rules below run as 128-tiles split over K (every CU gets a piece; the partial products are summed in a fixed order).
+// ------------------------------------------------------------------------------------------------
+// Routing: which kernels a product takes, decided from the arguments alone.  gemm_route makes no HIP call (shg_gemm_route reports
+// it on a machine without a GPU), and gemm_ex_tri launches from its result and from nothing else.  DESIGN.md lists the routes.
+// ------------------------------------------------------------------------------------------------
+struct GemmPiece {                  // one product = one kernel (plus the kernel that sums its partial products)
+    int kind = SHG_GEMM_ROUTE_NONE;
+    int slices = 1, chunk = 0;      // split-K: `slices` > 1 ranges of `chunk` entries of K each (the last one may be shorter)
+    bool strips = false;            // row-strip workgroup order
+    bool a_lower = false, b_upper = false;      // panel kernel: the K range ends at the diagonal of op(A) / op(B)
+};
+
+struct GemmRoute {
+    GemmPiece main;                 // the whole product, or its first m_main rows
+    int m_main = 0;                 // > 0: tail split -- the rows from m_main on are a product of their own ...
+    GemmPiece rest;                 // ... launched like this
+    int alias = 0;                  // bit 0: C is A, bit 1: C is B
+};
+
+static GemmPiece gemm_route_piece(bool ta, bool tb, int M, int N, int K, const double* A, int lda, const double* B, int ldb, const double* C,
+                                  int batch, bool upper_only, int tri) {
+    GemmPiece r;
+    if (M <= 0 || N <= 0 || batch <= 0) return r;
+    if (SHG_GEMM_TALL && K > 0 && gemm_tall_shape(ta, tb, M, N, K, batch, upper_only, tri, A, lda, B, ldb, C)) {
+        r.kind = SHG_GEMM_ROUTE_TALL;
+        return r;
+    }
+    if (K > 0 && gemv_shape(ta, tb, M, N, K, batch, upper_only, tri, A, B, C)) {
+        r.kind = SHG_GEMM_ROUTE_GEMV;
+        return r;
+    }
+    if (K > 0 && panel_shape(tb, M, N, K, batch, A, B, C) && !(upper_only && M != N)) {
+        r.kind = SHG_GEMM_ROUTE_PANEL;
+        r.a_lower = (tri & 2) != 0 && M == K;
+        r.b_upper = (tri & 4) != 0 && K == N;
+        return r;
+    }
+    if (K <= 0) {                      // empty sum: C = beta C
+        r.kind = SHG_GEMM_ROUTE_SCALE;
+        return r;
+    }
 #ifdef SHG_GEMM_TALL128
     const bool tall128 = K >= 2048 && batch == 1 && !upper_only && tri == 0 && N <= 256 && M >= 8192;
 #else
     const bool tall128 = false;
 #endif
-    if (SHG_GEMM_TAIL && !tall128 && K >= 2048 && batch == 1 && !upper_only && tri == 0 && !ta && (const double*)C != A && (const double*)C != B) {
+    // 128 x 128 output tiles; products with fewer of them than the card holds at once (512: the K = 128 panel updates of the
+    // blocked factorisation, the d = 1681 block products of the smoother alone or as a batch of two) take 64 x 64 tiles, four
+    // times as many workgroups: a single partial round of 128-tiles lasts as long as its longest tile (a batch of two
+    // 1681^3 products with a triangular operand: 389 us in 392 tiles, 24 TFLOP/s)
+    long long work_tiles = (long long)ceil_div(N, 128) * ceil_div(M, 128) * batch;
+    if (upper_only) work_tiles = (work_tiles + ceil_div(N, 128)) / 2;
+    // (a long K with too few 64-tiles to fill the chip is split below instead; an output that overwrites an operand -- the
+    //  in-place row panel U12 = U11^-T A12 of the factorisation -- relies on one workgroup owning a whole column tile of that
+    //  operand: 128-row tiles only)
+    const long long tiles64 = (long long)ceil_div(N, 64) * ceil_div(M, 64) * batch;
+    const bool split_candidate = batch <= 2 && !upper_only && K >= 512 && tiles64 < 256;
+    // (and products of at most 64 rows with many column tiles: a 128-row tile would be more than half empty)
+    const bool narrow = M <= 64 && !upper_only && tiles64 >= 512;
+    const bool small_tiles = (work_tiles < 512 || narrow) && !split_candidate && !tall128 && C != A && C != B;
+    r.kind = small_tiles ? SHG_GEMM_ROUTE_TILE64 : SHG_GEMM_ROUTE_TILE128;
+    const int XT = small_tiles ? 64 : 128;
+    const int gx = ceil_div(N, XT), gy = ceil_div(M, XT);
+    r.strips = SHG_GEMM_STRIPS && batch == 1 && !upper_only && gx >= 2 && gx <= 8 && gy >= 32;        // tall and skinny: row-strip order
+    // Few output tiles and a long K (block times a handful of right-hand sides): split K over grid.z into a workspace of
+    // partial products that a second kernel sums in a fixed order (deterministic, unlike atomics).
+    const int tiles = (r.strips ? 8 * gx * ceil_div(gy, 8) : gx * gy) * batch;      // workgroups of the launch (the strip grid is padded to 8 rows)
+    if (!small_tiles && batch <= 2 && !upper_only && tiles < 384 && K >= 512) {                 // fewer than 1.5 workgroups per CU
+        int slices = std::min(std::min(16, K / 128), std::max(1, 512 / tiles));
+#ifdef SHG_GEMM_TALL128
+        if (tall128) slices = SHG_GEMM_TALL128;
+#endif
+        if (slices > 1) {
+            const int chunk = round_up(ceil_div(K, slices), XK);
+            slices = ceil_div(K, chunk);
+            if (slices > 1) {
+                r.slices = slices;
+                r.chunk = chunk;
+            }
+        }
+    }
+    return r;
+}
+
+static GemmRoute gemm_route(bool ta, bool tb, int M, int N, int K, const double* A, int lda, const double* B, int ldb, const double* C, int ldc,
+                            int batch, bool upper_only, int tri) {
+    GemmRoute R;
+    if (M <= 0 || N <= 0 || batch <= 0) return R;
+    R.alias = (K > 0 && C == A ? 1 : 0) | (K > 0 && C == B ? 2 : 0);
+    R.main = gemm_route_piece(ta, tb, M, N, K, A, lda, B, ldb, C, batch, upper_only, tri);
+    if (R.main.kind == SHG_GEMM_ROUTE_TALL) return R;
+    // Tall products in 64-tiles whose last round of workgroups would be mostly empty (W [14637^2] X [14637 x 240]: 916 tiles on 768 workgroup
+    // slots -- the card works for four tiles per CU where 3.6 are needed): the rows of the whole rounds first, the remaining rows as a product of
+    // their own, which the rules above run as 128-tiles split over K (every CU gets a piece; the partial products are summed in a fixed order).
+    // Neither part is split again: the first has no remaining rows and the second at most 384 tiles.
+#ifdef SHG_GEMM_TALL128
+    const bool tall128 = K >= 2048 && batch == 1 && !upper_only && tri == 0 && N <= 256 && M >= 8192;
+#else
+    const bool tall128 = false;
+#endif
+    if (SHG_GEMM_TAIL && !tall128 && K >= 2048 && batch == 1 && !upper_only && tri == 0 && !ta && C != A && C != B) {
         const int col_tiles = ceil_div(N, 64), row_tiles = ceil_div(M, 64);
         const long long tiles = (long long)col_tiles * row_tiles;
         constexpr int kSlots = 768;                                      // 64-tile workgroups the card holds at once (three per CU)
@@ -561,18 +646,48 @@ int gemm_ex_tri(bool ta, bool tb, int M, int N, int K, double alpha, const doubl
         if (col_tiles <= 8 && tiles >= 512 && tiles > kSlots && rows_per_round >= 8) {
             const int whole = (row_tiles / rows_per_round) * rows_per_round, rest = row_tiles - whole;
             if (whole > 0 && rest > 0 && rest * 2 <= rows_per_round) {
-                const int m_main = whole * 64;
-                int rc = gemm_ex_tri(ta, tb, m_main, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch, upper_only, tri, stream);
-                if (rc) return rc;
-                return gemm_ex_tri(ta, tb, M - m_main, N, K, alpha, A + (size_t)m_main * lda, lda, strideA, B, ldb, strideB, beta, C + (size_t)m_main * ldc, ldc, strideC, batch,
-                                   upper_only, tri, stream);
+                R.m_main = whole * 64;
+                R.main = gemm_route_piece(ta, tb, R.m_main, N, K, A, lda, B, ldb, C, batch, upper_only, tri);
+                R.rest = gemm_route_piece(ta, tb, M - R.m_main, N, K, A + (size_t)R.m_main * lda, lda, B, ldb, C + (size_t)R.m_main * ldc, batch,
+                                          upper_only, tri);
             }
         }
     }
-    if (K > 0 && gemv_shape(ta, tb, M, N, K, batch, upper_only, tri, A, B, C)) return gemv(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, tri, stream);
-    if (K > 0 && panel_shape(tb, M, N, K, batch, A, B, C) && !(upper_only && M != N))
-        return panel_gemm(ta, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch, upper_only, (tri & 2) != 0 && M == K,
-                          (tri & 4) != 0 && K == N, stream);
+    return R;
+}
+
+// In-place products.  The kernels read an operand tile by tile while other workgroups already store their results, so an output
+// that starts at the address of an operand is safe only where ONE workgroup reads everything that it overwrites:
+//   C == B: op(B) = B, M == K <= 128 (one row tile: the workgroup of a column tile, or of a 16-column strip of the panel kernel,
+//           reads those columns of B in all K rows and writes the same columns of C), ldc == ldb, strideC == strideB
+//           -- the row panel U12 = U11^-T A12 of the factorisation;
+//   C == A: op(A) = A, N == K <= 128 (one column tile, the mirror image), ldc == lda, strideC == strideA.
+// In both the last load of a workgroup is separated from its first store by a barrier.  Everything else is refused.
+static const char* gemm_alias_error(bool ta, bool tb, int M, int N, int K, const double* A, int lda, long long strideA, const double* B, int ldb,
+                                    long long strideB, const double* C, int ldc, long long strideC, int batch) {
+    if (M <= 0 || N <= 0 || batch <= 0 || K <= 0) return nullptr;           // the operands are not read
+    if (C == A && !(!ta && N == K && N <= 128 && ldc == lda && strideC == strideA))
+        return "the output may overwrite A only where op(A) = A, N = K <= 128, ldc = lda and strideC = strideA";
+    if (C == B && !(!tb && M == K && M <= 128 && ldc == ldb && strideC == strideB))
+        return "the output may overwrite B only where op(B) = B, M = K <= 128, ldc = ldb and strideC = strideB";
+    return nullptr;
+}
+
+static int gemm_launch_piece(const GemmPiece& r, bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA,
+                             const double* B, int ldb, long long strideB, double beta, double* C, int ldc, long long strideC, int batch,
+                             bool upper_only, int tri, hipStream_t stream) {
+    switch (r.kind) {
+        case SHG_GEMM_ROUTE_NONE: return SHG_OK;
+        case SHG_GEMM_ROUTE_TALL: return gemm_tall(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, stream);
+        case SHG_GEMM_ROUTE_GEMV: return gemv(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, tri, stream);
+        case SHG_GEMM_ROUTE_PANEL:
+            return panel_gemm(ta, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch, upper_only, r.a_lower, r.b_upper, stream);
+        case SHG_GEMM_ROUTE_SCALE:
+            hipLaunchKernelGGL(scale_kernel, dim3(ceil_div(N, 256), M, batch), dim3(256), 0, stream, M, N, beta, C, ldc, strideC);
+            SHG_HIP(hipGetLastError());
+            return SHG_OK;
+        default: break;
+    }
     GemmExParams P;
     P.tri = tri;
     P.M = M;
@@ -590,74 +705,42 @@ int gemm_ex_tri(bool ta, bool tb, int M, int N, int K, double alpha, const doubl
     P.alpha = alpha;
     P.beta = beta;
     P.upper_only = upper_only ? 1 : 0;
-    if (K <= 0) {                      // empty sum: C = beta C
-        hipLaunchKernelGGL(scale_kernel, dim3(ceil_div(N, 256), M, batch), dim3(256), 0, stream, M, N, beta, C, ldc, strideC);
-        SHG_HIP(hipGetLastError());
-        return SHG_OK;
-    }
     P.Ktotal = 0;
     P.slices = 1;
     P.itemA = P.itemB = 0;
     P.strip_tiles = P.strip_rows = 0;
-    // 128 x 128 output tiles; products with fewer of them than the card holds at once (512: the K = 128 panel updates of the
-    // blocked factorisation, the d = 1681 block products of the smoother alone or as a batch of two) take 64 x 64 tiles, four
-    // times as many workgroups: a single partial round of 128-tiles lasts as long as its longest tile (a batch of two
-    // 1681^3 products with a triangular operand: 389 us in 392 tiles, 24 TFLOP/s)
-    long long work_tiles = (long long)ceil_div(N, 128) * ceil_div(M, 128) * batch;
-    if (upper_only) work_tiles = (work_tiles + ceil_div(N, 128)) / 2;
-    // (a long K with too few 64-tiles to fill the chip is split below instead; an output that overwrites an operand -- the
-    //  in-place row panel U12 = U11^-T A12 of the factorisation -- relies on one workgroup owning a whole column tile of that
-    //  operand: 128-row tiles only)
-    const long long tiles64 = (long long)ceil_div(N, 64) * ceil_div(M, 64) * batch;
-    const bool split_candidate = batch <= 2 && !upper_only && K >= 512 && tiles64 < 256;
-    // (and products of at most 64 rows with many column tiles: a 128-row tile would be more than half empty)
-    const bool narrow = M <= 64 && !upper_only && tiles64 >= 512;
-    const bool small_tiles = (work_tiles < 512 || narrow) && !split_candidate && !tall128 && (const double*)C != A && (const double*)C != B;
+    const bool small_tiles = r.kind == SHG_GEMM_ROUTE_TILE64;
     const int XT = small_tiles ? 64 : 128;
     dim3 grid(ceil_div(N, XT), ceil_div(M, XT), batch);
     const size_t lds = (size_t)4 * (small_tiles ? GemmExTile<64>::BUF : GemmExTile<128>::BUF) * sizeof(double);   // 73.7 KB (two workgroups per CU) / 41 KB
-    if (SHG_GEMM_STRIPS && batch == 1 && !upper_only && grid.x >= 2 && grid.x <= 8 && grid.y >= 32) {        // tall and skinny: row-strip order
+    if (r.strips) {
         P.strip_tiles = (int)grid.x;
         P.strip_rows = (int)grid.y;
         grid = dim3((unsigned)(8 * P.strip_tiles * ceil_div((int)grid.y, 8)), 1, 1);
     }
-    // Few output tiles and a long K (block times a handful of right-hand sides): split K over grid.z into a workspace of
-    // partial products that a second kernel sums in a fixed order (deterministic, unlike atomics).
-    const int tiles = (int)(grid.x * grid.y) * batch;
     double* partial = nullptr;
-    int slices = 1;
+    int slices = r.slices;
     std::unique_ptr<ScratchLease> lease;            // held until the kernel that sums the partial products is enqueued
-    if (!small_tiles && batch <= 2 && !upper_only && tiles < 384 && K >= 512) {                 // fewer than 1.5 workgroups per CU
-        slices = std::min(std::min(16, K / 128), std::max(1, 512 / tiles));
-#ifdef SHG_GEMM_TALL128
-        if (tall128) slices = SHG_GEMM_TALL128;
-#endif
-        if (slices > 1) {
-            const int chunk = round_up(ceil_div(K, slices), XK);
-            slices = ceil_div(K, chunk);
-            if (slices > 1) {
-                lease.reset(new ScratchLease(stream));
-                partial = (double*)lease->get(kScratchSplitK, (size_t)batch * slices * M * N * sizeof(double));
-            }
-            if (slices > 1 && partial != nullptr) {
-                P.K = chunk;
-                P.Ktotal = K;
-                P.slices = slices;
-                P.itemA = strideA;
-                P.itemB = strideB;
-                P.strideA = ta ? (long long)chunk * lda : chunk;
-                P.strideB = tb ? chunk : (long long)chunk * ldb;
-                P.C = partial;
-                P.ldc = N;
-                P.strideC = (long long)M * N;
-                P.alpha = 1.0;
-                P.beta = 0.0;
-                P.tri = 0;                              // (K slices and triangular K ranges are not combined)
-                grid.z = slices * batch;
-            } else {
-                slices = 1;
-                partial = nullptr;
-            }
+    if (slices > 1) {
+        lease.reset(new ScratchLease(stream));
+        partial = (double*)lease->get(kScratchSplitK, (size_t)batch * slices * M * N * sizeof(double));
+        if (partial != nullptr) {
+            P.K = r.chunk;
+            P.Ktotal = K;
+            P.slices = slices;
+            P.itemA = strideA;
+            P.itemB = strideB;
+            P.strideA = ta ? (long long)r.chunk * lda : r.chunk;
+            P.strideB = tb ? r.chunk : (long long)r.chunk * ldb;
+            P.C = partial;
+            P.ldc = N;
+            P.strideC = (long long)M * N;
+            P.alpha = 1.0;
+            P.beta = 0.0;
+            P.tri = 0;                              // (K slices and triangular K ranges are not combined)
+            grid.z = slices * batch;
+        } else {
+            slices = 1;                             // no workspace: the product runs unsplit (the one departure from the route)
         }
     }
 #define SHG_GEMM_EX(TA_, TB_)                                                                                                          \
@@ -681,6 +764,19 @@ int gemm_ex_tri(bool ta, bool tb, int M, int N, int K, double alpha, const doubl
     }
     SHG_HIP(hipGetLastError());
     return SHG_OK;
+}
+
+// tri: triangular structure of the operands (see GemmExParams::tri); entries on the zero side are not read
+int gemm_ex_tri(bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B, int ldb,
+                long long strideB, double beta, double* C, int ldc, long long strideC, int batch, bool upper_only, int tri, hipStream_t stream) {
+    if (const char* why = gemm_alias_error(ta, tb, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch)) return fail(SHG_ERR_INVALID, "gemm: %s", why);
+    const GemmRoute R = gemm_route(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, batch, upper_only, tri);
+    if (R.m_main == 0)
+        return gemm_launch_piece(R.main, ta, tb, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch, upper_only, tri, stream);
+    int rc = gemm_launch_piece(R.main, ta, tb, R.m_main, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch, upper_only, tri, stream);
+    if (rc) return rc;
+    return gemm_launch_piece(R.rest, ta, tb, M - R.m_main, N, K, alpha, A + (size_t)R.m_main * lda, lda, strideA, B, ldb, strideB, beta,
+                             C + (size_t)R.m_main * ldc, ldc, strideC, batch, upper_only, tri, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1236,6 +1332,31 @@ int potrf_inverse_upper(int n, double* A, int lda, double* X, int ldx, double* w
 
 }  // namespace shg
 
+namespace shg {
+// the argument rules of shg_gemm_ex (and of shg_gemm_route, which takes the same arguments), checked before the first HIP call
+static int gemm_ex_check(const char* name, int M, int N, int K, bool ta, bool tb, const double* A, int lda, long long strideA, const double* B, int ldb,
+                         long long strideB, const double* C, int ldc, long long strideC, int batch, int flags) {
+    SHG_REQUIRE(M >= 0 && N >= 0 && K >= 0 && batch >= 0, "%s: negative dimension", name);
+    SHG_REQUIRE((flags & ~(SHG_GEMM_A_UPPER | SHG_GEMM_A_LOWER | SHG_GEMM_B_UPPER | SHG_GEMM_B_LOWER | SHG_GEMM_UPPER_ONLY)) == 0, "%s: unknown flag bits in %d",
+                name, flags);
+    SHG_REQUIRE(!((flags & SHG_GEMM_A_UPPER) && (flags & SHG_GEMM_A_LOWER)), "%s: op(A) cannot be upper and lower triangular", name);
+    SHG_REQUIRE(!((flags & SHG_GEMM_B_UPPER) && (flags & SHG_GEMM_B_LOWER)), "%s: op(B) cannot be upper and lower triangular", name);
+    SHG_REQUIRE(!(flags & (SHG_GEMM_A_UPPER | SHG_GEMM_A_LOWER)) || M == K, "%s: a triangular op(A) needs M == K", name);
+    SHG_REQUIRE(!(flags & (SHG_GEMM_B_UPPER | SHG_GEMM_B_LOWER)) || K == N, "%s: a triangular op(B) needs K == N", name);
+    SHG_REQUIRE(!(flags & SHG_GEMM_UPPER_ONLY) || M == N, "%s: upper_only needs M == N", name);
+    SHG_REQUIRE(strideA >= 0 && strideB >= 0 && strideC >= 0, "%s: negative stride", name);
+    if (M == 0 || N == 0 || batch == 0) return SHG_OK;
+    SHG_REQUIRE(C != nullptr && ldc >= N, "%s: bad output", name);
+    SHG_REQUIRE(batch == 1 || strideC > 0, "%s: the items of a batch need an output each (strideC > 0)", name);
+    if (K > 0) {
+        SHG_REQUIRE(A && B, "%s: NULL pointer", name);
+        SHG_REQUIRE(lda >= (ta ? M : K) && ldb >= (tb ? K : N), "%s: leading dimension too small", name);
+    }
+    if (const char* why = gemm_alias_error(ta, tb, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch)) return fail(SHG_ERR_INVALID, "%s: %s", name, why);
+    return SHG_OK;
+}
+}  // namespace shg
+
 using namespace shg;
 
 extern "C" int shg_gemm(int transa, int transb, int M, int N, int K, double alpha, const double* A, int lda, const double* B, int ldb,
@@ -1247,7 +1368,68 @@ extern "C" int shg_gemm(int transa, int transb, int M, int N, int K, double alph
         SHG_REQUIRE(A && B, "shg_gemm: NULL pointer");
         SHG_REQUIRE(lda >= (transa ? M : K) && ldb >= (transb ? K : N), "shg_gemm: leading dimension too small");
     }
+    if (const char* why = gemm_alias_error(transa != 0, transb != 0, M, N, K, A, lda, 0, B, ldb, 0, C, ldc, 0, 1)) return fail(SHG_ERR_INVALID, "shg_gemm: %s", why);
     return gemm_ex(transa != 0, transb != 0, M, N, K, alpha, A, lda, 0, B, ldb, 0, beta, C, ldc, 0, 1, false, (hipStream_t)stream);
+}
+
+// The public door keeps the promise "the zero side of a triangular operand is not read" at the level of single entries: the
+// kernels skip whole K tiles of zeros but multiply the entries next to the diagonal in (the solver's own operands hold zeros
+// there), so a triangular operand reaches them as a zero-filled copy of its triangle.  As the kernels see it, it never aliases C.
+extern "C" int shg_gemm_ex(int transa, int transb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B,
+                           int ldb, long long strideB, double beta, double* C, int ldc, long long strideC, int batch, int flags, void* stream_) {
+    const bool ta = transa != 0, tb = transb != 0;
+    int rc = gemm_ex_check("shg_gemm_ex", M, N, K, ta, tb, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch, flags);
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    std::unique_ptr<ScratchLease> lease;
+    if ((flags & 15) && M > 0 && N > 0 && K > 0 && batch > 0) {
+        const bool triA = (flags & (SHG_GEMM_A_UPPER | SHG_GEMM_A_LOWER)) != 0, triB = (flags & (SHG_GEMM_B_UPPER | SHG_GEMM_B_LOWER)) != 0;
+        const int copiesA = triA ? (strideA == 0 ? 1 : batch) : 0, copiesB = triB ? (strideB == 0 ? 1 : batch) : 0;
+        const size_t each = (size_t)K * K;
+        lease.reset(new ScratchLease(stream));
+        double* copy = (double*)lease->get(kScratchTriangle, (size_t)(copiesA + copiesB) * each * sizeof(double));
+        if (copy == nullptr) return fail(SHG_ERR_NOMEM, "shg_gemm_ex: no workspace for the triangular operands");
+        if (triA) {                   // op(A) upper = A upper, or A^T upper = A lower
+            rc = triangle_copy(K, A, lda, strideA, copiesA, copy, ((flags & SHG_GEMM_A_UPPER) != 0) != ta, stream);
+            if (rc) return rc;
+            A = copy;
+            lda = K;
+            strideA = strideA == 0 ? 0 : (long long)each;
+        }
+        if (triB) {
+            double* copyB = copy + (size_t)copiesA * each;
+            rc = triangle_copy(K, B, ldb, strideB, copiesB, copyB, ((flags & SHG_GEMM_B_UPPER) != 0) != tb, stream);
+            if (rc) return rc;
+            B = copyB;
+            ldb = K;
+            strideB = strideB == 0 ? 0 : (long long)each;
+        }
+    }
+    return gemm_ex_tri(ta, tb, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch, (flags & SHG_GEMM_UPPER_ONLY) != 0, flags & 15,
+                       stream);
+}
+
+extern "C" int shg_gemm_route(int transa, int transb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B,
+                              int ldb, long long strideB, double beta, const double* C, int ldc, long long strideC, int batch, int flags,
+                              int64_t which[8]) {
+    (void)alpha;
+    (void)beta;
+    SHG_REQUIRE(which != nullptr, "shg_gemm_route: NULL result");
+    const int rc = gemm_ex_check("shg_gemm_route", M, N, K, transa != 0, transb != 0, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch, flags);
+    if (rc) return rc;
+    static const double copies[2] = {0.0, 0.0};        // stand-ins for the copies of triangular operands: they alias nothing
+    if (flags & (SHG_GEMM_A_UPPER | SHG_GEMM_A_LOWER)) A = &copies[0], lda = K;
+    if (flags & (SHG_GEMM_B_UPPER | SHG_GEMM_B_LOWER)) B = &copies[1], ldb = K;
+    const GemmRoute R = gemm_route(transa != 0, transb != 0, M, N, K, A, lda, B, ldb, C, ldc, batch, (flags & SHG_GEMM_UPPER_ONLY) != 0, flags & 15);
+    which[0] = R.main.kind;
+    which[1] = R.main.slices;
+    which[2] = R.main.chunk;
+    which[3] = R.main.strips ? 1 : 0;
+    which[4] = R.m_main;
+    which[5] = (R.main.a_lower ? 1 : 0) | (R.main.b_upper ? 2 : 0);
+    which[6] = R.alias;
+    which[7] = R.m_main > 0 ? (int64_t)R.rest.kind | (int64_t)R.rest.slices << 8 | (int64_t)(R.rest.strips ? 1 : 0) << 16 : 0;
+    return SHG_OK;
 }
 
 namespace shg {

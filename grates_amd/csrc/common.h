@@ -23,9 +23,12 @@ int fail(int code, const char* fmt, ...);
 // kernel in its place, never).  rows x cols doubles with leading dimension ld (ld == cols: one contiguous run).
 int zero_fill(double* p, long long ld, long long cols, long long rows, hipStream_t stream);
 int zero_fill(int* p, hipStream_t stream);
+// one triangle of square matrices into contiguous [batch][n][n] storage, zeros on the other side, which is not read (plan.hip)
+int triangle_copy(int n, const double* src, int ld, long long stride, int batch, double* dst, bool upper, hipStream_t stream);
 // grow-only scratch of a stream (plan.hip), kept until shg_scratch_release(); one slot per buffer that is live at the same time
 enum ScratchSlot { kScratchSplitK = 0, kScratchAnaFold = 1, kScratchAnaTransform = 2, kScratchAnaSolution = 3, kScratchAnaFlag = 4,
                    kScratchSeriesIn = 5, kScratchSeriesOut = 6 /* order-major copies of a batch in the reference layout (filters.hip) */,
+                   kScratchTriangle = 7 /* zero-filled copies of the triangular operands of shg_gemm_ex (blas.hip) */,
                    kScratchBlocks = 8 /* and up: the workspaces of one block-matrix call (blockchol.hip) */ };
 class ScratchLease {          // the scratch buffers of one stream, held while the operations that use them are enqueued (plan.hip)
 public:

@@ -61,6 +61,22 @@ int zero_fill(double* p, long long ld, long long cols, long long rows, hipStream
     return SHG_OK;
 }
 
+// dst [batch][n][n] = the upper (else lower) triangle of src [n][ld] (items `stride` apart); the other side is zero and is not read
+__global__ void triangle_copy_kernel(int n, const double* __restrict__ src, int ld, long long stride, double* __restrict__ dst, int upper) {
+    const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (j >= n) return;
+    const bool keep = upper ? j >= i : j <= i;
+    dst[((size_t)blockIdx.z * n + i) * n + j] = keep ? src[(size_t)blockIdx.z * stride + (size_t)i * ld + j] : 0.0;
+}
+
+int triangle_copy(int n, const double* src, int ld, long long stride, int batch, double* dst, bool upper, hipStream_t stream) {
+    if (n <= 0 || batch <= 0) return SHG_OK;
+    SHG_REQUIRE(n <= 65535 && batch <= 65535, "triangle_copy: %d x %d matrices", batch, n);
+    hipLaunchKernelGGL(triangle_copy_kernel, dim3(ceil_div(n, 256), n, batch), dim3(256), 0, stream, n, src, ld, stride, dst, upper ? 1 : 0);
+    SHG_HIP(hipGetLastError());
+    return SHG_OK;
+}
+
 int zero_fill(int* p, hipStream_t stream) {
     hipLaunchKernelGGL(zero_int_kernel, dim3(1), dim3(1), 0, stream, p);
     SHG_HIP(hipGetLastError());

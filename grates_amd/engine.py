@@ -954,6 +954,70 @@ def gemm(A, B, transa=False, transb=False, alpha=1.0, beta=0.0, out=None):
     return out
 
 
+# flags of shg_gemm_ex (include/shg.h): triangular operands and the upper-tiles-only launch
+GEMM_A_UPPER, GEMM_A_LOWER, GEMM_B_UPPER, GEMM_B_LOWER, GEMM_UPPER_ONLY = 1, 2, 4, 8, 16
+GEMM_ROUTE_KINDS = ('NONE', 'TALL', 'GEMV', 'PANEL', 'TILE64', 'TILE128', 'SCALE')      # shg_gemm_route_kind
+
+
+def _address(x):
+    return int(x) if isinstance(x, int) else int(x.data_ptr())
+
+
+def gemm_route(transa, transb, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch=1, flags=0):
+    """The kernels shg_gemm_ex (and shg_gemm: strides 0, batch 1, flags 0) would launch for these arguments, as a dict.
+    A, B, C are tensors or plain addresses (alignment and aliasing steer the choice; nothing is read).  Host logic only:
+    works without a GPU.  Raises ShgError for arguments that shg_gemm_ex refuses."""
+    which = (ctypes.c_int64 * 8)()
+    _lib.call('shg_gemm_route', int(bool(transa)), int(bool(transb)), M, N, K, 1.0, ctypes.c_void_p(_address(A)), lda, strideA,
+              ctypes.c_void_p(_address(B)), ldb, strideB, 0.0, ctypes.c_void_p(_address(C)), ldc, strideC, batch, flags, which)
+    route = {'kind': GEMM_ROUTE_KINDS[which[0]], 'slices': which[1], 'chunk': which[2], 'strips': bool(which[3]), 'm_main': which[4],
+             'a_lower': bool(which[5] & 1), 'b_upper': bool(which[5] & 2), 'alias': {0: '', 1: 'A', 2: 'B', 3: 'AB'}[which[6]], 'rest': None}
+    if which[4] > 0:
+        route['rest'] = {'kind': GEMM_ROUTE_KINDS[which[7] & 255], 'slices': (which[7] >> 8) & 255, 'strips': bool(which[7] >> 16 & 1)}
+    return route
+
+
+def gemm_ex_args(A, B, out, transa=False, transb=False):
+    """(transa, transb, M, N, K, A, lda, strideA, B, ldb, strideB, out, ldc, strideC, batch) of a call of gemm_ex -- the leading
+    arguments of gemm_route.  Operands are 2-d, or 3-d [batch][rows][columns]; a 2-d operand beside 3-d ones is repeated (stride 0)."""
+    batch = 1
+    for t in (A, B, out):
+        if t.dim() not in (2, 3) or (t.numel() > 0 and t.shape[-1] > 1 and t.stride(-1) != 1):
+            raise ValueError('gemm_ex operands must be two- or three-dimensional with a contiguous last dimension')
+        if t.dim() == 3:
+            if batch != 1 and t.shape[0] != batch:
+                raise ValueError('gemm_ex: batch counts differ')
+            batch = t.shape[0]
+    if out.dim() == 2 and batch != 1:
+        raise ValueError('gemm_ex: a batch needs a three-dimensional output')
+    M = A.shape[-1] if transa else A.shape[-2]
+    K = A.shape[-2] if transa else A.shape[-1]
+    Kb = B.shape[-1] if transb else B.shape[-2]
+    N = B.shape[-2] if transb else B.shape[-1]
+    if K != Kb:
+        raise ValueError('gemm_ex: inner dimensions differ ({0} vs {1})'.format(K, Kb))
+    if tuple(out.shape[-2:]) != (M, N):
+        raise ValueError('gemm_ex: output must be ({0}, {1})'.format(M, N))
+    stride = lambda t: t.stride(0) if t.dim() == 3 and t.shape[0] > 1 else 0      # noqa: E731
+    return (bool(transa), bool(transb), M, N, K, A, max(A.stride(-2), 1), stride(A), B, max(B.stride(-2), 1), stride(B),
+            out, max(out.stride(-2), 1), stride(out), batch)
+
+
+def gemm_ex(A, B, out, transa=False, transb=False, alpha=1.0, beta=0.0, flags=0):
+    """out_i = alpha op(A_i) op(B_i) + beta out_i on the fp64 MFMA GEMM for device tensors (see gemm_ex_args): strided batches,
+    triangular operands (GEMM_A_UPPER ...: the zero side is not read) and GEMM_UPPER_ONLY (output tiles entirely below the
+    diagonal are not written).  shg_gemm_ex of include/shg.h; `out` may be B or A in the in-place forms listed there."""
+    torch = require_gpu()
+    for t in (A, B, out):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
+            raise ValueError('gemm_ex: fp64 device tensors expected')
+    ta, tb, M, N, K, A, lda, sA, B, ldb, sB, out, ldc, sC, batch = gemm_ex_args(A, B, out, transa, transb)
+    Plan._written(out)
+    _lib.call('shg_gemm_ex', int(ta), int(tb), M, N, K, float(alpha), _ptr(A), lda, sA, _ptr(B), ldb, sB, float(beta), _ptr(out), ldc, sC, batch,
+              int(flags), _stream())
+    return out
+
+
 def potrf(A, check=True):
     """Upper Cholesky factor U (A = U^T U) of a symmetric positive definite device matrix, in place; the strictly lower
     triangle is zeroed.  Raises numpy.linalg.LinAlgError like scipy.linalg.cholesky when a pivot is not positive."""

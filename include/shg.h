@@ -232,6 +232,56 @@ int shg_dgemm(int M, int N, int K, const double* A, int lda, const double* B, in
  * ------------------------------------------------------------------------------------------------ */
 int shg_gemm(int transa, int transb, int M, int N, int K, double alpha, const double* A, int lda, const double* B, int ldb,
              double beta, double* C, int ldc, void* stream);
+/* In-place products of shg_gemm and shg_gemm_ex.  The output may start at the address of an operand in two forms only:
+ *     C == B:  transb == 0, M == K <= 128, ldc == ldb (and strideC == strideB)    -- B <- alpha op(A) B + beta B
+ *     C == A:  transa == 0, N == K <= 128, ldc == lda (and strideC == strideA)    -- A <- alpha A op(B) + beta A
+ * (one workgroup then reads every entry that it overwrites).  Every other call with C == A or C == B returns SHG_ERR_INVALID
+ * before any HIP call.  An operand that overlaps the output WITHOUT starting at its address gives undefined results, as in BLAS;
+ * disjoint blocks of one matrix (interleaved rows, different columns) are separate arrays in this sense and are fine. */
+
+/* shg_gemm_ex: the strided-batched, structure-aware form of shg_gemm that the block solver uses internally.
+ *     C_i = alpha op(A_i) op(B_i) + beta C_i,   X_i = X + i strideX (elements),   i = 0 .. batch - 1
+ *   A stride of 0 repeats an operand for every item; strideC must be positive when batch > 1 (the outputs must not overlap).
+ *   flags: SHG_GEMM_A_UPPER / _A_LOWER   op(A) is upper / lower triangular (needs M == K; at most one of the two)
+ *          SHG_GEMM_B_UPPER / _B_LOWER   op(B) is upper / lower triangular (needs K == N; at most one of the two)
+ *              entries on the zero side of a triangular operand are not read (they may hold anything, NaN included): the
+ *              call works on a zero-filled copy of the triangle in stream scratch, one extra pass over K^2 entries per item
+ *          SHG_GEMM_UPPER_ONLY           only the upper triangle of C is wanted (needs M == N): output tiles that lie entirely
+ *              below the diagonal are not written -- every block C[128 a .. 128 a + 127][128 b .. 128 b + 127] with a > b keeps
+ *              its contents; which other entries below the diagonal are written is unspecified, those on and above it all are
+ *   Leading dimensions and NULL pointers as in shg_gemm; violations return SHG_ERR_INVALID before any HIP call. */
+enum {
+    SHG_GEMM_A_UPPER = 1,
+    SHG_GEMM_A_LOWER = 2,
+    SHG_GEMM_B_UPPER = 4,
+    SHG_GEMM_B_LOWER = 8,
+    SHG_GEMM_UPPER_ONLY = 16
+};
+int shg_gemm_ex(int transa, int transb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B,
+                int ldb, long long strideB, double beta, double* C, int ldc, long long strideC, int batch, int flags, void* stream);
+
+/* Host-only diagnostic: the kernels that shg_gemm_ex (and shg_gemm: strides 0, batch 1, flags 0) would launch for these arguments.
+ * Takes the arguments of shg_gemm_ex, pointers included (alignment and aliasing steer the choice), checks them like shg_gemm_ex,
+ * makes no HIP call and touches no memory but `which`:
+ *   which[0] route kind (below) of the product, or of its first which[4] rows
+ *   which[1] split-K slices (1: not split), which[2] entries of K per slice (0: not split)
+ *   which[3] 1: row-strip workgroup order
+ *   which[4] tail split: > 0: rows of the first product; the remaining rows are a second product with
+ *   which[7]    kind | slices << 8 | strip order << 16   (0 without a tail split)
+ *   which[5] panel kernel: bit 0 the K range ends at the diagonal of a lower triangular op(A), bit 1: of an upper triangular op(B)
+ *   which[6] bit 0: C is A, bit 1: C is B
+ * The thresholds behind the choice are performance tuning, not contract (DESIGN.md "Routes of the dense product"). */
+typedef enum {
+    SHG_GEMM_ROUTE_NONE = 0,      /* empty output: nothing is launched                                       */
+    SHG_GEMM_ROUTE_TALL = 1,      /* whole-width stream-K kernel for 178 .. 240 columns                      */
+    SHG_GEMM_ROUTE_GEMV = 2,      /* one wave per output row, at most 8 columns                              */
+    SHG_GEMM_ROUTE_PANEL = 3,     /* K <= 128 and a thin output: the whole K range in registers              */
+    SHG_GEMM_ROUTE_TILE64 = 4,    /* 64 x 64 output tiles                                                    */
+    SHG_GEMM_ROUTE_TILE128 = 5,   /* 128 x 128 output tiles, possibly split over K                           */
+    SHG_GEMM_ROUTE_SCALE = 6      /* K == 0: C = beta C                                                      */
+} shg_gemm_route_kind;
+int shg_gemm_route(int transa, int transb, int M, int N, int K, double alpha, const double* A, int lda, long long strideA, const double* B,
+                   int ldb, long long strideB, double beta, const double* C, int ldc, long long strideC, int batch, int flags, int64_t which[8]);
 int shg_potrf(int n, double* A, int lda, int* info, void* stream);
 /* Y = alpha X + beta Y on [rows][cols] blocks: _scale / _axpy of blocks and vectors (grates/lstsq.py:889-903, 1107-1117) */
 int shg_axpby(int rows, int cols, double alpha, const double* X, int ldx, double beta, double* Y, int ldy, void* stream);
