@@ -281,10 +281,12 @@ void recursion_tables(int N, std::vector<double>& a, std::vector<double>& b) {
 }
 
 // True when meridians obey lon[nlon-1-j] = -lon[j], lon[nlon/2-1-j] = -pi - lon[j], lon[nlon/2+j] = lon[j] + pi
-// to within a few ulp of pi (any equi-angular cell-centred grid, grates/grid.py:1149, 1186).
+// to within a few ulp of pi (any equi-angular cell-centred grid, grates/grid.py:1149, 1186).  The bound is the one of
+// has_rotation_symmetry (synthesis_rot.hip): each test below sums two meridians, so a caller's raster whose meridians are each
+// within 1e-15 rad of the equi-angular one (2e-15 the pair, 7e-16 the raster's own rounding) passes both tests or neither.
 static bool has_fourfold_symmetry(int nlon, const double* lon) {
     if (nlon < 4 || nlon % 4 != 0) return false;
-    const double tol = 2e-15;
+    const double tol = 3e-15;
     const double pi = 3.14159265358979323846;
     for (int j = 0; j < nlon / 4; ++j) {
         if (std::fabs(lon[nlon - 1 - j] + lon[j]) > tol) return false;

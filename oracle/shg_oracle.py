@@ -302,18 +302,29 @@ GM_DEFAULT = 3.9860044150e+14
 R_DEFAULT = 6.3781363000e+06
 
 
+def synthesis_tables(anm, colat, kn, lon):
+    """Table-level core of the regular-grid synthesis: V[i][j] = sum_nm kn[i][n] P_nm(colat_i) (C_nm cos m lon_j + S_nm sin m lon_j)
+    for the caller's own colat [nlat], kn [nlat, N+1] and lon [nlon]; every parallel is evaluated on its own from the tables it is
+    given (no use of any symmetry between parallels or meridians).  N+1 dgemms as in the reference, gravityfield.py:358-368.
+    Returns value_array [nlat, nlon]."""
+    N = anm.shape[0] - 1
+    colat = np.atleast_1d(np.asarray(colat, dtype=float))
+    lon = np.atleast_1d(np.asarray(lon, dtype=float))
+    Pnm = scale_packed_by_degree(legendre_functions(N, colat), np.asarray(kn, dtype=float))
+    Pnm *= anm[np.newaxis, :, :]
+    cs = trigonometric_functions(N, lon)
+    values = np.zeros((colat.size, lon.size))
+    for k in range(N + 1):
+        values += Pnm[:, k, :] @ cs[:, k, :].T
+    return values
+
+
 def synthesis_regular(anm, meridians, parallels, kernel, GM=GM_DEFAULT, R=R_DEFAULT, a=GRS80_A, f=GRS80_F):
     """Regular-grid synthesis, N+1 dgemms as in the reference.  gravityfield.py:352-368.
     Returns value_array [nlat, nlon]."""
     N = anm.shape[0] - 1
     colat, _, kn = kn_table(kernel, N, parallels, GM, R, a, f)
-    Pnm = scale_packed_by_degree(legendre_functions(N, colat), kn)
-    Pnm *= anm[np.newaxis, :, :]
-    cs = trigonometric_functions(N, meridians)
-    values = np.zeros((parallels.size, meridians.size))
-    for k in range(N + 1):
-        values += Pnm[:, k, :] @ cs[:, k, :].T
-    return values
+    return synthesis_tables(anm, colat, kn, meridians)
 
 
 def synthesis_points(anm, longitude, latitude, kernel, GM=GM_DEFAULT, R=R_DEFAULT, a=GRS80_A, f=GRS80_F):
@@ -334,18 +345,24 @@ def synthesis_points(anm, longitude, latitude, kernel, GM=GM_DEFAULT, R=R_DEFAUL
 # ----------------------------------------------------------------------------------------------
 
 
+def synthesis_matrix_per_order_tables(m, min_degree, max_degree, colat, kn, lon):
+    """Table-level core of synthesis_matrix_per_order: the design matrix of order m from the caller's own colat [nlat],
+    kn [nlat, N+1] and lon [nlon] -- rows ordered parallel-major, columns n = max(m, nmin)..N.  grid.py:641-663"""
+    Pm = (legendre_functions_per_order(max_degree, m, colat) * kn[:, m:])[:, max(min_degree - m, 0):]
+    if m == 0:
+        return np.repeat(Pm, lon.size, axis=0)
+    c = np.cos(m * lon)
+    s = np.sin(m * lon)
+    Ac = (Pm[:, np.newaxis, :] * c[np.newaxis, :, np.newaxis]).reshape(-1, Pm.shape[1])
+    As = (Pm[:, np.newaxis, :] * s[np.newaxis, :, np.newaxis]).reshape(-1, Pm.shape[1])
+    return Ac, As
+
+
 def synthesis_matrix_per_order(m, min_degree, max_degree, meridians, parallels, kernel, GM=GM_DEFAULT, R=R_DEFAULT,
                                a=GRS80_A, f=GRS80_F):
     """grid.py:627-663 -- rows ordered parallel-major, columns n = max(m, nmin)..N."""
     colat, _, kn = kn_table(kernel, max_degree, parallels, GM, R, a, f)
-    Pm = (legendre_functions_per_order(max_degree, m, colat) * kn[:, m:])[:, max(min_degree - m, 0):]
-    if m == 0:
-        return np.repeat(Pm, meridians.size, axis=0)
-    c = np.cos(m * meridians)
-    s = np.sin(m * meridians)
-    Ac = (Pm[:, np.newaxis, :] * c[np.newaxis, :, np.newaxis]).reshape(-1, Pm.shape[1])
-    As = (Pm[:, np.newaxis, :] * s[np.newaxis, :, np.newaxis]).reshape(-1, Pm.shape[1])
-    return Ac, As
+    return synthesis_matrix_per_order_tables(m, min_degree, max_degree, colat, kn, meridians)
 
 
 def vector_indices(min_degree, max_degree, order, cs=None):
@@ -369,12 +386,17 @@ def synthesis_matrix(min_degree, max_degree, meridians, parallels, kernel, GM=GM
     return A
 
 
-def analysis_regular(values, area, min_degree, max_degree, meridians, parallels, kernel, GM=GM_DEFAULT, R=R_DEFAULT,
-                     a=GRS80_A, f=GRS80_F, orders=None):
-    """Area-weighted least squares per order and per cos/sin.  grid.py:665-696, 752-790.
-    values, area: flattened [nlat*nlon].  Returns anm [N+1, N+1].
+def analysis_tables(values, area, min_degree, max_degree, colat, kn, lon, orders=None):
+    """Table-level core of the regular-grid analysis: area-weighted least squares per order and per cos/sin with the design
+    matrices of the caller's own colat [nlat], kn [nlat, N+1] and lon [nlon] (every parallel from its own table row).
+    grid.py:665-696, 752-790.  values, area: flattened [nlat*nlon].  Returns anm [N+1, N+1].
     orders: the orders to solve (default: all, like the reference's loop grid.py:779-785); the orders are independent
     least-squares problems, the others stay zero (bounded samples of the benchmark's CPU baseline)."""
+    colat = np.atleast_1d(np.asarray(colat, dtype=float))
+    kn = np.asarray(kn, dtype=float)
+    lon = np.atleast_1d(np.asarray(lon, dtype=float))
+    area = np.ravel(area)
+    values = np.ravel(values)
     anm = np.zeros((max_degree + 1, max_degree + 1))
     w = area[:, np.newaxis]
     wanted = set(range(max_degree + 1)) if orders is None else set(int(m) for m in orders)
@@ -383,13 +405,22 @@ def analysis_regular(values, area, min_degree, max_degree, meridians, parallels,
         return np.linalg.solve((A * w).T @ A, (A * w).T) @ values
 
     if 0 in wanted:
-        anm[min_degree:, 0] = lsq(synthesis_matrix_per_order(0, min_degree, max_degree, meridians, parallels, kernel, GM, R, a, f))
+        anm[min_degree:, 0] = lsq(synthesis_matrix_per_order_tables(0, min_degree, max_degree, colat, kn, lon))
     for m in sorted(wanted - {0}):
-        Ac, As = synthesis_matrix_per_order(m, min_degree, max_degree, meridians, parallels, kernel, GM, R, a, f)
+        Ac, As = synthesis_matrix_per_order_tables(m, min_degree, max_degree, colat, kn, lon)
         start = max(m, min_degree)
         anm[start:, m] = lsq(Ac)
         anm[m - 1, start:] = lsq(As)
     return anm
+
+
+def analysis_regular(values, area, min_degree, max_degree, meridians, parallels, kernel, GM=GM_DEFAULT, R=R_DEFAULT,
+                     a=GRS80_A, f=GRS80_F, orders=None):
+    """Area-weighted least squares per order and per cos/sin.  grid.py:665-696, 752-790.
+    values, area: flattened [nlat*nlon].  Returns anm [N+1, N+1].
+    orders: the orders to solve (default: all); see analysis_tables."""
+    colat, _, kn = kn_table(kernel, max_degree, parallels, GM, R, a, f)
+    return analysis_tables(values, area, min_degree, max_degree, colat, kn, meridians, orders=orders)
 
 
 def analysis_matrix_regular(area, min_degree, max_degree, meridians, parallels, kernel, GM=GM_DEFAULT, R=R_DEFAULT,
