@@ -106,6 +106,8 @@ PROTOTYPES = {
                                            ctypes.c_double, c_double_p, ctypes.c_void_p],
     'shg_gravitational_gradients_points_om': [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_void_p],
+    'shg_acceleration_design': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                c_double_p, ctypes.c_int, ctypes.c_void_p],
 }
 STRING_GETTERS = ('shg_last_error', 'shg_version')
 

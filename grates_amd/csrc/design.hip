@@ -1,0 +1,193 @@
+// Design matrix of the gravitational acceleration at points: the partial derivatives of g (acceleration.hip) with respect to the
+// coefficients, transposed, At [P][3][ldt] with the points innermost and the rows in the degree-wise order of
+// utilities.ravel_coefficients (C_n0, C_n1, S_n1, C_n2, ... for n = min_degree .. N).
+//
+// g is linear in the coefficients and the grouping at the head of acceleration.hip gives every column directly.  With the solid
+// harmonics of degree n' = n + 1,
+//   Yc_{n'k} = (R/r)^(n'+1) P_{n'k} cos(k lon)      Ys_{n'k} = (R/r)^(n'+1) P_{n'k} sin(k lon),
+// and the factors f-, f0, f+ of (n, m) (f- of order 1 and f+ of order 0 carry the reference's extra sqrt(2)), in units of GM / (2 R^2):
+//   d g_x / d C_nm = f- Yc_{n+1,m-1} - f+ Yc_{n+1,m+1}      d g_x / d S_nm =  f- Ys_{n+1,m-1} - f+ Ys_{n+1,m+1}
+//   d g_y / d C_nm = -f- Ys_{n+1,m-1} - f+ Ys_{n+1,m+1}     d g_y / d S_nm =  f- Yc_{n+1,m-1} + f+ Yc_{n+1,m+1}
+//   d g_z / d C_nm = -2 f0 Yc_{n+1,m}                       d g_z / d S_nm = -2 f0 Ys_{n+1,m}
+// (the minus terms exist for m >= 1 only).  No sum over degrees: an entry is one or two products.
+//
+// Two kernels per pass of points: design_harmonics_kernel runs the column recursion of acceleration_points_kernel once per point and
+// writes Y [packed (n', k)][2][ldy] of degree N + 1 to a workspace; design_gather_kernel forms every row of At from at most two
+// entries of Y per component, following a host-built table of (slot of Y, factor) terms.  The table is all the gather kernel knows
+// about the acceleration: another linear functional of the solid harmonics is another table.
+#include "common.h"
+
+#include <cmath>
+
+namespace shg {
+
+// 256 lanes = 256 points.  (r, colatitude, longitude) come from xyz as grid.cartesian2spherical computes them (the operation order of
+// acceleration_points_kernel), (R/r)^(n'+1) is carried along the degree loop.  The recursion factors a, b of one (n', k) lie side by
+// side and are read with wave-uniform addresses: no LDS, whatever the degree.
+__global__ __launch_bounds__(256) void design_harmonics_kernel(int N1, int npts, const double* __restrict__ xyz, const double2* __restrict__ ab, double R,
+                                                               double* __restrict__ Y, size_t ldy) {
+    const int pt = blockIdx.x * 256 + threadIdx.x;
+    const bool ok = pt < npts;
+    const double* xp = xyz + (size_t)(ok ? pt : 0) * 3;
+    const double x = xp[0], y = xp[1], z = xp[2];
+    const double r = sqrt((x * x + y * y) + z * z);                  // np.sum over axis 1: ((x^2 + y^2) + z^2)
+    const double th = atan2(sqrt(x * x + y * y), z);
+    const double lam = atan2(y, x);
+    const double u = R / r;
+    const double t = cos(th);
+    const double s = sqrt(1.0 - t * t);
+    double pmm = 1.0, rk = u;                                        // rk = (R/r)^(k+1)
+    for (int k = 0; k <= N1; ++k) {
+        if (k == 1)
+            pmm = sqrt(3.0) * s;
+        else if (k >= 2)
+            pmm = sqrt((2.0 * k + 1.0) / (2.0 * k)) * s * pmm;
+        if (k >= 1) rk *= u;
+        double sk, ck;
+        sincos((double)k * lam, &sk, &ck);
+        double p1 = pmm, p2 = 0.0, rad = rk;
+        const int off = order_offset(N1, k);
+        for (int n = k; n <= N1; ++n) {
+            if (n > k) {
+                const double2 f = ab[off + n - k];
+                const double p = (f.x * t) * p1 - f.y * p2;
+                p2 = p1;
+                p1 = p;
+            }
+            const double pk = p1 * rad;
+            rad *= u;
+            if (ok) {
+                double* yo = Y + (size_t)(off + n - k) * 2 * ldy + pt;
+                yo[0] = pk * ck;
+                yo[ldy] = pk * sk;
+            }
+        }
+    }
+}
+
+// Row `blockIdx.x` of a transposed design matrix with C components whose entries are sums of at most T terms factor * Y[slot]
+// (slot = 2 packed + (0 cosine | 1 sine); slot < 0: no term): out [rows][C][ldt], 256 points per workgroup (blockIdx.y).  The slots
+// and factors of a row are wave-uniform.  Every entry is scaled by `scale` and then by the square root of the point's weight
+// (wl 0: none, 1: w [npts], 2: w [npts][C]).
+template <int C, int T>
+__global__ __launch_bounds__(256) void design_gather_kernel(int npts, const double* __restrict__ Y, size_t ldy, const int* __restrict__ slot,
+                                                            const double* __restrict__ factor, const double* __restrict__ w, int wl, double scale,
+                                                            double* __restrict__ out, size_t ldt) {
+    const int pt = blockIdx.y * 256 + threadIdx.x;
+    if (pt >= npts) return;
+    const size_t row = blockIdx.x;
+    const double wp = wl == 1 ? sqrt(w[pt]) : 1.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        double v = 0.0;
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            const int sl = slot[(row * C + c) * T + j];
+            if (sl >= 0) v = v + factor[(row * C + c) * T + j] * Y[(size_t)sl * ldy + pt];
+        }
+        const double sw = wl == 2 ? sqrt(w[(size_t)pt * C + c]) : wp;
+        out[(row * C + c) * ldt + pt] = (v * scale) * sw;
+    }
+}
+
+// terms of the rows of the acceleration's design matrix, [P][3][2] each, rows in the order of utilities.degreewise_array_index
+static void acceleration_design_table(int N, int min_degree, std::vector<int>& slot, std::vector<double>& factor) {
+    const int N1 = N + 1;
+    const size_t P = (size_t)(N + 1) * (N + 1) - (size_t)min_degree * min_degree;
+    slot.assign(P * 6, -1);
+    factor.assign(P * 6, 0.0);
+    size_t row = 0;
+    for (int n = min_degree; n <= N; ++n) {
+        const double dn = n;
+        const double base = sqrt((2.0 * dn + 1.0) / (2.0 * dn + 3.0));
+        for (int j = 0; j <= 2 * n; ++j, ++row) {
+            const int m = (j + 1) / 2;
+            const int sine = (j > 0 && j % 2 == 0) ? 1 : 0;
+            const double dm = m;
+            int* sl = &slot[row * 6];
+            double* f = &factor[row * 6];
+            // the solid harmonic of (n + 1, k) that multiplies this coefficient: the same kind (cosine | sine) in x and z, the other in y
+            auto term = [&](int c, int j2, int k, int kind, double value) {
+                if (kind == 1 && k == 0) return;                     // Ys of order 0 is zero
+                sl[c * 2 + j2] = 2 * (order_offset(N1, k) + n + 1 - k) + kind;
+                f[c * 2 + j2] = value;
+            };
+            if (m >= 1) {                                            // minus term: P_{n+1,m-1}
+                double fm = sqrt((dn - dm + 1.0) * (dn - dm + 2.0)) * base;
+                if (m == 1) fm *= sqrt(2.0);
+                term(0, 0, m - 1, sine, fm);
+                term(1, 0, m - 1, 1 - sine, sine ? fm : -fm);
+            }
+            {                                                        // plus term: P_{n+1,m+1}
+                double fp = sqrt((dn + dm + 1.0) * (dn + dm + 2.0)) * base;
+                if (m == 0) fp *= sqrt(2.0);
+                term(0, 1, m + 1, sine, -fp);
+                term(1, 1, m + 1, 1 - sine, sine ? fp : -fp);
+            }
+            const double f0 = sqrt((dn - dm + 1.0) * (dn + dm + 1.0)) * base;
+            term(2, 0, m, sine, -2.0 * f0);
+        }
+    }
+}
+
+}  // namespace shg
+
+using namespace shg;
+
+static int acceleration_design(int N, int min_degree, const double* xyz, int M, const double* weights, int wl, double GM, double R, double* At, int ldt,
+                               hipStream_t stream) {
+    const int N1 = N + 1;
+    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
+    const long long packed = packed_count(N1);
+    // points per pass: Y of a pass stays under 256 MB (the budget of the acceleration's Q), in whole workgroups, at least one
+    const long long budget = (256LL << 20) / 8 / (2 * packed) / 256 * 256;
+    const int pass = (int)std::min<long long>({std::max<long long>(budget, 256), ((long long)M + 255) / 256 * 256, 65535LL * 256});
+    const double scale = GM / (2.0 * R * R);
+    Workspace ws = Workspace::plain(stream);
+    double2* ab;
+    double *Y, *factor;
+    int* slot;
+    if (!ws.alloc(ab, (size_t)packed, Y, (size_t)packed * 2 * pass, factor, (size_t)P * 6, slot, (size_t)P * 6))
+        return fail(SHG_ERR_NOMEM, "shg_acceleration_design: workspace allocation failed");
+    {   // recursion factors of degree N + 1 (a and b of one (n', k) side by side) and the terms of the rows
+        std::vector<double> a, b, h(2 * (size_t)packed), f;
+        std::vector<int> sl;
+        recursion_tables(N1, a, b);
+        for (size_t i = 0; i < a.size(); ++i) {
+            h[2 * i] = a[i];
+            h[2 * i + 1] = b[i];
+        }
+        acceleration_design_table(N, min_degree, sl, f);
+        SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(factor, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(slot, sl.data(), sl.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipStreamSynchronize(stream));
+    }
+    for (int p0 = 0; p0 < M; p0 += pass) {
+        const int np = std::min(pass, M - p0);
+        hipLaunchKernelGGL(design_harmonics_kernel, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N1, np, xyz + (size_t)p0 * 3, ab, R, Y, (size_t)pass);
+        const double* w = wl == 0 ? nullptr : weights + (size_t)p0 * (wl == 2 ? 3 : 1);
+        hipLaunchKernelGGL((design_gather_kernel<3, 2>), dim3((unsigned)P, ceil_div(np, 256)), dim3(256), 0, stream, np, Y, (size_t)pass, slot, factor, w, wl,
+                           scale, At + p0, (size_t)ldt);
+        SHG_HIP(hipGetLastError());
+    }
+    return SHG_OK;
+}
+
+// Arguments are checked before the first HIP call (the CPU tests call this without a device).
+extern "C" int shg_acceleration_design(int N, int min_degree, const double* xyz, int M, const double* weights, int weight_layout, double GM, double R,
+                                       double* At, int ldt, void* stream) {
+    const char* fn = "shg_acceleration_design";
+    SHG_REQUIRE(N >= 0 && min_degree >= 0 && M >= 0, "%s: negative size (N %d, min_degree %d, M %d)", fn, N, min_degree, M);
+    SHG_REQUIRE(min_degree <= N, "%s: min_degree %d above N %d", fn, min_degree, N);
+    SHG_REQUIRE(N <= 32766, "%s: N %d is too large", fn, N);
+    SHG_REQUIRE(weight_layout == SHG_WEIGHTS_NONE || weight_layout == SHG_WEIGHTS_POINT || weight_layout == SHG_WEIGHTS_COMPONENT,
+                "%s: weight layout %d, expected 0 (none), 1 (per point) or 2 (per component)", fn, weight_layout);
+    SHG_REQUIRE(std::isfinite(GM) && std::isfinite(R) && R > 0.0, "%s: GM and R must be finite and R positive (GM %g, R %g)", fn, GM, R);
+    SHG_REQUIRE(ldt >= M, "%s: ldt %d below M %d", fn, ldt, M);
+    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
+    SHG_REQUIRE(P * 3 * ldt <= (1LL << 40), "%s: output of %lld values is too large", fn, P * 3 * ldt);
+    if (M == 0) return SHG_OK;
+    SHG_REQUIRE(xyz && At && (weights || weight_layout == SHG_WEIGHTS_NONE), "%s: NULL pointer", fn);
+    return acceleration_design(N, min_degree, xyz, M, weights, weight_layout, GM, R, At, ldt, (hipStream_t)stream);
+}

@@ -765,6 +765,44 @@ def gravitational_gradients_points(max_degree, xyz, coefficients, GM, R):
     return out
 
 
+def check_observation_weights(weights, points):
+    """The layout of the weights of `points` observed positions: None (returns 0), w [M] per point (1) or w [M, 3] per component
+    (2), finite and >= 0; ValueError otherwise.  Host arrays are checked on the host, before anything reaches the device."""
+    if weights is None:
+        return 0
+    shape = tuple(weights.shape)
+    if shape != (points,) and shape != (points, 3):
+        raise ValueError('weights must have shape ({0},) or ({0}, 3), got {1}'.format(points, shape))
+    if isinstance(weights, np.ndarray):
+        valid = bool(np.all(np.isfinite(weights) & (weights >= 0)))
+    else:
+        valid = bool((weights.isfinite() & (weights >= 0)).all())
+    if not valid:
+        raise ValueError('weights must be finite and not negative')
+    return len(shape)
+
+
+def acceleration_design(max_degree, xyz, GM, R, min_degree=0, weights=None):
+    """Transposed design matrix At [P, 3, M] (device) of the gravitational acceleration at the positions xyz [M, 3]: At[p, c, i] is the
+    derivative of component c of g at point i with respect to coefficient p of utilities.ravel_coefficients(., min_degree, max_degree),
+    P = (max_degree + 1)^2 - min_degree^2 (shg_acceleration_design).  weights [M] or [M, 3] scale the entries by sqrt(w)."""
+    min_degree, max_degree = int(min_degree), int(max_degree)
+    if min_degree < 0 or min_degree > max_degree:
+        raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
+    if len(xyz.shape) != 2 or xyz.shape[1] != 3:
+        raise ValueError('positions must have shape (M, 3), got {0}'.format(tuple(xyz.shape)))
+    M = int(xyz.shape[0])
+    layout = check_observation_weights(weights, M)
+    torch = require_gpu()
+    x = to_device(xyz)
+    w = to_device(weights, x.device) if layout else None
+    P = (max_degree + 1) ** 2 - min_degree ** 2
+    out = torch.empty((P, 3, M), dtype=torch.float64, device=x.device)
+    _lib.call('shg_acceleration_design', max_degree, min_degree, _ptr(x), M, _ptr(w) if layout else None, layout, float(GM), float(R), _ptr(out),
+              M, _stream())
+    return out
+
+
 class OrderMajorSeries:
     """A time series of coefficient sets that stays on the device between operators (the batching of TimeSeries.to_array,
     grates/gravityfield.py:964-980, in the layout the order-wise operators work on): `data` [(N+1)^2, Bpad] with the epochs fastest

@@ -308,6 +308,21 @@ def _host_legendre_per_order(max_degree, order, colat):
     return out
 
 
+def acceleration_design_matrix(xyz, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, as_tensor=False):
+    """
+    Design matrix A [3 M, P] of the gravitational acceleration at the cartesian positions xyz (M, 3) with respect to the coefficients
+    of degrees min_degree .. max_degree: row 3 i + c is component c at point i, the columns follow utilities.ravel_coefficients, so
+    that ``A @ ravel_coefficients(anm, min_degree, max_degree)`` equals ``gravitational_acceleration(xyz).ravel()`` of a field without
+    coefficients below min_degree.  Always computed on the GPU (shg_acceleration_design; there is no host implementation); weights
+    (M,) per point or (M, 3) per component scale the rows by sqrt(w).  Returns an ndarray, or the float64 device tensor with
+    as_tensor=True.  The kernel builds the transposed matrix (engine.acceleration_design, what NormalEquations.from_accelerations
+    accumulates block by block); the transposition here is a copy meant for modest sizes.
+    """
+    At = engine.acceleration_design(max_degree, xyz, GM, R, min_degree, weights)
+    A = At.permute(2, 1, 0).reshape(3 * At.shape[2], At.shape[0])
+    return A if as_tensor else engine.to_host(A)
+
+
 def synthesize(anm_batch, grid, kernel='ewh', GM=3.9860044150e+14, R=6.3781363000e+06):
     """
     Batched synthesis: anm_batch [B, N+1, N+1] (ndarray or device tensor) -> device tensor

@@ -548,6 +548,60 @@ class NormalEquations:
         self.observation_square_sum, self.observation_count = observation_square_sum, observation_count
         self.status = 'normal_matrix'
 
+    DESIGN_BLOCK_BYTES = 256 << 20      # budget of one block of the transposed design matrix in from_accelerations
+
+    @classmethod
+    def from_accelerations(cls, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
+        """
+        Normal equations of the coefficients of degrees min_degree .. max_degree (in the order of utilities.ravel_coefficients) from
+        accelerations g [M, 3] observed at the cartesian positions xyz [M, 3] (host arrays or device tensors; g is usually reduced by
+        a reference field).  weights [M] per point or [M, 3] per component (finite, >= 0; default 1) are those of the observations.
+
+        The points are taken in blocks of `block_points` (default: the largest multiple of 256 that keeps a block of the design
+        matrix within 256 MB, at least 256).  Per block the transposed design matrix At [P, 3 Mb], scaled by sqrt(w), comes from
+        shg_acceleration_design, and N += At At^T, n += At (sqrt(w) g) and l^T P l += |sqrt(w) g|^2 run on the fp64 MFMA product
+        (both triangles of N are computed; the upper one is mirrored at the end, so that N is exactly symmetric).
+
+        Returns NormalEquations with a one-block BlockMatrix [P, P] and the right-hand side [P, 1] on the device, and
+        observation_count = 3 M: components of zero weight still count as observations.
+        """
+        min_degree, max_degree = int(min_degree), int(max_degree)
+        if min_degree < 0 or min_degree > max_degree:
+            raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
+        for name, array in (('positions', xyz), ('accelerations', g)):
+            if len(array.shape) != 2 or array.shape[1] != 3:
+                raise ValueError('{0} must have shape (M, 3), got {1}'.format(name, tuple(array.shape)))
+        M = int(xyz.shape[0])
+        if int(g.shape[0]) != M:
+            raise ValueError('{0} positions but {1} accelerations'.format(M, int(g.shape[0])))
+        layout = engine.check_observation_weights(weights, M)
+        P = (max_degree + 1) ** 2 - min_degree ** 2
+        if block_points is None:
+            block_points = max(cls.DESIGN_BLOCK_BYTES // (24 * P) // 256 * 256, 256)
+        block_points = int(block_points)
+        if block_points < 1:
+            raise ValueError('block_points must be positive, got {0}'.format(block_points))
+
+        torch = engine.require_gpu()
+        x, l = engine.to_device(xyz), engine.to_device(g)
+        if layout:
+            w = engine.to_device(weights)
+            l = l * torch.sqrt(w if layout == 2 else w[:, None])
+        normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
+        for first in range(0, M, block_points):
+            last = min(first + block_points, M)
+            At = engine.acceleration_design(max_degree, x[first:last], GM, R, min_degree, None if not layout else w[first:last])
+            At = At.reshape(P, 3 * (last - first))
+            lb = l[first:last].t().reshape(-1, 1)                      # component-major, as the columns of At
+            engine.gemm(At, At, transb=True, beta=1.0, out=normals)
+            engine.gemm(At, lb, beta=1.0, out=side)
+            engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
+        normals.triu_()
+        normals.add_(torch.triu(normals, 1).t())
+        matrix = BlockMatrix([0, P], [0, P])
+        matrix._set_device(0, 0, normals)
+        return cls(matrix, side, float(square_sum.item()), 3 * M)
+
     def __cholesky(self):
         """factor the matrix once; a matrix that already holds covariances cannot be factored again (ValueError, as upstream)"""
         if self.status == 'covariance_matrix' or self.status not in ('normal_matrix', 'cholesky_factor'):

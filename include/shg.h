@@ -454,6 +454,26 @@ int shg_gravitational_gradients_points(int N, const double* xyz, int M, int layo
 int shg_gravitational_gradients_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM,
                                           double R, double* T, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Design matrix of the gravitational acceleration at points (the partial derivatives of shg_acceleration_points with respect to
+ * the coefficients; no reference counterpart)
+ *   At [P][3][ldt], transposed: row p is coefficient p of utilities.ravel_coefficients(., min_degree, N) (C_n0, C_n1, S_n1, C_n2, ...
+ *   for n = min_degree .. N; P = (N+1)^2 - min_degree^2, the column order of shg_synthesis_matrix), then the component x, y, z, then
+ *   the M points xyz [M][3] innermost (ldt >= M; the entries from M to ldt of a row are not touched).  For a field without
+ *   coefficients below min_degree, sum_p At[p][c][i] x_p = g[i][c] of shg_acceleration_points.
+ *   Every entry is one or two products of a solid harmonic of degree n + 1 with a constant: a first kernel writes the solid harmonics
+ *   of degree N + 1 of a pass of points to a workspace (at most 256 MB per pass), a second forms the rows from them.
+ *   weights: SHG_WEIGHTS_NONE (weights is not read), SHG_WEIGHTS_POINT w [M] or SHG_WEIGHTS_COMPONENT w [M][3], finite and >= 0:
+ *   the entries of point i (component c) are multiplied by sqrt(w), as the last operation.
+ *   No atomics: the entries of a point do not depend on the other points of the call, and repeated calls are bitwise equal.  Points
+ *   at the poles and below R are fine; r = 0 is not.
+ *   Arguments are checked before the first HIP call (negative sizes, min_degree > N, N > 32766, NULL pointers, GM or R not finite,
+ *   R <= 0, ldt < M, more than 2^40 values of At); M = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+enum { SHG_WEIGHTS_NONE = 0, SHG_WEIGHTS_POINT = 1, SHG_WEIGHTS_COMPONENT = 2 };
+int shg_acceleration_design(int N, int min_degree, const double* xyz, int M, const double* weights, int weight_layout, double GM, double R,
+                            double* At, int ldt, void* stream);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
