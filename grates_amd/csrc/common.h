@@ -250,6 +250,11 @@ __device__ inline double swap_half_row(double x) {
 }
 
 constexpr int kRotMaxClasses = 6; // classes r = 0 .. R / 2 of the rotation-folded synthesis kernel, R <= 10
+// Order pruning of that kernel (synthesis_rot.hip): one record of kRotLevelInts ints per latitude block,
+//   [0] npieces  [1] nslot  [2] nrec  [3] ntrip  [4] first trig piece of the level's stream  [5] first record of its item table
+//   [8 ..] cls_nk[kRotMaxClasses]  [14 ..] cls_cnt[kRotMaxClasses]
+constexpr int kRotLevelInts = 24;
+constexpr int kRotPruneMaxDegree = 128;   // cut-offs are worked out for plans up to this degree (the panel of that kernel fits the LDS up to ~110)
 constexpr int kEpochTile = 8;    // epochs handled together by one wave of the Legendre stage
 constexpr int kLatTile = 64;     // parallels per wave of the Legendre stage (lane <-> parallel)
 
@@ -263,7 +268,15 @@ struct shg_plan {
     bool sym4 = false;      // 4-fold longitude symmetry path
     int rotR = 0;           // rotations of the meridian set used by the rotation-folded kernel (synthesis_rot.hip): 10, 9, 6, 3 or 0 = not applicable
     std::vector<double> lon_host;   // meridians as given (the trig stream of that kernel is rebuilt when shg_plan_set_rotations changes R)
-    shg::DeviceArray<double> rot_trig; // [column tiles][k-steps][64 lanes][2] cos / signed sin stream of that kernel
+    shg::DeviceArray<double> rot_trig; // [column tiles][k-steps][64 lanes][2] cos / signed sin stream of that kernel, one per level of rot_level_set
+    // order pruning of that kernel: a latitude block near a pole keeps the orders 0 .. level only (synthesis_rot.hip)
+    bool order_pruning = true;        // shg_plan_set_order_pruning
+    std::vector<int> rot_levels;      // per latitude block of that kernel: largest order kept (N = everything)
+    std::vector<int> rot_level_set;   // the distinct levels, N first, then descending: one layout, trig stream and item table each
+    std::vector<int> rot_trig_piece;  // per level: first piece of its trig stream in rot_trig
+    std::vector<int> rot_item_rec, rot_item_nrec, rot_item_ntrip;   // per level: first record / records per wave / trips of its item table in itemtab_d
+    shg::DeviceArray<int> rot_levtab_d;   // [2][blocks][kRotLevelInts]: the level records of the blocks with pruning on, then off (every block at N)
+    bool rot_levtab_valid = false;
     bool sym_ns = false;    // parallels (colatitude and kn rows) symmetric about the equator
     int ngroups = 1;        // 4 (sym4) or 1
     int goff[5] = {0, 0, 0, 0, 0};   // first K slot of each group (multiples of 4), goff[ngroups] = K
@@ -365,6 +378,10 @@ int rot_layout(int R, int N, int nk[kRotMaxClasses], int cnt[kRotMaxClasses], st
 int rot_choose(int nlon, const double* lon_h, int N);
 int rot_applicable(const shg_plan* p);
 int build_rot_trig(shg_plan* p, const double* lon_h);
+void rot_order_cutoffs(int N, int nlat, const double* colat, const double* kn, bool ns, std::vector<int>& levels);
+std::vector<int> rot_level_list(int N, const std::vector<int>& levels);
+void rot_trig_stream(int R, int N, int level, int nlon, const double* lon_h, std::vector<double>& tab);
+void item_table_host(const shg_plan* p, int N, int level, int od, const std::vector<int>& qoff, int rotR, std::vector<int>& table, int& nrec, int& ntrip);
 int synthesis_rot(shg_plan* p, const double* anm, int B, double* grid, hipStream_t stream);
 int rot_kernel_waves();           // waves per workgroup of the rotation-folded kernel
 int rot_set_stage_limit(shg_plan* p, int limit);

@@ -425,6 +425,11 @@ extern "C" int shg_plan_create(shg_plan** out, int N, int nlat, const double* co
     // rotation-folded kernel: the largest rotation count the meridians allow (0.25 degree grid: 10, 0.5 degree grid: 3)
     p->rotR = rot_choose(nlon, lon_h, N);
     p->lon_host.assign(lon_h, lon_h + nlon);
+    // order pruning of that kernel: cut-off level of every latitude block (the degrees it serves, N <~ 110, make this a few million flops)
+    if (N >= 1 && N <= kRotPruneMaxDegree) {
+        rot_order_cutoffs(N, nlat, colat_h, kn_h, p->sym_ns, p->rot_levels);
+        p->rot_level_set = rot_level_list(N, p->rot_levels);
+    }
 
     // ---- K slots of the longitude stage
     if (p->sym4) {
@@ -556,6 +561,73 @@ extern "C" int shg_plan_set_stage_limit(shg_plan* p, int limit) {
     SHG_REQUIRE(p != nullptr, "shg_plan_set_stage_limit: NULL plan");
     std::unique_lock<std::mutex> lock(p->mtx);
     return rot_set_stage_limit(p, limit);
+}
+
+extern "C" int shg_plan_set_order_pruning(shg_plan* p, int enable) {
+    SHG_REQUIRE(p != nullptr, "shg_plan_set_order_pruning: NULL plan");
+    SHG_REQUIRE(enable == 0 || enable == 1, "shg_plan_set_order_pruning: %d not in {0, 1}", enable);
+    std::unique_lock<std::mutex> lock(p->mtx);
+    p->order_pruning = enable != 0;
+    return SHG_OK;
+}
+
+extern "C" int shg_plan_order_cutoffs(const shg_plan* p, int* levels, int capacity, int* nblocks, int* enabled) {
+    SHG_REQUIRE(p != nullptr && nblocks != nullptr, "shg_plan_order_cutoffs: NULL argument");
+    SHG_REQUIRE(capacity >= 0 && (levels != nullptr || capacity == 0), "shg_plan_order_cutoffs: NULL table of %d entries", capacity);
+    const bool applies = rot_applicable(p) && !p->rot_levels.empty();
+    *nblocks = applies ? (int)p->rot_levels.size() : 0;
+    if (enabled) *enabled = applies && p->order_pruning ? 1 : 0;
+    for (int i = 0; i < *nblocks && i < capacity; ++i) levels[i] = p->rot_levels[i];
+    return SHG_OK;
+}
+
+extern "C" int shg_rot_order_cutoffs(int N, int nlat, const double* colat_h, const double* kn_h, int* levels, int capacity, int* nblocks) {
+    SHG_REQUIRE(N >= 1 && N <= kRotPruneMaxDegree, "shg_rot_order_cutoffs: degree %d out of range [1, %d]", N, kRotPruneMaxDegree);
+    SHG_REQUIRE(nlat > 0 && colat_h && kn_h && nblocks, "shg_rot_order_cutoffs: NULL or empty table");
+    SHG_REQUIRE(capacity >= 0 && (levels != nullptr || capacity == 0), "shg_rot_order_cutoffs: NULL table of %d entries", capacity);
+    std::vector<int> badmap, lv;
+    std::vector<char> badrow;
+    int nbad = 0;
+    const bool ns = has_north_south_symmetry(N, nlat, colat_h, kn_h, badmap, nbad, badrow);
+    rot_order_cutoffs(N, nlat, colat_h, kn_h, ns, lv);
+    *nblocks = (int)lv.size();
+    for (int i = 0; i < *nblocks && i < capacity; ++i) levels[i] = lv[i];
+    return SHG_OK;
+}
+
+extern "C" int shg_rot_level_tables(int R, int N, int level, int ns, int nlon, const double* lon_h, int32_t header[24], double* trig, int64_t trig_capacity,
+                                    int32_t* items, int64_t items_capacity) {
+    SHG_REQUIRE(R == 3 || R == 6 || R == 9 || R == 10, "shg_rot_level_tables: %d rotations not in {3, 6, 9, 10}", R);
+    SHG_REQUIRE(N >= 1 && N <= kRotPruneMaxDegree && level >= 1 && level <= N, "shg_rot_level_tables: level %d of degree %d out of range", level, N);
+    SHG_REQUIRE(nlon >= 2 * R && nlon % (2 * R) == 0 && lon_h && header, "shg_rot_level_tables: NULL table or nlon %d no multiple of %d", nlon, 2 * R);
+    SHG_REQUIRE(trig_capacity >= 0 && items_capacity >= 0 && (trig || trig_capacity == 0) && (items || items_capacity == 0), "shg_rot_level_tables: NULL table");
+    for (int i = 0; i < kRotLevelInts; ++i) header[i] = 0;
+    int nk[kRotMaxClasses], cnt[kRotMaxClasses];
+    header[1] = rot_layout(R, level, nk, cnt, nullptr);
+    header[0] = header[1] / 4;
+    for (int c = 0; c < kRotMaxClasses; ++c) {
+        header[8 + c] = nk[c];
+        header[8 + kRotMaxClasses + c] = cnt[c];
+    }
+    std::vector<double> tab;
+    rot_trig_stream(R, N, level, nlon, lon_h, tab);
+    const int od = ns ? 16 : 8;
+    std::vector<int> qoff(N + 2), table;
+    int q = 0;
+    for (int m = 0; m <= N; ++m) {
+        qoff[m] = q;
+        q += (N + 1 - m + od - 1) / od;
+    }
+    qoff[N + 1] = q;
+    int nrec = 0, ntrip = 0;
+    item_table_host(nullptr, N, level, od, qoff, R, table, nrec, ntrip);
+    header[2] = nrec;
+    header[3] = ntrip;
+    header[4] = (int32_t)(tab.size() / 128);          // pieces of the stream, the spare one included
+    header[5] = (int32_t)(table.size() / 4);          // records of the item table
+    for (size_t i = 0; i < tab.size() && (int64_t)i < trig_capacity; ++i) trig[i] = tab[i];
+    for (size_t i = 0; i < table.size() && (int64_t)i < items_capacity; ++i) items[i] = table[i];
+    return SHG_OK;
 }
 
 extern "C" int shg_plan_set_rotations(shg_plan* p, int R) {

@@ -655,28 +655,34 @@ int build_pkf_table(shg_plan* p, bool ns, int rotR, hipStream_t stream) {
 //   z    = panel slot of the cosine part | (panel slot of the sine part + 1) << 16   (0 in the upper half: order 0)
 //   w    = bit 0 item valid, bit 1 second octet valid, bit 2 last item of its order
 // padded per wave to 4 * ntrip + 8 records (the kernel runs ntrip trips of four items and prefetches one trip ahead).
-static int build_item_table(shg_plan* p, int od, const std::vector<int>& qoff, int rotR, hipStream_t stream) {
-    const int N = p->N;
+// `level`: the orders 0 .. level only (rotation-folded kernel with order pruning: the panel slots are those of that level's layout;
+// the orders are dealt in ascending order, so a level's lists are the front of the full ones).
+void item_table_host(const shg_plan* p, int N, int level, int od, const std::vector<int>& qoff, int rotR, std::vector<int>& table, int& nrec, int& ntrip) {
     std::vector<int> slot16;
     if (rotR) {
         int nk[kRotMaxClasses], cn[kRotMaxClasses];
-        rot_layout(rotR, N, nk, cn, &slot16);
+        rot_layout(rotR, level, nk, cn, &slot16);
     }
     const int nw = rotR ? rot_kernel_waves() : 8;        // waves that share the orders of a tile
     std::vector<std::vector<int>> rec(nw);
     size_t longest = 0;
-    for (int m = 0; m <= N; ++m) {                       // orders by decreasing length, each to the wave with the fewest items so far
+    for (int m = 0; m <= level; ++m) {                   // orders by decreasing length, each to the wave with the fewest items so far
         {
             int w = 0;
             for (int v = 1; v < nw; ++v)
                 if (rec[v].size() < rec[w].size()) w = v;
             const int cnt = N + 1 - m, q = (cnt + od - 1) / od;
-            // panel slots (+1 for the sine part, 0 = none).  With order 0 folded out of the K loop (fold0) it sits behind the groups.
-            const int* go = p->fold0 ? p->goff_f : p->goff;
-            const int even_shift = p->fold0 ? 1 : 0;
-            const int slot_c = m == 0 && p->fold0 ? p->K_f : go[m & 1] + (m >> 1) - ((m & 1) ? 0 : even_shift);
-            const int slot_s = m >= 1 ? go[2 + (m & 1)] + ((m & 1) ? (m >> 1) : (m >> 1) - 1) + 1 : 0;
-            const int zrec = rotR ? slot16[m] : (slot_c | (slot_s << 16));
+            int zrec;
+            if (rotR)
+                zrec = slot16[m];
+            else {
+                // panel slots (+1 for the sine part, 0 = none).  With order 0 folded out of the K loop (fold0) it sits behind the groups.
+                const int* go = p->fold0 ? p->goff_f : p->goff;
+                const int even_shift = p->fold0 ? 1 : 0;
+                const int slot_c = m == 0 && p->fold0 ? p->K_f : go[m & 1] + (m >> 1) - ((m & 1) ? 0 : even_shift);
+                const int slot_s = m >= 1 ? go[2 + (m & 1)] + ((m & 1) ? (m >> 1) : (m >> 1) - 1) + 1 : 0;
+                zrec = slot_c | (slot_s << 16);
+            }
             for (int j0 = 0; j0 < q; j0 += 2) {
                 const int o0 = qoff[m] + j0, o1 = o0 + (j0 + 1 < q ? 1 : 0);
                 const int flags = 1 | ((j0 + 1) * od < cnt ? 2 : 0) | (j0 + 2 >= q ? 4 : 0);
@@ -685,15 +691,9 @@ static int build_item_table(shg_plan* p, int od, const std::vector<int>& qoff, i
         }
     }
     for (int w = 0; w < nw; ++w) longest = std::max(longest, rec[w].size() / 4);
-    // octet -> (order, octet inside the order) for the gather repack
-    std::vector<int> octinfo((size_t)qoff[N + 1], 0);
-    for (int m = 0; m <= N; ++m)
-        for (int o = qoff[m]; o < qoff[m + 1]; ++o) octinfo[o] = m | ((o - qoff[m]) << 8);
-    if (p->octinfo_d) SHG_HIP(hipDeviceSynchronize());
-    if (p->octinfo_d.assign(std::max<size_t>(octinfo.size(), 1)) != hipSuccess) return fail(SHG_ERR_NOMEM, "octet table allocation failed");
-    SHG_HIP(hipMemcpy(p->octinfo_d.get(), octinfo.data(), octinfo.size() * sizeof(int), hipMemcpyHostToDevice));
-    const int ntrip = (int)((longest + 3) / 4), nrec = 4 * ntrip + 8;
-    std::vector<int> table((size_t)nw * nrec * 4, 0);
+    ntrip = (int)((longest + 3) / 4);
+    nrec = 4 * ntrip + 8;
+    table.assign((size_t)nw * nrec * 4, 0);
     for (int w = 0; w < nw; ++w) {
         const int pad = rec[w].empty() ? 0 : rec[w][0];              // a valid octet for the padding records
         for (int t = 0; t < nrec; ++t)
@@ -702,13 +702,41 @@ static int build_item_table(shg_plan* p, int od, const std::vector<int>& qoff, i
                 table[((size_t)w * nrec + t) * 4 + c] = src < rec[w].size() ? rec[w][src] : (c < 2 ? pad : 0);
             }
     }
+}
+
+static int build_item_table(shg_plan* p, int od, const std::vector<int>& qoff, int rotR, hipStream_t stream) {
+    const int N = p->N;
+    // octet -> (order, octet inside the order) for the gather repack
+    std::vector<int> octinfo((size_t)qoff[N + 1], 0);
+    for (int m = 0; m <= N; ++m)
+        for (int o = qoff[m]; o < qoff[m + 1]; ++o) octinfo[o] = m | ((o - qoff[m]) << 8);
+    if (p->octinfo_d) SHG_HIP(hipDeviceSynchronize());
+    if (p->octinfo_d.assign(std::max<size_t>(octinfo.size(), 1)) != hipSuccess) return fail(SHG_ERR_NOMEM, "octet table allocation failed");
+    SHG_HIP(hipMemcpy(p->octinfo_d.get(), octinfo.data(), octinfo.size() * sizeof(int), hipMemcpyHostToDevice));
+    // rotation-folded kernel: one table per pruning level behind each other, the full one (level N) first
+    const std::vector<int> full(1, N);
+    const std::vector<int>& levels = rotR && !p->rot_level_set.empty() ? p->rot_level_set : full;
+    std::vector<int> table, first, nrecs, ntrips;
+    for (int level : levels) {
+        std::vector<int> t;
+        int nrec = 0, ntrip = 0;
+        item_table_host(p, N, level, od, qoff, rotR, t, nrec, ntrip);
+        first.push_back((int)(table.size() / 4));
+        nrecs.push_back(nrec);
+        ntrips.push_back(ntrip);
+        table.insert(table.end(), t.begin(), t.end());
+    }
     if (p->itemtab_d) SHG_HIP(hipDeviceSynchronize());
     if (p->itemtab_d.assign(table.size()) != hipSuccess) return fail(SHG_ERR_NOMEM, "work item table allocation failed");
     SHG_HIP(hipMemcpyAsync(p->itemtab_d.get(), table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     SHG_HIP(hipStreamSynchronize(stream));                             // the host vector goes out of scope
-    p->itemtab_nrec = nrec;
+    p->itemtab_nrec = nrecs[0];
     p->itemtab_rot = rotR;
-    p->itemtab_ntrip = ntrip;
+    p->itemtab_ntrip = ntrips[0];
+    p->rot_item_rec = first;
+    p->rot_item_nrec = nrecs;
+    p->rot_item_ntrip = ntrips;
+    p->rot_levtab_valid = false;
     return SHG_OK;
 }
 

@@ -95,6 +95,8 @@ struct RotParams {
     const int* blockmap;
     const int* badmap;
     const double* trig;       // [column tile][npieces][64 lanes][2]: (cos(m mu), s_m sin(m mu)) of order slot 4 ks + lane / 16, column 16 ct + lane % 16
+    const int* levtab;        // [nit][kRotLevelInts] order pruning: layout, trig stream and item table of every latitude block (common.h); the fields
+                              // npieces, cls_nk, cls_cnt, nslot, nrec, ntrip, trig and itemtab above hold the full level and are replaced by the block's
     double* G;
 };
 
@@ -695,9 +697,29 @@ __global__ __launch_bounds__(128 * EP) void synthesis_rot_kernel(RotParams P) {
 
     double2_t* const panel = reinterpret_cast<double2_t*>(As + NW * kRingSlots * 128);      // [(slot * PR + row)], behind the rings of the waves
 
+    // ---- order pruning: the layout, trig stream and item table of this latitude block (a polar block keeps the orders up to its level
+    //      only and uses the front slots of the panel, its order-0 slot behind them).  Scalar loads of wave-uniform values, once; from
+    //      here on the kernel runs on them as it did on the launch parameters.
+    {
+        typedef int int4_v __attribute__((ext_vector_type(4)));
+        typedef const int4_v __attribute__((address_space(4))) clev_t;
+        static_assert(kMaxClasses == 6 && kRotLevelInts == 24, "level record layout");
+        clev_t* lv = reinterpret_cast<clev_t*>(reinterpret_cast<unsigned long long>(P.levtab + (size_t)__builtin_amdgcn_readfirstlane(it) * kRotLevelInts));
+        const int4_v h = lv[0], o = lv[1], a = lv[2], b = lv[3], c = lv[4];
+        P.npieces = h.x;
+        P.nslot = h.y;
+        P.nrec = h.z;
+        P.ntrip = h.w;
+        P.trig += (size_t)o.x * 128;
+        P.itemtab += o.y;
+        P.cls_nk[0] = a.x, P.cls_nk[1] = a.y, P.cls_nk[2] = a.z, P.cls_nk[3] = a.w, P.cls_nk[4] = b.x, P.cls_nk[5] = b.y;
+        P.cls_cnt[0] = b.z, P.cls_cnt[1] = b.w, P.cls_cnt[2] = c.x, P.cls_cnt[3] = c.y, P.cls_cnt[4] = c.z, P.cls_cnt[5] = c.w;
+    }
+
     // ---- zero the padding slots of the panel
     {
         int s0 = 0;
+#pragma unroll
         for (int c = 0; c < T::kClasses; ++c) {
             for (int s = s0 + P.cls_cnt[c]; s < s0 + 4 * P.cls_nk[c]; ++s)
                 if (tid < PR) panel[s * PR + tid] = (double2_t){0.0, 0.0};
@@ -851,16 +873,18 @@ int rot_choose(int nlon, const double* lon_h, int N) {
     return fallback;
 }
 
-// trig stream [nct][npieces][64][2] (+ one spare piece), built on the host like the other cos/sin tables (grates/utilities.py:272-273)
-int build_rot_trig(shg_plan* p, const double* lon_h) {
-    const int R = p->rotR, N = p->N, nlon = p->nlon, nd = nlon / (2 * R), nct = ceil_div(nd, 16);
+// trig stream [nct][npieces][64][2] (+ one spare piece) of the orders 1 .. level, built on the host like the other cos/sin tables
+// (grates/utilities.py:272-273)
+void rot_trig_stream(int R, int N, int level, int nlon, const double* lon_h, std::vector<double>& tab) {
+    (void)N;
+    const int nd = nlon / (2 * R), nct = ceil_div(nd, 16);
     int nk[kMaxClasses], cnt[kMaxClasses];
     std::vector<int> order_slot;
-    const int nslot = rot_layout(R, N, nk, cnt, &order_slot);
+    const int nslot = rot_layout(R, level, nk, cnt, &order_slot);
     const int npieces = nslot / 4;
     std::vector<int> slot_order(nslot, -1);
-    for (int m = 1; m <= N; ++m) slot_order[order_slot[m]] = m;
-    std::vector<double> tab(((size_t)nct * npieces + 1) * 128, 0.0);
+    for (int m = 1; m <= level; ++m) slot_order[order_slot[m]] = m;
+    tab.assign(((size_t)nct * npieces + 1) * 128, 0.0);
     for (int ct = 0; ct < nct; ++ct)
         for (int ks = 0; ks < npieces; ++ks)
             for (int l = 0; l < 64; ++l) {
@@ -873,7 +897,111 @@ int build_rot_trig(shg_plan* p, const double* lon_h) {
                 dst[0] = std::cos(arg);
                 dst[1] = sg * std::sin(arg);
             }
-    return upload(p->rot_trig, tab);
+}
+
+// The streams of all levels of the plan behind each other (each with its spare piece), the full one first.
+int build_rot_trig(shg_plan* p, const double* lon_h) {
+    const std::vector<int> full(1, p->N);
+    const std::vector<int>& levels = p->rot_level_set.empty() ? full : p->rot_level_set;
+    std::vector<double> all, tab;
+    p->rot_trig_piece.clear();
+    for (int level : levels) {
+        rot_trig_stream(p->rotR, p->N, level, p->nlon, lon_h, tab);
+        p->rot_trig_piece.push_back((int)(all.size() / 128));
+        all.insert(all.end(), tab.begin(), tab.end());
+    }
+    p->rot_levtab_valid = false;
+    return upload(p->rot_trig, all);
+}
+
+// Order pruning.  P_nm(theta) ~ sin^m theta: on a parallel close to a pole the orders above some m_c contribute nothing that an fp64
+// sum can hold.  Per parallel, m_c is the largest order of which any degree reaches |kn P_nm| >= tau x the parallel's largest |kn P_nm|
+// over all (n, m); a latitude block of the kernel (8 northern parallels and their mirror images, or 16 parallels without the north-south
+// symmetry) takes the largest m_c of its parallels, rounded up to a level: the orders 0 .. level with level + 1 a multiple of
+// kRotLevelStep, at most N.  The cut-off depends on the colatitudes, kn and N only, never on the coefficients.
+// tau = 1e-30: a dropped term is at most tau x the parallel's largest factor M times a coefficient, and there are fewer than (N + 1)^2 < 2e4
+// of them (N <= kRotPruneMaxDegree), so what is dropped is below 2e-26 M max|c|.  The grid values of that parallel are sums of factors up
+// to M times coefficients: unless the coefficients that meet the large factors are 1e10 times smaller than those of the dropped orders,
+// that is 1e-10 of the rounding unit (1.1e-16) of the values themselves and 1e-14 of the project's tolerance (1e-12 of the field maximum).
+constexpr double kRotPruneTau = 1e-30;
+constexpr int kRotLevelStep = 10;
+
+void rot_order_cutoffs(int N, int nlat, const double* colat, const double* kn, bool ns, std::vector<int>& levels) {
+    const int nh = nlat / 2;
+    const int nit = ns ? ceil_div(nh, 8) : ceil_div(nlat, 16);
+    levels.assign(nit, 0);
+    std::vector<double> a, b, big(N + 1);
+    recursion_tables(N, a, b);
+    for (int i = 0; i < nlat; ++i) {
+        const double t = std::cos(colat[i]), st = std::sin(colat[i]);
+        const double* k = kn + (size_t)i * (N + 1);
+        double pmm = 1.0, all = 0.0;
+        bool finite = true;
+        for (int m = 0; m <= N; ++m) {
+            if (m == 1) pmm = std::sqrt(3.0) * st;
+            if (m > 1) pmm = std::sqrt((2.0 * m + 1.0) / (2.0 * m)) * st * pmm;
+            const int off = order_offset(N, m);
+            double p1 = pmm, p2 = 0.0, mx = std::fabs(p1 * k[m]);
+            for (int n = m + 1; n <= N; ++n) {
+                const double pn = (a[off + n - m] * t) * p1 - b[off + n - m] * p2;
+                p2 = p1;
+                p1 = pn;
+                const double v = std::fabs(pn * k[n]);
+                if (!(v <= mx)) mx = v;                      // (keeps a NaN)
+            }
+            big[m] = mx;
+            if (!std::isfinite(mx)) finite = false;
+            if (mx > all) all = mx;
+        }
+        int mc = N;                                          // nothing to compare with: keep everything
+        if (finite && all > 0.0) {
+            mc = 0;
+            for (int m = N; m >= 1; --m)
+                if (big[m] >= kRotPruneTau * all) {
+                    mc = m;
+                    break;
+                }
+        }
+        const int block = ns ? (i < nh ? i : nlat - 1 - i) >> 3 : i >> 4;
+        if (block < nit) levels[block] = std::max(levels[block], mc);
+    }
+    for (int& l : levels) l = std::min(N, ceil_div(l + 1, kRotLevelStep) * kRotLevelStep - 1);
+}
+
+// the distinct levels of a plan: N first (the full tables, which a plan with pruning off uses for every block), then descending
+std::vector<int> rot_level_list(int N, const std::vector<int>& levels) {
+    std::vector<int> set(levels);
+    set.push_back(N);
+    std::sort(set.begin(), set.end(), [](int x, int y) { return x > y; });
+    set.erase(std::unique(set.begin(), set.end()), set.end());
+    return set;
+}
+
+// level records of the latitude blocks (common.h: kRotLevelInts), pruning on, then off
+static int build_rot_levtab(shg_plan* p, int R, int nit) {
+    if (p->rot_levtab_valid && p->rot_levtab_d.size() == (size_t)2 * nit * kRotLevelInts) return SHG_OK;
+    const std::vector<int>& set = p->rot_level_set;
+    if ((int)p->rot_levels.size() != nit || set.empty() || set[0] != p->N || p->rot_trig_piece.size() != set.size() || p->rot_item_rec.size() != set.size())
+        return fail(SHG_ERR_INVALID, "rotation-folded synthesis kernel: the level tables of the plan are incomplete");
+    std::vector<int> tab((size_t)2 * nit * kRotLevelInts, 0);
+    for (int off = 0; off < 2; ++off)
+        for (int it = 0; it < nit; ++it) {
+            const int level = off ? p->N : p->rot_levels[it];
+            const size_t l = std::find(set.begin(), set.end(), level) - set.begin();
+            if (l >= set.size()) return fail(SHG_ERR_INVALID, "rotation-folded synthesis kernel: level %d has no tables", level);
+            int* rec = &tab[((size_t)off * nit + it) * kRotLevelInts];
+            rec[1] = rot_layout(R, level, rec + 8, rec + 8 + kMaxClasses, nullptr);
+            rec[0] = rec[1] / 4;
+            rec[2] = p->rot_item_nrec[l];
+            rec[3] = p->rot_item_ntrip[l];
+            rec[4] = p->rot_trig_piece[l];
+            rec[5] = p->rot_item_rec[l];
+        }
+    if (p->rot_levtab_d) SHG_HIP(hipDeviceSynchronize());
+    const int rc = upload(p->rot_levtab_d, tab);
+    if (rc) return rc;
+    p->rot_levtab_valid = true;
+    return SHG_OK;
 }
 
 template <int R>
@@ -933,6 +1061,9 @@ int synthesis_rot(shg_plan* p, const double* anm, int B, double* grid, hipStream
         P.blockmap = p->blockmap_d.get();
     }
     P.trig = p->rot_trig.get();
+    rc = build_rot_levtab(p, R, nit);
+    if (rc) return rc;
+    P.levtab = p->rot_levtab_d.get() + (p->order_pruning ? 0 : (size_t)nit * kRotLevelInts);
     P.G = grid;
 #ifdef SHG_TIMELINE
     P.tl = getenv("SHG_TIMELINE_PTR") ? (unsigned long long*)strtoull(getenv("SHG_TIMELINE_PTR"), nullptr, 0) : nullptr;

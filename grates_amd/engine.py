@@ -89,8 +89,13 @@ class Plan:
     def info(self):
         arr = (ctypes.c_int64 * 8)()
         _lib.call('shg_plan_info', self._handle, arr)
+        nblocks, enabled = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.call('shg_plan_order_cutoffs', self._handle, None, 0, ctypes.byref(nblocks), ctypes.byref(enabled))
+        levels = (ctypes.c_int * max(nblocks.value, 1))()
+        _lib.call('shg_plan_order_cutoffs', self._handle, levels, nblocks.value, ctypes.byref(nblocks), ctypes.byref(enabled))
         return {'max_degree': arr[0], 'nlat': arr[1], 'nlon': arr[2], 'fourfold_symmetry': bool(arr[3] & 1), 'north_south_symmetry': bool(arr[3] & 2),
-                'rotation_symmetry': bool(arr[3] & 4), 'epochs_per_pass': arr[4], 'k_slots': arr[5], 'fused': bool(arr[6]), 'path': int(arr[7]) & 0xff, 'rotations': int(arr[7]) >> 8}
+                'rotation_symmetry': bool(arr[3] & 4), 'epochs_per_pass': arr[4], 'k_slots': arr[5], 'fused': bool(arr[6]), 'path': int(arr[7]) & 0xff, 'rotations': int(arr[7]) >> 8,
+                'order_pruning': bool(enabled.value), 'order_cutoffs': [int(levels[i]) for i in range(nblocks.value)]}
 
     def set_path(self, path):
         """'auto', 'staged' (three kernels, any grid), 'fused' (single kernel on 4-fold symmetric meridians), 'fused32' (32-row
@@ -102,6 +107,11 @@ class Plan:
         """Rotation-folded kernel only: at most `limit` workgroups in their Legendre stage at once (< 0: sixteenths of the CUs, 0 = off,
         the default).  A tuning knob whose sign differs between boxes (include/shg.h)."""
         _lib.call('shg_plan_set_stage_limit', self._handle, int(limit))
+
+    def set_order_pruning(self, enable):
+        """Rotation-folded kernel only: latitude blocks next to a pole skip the orders that cannot reach them (on by default; off
+        for comparisons).  `info()['order_cutoffs']` lists the largest order every block keeps."""
+        _lib.call('shg_plan_set_order_pruning', self._handle, 1 if enable else 0)
 
     def set_rotations(self, R):
         """Rotation count of the rotation-folded kernel: 0 (the plan's own choice), 3, 6, 9 or 10; the meridians must be invariant

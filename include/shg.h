@@ -59,8 +59,9 @@ int shg_plan_set_chunk(shg_plan* plan, int epochs_per_pass);
 /* Synthesis path: 0 = automatic, 1 = three-kernel path (pack, Legendre stage, longitude stage; any grid, any degree),
  * 2 = single fused kernel (4-fold symmetric meridians, degree <= 126), 5 = fused kernel with 32-row panels (both symmetries,
  * degree <= ~210; chosen automatically above degree 126), 6 = single fused kernel for equi-angular cell-centred meridians that
- * folds the longitude stage over 6 (nlon a multiple of 96) or 3 (nlon a multiple of 48) rotations and the reflection of the
- * meridian set (degree <= ~110; the automatic choice where it applies).  Kernels 2 and 6 use the north-south symmetry of the
+ * folds the longitude stage over 10, 9, 6 or 3 rotations (the first of these for which nlon is a multiple of 2 R and nlon / R a
+ * multiple of 16, see shg_plan_set_rotations) and the reflection of the meridian set (degree <= ~110; the automatic choice where
+ * it applies).  Kernels 2 and 6 use the north-south symmetry of the
  * parallels when the grid has it and their plain variant otherwise; the variant is not a choice of the caller. */
 int shg_plan_set_path(shg_plan* plan, int path);
 
@@ -75,6 +76,21 @@ int shg_plan_set_stage_limit(shg_plan* plan, int limit);
  * nlon / R a multiple of 16, and the panel of that count must fit the LDS.  Waits for the device (the tables are rebuilt).
  * shg_plan_info reports the count in use in bits 8.. of which[7]. */
 int shg_plan_set_rotations(shg_plan* plan, int R);
+
+/* Kernel 6 only: order pruning.  P_nm(theta) ~ sin^m theta, so a block of parallels next to a pole keeps the orders 0 .. level only,
+ * where no higher order has a term |kn P_nm| above 1e-30 of the largest term of any parallel of the block (levels end at 9, 19, ...
+ * and at N; they depend on the colatitudes, kn and N, not on the coefficients).  enable = 1 (the default; the grids measured bit-identical and the
+ * d/o-96 / 0.25 degree kernel 3.6 % faster on MI355X) or 0: every block keeps all orders, the launch of the kernel
+ * without pruning (for comparisons).  shg_plan_order_cutoffs reports the level of every latitude block of kernel 6 (8 northern parallels and
+ * their mirror images, or 16 parallels without the north-south symmetry; *nblocks = 0 where kernel 6 does not apply) and whether
+ * they are in use.  shg_rot_order_cutoffs works the same levels out from host tables alone, and shg_rot_level_tables builds the
+ * tables of one level (header: 24 ints -- k-steps, panel slots, item records per wave, trips, trig pieces, item records, 0, 0,
+ * k-steps of the 6 classes, orders of the 6 classes; trig stream [pieces][64][2]; work items [records][4]): neither needs a device. */
+int shg_plan_set_order_pruning(shg_plan* plan, int enable);
+int shg_plan_order_cutoffs(const shg_plan* plan, int* levels, int capacity, int* nblocks, int* enabled);
+int shg_rot_order_cutoffs(int N, int nlat, const double* colat_h, const double* kn_h, int* levels, int capacity, int* nblocks);
+int shg_rot_level_tables(int R, int N, int level, int ns, int nlon, const double* lon_h, int32_t header[24], double* trig,
+                         int64_t trig_capacity, int32_t* items, int64_t items_capacity);
 
 /* Introspection: which[0]=N, [1]=nlat, [2]=nlon, [3]=bit 0: 4-fold longitude symmetry, bit 1: parallels symmetric about the
  * equator, bit 2: the rotation-folded kernel (path 6) applies, [4]=epochs per pass, [5]=K slots of the longitude stage, [6]=1 if synthesis uses the fused kernel, [7]=path | rotation count of kernel 6 << 8. */
