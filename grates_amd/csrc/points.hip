@@ -187,12 +187,35 @@ static int upload_recursion_tables(Workspace& ws, int N, double*& tab, hipStream
     return SHG_OK;
 }
 
+// LDS one workgroup of the current device may be given (160 KB on CDNA4); 64 KB, what every launch gets without asking, when the
+// runtime does not say
+static size_t device_lds_bytes() {
+    int dev = 0, bytes = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return 64 * 1024;
+    }
+    return std::max<size_t>(64 * 1024, (size_t)bytes);
+}
+
 extern "C" int shg_synthesis_points(int N, const double* colat, const double* lon, const double* kn, int npts, const double* anm,
                                     int B, double* values, void* stream_) {
     SHG_REQUIRE(N >= 0 && npts >= 0 && B >= 0, "shg_synthesis_points: negative size");
     if (npts == 0 || B == 0) return SHG_OK;
     SHG_REQUIRE(colat && lon && kn && anm && values, "shg_synthesis_points: NULL pointer");
     hipStream_t stream = (hipStream_t)stream_;
+    // The recursion kernel stages the coefficients of one order, [N + 1][2][16] doubles = 256 (N + 1) bytes, in LDS: from d/o 256 on
+    // that is more than the 64 KB a launch gets without the opt-in, and from d/o 640 on more than a CDNA4 compute unit has -- such
+    // a series takes the GEMM path, however short it is.
+    const size_t slab = (size_t)(N + 1) * 2 * kPtEpochs * sizeof(double);
+    bool gemm_path = B >= 48;
+    if (!gemm_path && slab > 64 * 1024) {
+        const size_t lds_max = device_lds_bytes();
+        if (slab > lds_max)
+            gemm_path = true;
+        else
+            SHG_SET_LDS_ONCE(synthesis_points_kernel, lds_max);
+    }
     int rc = SHG_OK;
     {   // (workspaces are freed in the reverse order of their scopes: the chunk buffers, knT, the recursion table)
         Workspace tables = Workspace::plain(stream);
@@ -205,7 +228,7 @@ extern "C" int shg_synthesis_points(int N, const double* colat, const double* lo
         // Many epochs: values = Y X as one fp64 MFMA GEMM per chunk of points, with the rows of the spherical harmonic matrix
         // Y[pt][p] = PK[p][pt] cs[rank(p)][pt] generated inside the kernel from per-point tables (MODE_SYNTH of gemm.hip): the
         // recursion runs once per point instead of once per point and group of 16 epochs.
-        if (B >= 48) {
+        if (gemm_path) {
             const int Pfull = (N + 1) * (N + 1);
             const int chunk = point_chunk(npts, Pfull);
             Workspace ws = Workspace::plain(stream);
@@ -227,7 +250,7 @@ extern "C" int shg_synthesis_points(int N, const double* colat, const double* lo
                 }
             }
         } else {
-            hipLaunchKernelGGL(synthesis_points_kernel, dim3(ceil_div(npts, 64), ceil_div(B, kPtEpochs)), dim3(64), (size_t)(N + 1) * 2 * kPtEpochs * sizeof(double), stream, N, npts, B, colat, lon,
+            hipLaunchKernelGGL(synthesis_points_kernel, dim3(ceil_div(npts, 64), ceil_div(B, kPtEpochs)), dim3(64), slab, stream, N, npts, B, colat, lon,
                                knT, tab, tab + packed_count(N), anm, values);
         }
     }

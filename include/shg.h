@@ -114,7 +114,11 @@ int shg_synthesis(shg_plan* plan, const double* anm, int B, double* grid, void* 
 
 /* Point-list synthesis, one thread block per block of points
  *   replaces PotentialCoefficients.to_grid, AttributeError branch  (grates/gravityfield.py:370-388)
- *   colat, lon [npts]; kn [npts][N+1]; anm [B][N+1][N+1]; values [B][npts]                            */
+ *   colat, lon [npts]; kn [npts][N+1]; anm [B][N+1][N+1]; values [B][npts]
+ *   Any degree: fewer than 48 epochs run a recursion kernel that keeps 256 (N+1) bytes of coefficients in LDS, as long as the
+ *   device grants a workgroup that much (d/o 639 on CDNA4); beyond that, and from 48 epochs on, the values are one GEMM per
+ *   chunk of points with generated harmonic rows.  That path allocates its Legendre table, up to 2 GB per chunk, whatever
+ *   the number of epochs: a short series beyond the LDS limit pays for it.                                */
 int shg_synthesis_points(int N, const double* colat, const double* lon, const double* kn, int npts,
                          const double* anm, int B, double* values, void* stream);
 
