@@ -113,6 +113,9 @@ PROTOTYPES = {
                                               ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_void_p],
     'shg_acceleration_design': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                 c_double_p, ctypes.c_int, ctypes.c_void_p],
+    'shg_gradient_design': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_double,
+                            ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_void_p],
+    'shg_gradient_design_terms': [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), c_double_p, ctypes.c_longlong],
 }
 STRING_GETTERS = ('shg_last_error', 'shg_version')
 

@@ -15,6 +15,10 @@
 // writes Y [packed (n', k)][2][ldy] of degree N + 1 to a workspace; design_gather_kernel forms every row of At from at most two
 // entries of Y per component, following a host-built table of (slot of Y, factor) terms.  The table is all the gather kernel knows
 // about the acceleration: another linear functional of the solid harmonics is another table.
+//
+// The design matrix of the gradient tensor (second half of this file) is that other table, of at most four terms on Y of degree N + 2,
+// with a gather kernel of its own that rotates the six entries of a point into a per-point instrument frame and keeps only the
+// selected components.
 #include "common.h"
 
 #include <cmath>
@@ -23,7 +27,10 @@ namespace shg {
 
 // 256 lanes = 256 points.  (r, colatitude, longitude) come from xyz as grid.cartesian2spherical computes them (the operation order of
 // acceleration_points_kernel), (R/r)^(n'+1) is carried along the degree loop.  The recursion factors a, b of one (n', k) lie side by
-// side and are read with wave-uniform addresses: no LDS, whatever the degree.
+// side and are read with wave-uniform addresses: no LDS, whatever the degree.  kDirect takes cos and sin of the colatitude straight from
+// xyz (t = z / r, s = rho / r: the form of gradients_points_kernel, exact next to the axis) instead of the reference's
+// s = sqrt(1 - t^2), which the acceleration and its design matrix follow.
+template <bool kDirect>
 __global__ __launch_bounds__(256) void design_harmonics_kernel(int N1, int npts, const double* __restrict__ xyz, const double2* __restrict__ ab, double R,
                                                                double* __restrict__ Y, size_t ldy) {
     const int pt = blockIdx.x * 256 + threadIdx.x;
@@ -34,8 +41,8 @@ __global__ __launch_bounds__(256) void design_harmonics_kernel(int N1, int npts,
     const double th = atan2(sqrt(x * x + y * y), z);
     const double lam = atan2(y, x);
     const double u = R / r;
-    const double t = cos(th);
-    const double s = sqrt(1.0 - t * t);
+    const double t = kDirect ? z / r : cos(th);
+    const double s = kDirect ? sqrt(x * x + y * y) / r : sqrt(1.0 - t * t);
     double pmm = 1.0, rk = u;                                        // rk = (R/r)^(k+1)
     for (int k = 0; k <= N1; ++k) {
         if (k == 1)
@@ -130,6 +137,158 @@ static void acceleration_design_table(int N, int min_degree, std::vector<int>& s
     }
 }
 
+// ---- design matrix of the gradient tensor -------------------------------------------------------------------------------------------
+// T = d^2 V / dx_c dx_d is the acceleration's map D (head of gradients.hip) applied twice, so its partial derivative with respect to
+// one coefficient is a sum of at most four terms factor * Y[slot] on the solid harmonics of degree N + 2, in units of GM / (4 R^3):
+// D_c turns the unit coefficient (n, m, kind) into at most two of degree n + 1, D_d each of those into at most two of degree n + 2,
+// and terms that meet on one slot (the order m of xx, xy and yy) are merged on the host.
+constexpr int kGradTerms = 4;
+constexpr int kGradRows = 16;                         // rows of At per workgroup of gradient_design_kernel
+
+struct SolidTerm {
+    int n, k, kind;                                   // kind 0: cosine, 1: sine
+    double f;
+};
+
+// D_c (0: x, 1: y, 2: z) of the single coefficient `in`: the terms of degree in.n + 1 (the rows of acceleration_design_table)
+static int d_terms(int c, const SolidTerm& in, SolidTerm out[2]) {
+    int count = 0;
+    const int n = in.n, m = in.k, sine = in.kind;
+    const double dn = n, dm = m;
+    const double base = sqrt((2.0 * dn + 1.0) / (2.0 * dn + 3.0));
+    auto put = [&](int k, int kind, double value) {
+        if (kind == 1 && k == 0) return;                             // Ys of order 0 is zero
+        out[count++] = SolidTerm{n + 1, k, kind, in.f * value};
+    };
+    if (c == 2) {
+        const double f0 = sqrt((dn - dm + 1.0) * (dn + dm + 1.0)) * base;
+        put(m, sine, -2.0 * f0);
+        return count;
+    }
+    if (m >= 1) {                                                    // minus term: P_{n+1,m-1}
+        double fm = sqrt((dn - dm + 1.0) * (dn - dm + 2.0)) * base;
+        if (m == 1) fm *= sqrt(2.0);
+        if (c == 0)
+            put(m - 1, sine, fm);
+        else
+            put(m - 1, 1 - sine, sine ? fm : -fm);
+    }
+    double fp = sqrt((dn + dm + 1.0) * (dn + dm + 2.0)) * base;      // plus term: P_{n+1,m+1}
+    if (m == 0) fp *= sqrt(2.0);
+    if (c == 0)
+        put(m + 1, sine, -fp);
+    else
+        put(m + 1, 1 - sine, sine ? fp : -fp);
+    return count;
+}
+
+// terms of the rows of the gradient tensor's design matrix, [P][6][kGradTerms] each (xx, xy, xz, yy, yz, zz: D_d of D_c, c <= d), rows
+// in the order of utilities.degreewise_array_index; slot = 2 packed(n + 2, k) + kind at degree N + 2, -1: no term
+static void gradient_design_table(int N, int min_degree, int* slot, double* factor) {
+    const int N2 = N + 2;
+    size_t row = 0;
+    for (int n = min_degree; n <= N; ++n) {
+        for (int j = 0; j <= 2 * n; ++j, ++row) {
+            const SolidTerm unit{n, (j + 1) / 2, (j > 0 && j % 2 == 0) ? 1 : 0, 1.0};
+            int comp = 0;
+            for (int c = 0; c < 3; ++c) {
+                SolidTerm first[2];
+                const int n1 = d_terms(c, unit, first);
+                for (int d = c; d < 3; ++d, ++comp) {
+                    int* sl = slot + (row * 6 + comp) * kGradTerms;
+                    double* f = factor + (row * 6 + comp) * kGradTerms;
+                    int used = 0;
+                    for (int i = 0; i < kGradTerms; ++i) {
+                        sl[i] = -1;
+                        f[i] = 0.0;
+                    }
+                    for (int i = 0; i < n1; ++i) {
+                        SolidTerm second[2];
+                        const int n2 = d_terms(d, first[i], second);
+                        for (int q = 0; q < n2; ++q) {
+                            const int s = 2 * (order_offset(N2, second[q].k) + n + 2 - second[q].k) + second[q].kind;
+                            int at = 0;
+                            while (at < used && sl[at] != s) ++at;
+                            if (at == used) sl[used++] = s;
+                            f[at] = f[at] + second[q].f;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Rows blockIdx.x * kGradRows ... of the transposed design matrix of the gradient tensor, 256 points per workgroup (blockIdx.y):
+// out [rows][K][ldt] with the K components of `mask` (bit j: component j of xx, xy, xz, yy, yz, zz) in ascending order.  A lane keeps
+// the frame of its point (kFrames: F [3][3], row a = instrument axis a) and the square roots of its weights across the rows of the
+// workgroup; per row it forms the six Earth-fixed entries from the table (wave-uniform slots and factors), then
+// T'_ab = f_a . (T f_b) for the selected components (T f_b once per b, from the six entries), scales by `scale` and by sqrt(w)
+// (wl 0: none, 1: w [npts], 2: w [npts][K]) and stores.
+template <bool kFrames>
+__global__ __launch_bounds__(256) void gradient_design_kernel(int npts, long long rows, const double* __restrict__ Y, size_t ldy,
+                                                              const int* __restrict__ slot, const double* __restrict__ factor,
+                                                              const double* __restrict__ frames, int mask, int K, const double* __restrict__ w, int wl,
+                                                              double scale, double* __restrict__ out, size_t ldt) {
+    const int pt = blockIdx.y * 256 + threadIdx.x;
+    if (pt >= npts) return;
+    double F[3][3];
+    if (kFrames) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) F[i / 3][i % 3] = frames[(size_t)pt * 9 + i];
+    }
+    double sw[6];
+    {
+        const double wp = wl == 1 ? sqrt(w[pt]) : 1.0;
+        int k = 0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            sw[j] = wp;
+            if ((mask >> j) & 1) {
+                if (wl == 2) sw[j] = sqrt(w[(size_t)pt * K + k]);
+                ++k;
+            }
+        }
+    }
+    const size_t row0 = (size_t)blockIdx.x * kGradRows;
+    const size_t row1 = min((unsigned long long)(row0 + kGradRows), (unsigned long long)rows);
+    for (size_t row = row0; row < row1; ++row) {
+        double t[6];                                                 // xx, xy, xz, yy, yz, zz in the Earth-fixed frame
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            double v = 0.0;
+#pragma unroll
+            for (int j = 0; j < kGradTerms; ++j) {
+                const int sl = slot[(row * 6 + c) * kGradTerms + j];
+                if (sl >= 0) v = v + factor[(row * 6 + c) * kGradTerms + j] * Y[(size_t)sl * ldy + pt];
+            }
+            t[c] = v;
+        }
+        double u[3][3] = {};                                         // u[b] = T f_b
+        if (kFrames) {
+            const int need[3] = {mask & 1, mask & (2 | 8), mask & (4 | 16 | 32)};
+#pragma unroll
+            for (int b = 0; b < 3; ++b)
+                if (need[b]) {
+                    u[b][0] = (t[0] * F[b][0] + t[1] * F[b][1]) + t[2] * F[b][2];
+                    u[b][1] = (t[1] * F[b][0] + t[3] * F[b][1]) + t[4] * F[b][2];
+                    u[b][2] = (t[2] * F[b][0] + t[4] * F[b][1]) + t[5] * F[b][2];
+                }
+        }
+        double* o = out + row * K * ldt + pt;
+        int j = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = a; b < 3; ++b, ++j)
+                if ((mask >> j) & 1) {
+                    const double v = kFrames ? (F[a][0] * u[b][0] + F[a][1] * u[b][1]) + F[a][2] * u[b][2] : t[j];
+                    *o = (v * scale) * sw[j];
+                    o += ldt;
+                }
+    }
+}
+
 }  // namespace shg
 
 using namespace shg;
@@ -165,7 +324,8 @@ static int acceleration_design(int N, int min_degree, const double* xyz, int M, 
     }
     for (int p0 = 0; p0 < M; p0 += pass) {
         const int np = std::min(pass, M - p0);
-        hipLaunchKernelGGL(design_harmonics_kernel, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N1, np, xyz + (size_t)p0 * 3, ab, R, Y, (size_t)pass);
+        hipLaunchKernelGGL(design_harmonics_kernel<false>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N1, np, xyz + (size_t)p0 * 3, ab, R, Y,
+                           (size_t)pass);
         const double* w = wl == 0 ? nullptr : weights + (size_t)p0 * (wl == 2 ? 3 : 1);
         hipLaunchKernelGGL((design_gather_kernel<3, 2>), dim3((unsigned)P, ceil_div(np, 256)), dim3(256), 0, stream, np, Y, (size_t)pass, slot, factor, w, wl,
                            scale, At + p0, (size_t)ldt);
@@ -190,4 +350,90 @@ extern "C" int shg_acceleration_design(int N, int min_degree, const double* xyz,
     if (M == 0) return SHG_OK;
     SHG_REQUIRE(xyz && At && (weights || weight_layout == SHG_WEIGHTS_NONE), "%s: NULL pointer", fn);
     return acceleration_design(N, min_degree, xyz, M, weights, weight_layout, GM, R, At, ldt, (hipStream_t)stream);
+}
+
+static int gradient_design(int N, int min_degree, const double* xyz, int M, const double* frames, int mask, const double* weights, int wl, double GM,
+                           double R, double* At, int ldt, hipStream_t stream) {
+    const int N2 = N + 2;
+    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
+    const long long packed = packed_count(N2);
+    const int K = __builtin_popcount((unsigned)mask);
+    // points per pass: Y of a pass stays under 256 MB, in whole workgroups, at least one (the rule of acceleration_design)
+    const long long budget = (256LL << 20) / 8 / (2 * packed) / 256 * 256;
+    const int pass = (int)std::min<long long>({std::max<long long>(budget, 256), ((long long)M + 255) / 256 * 256, 65535LL * 256});
+    const double scale = GM / (4.0 * R * R * R);
+    Workspace ws = Workspace::plain(stream);
+    double2* ab;
+    double *Y, *factor;
+    int* slot;
+    if (!ws.alloc(ab, (size_t)packed, Y, (size_t)packed * 2 * pass, factor, (size_t)P * 6 * kGradTerms, slot, (size_t)P * 6 * kGradTerms))
+        return fail(SHG_ERR_NOMEM, "shg_gradient_design: workspace allocation failed");
+    {   // recursion factors of degree N + 2 (a and b of one (n'', k) side by side) and the terms of the rows
+        std::vector<double> a, b, h(2 * (size_t)packed), f((size_t)P * 6 * kGradTerms);
+        std::vector<int> sl((size_t)P * 6 * kGradTerms);
+        recursion_tables(N2, a, b);
+        for (size_t i = 0; i < a.size(); ++i) {
+            h[2 * i] = a[i];
+            h[2 * i + 1] = b[i];
+        }
+        gradient_design_table(N, min_degree, sl.data(), f.data());
+        SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(factor, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(slot, sl.data(), sl.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipStreamSynchronize(stream));
+    }
+    const unsigned row_groups = (unsigned)ceil_div64(P, kGradRows);
+    for (int p0 = 0; p0 < M; p0 += pass) {
+        const int np = std::min(pass, M - p0);
+        hipLaunchKernelGGL(design_harmonics_kernel<true>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N2, np, xyz + (size_t)p0 * 3, ab, R, Y,
+                           (size_t)pass);
+        const double* w = wl == 0 ? nullptr : weights + (size_t)p0 * (wl == 2 ? K : 1);
+        const dim3 grid(row_groups, ceil_div(np, 256));
+        if (frames)
+            hipLaunchKernelGGL(gradient_design_kernel<true>, grid, dim3(256), 0, stream, np, P, Y, (size_t)pass, slot, factor, frames + (size_t)p0 * 9,
+                               mask, K, w, wl, scale, At + p0, (size_t)ldt);
+        else
+            hipLaunchKernelGGL(gradient_design_kernel<false>, grid, dim3(256), 0, stream, np, P, Y, (size_t)pass, slot, factor, nullptr, mask, K, w, wl,
+                               scale, At + p0, (size_t)ldt);
+        SHG_HIP(hipGetLastError());
+    }
+    return SHG_OK;
+}
+
+// the rules the two gradient entry points share
+static int check_gradient_degrees(const char* fn, int N, int min_degree) {
+    SHG_REQUIRE(N >= 0 && min_degree >= 0, "%s: negative size (N %d, min_degree %d)", fn, N, min_degree);
+    SHG_REQUIRE(min_degree <= N, "%s: min_degree %d above N %d", fn, min_degree, N);
+    SHG_REQUIRE(N <= 32765, "%s: N %d is too large", fn, N);
+    return SHG_OK;
+}
+
+// Host only: no HIP call.
+extern "C" int shg_gradient_design_terms(int N, int min_degree, int32_t* slot, double* factor, long long capacity) {
+    const char* fn = "shg_gradient_design_terms";
+    if (int rc = check_gradient_degrees(fn, N, min_degree)) return rc;
+    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
+    SHG_REQUIRE(capacity >= 6 * kGradTerms * P, "%s: capacity %lld below the %lld entries of the table", fn, capacity, 6 * kGradTerms * P);
+    SHG_REQUIRE(slot && factor, "%s: NULL pointer", fn);
+    gradient_design_table(N, min_degree, slot, factor);
+    return SHG_OK;
+}
+
+// Arguments are checked before the first HIP call (the CPU tests call this without a device).
+extern "C" int shg_gradient_design(int N, int min_degree, const double* xyz, int M, const double* frames, int components, const double* weights,
+                                   int weight_layout, double GM, double R, double* At, int ldt, void* stream) {
+    const char* fn = "shg_gradient_design";
+    SHG_REQUIRE(M >= 0, "%s: negative size (M %d)", fn, M);
+    if (int rc = check_gradient_degrees(fn, N, min_degree)) return rc;
+    SHG_REQUIRE(components >= 1 && components <= 63, "%s: components %d, expected a set of SHG_GRAD_XX ... SHG_GRAD_ZZ (1 .. 63)", fn, components);
+    SHG_REQUIRE(weight_layout == SHG_WEIGHTS_NONE || weight_layout == SHG_WEIGHTS_POINT || weight_layout == SHG_WEIGHTS_COMPONENT,
+                "%s: weight layout %d, expected 0 (none), 1 (per point) or 2 (per component)", fn, weight_layout);
+    SHG_REQUIRE(std::isfinite(GM) && std::isfinite(R) && R > 0.0, "%s: GM and R must be finite and R positive (GM %g, R %g)", fn, GM, R);
+    SHG_REQUIRE(ldt >= M, "%s: ldt %d below M %d", fn, ldt, M);
+    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
+    const long long K = __builtin_popcount((unsigned)components);
+    SHG_REQUIRE(ldt == 0 || P * K <= (1LL << 40) / ldt, "%s: output of %lld x %lld x %d values is too large", fn, P, K, ldt);
+    if (M == 0) return SHG_OK;
+    SHG_REQUIRE(xyz && At && (weights || weight_layout == SHG_WEIGHTS_NONE), "%s: NULL pointer", fn);
+    return gradient_design(N, min_degree, xyz, M, frames, components, weights, weight_layout, GM, R, At, ldt, (hipStream_t)stream);
 }

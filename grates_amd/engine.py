@@ -775,14 +775,15 @@ def gravitational_gradients_points(max_degree, xyz, coefficients, GM, R):
     return out
 
 
-def check_observation_weights(weights, points):
-    """The layout of the weights of `points` observed positions: None (returns 0), w [M] per point (1) or w [M, 3] per component
-    (2), finite and >= 0; ValueError otherwise.  Host arrays are checked on the host, before anything reaches the device."""
+def check_observation_weights(weights, points, components=3):
+    """The layout of the weights of `points` observed positions with `components` observed values each: None (returns 0), w [M] per
+    point (1) or w [M, components] per component (2), finite and >= 0; ValueError otherwise.  Host arrays are checked on the host,
+    before anything reaches the device."""
     if weights is None:
         return 0
     shape = tuple(weights.shape)
-    if shape != (points,) and shape != (points, 3):
-        raise ValueError('weights must have shape ({0},) or ({0}, 3), got {1}'.format(points, shape))
+    if shape != (points,) and shape != (points, components):
+        raise ValueError('weights must have shape ({0},) or ({0}, {1}), got {2}'.format(points, components, shape))
     if isinstance(weights, np.ndarray):
         valid = bool(np.all(np.isfinite(weights) & (weights >= 0)))
     else:
@@ -810,6 +811,77 @@ def acceleration_design(max_degree, xyz, GM, R, min_degree=0, weights=None):
     out = torch.empty((P, 3, M), dtype=torch.float64, device=x.device)
     _lib.call('shg_acceleration_design', max_degree, min_degree, _ptr(x), M, _ptr(w) if layout else None, layout, float(GM), float(R), _ptr(out),
               M, _stream())
+    return out
+
+
+GRADIENT_COMPONENTS = ('xx', 'xy', 'xz', 'yy', 'yz', 'zz')       # canonical order: bit j of shg_gradient_design's component set
+FRAME_TOLERANCE = 1e-12                                          # |F F^T - I| of an instrument frame
+
+
+def gradient_components(components):
+    """The positions in GRADIENT_COMPONENTS of the selected tensor components, ascending: `components` is a sequence of distinct
+    names in any order, None for all six; ValueError otherwise."""
+    if components is None:
+        return list(range(6))
+    names = [components] if isinstance(components, str) else list(components)
+    unknown = [name for name in names if name not in GRADIENT_COMPONENTS]
+    if unknown:
+        raise ValueError('unknown gradient component {0!r}: expected names from {1}'.format(unknown[0], GRADIENT_COMPONENTS))
+    if len(set(names)) != len(names):
+        raise ValueError('gradient components must be distinct, got {0}'.format(tuple(names)))
+    if not names:
+        raise ValueError('at least one gradient component expected')
+    return sorted(GRADIENT_COMPONENTS.index(name) for name in names)
+
+
+def check_frames(frames, points):
+    """Instrument frames [M, 3, 3] (row a: axis a in Earth-fixed coordinates) must have orthonormal rows, |F F^T - I| <=
+    FRAME_TOLERANCE: host arrays are checked on the host, device tensors by one reduction on the device; ValueError otherwise."""
+    shape = tuple(frames.shape)
+    if shape != (points, 3, 3):
+        raise ValueError('frames must have shape ({0}, 3, 3), got {1}'.format(points, shape))
+    if points == 0:
+        return
+    if isinstance(frames, np.ndarray):
+        defect = float(np.abs(np.einsum('iac,ibc->iab', frames, frames) - np.eye(3)).max())
+    else:
+        torch = require_gpu()
+        eye = torch.eye(3, dtype=frames.dtype, device=frames.device)
+        defect = float((frames @ frames.transpose(1, 2) - eye).abs().max().item())
+    if not defect <= FRAME_TOLERANCE:
+        raise ValueError('frames must have orthonormal rows: |F F^T - I| is {0:.3g}, above {1:g}'.format(defect, FRAME_TOLERANCE))
+
+
+def gradient_design(max_degree, xyz, GM, R, min_degree=0, frames=None, components=None, weights=None):
+    """Transposed design matrix At [P, K, M] (device) of the gravitational gradient tensor at the positions xyz [M, 3]: At[p, k, i] is
+    the derivative of the k-th selected component of T' = F T F^T at point i with respect to coefficient p of
+    utilities.ravel_coefficients(., min_degree, max_degree) (shg_gradient_design).  frames [M, 3, 3] hold the instrument axes as rows
+    (None: the Earth-fixed tensor); components is a sequence of distinct names from GRADIENT_COMPONENTS in any order (None: all six),
+    the output always in canonical order; weights [M] or [M, K] scale the entries by sqrt(w)."""
+    min_degree, max_degree = int(min_degree), int(max_degree)
+    if min_degree < 0 or min_degree > max_degree:
+        raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
+    if len(xyz.shape) != 2 or xyz.shape[1] != 3:
+        raise ValueError('positions must have shape (M, 3), got {0}'.format(tuple(xyz.shape)))
+    M = int(xyz.shape[0])
+    picked = gradient_components(components)
+    layout = check_observation_weights(weights, M, len(picked))
+    if frames is not None:
+        check_frames(frames, M)
+    x = to_device(xyz)
+    return gradient_design_checked(max_degree, min_degree, x, None if frames is None else to_device(frames, x.device), picked,
+                                   to_device(weights, x.device) if layout else None, GM, R)
+
+
+def gradient_design_checked(max_degree, min_degree, x, frames, picked, weights, GM, R):
+    """shg_gradient_design on device tensors that gradient_design (or NormalEquations.from_gradients, once for all its blocks) has
+    checked: positions x [M, 3], frames [M, 3, 3] or None, the ascending component positions `picked`, weights [M], [M, K] or None."""
+    torch = require_gpu()
+    M, K = int(x.shape[0]), len(picked)
+    P = (max_degree + 1) ** 2 - min_degree ** 2
+    out = torch.empty((P, K, M), dtype=torch.float64, device=x.device)
+    _lib.call('shg_gradient_design', max_degree, min_degree, _ptr(x), M, None if frames is None else _ptr(frames), sum(1 << j for j in picked),
+              None if weights is None else _ptr(weights), 0 if weights is None else weights.dim(), float(GM), float(R), _ptr(out), M, _stream())
     return out
 
 

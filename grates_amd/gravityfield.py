@@ -323,6 +323,24 @@ def acceleration_design_matrix(xyz, min_degree, max_degree, GM=3.9860044150e+14,
     return A if as_tensor else engine.to_host(A)
 
 
+def gradient_design_matrix(xyz, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None, weights=None,
+                           as_tensor=False):
+    """
+    Design matrix A [K M, P] of the gravitational gradient tensor at the cartesian positions xyz (M, 3) with respect to the
+    coefficients of degrees min_degree .. max_degree: row K i + j is the j-th selected component at point i, the columns follow
+    utilities.ravel_coefficients.  frames (M, 3, 3) hold the instrument axes of every point as rows, in Earth-fixed coordinates (rows
+    orthonormal within 1e-12, else ValueError), and the components are those of T' = F T F^T; without frames they are those of
+    gravitational_gradients(xyz).  components is a sequence of distinct names from ('xx', 'xy', 'xz', 'yy', 'yz', 'zz') in any order
+    (default: all six); the rows always come in that canonical order.  weights (M,) per point or (M, K) per selected component scale
+    the rows by sqrt(w).  Always computed on the GPU (shg_gradient_design); returns an ndarray, or the float64 device tensor with
+    as_tensor=True.  The kernel builds the transposed matrix (engine.gradient_design, what NormalEquations.from_gradients accumulates
+    block by block); the transposition here is a copy meant for modest sizes.
+    """
+    At = engine.gradient_design(max_degree, xyz, GM, R, min_degree, frames, components, weights)
+    A = At.permute(2, 1, 0).reshape(At.shape[1] * At.shape[2], At.shape[0])
+    return A if as_tensor else engine.to_host(A)
+
+
 def synthesize(anm_batch, grid, kernel='ewh', GM=3.9860044150e+14, R=6.3781363000e+06):
     """
     Batched synthesis: anm_batch [B, N+1, N+1] (ndarray or device tensor) -> device tensor

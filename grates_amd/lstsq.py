@@ -602,6 +602,69 @@ class NormalEquations:
         matrix._set_device(0, 0, normals)
         return cls(matrix, side, float(square_sum.item()), 3 * M)
 
+    @classmethod
+    def from_gradients(cls, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
+                       weights=None, block_points=None):
+        """
+        Normal equations of the coefficients of degrees min_degree .. max_degree (in the order of utilities.ravel_coefficients) from
+        gravitational gradients observed at the cartesian positions xyz [M, 3] (host arrays or device tensors; usually reduced by a
+        reference field).  frames [M, 3, 3] hold the instrument axes of every point as rows, in Earth-fixed coordinates (None: the
+        observations are Earth-fixed); components is a sequence of distinct names from ('xx', 'xy', 'xz', 'yy', 'yz', 'zz') in any
+        order (default: all six), K of them.  gradients is [M, K] in that canonical order, or [M, 3, 3], of which the selected
+        upper-triangle entries are taken.  weights [M] per point or [M, K] per selected component (finite, >= 0; default 1).
+
+        The block loop of from_accelerations with At [P, K Mb] from shg_gradient_design; the default block is the largest multiple of
+        256 points that keeps At within 256 MB, at least 256.  Returns NormalEquations with a one-block BlockMatrix [P, P] and the
+        right-hand side [P, 1] on the device, and observation_count = K M.
+        """
+        min_degree, max_degree = int(min_degree), int(max_degree)
+        if min_degree < 0 or min_degree > max_degree:
+            raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
+        if len(xyz.shape) != 2 or xyz.shape[1] != 3:
+            raise ValueError('positions must have shape (M, 3), got {0}'.format(tuple(xyz.shape)))
+        M = int(xyz.shape[0])
+        picked = engine.gradient_components(components)
+        K = len(picked)
+        shape = tuple(gradients.shape)
+        full = len(shape) == 3 and shape[1:] == (3, 3)
+        if not full and (len(shape) != 2 or shape[1] != K):
+            raise ValueError('gradients must have shape (M, {0}) or (M, 3, 3), got {1}'.format(K, shape))
+        if shape[0] != M:
+            raise ValueError('{0} positions but {1} gradients'.format(M, shape[0]))
+        layout = engine.check_observation_weights(weights, M, K)
+        if frames is not None:
+            engine.check_frames(frames, M)
+        P = (max_degree + 1) ** 2 - min_degree ** 2
+        if block_points is None:
+            block_points = max(cls.DESIGN_BLOCK_BYTES // (8 * K * P) // 256 * 256, 256)
+        block_points = int(block_points)
+        if block_points < 1:
+            raise ValueError('block_points must be positive, got {0}'.format(block_points))
+
+        torch = engine.require_gpu()
+        x, l = engine.to_device(xyz), engine.to_device(gradients)
+        f = engine.to_device(frames) if frames is not None else None
+        if full:
+            l = torch.stack([l[:, j // 3, j % 3] for j in ((0, 1, 2, 4, 5, 8)[i] for i in picked)], dim=1)
+        if layout:
+            w = engine.to_device(weights)
+            l = l * torch.sqrt(w if layout == 2 else w[:, None])
+        normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
+        for first in range(0, M, block_points):
+            last = min(first + block_points, M)
+            At = engine.gradient_design_checked(max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked,
+                                                None if not layout else w[first:last], GM, R)
+            At = At.reshape(P, K * (last - first))
+            lb = l[first:last].t().reshape(-1, 1)                      # component-major, as the columns of At
+            engine.gemm(At, At, transb=True, beta=1.0, out=normals)
+            engine.gemm(At, lb, beta=1.0, out=side)
+            engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
+        normals.triu_()
+        normals.add_(torch.triu(normals, 1).t())
+        matrix = BlockMatrix([0, P], [0, P])
+        matrix._set_device(0, 0, normals)
+        return cls(matrix, side, float(square_sum.item()), K * M)
+
     def __cholesky(self):
         """factor the matrix once; a matrix that already holds covariances cannot be factored again (ValueError, as upstream)"""
         if self.status == 'covariance_matrix' or self.status not in ('normal_matrix', 'cholesky_factor'):

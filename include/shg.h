@@ -494,6 +494,35 @@ enum { SHG_WEIGHTS_NONE = 0, SHG_WEIGHTS_POINT = 1, SHG_WEIGHTS_COMPONENT = 2 };
 int shg_acceleration_design(int N, int min_degree, const double* xyz, int M, const double* weights, int weight_layout, double GM, double R,
                             double* At, int ldt, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Design matrix of the gravitational gradient tensor at points, in per-point instrument frames (the partial derivatives of
+ * shg_gravitational_gradients_points with respect to the coefficients; no reference counterpart)
+ *   At [P][K][ldt], transposed like shg_acceleration_design: row p is coefficient p of utilities.ravel_coefficients(., min_degree, N),
+ *   then the K = popcount(components) selected tensor components in ascending bit order (xx, xy, xz, yy, yz, zz), then the M points
+ *   xyz [M][3] innermost (ldt >= M; the entries from M to ldt of a row are not touched).  At[p][k][i] = d T'_ab(point i) / d x_p in
+ *   s^-2.
+ *   frames == NULL: T' = T, the Earth-fixed tensor.  Otherwise frames [M][3][3], row a of frames[i] the instrument axis a in
+ *   Earth-fixed coordinates, and T' = F T F^T; the rows must be orthonormal, which is not checked here.
+ *   An Earth-fixed entry is the acceleration's first-derivative map applied twice to a unit coefficient: at most four terms
+ *   factor * Y[slot] on the solid harmonics of degree N + 2, in units of GM / (4 R^3) (terms on one slot are merged).  A first kernel
+ *   writes the solid harmonics of a pass of points to a workspace (at most 256 MB per pass; the colatitude enters as z / r and
+ *   rho / r, as in shg_gravitational_gradients_points), a second forms the six entries of a row per point, rotates the selected ones
+ *   (each off-diagonal value once) and stores them.
+ *   weights: SHG_WEIGHTS_NONE, SHG_WEIGHTS_POINT w [M] or SHG_WEIGHTS_COMPONENT w [M][K] over the selected components, finite and
+ *   >= 0: the entries are multiplied by sqrt(w), as the last operation.
+ *   No atomics: the entries of a point do not depend on the other points of the call or on the other selected components, and
+ *   repeated calls are bitwise equal.  Points at the poles and below R are fine; r = 0 is not.
+ *   Arguments are checked before the first HIP call (the rules of shg_acceleration_design with N <= 32765, components in 1 .. 63,
+ *   at most 2^40 values of At); M = 0 returns 0 at once.
+ *   shg_gradient_design_terms  host only, no HIP call: the table of the Earth-fixed entries, slot / factor [P][6][4] (capacity >= 24 P
+ *   entries each): slot = 2 packed(n'', k) + (0 cosine | 1 sine) at degree N + 2 (packed(n, k) = k (N + 3) - k (k - 1) / 2 + n - k), or
+ *   -1 for no term; the factors carry the signs but not GM / (4 R^3).  The device call uses the same builder.
+ * ------------------------------------------------------------------------------------------------ */
+enum { SHG_GRAD_XX = 1, SHG_GRAD_XY = 2, SHG_GRAD_XZ = 4, SHG_GRAD_YY = 8, SHG_GRAD_YZ = 16, SHG_GRAD_ZZ = 32 };
+int shg_gradient_design(int N, int min_degree, const double* xyz, int M, const double* frames, int components, const double* weights,
+                        int weight_layout, double GM, double R, double* At, int ldt, void* stream);
+int shg_gradient_design_terms(int N, int min_degree, int32_t* slot, double* factor, long long capacity);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
