@@ -116,6 +116,9 @@ PROTOTYPES = {
     'shg_gradient_design': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_double,
                             ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_void_p],
     'shg_gradient_design_terms': [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), c_double_p, ctypes.c_longlong],
+    'shg_los_design': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p, ctypes.c_double, ctypes.c_double,
+                       c_double_p, ctypes.c_int, ctypes.c_void_p],
+    'shg_los_design_pass': [ctypes.c_int],
 }
 STRING_GETTERS = ('shg_last_error', 'shg_version')
 

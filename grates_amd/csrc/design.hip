@@ -19,6 +19,9 @@
 // The design matrix of the gradient tensor (second half of this file) is that other table, of at most four terms on Y of degree N + 2,
 // with a gather kernel of its own that rotates the six entries of a point into a per-point instrument frame and keeps only the
 // selected components.
+//
+// The line-of-sight gravity difference of satellite pairs (third part) needs no table of its own: its gather kernel reads the
+// acceleration's table at the two satellites of a pair, takes the difference and projects it on the line of sight.
 #include "common.h"
 
 #include <cmath>
@@ -29,13 +32,18 @@ namespace shg {
 // acceleration_points_kernel), (R/r)^(n'+1) is carried along the degree loop.  The recursion factors a, b of one (n', k) lie side by
 // side and are read with wave-uniform addresses: no LDS, whatever the degree.  kDirect takes cos and sin of the colatitude straight from
 // xyz (t = z / r, s = rho / r: the form of gradients_points_kernel, exact next to the axis) instead of the reference's
-// s = sqrt(1 - t^2), which the acceleration and its design matrix follow.
+// s = sqrt(1 - t^2), which the acceleration and its design matrix follow.  A launch with gridDim.y = 2 runs two sets of npts points,
+// xyz and xyz_second, and writes the second set's harmonics to the columns `second` .. of Y (the two satellites of the line-of-sight
+// design); with gridDim.y = 1 neither is looked at.
 template <bool kDirect>
-__global__ __launch_bounds__(256) void design_harmonics_kernel(int N1, int npts, const double* __restrict__ xyz, const double2* __restrict__ ab, double R,
-                                                               double* __restrict__ Y, size_t ldy) {
+__global__ __launch_bounds__(256) void design_harmonics_kernel(int N1, int npts, const double* __restrict__ xyz, const double* __restrict__ xyz_second,
+                                                               const double2* __restrict__ ab, double R, double* __restrict__ Y_first, size_t ldy,
+                                                               size_t second) {
     const int pt = blockIdx.x * 256 + threadIdx.x;
     const bool ok = pt < npts;
-    const double* xp = xyz + (size_t)(ok ? pt : 0) * 3;
+    // blockIdx.y = 1 (the line-of-sight design only): a second set of npts points, whose harmonics go to the columns `second` ..
+    double* __restrict__ Y = blockIdx.y ? Y_first + second : Y_first;
+    const double* xp = (blockIdx.y ? xyz_second : xyz) + (size_t)(ok ? pt : 0) * 3;
     const double x = xp[0], y = xp[1], z = xp[2];
     const double r = sqrt((x * x + y * y) + z * z);                  // np.sum over axis 1: ((x^2 + y^2) + z^2)
     const double th = atan2(sqrt(x * x + y * y), z);
@@ -289,6 +297,68 @@ __global__ __launch_bounds__(256) void gradient_design_kernel(int npts, long lon
     }
 }
 
+// ---- design matrix of the line-of-sight gravity difference of satellite pairs ---------------------------------------------------------
+// l_i = e_i . (g(b_i) - g(a_i)): no new table.  A row is the difference of the acceleration's rows at the two satellites, projected on
+// the line of sight of the pair, so the gather kernel reads the terms of acceleration_design_table at two points.
+constexpr int kLosRows = 16;                          // rows of At per workgroup of los_design_kernel
+
+// pairs per pass: the harmonics of both satellites share the 256 MB of the acceleration's pass, so a pass holds half as many pairs
+// as that one holds points, in whole workgroups, at least one
+static long long los_design_pass(int N) {
+    const long long packed = packed_count(N + 1);
+    return std::max<long long>((256LL << 20) / 8 / (4 * packed) / 256 * 256, 256);
+}
+
+// Rows blockIdx.x * kLosRows ... of the transposed design matrix of the line-of-sight difference, 256 pairs per workgroup
+// (blockIdx.y): out [rows][ldt].  Y holds the solid harmonics of the pass, those of the a-points in the columns 0 .. and those of the
+// b-points in the columns `half` .. of every slot.  A lane keeps the line of sight e and sqrt(w) of its pair across the rows of the
+// workgroup.  kUnit: e = (b - a) / |b - a| from the positions, |d| = sqrt((dx^2 + dy^2) + dz^2) and one division per component;
+// otherwise e = directions [npairs][3] as given.  Per row (wave-uniform slots and factors) the unscaled component sums at b and at a,
+// their difference per component, the projection (e_x d_x + e_y d_y) + e_z d_z, then * scale, then * sqrt(w), one store.
+template <bool kUnit>
+__global__ __launch_bounds__(256) void los_design_kernel(int npairs, long long rows, const double* __restrict__ xyz_a, const double* __restrict__ xyz_b,
+                                                         const double* __restrict__ directions, const double* __restrict__ Y, size_t ldy, size_t half,
+                                                         const int* __restrict__ slot, const double* __restrict__ factor, const double* __restrict__ w,
+                                                         double scale, double* __restrict__ out, size_t ldt) {
+    const int pt = blockIdx.y * 256 + threadIdx.x;
+    if (pt >= npairs) return;
+    double e[3];
+    if (kUnit) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) e[c] = xyz_b[(size_t)pt * 3 + c] - xyz_a[(size_t)pt * 3 + c];
+        const double len = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) e[c] = e[c] / len;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) e[c] = directions[(size_t)pt * 3 + c];
+    }
+    const double sw = w ? sqrt(w[pt]) : 1.0;
+    const double* Ya = Y + pt;
+    const double* Yb = Y + half + pt;
+    const size_t row0 = (size_t)blockIdx.x * kLosRows;
+    const size_t row1 = min((unsigned long long)(row0 + kLosRows), (unsigned long long)rows);
+    for (size_t row = row0; row < row1; ++row) {
+        double d[3];                                                 // g_c(b) - g_c(a), unscaled
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double va = 0.0, vb = 0.0;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int sl = slot[(row * 3 + c) * 2 + j];
+                if (sl >= 0) {
+                    const double f = factor[(row * 3 + c) * 2 + j];
+                    vb = vb + f * Yb[(size_t)sl * ldy];
+                    va = va + f * Ya[(size_t)sl * ldy];
+                }
+            }
+            d[c] = vb - va;
+        }
+        const double v = (e[0] * d[0] + e[1] * d[1]) + e[2] * d[2];
+        out[row * ldt + pt] = (v * scale) * sw;
+    }
+}
+
 }  // namespace shg
 
 using namespace shg;
@@ -324,8 +394,8 @@ static int acceleration_design(int N, int min_degree, const double* xyz, int M, 
     }
     for (int p0 = 0; p0 < M; p0 += pass) {
         const int np = std::min(pass, M - p0);
-        hipLaunchKernelGGL(design_harmonics_kernel<false>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N1, np, xyz + (size_t)p0 * 3, ab, R, Y,
-                           (size_t)pass);
+        hipLaunchKernelGGL(design_harmonics_kernel<false>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N1, np, xyz + (size_t)p0 * 3, nullptr, ab, R, Y,
+                           (size_t)pass, (size_t)0);
         const double* w = wl == 0 ? nullptr : weights + (size_t)p0 * (wl == 2 ? 3 : 1);
         hipLaunchKernelGGL((design_gather_kernel<3, 2>), dim3((unsigned)P, ceil_div(np, 256)), dim3(256), 0, stream, np, Y, (size_t)pass, slot, factor, w, wl,
                            scale, At + p0, (size_t)ldt);
@@ -385,8 +455,8 @@ static int gradient_design(int N, int min_degree, const double* xyz, int M, cons
     const unsigned row_groups = (unsigned)ceil_div64(P, kGradRows);
     for (int p0 = 0; p0 < M; p0 += pass) {
         const int np = std::min(pass, M - p0);
-        hipLaunchKernelGGL(design_harmonics_kernel<true>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N2, np, xyz + (size_t)p0 * 3, ab, R, Y,
-                           (size_t)pass);
+        hipLaunchKernelGGL(design_harmonics_kernel<true>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N2, np, xyz + (size_t)p0 * 3, nullptr, ab, R, Y,
+                           (size_t)pass, (size_t)0);
         const double* w = wl == 0 ? nullptr : weights + (size_t)p0 * (wl == 2 ? K : 1);
         const dim3 grid(row_groups, ceil_div(np, 256));
         if (frames)
@@ -436,4 +506,73 @@ extern "C" int shg_gradient_design(int N, int min_degree, const double* xyz, int
     if (M == 0) return SHG_OK;
     SHG_REQUIRE(xyz && At && (weights || weight_layout == SHG_WEIGHTS_NONE), "%s: NULL pointer", fn);
     return gradient_design(N, min_degree, xyz, M, frames, components, weights, weight_layout, GM, R, At, ldt, (hipStream_t)stream);
+}
+
+static int los_design(int N, int min_degree, const double* xyz_a, const double* xyz_b, const double* directions, int M, const double* weights, double GM,
+                      double R, double* At, int ldt, hipStream_t stream) {
+    const int N1 = N + 1;
+    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
+    const long long packed = packed_count(N1);
+    const int pass = (int)std::min<long long>({los_design_pass(N), ((long long)M + 255) / 256 * 256, 65535LL * 256});
+    const size_t ldy = 2 * (size_t)pass;                             // a-points in the columns 0 .., b-points in the columns pass ..
+    const double scale = GM / (2.0 * R * R);
+    Workspace ws = Workspace::plain(stream);
+    double2* ab;
+    double *Y, *factor;
+    int* slot;
+    if (!ws.alloc(ab, (size_t)packed, Y, (size_t)packed * 2 * ldy, factor, (size_t)P * 6, slot, (size_t)P * 6))
+        return fail(SHG_ERR_NOMEM, "shg_los_design: workspace allocation failed");
+    {   // recursion factors of degree N + 1 and the acceleration's terms of the rows, as in acceleration_design
+        std::vector<double> a, b, h(2 * (size_t)packed), f;
+        std::vector<int> sl;
+        recursion_tables(N1, a, b);
+        for (size_t i = 0; i < a.size(); ++i) {
+            h[2 * i] = a[i];
+            h[2 * i + 1] = b[i];
+        }
+        acceleration_design_table(N, min_degree, sl, f);
+        SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(factor, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(slot, sl.data(), sl.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipStreamSynchronize(stream));
+    }
+    const unsigned row_groups = (unsigned)ceil_div64(P, kLosRows);
+    for (int p0 = 0; p0 < M; p0 += pass) {
+        const int np = std::min(pass, M - p0);
+        const double *xa = xyz_a + (size_t)p0 * 3, *xb = xyz_b + (size_t)p0 * 3;
+        // one launch for both satellites (blockIdx.y): the kernel's time hardly depends on the number of workgroups at these sizes
+        hipLaunchKernelGGL(design_harmonics_kernel<false>, dim3(ceil_div(np, 256), 2), dim3(256), 0, stream, N1, np, xa, xb, ab, R, Y, ldy, (size_t)pass);
+        const double* w = weights ? weights + p0 : nullptr;
+        const dim3 grid(row_groups, ceil_div(np, 256));
+        if (directions)
+            hipLaunchKernelGGL(los_design_kernel<false>, grid, dim3(256), 0, stream, np, P, xa, xb, directions + (size_t)p0 * 3, Y, ldy, (size_t)pass, slot,
+                               factor, w, scale, At + p0, (size_t)ldt);
+        else
+            hipLaunchKernelGGL(los_design_kernel<true>, grid, dim3(256), 0, stream, np, P, xa, xb, nullptr, Y, ldy, (size_t)pass, slot, factor, w, scale,
+                               At + p0, (size_t)ldt);
+        SHG_HIP(hipGetLastError());
+    }
+    return SHG_OK;
+}
+
+// Host only: no HIP call.  Pairs per pass of shg_los_design at degree N (before the call's own M caps it), -1 for a degree it refuses.
+extern "C" int shg_los_design_pass(int N) {
+    if (N < 0 || N > 32766) return -1;
+    return (int)los_design_pass(N);
+}
+
+// Arguments are checked before the first HIP call (the CPU tests call this without a device).
+extern "C" int shg_los_design(int N, int min_degree, const double* xyz_a, const double* xyz_b, const double* directions, int M, const double* weights,
+                              double GM, double R, double* At, int ldt, void* stream) {
+    const char* fn = "shg_los_design";
+    SHG_REQUIRE(N >= 0 && min_degree >= 0 && M >= 0, "%s: negative size (N %d, min_degree %d, M %d)", fn, N, min_degree, M);
+    SHG_REQUIRE(min_degree <= N, "%s: min_degree %d above N %d", fn, min_degree, N);
+    SHG_REQUIRE(N <= 32766, "%s: N %d is too large", fn, N);
+    SHG_REQUIRE(std::isfinite(GM) && std::isfinite(R) && R > 0.0, "%s: GM and R must be finite and R positive (GM %g, R %g)", fn, GM, R);
+    SHG_REQUIRE(ldt >= M, "%s: ldt %d below M %d", fn, ldt, M);
+    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
+    SHG_REQUIRE(ldt == 0 || P <= (1LL << 40) / ldt, "%s: output of %lld x %d values is too large", fn, P, ldt);
+    if (M == 0) return SHG_OK;
+    SHG_REQUIRE(xyz_a && xyz_b && At, "%s: NULL pointer", fn);
+    return los_design(N, min_degree, xyz_a, xyz_b, directions, M, weights, GM, R, At, ldt, (hipStream_t)stream);
 }

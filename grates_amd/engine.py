@@ -885,6 +885,89 @@ def gradient_design_checked(max_degree, min_degree, x, frames, picked, weights, 
     return out
 
 
+def check_pair_positions(xyz_a, xyz_b):
+    """The positions of M satellite pairs, xyz_a [M, 3] and xyz_b [M, 3]: returns M; ValueError otherwise.  Looks at the shapes only."""
+    for name, array in (('positions of the first satellite', xyz_a), ('positions of the second satellite', xyz_b)):
+        if len(array.shape) != 2 or array.shape[1] != 3:
+            raise ValueError('{0} must have shape (M, 3), got {1}'.format(name, tuple(array.shape)))
+    if int(xyz_a.shape[0]) != int(xyz_b.shape[0]):
+        raise ValueError('{0} positions of the first satellite but {1} of the second'.format(int(xyz_a.shape[0]), int(xyz_b.shape[0])))
+    return int(xyz_a.shape[0])
+
+
+def check_directions(directions, M):
+    """Lines of sight [M, 3] must be finite and of unit length, | |e| - 1 | <= FRAME_TOLERANCE: host arrays are checked on the host,
+    device tensors by one reduction on the device; ValueError otherwise."""
+    shape = tuple(directions.shape)
+    if shape != (M, 3):
+        raise ValueError('directions must have shape ({0}, 3), got {1}'.format(M, shape))
+    if M == 0:
+        return
+    if isinstance(directions, np.ndarray):
+        defect = float(np.abs(np.sqrt(np.sum(directions * directions, axis=1)) - 1.0).max())
+    else:
+        defect = float(((directions * directions).sum(dim=1).sqrt() - 1.0).abs().max().item())
+    if not defect <= FRAME_TOLERANCE:                                # a NaN or an infinity anywhere makes the defect NaN or inf
+        raise ValueError('directions must be finite unit vectors: | |e| - 1 | is {0:.3g}, above {1:g}'.format(defect, FRAME_TOLERANCE))
+
+
+def check_pairs_apart(xyz_a, xyz_b):
+    """No pair may coincide where the line of sight comes from the positions (a == b has none): host arrays are checked on the host,
+    device tensors by one reduction on the device; ValueError otherwise."""
+    if int(xyz_a.shape[0]) == 0:
+        return
+    if isinstance(xyz_a, np.ndarray) and isinstance(xyz_b, np.ndarray):
+        count = int(np.count_nonzero(np.all(xyz_a == xyz_b, axis=1)))
+    else:
+        a = to_device(xyz_a)
+        count = int((a == to_device(xyz_b, a.device)).all(dim=1).sum().item())
+    if count:
+        raise ValueError('{0} pairs have both satellites at the same position: their line of sight is undefined, pass directions'.format(count))
+
+
+def los_design(max_degree, xyz_a, xyz_b, GM, R, min_degree=0, directions=None, weights=None):
+    """Transposed design matrix At [P, M] (device) of the line-of-sight gravity difference of the satellite pairs xyz_a [M, 3],
+    xyz_b [M, 3]: At[p, i] is the derivative of e_i . (g(b_i) - g(a_i)) with respect to coefficient p of
+    utilities.ravel_coefficients(., min_degree, max_degree), P = (max_degree + 1)^2 - min_degree^2 (shg_los_design).  directions
+    [M, 3] are the lines of sight e (unit vectors; None: (b - a) / |b - a|, and no pair may then coincide); weights [M] scale the
+    entries by sqrt(w)."""
+    min_degree, max_degree = int(min_degree), int(max_degree)
+    if min_degree < 0 or min_degree > max_degree:
+        raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
+    M = check_pair_positions(xyz_a, xyz_b)
+    layout = check_observation_weights(weights, M, 1)
+    if layout and len(weights.shape) != 1:
+        raise ValueError('weights must have shape ({0},), got {1}'.format(M, tuple(weights.shape)))
+    if directions is not None:
+        check_directions(directions, M)
+    else:
+        check_pairs_apart(xyz_a, xyz_b)
+    a = to_device(xyz_a)
+    return los_design_checked(max_degree, min_degree, a, to_device(xyz_b, a.device), None if directions is None else to_device(directions, a.device),
+                              to_device(weights, a.device) if layout else None, GM, R)
+
+
+def los_design_checked(max_degree, min_degree, a, b, directions, weights, GM, R):
+    """shg_los_design on device tensors that los_design (or NormalEquations.from_line_of_sight, once for all its blocks) has checked:
+    positions a, b [M, 3], directions [M, 3] or None, weights [M] or None."""
+    torch = require_gpu()
+    M = int(a.shape[0])
+    P = (max_degree + 1) ** 2 - min_degree ** 2
+    out = torch.empty((P, M), dtype=torch.float64, device=a.device)
+    _lib.call('shg_los_design', max_degree, min_degree, _ptr(a), _ptr(b), None if directions is None else _ptr(directions), M,
+              None if weights is None else _ptr(weights), float(GM), float(R), _ptr(out), M, _stream())
+    return out
+
+
+def los_design_pass(max_degree):
+    """Pairs per pass of shg_los_design at this degree: the solid harmonics of both satellites share the 256 MB of a pass of the
+    acceleration's design matrix (host only, no HIP call)."""
+    count = _lib.load().shg_los_design_pass(int(max_degree))
+    if count < 0:
+        raise ValueError('max_degree {0} is out of range'.format(max_degree))
+    return count
+
+
 class OrderMajorSeries:
     """A time series of coefficient sets that stays on the device between operators (the batching of TimeSeries.to_array,
     grates/gravityfield.py:964-980, in the layout the order-wise operators work on): `data` [(N+1)^2, Bpad] with the epochs fastest

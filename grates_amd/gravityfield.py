@@ -287,6 +287,23 @@ class PotentialCoefficients:
         T = engine.gravitational_gradients_points(self.max_degree, xyz, self.anm[np.newaxis, :, :], self.GM, self.R)[0]
         return T if as_tensor else engine.to_host(T)
 
+    def line_of_sight_acceleration(self, xyz_a, xyz_b, directions=None, as_tensor=False):
+        """
+        Line-of-sight gravity difference [m/s^2] of M satellite pairs at the cartesian positions xyz_a (M, 3) and xyz_b (M, 3):
+        l_i = e_i . (g(b_i) - g(a_i)), [M], the inter-satellite observation in the acceleration approach.  directions (M, 3) are the
+        lines of sight e (unit vectors within 1e-12, else ValueError); without them e = (b - a) / |b - a|, and no pair may coincide.
+        One call of the GPU acceleration kernel (shg_acceleration_points) on the stacked 2 M points, then the difference and the
+        projection in torch.  Returns an ndarray, or the float64 device tensor with as_tensor=True.
+        """
+        M = engine.check_pair_positions(xyz_a, xyz_b)
+        if directions is not None:
+            engine.check_directions(directions, M)
+        else:
+            engine.check_pairs_apart(xyz_a, xyz_b)
+        g = self.gravitational_acceleration(_stack_pairs(xyz_a, xyz_b), as_tensor=True)
+        l = _project_line_of_sight(g, xyz_a, xyz_b, directions)
+        return l if as_tensor else engine.to_host(l)
+
 
 def _host_legendre_per_order(max_degree, order, colat):
     """Host NumPy per-order Legendre recursion (formulas of grates/utilities.py:62-115, 138-151) for the few
@@ -339,6 +356,44 @@ def gradient_design_matrix(xyz, min_degree, max_degree, GM=3.9860044150e+14, R=6
     At = engine.gradient_design(max_degree, xyz, GM, R, min_degree, frames, components, weights)
     A = At.permute(2, 1, 0).reshape(At.shape[1] * At.shape[2], At.shape[0])
     return A if as_tensor else engine.to_host(A)
+
+
+def line_of_sight_design_matrix(xyz_a, xyz_b, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None, weights=None,
+                                as_tensor=False):
+    """
+    Design matrix A [M, P] of the line-of-sight gravity difference of M satellite pairs, l_i = e_i . (g(b_i) - g(a_i)), at the
+    cartesian positions xyz_a (M, 3) and xyz_b (M, 3) with respect to the coefficients of degrees min_degree .. max_degree: one row per
+    pair, the columns follow utilities.ravel_coefficients, so that ``A @ ravel_coefficients(anm, min_degree, max_degree)`` equals
+    ``line_of_sight_acceleration(xyz_a, xyz_b)`` of a field without coefficients below min_degree.  directions (M, 3) are the lines of
+    sight e (unit vectors within 1e-12, else ValueError); without them e = (b - a) / |b - a|, and no pair may coincide.  weights (M,)
+    scale the rows by sqrt(w).  Always computed on the GPU (shg_los_design); returns an ndarray, or the float64 device tensor with
+    as_tensor=True.  The kernel builds the transposed matrix (engine.los_design, what NormalEquations.from_line_of_sight accumulates
+    block by block); the transposition here is a copy meant for modest sizes.
+    """
+    A = engine.los_design(max_degree, xyz_a, xyz_b, GM, R, min_degree, directions, weights).t().contiguous()
+    return A if as_tensor else engine.to_host(A)
+
+
+def _project_line_of_sight(g, xyz_a, xyz_b, directions):
+    """e . (g_b - g_a) [..., M] in torch from the accelerations g [..., 2 M, 3] of the stacked points (a first, then b): the
+    difference per component first, then the projection, as shg_los_design orders them"""
+    M = g.shape[-2] // 2
+    d = g[..., M:, :] - g[..., :M, :]
+    if directions is None:
+        e = engine.to_device(xyz_b, g.device) - engine.to_device(xyz_a, g.device)
+        e = e / ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]).sqrt()[..., None]
+    else:
+        e = engine.to_device(directions, g.device)
+    return (e[..., 0] * d[..., 0] + e[..., 1] * d[..., 1]) + e[..., 2] * d[..., 2]     # element-wise: one fixed order of operations
+
+
+def _stack_pairs(xyz_a, xyz_b):
+    """the 2 M points of M pairs, a first, then b, along the point axis, on the host or on the device as given"""
+    if isinstance(xyz_a, np.ndarray) and isinstance(xyz_b, np.ndarray):
+        return np.concatenate((xyz_a, xyz_b), axis=-2)
+    import torch
+    a = engine.to_device(xyz_a)
+    return torch.cat((a, engine.to_device(xyz_b, a.device)), dim=-2)
 
 
 def synthesize(anm_batch, grid, kernel='ewh', GM=3.9860044150e+14, R=6.3781363000e+06):
@@ -641,6 +696,29 @@ class TimeSeries:
                 import torch
                 T = torch.stack([d.gravitational_gradients(xyz[k] if per_epoch else xyz, as_tensor=True) for k, d in enumerate(fields)])
         return T if as_tensor else engine.to_host(T)
+
+    def line_of_sight_acceleration(self, xyz_a, xyz_b, directions=None, as_tensor=False):
+        """
+        Line-of-sight gravity difference [m/s^2] of every epoch, [T, M], l[t, i] = e_i . (g_t(b_i) - g_t(a_i)), of M satellite pairs
+        at the positions xyz_a and xyz_b: both [M, 3] for all epochs or both [T, M, 3] (pairs of their own per epoch).  directions, of
+        the shape of the positions, are the lines of sight e (unit vectors within 1e-12); without them e = (b - a) / |b - a|, and no
+        pair may coincide.  One gravitational_acceleration call on the stacked 2 M points, then the difference and the projection in
+        torch.  Returns an ndarray, or the float64 device tensor with as_tensor=True.
+        """
+        per_epoch = engine.check_acceleration_points(xyz_a, len(self))
+        shape = tuple(xyz_a.shape)
+        if tuple(xyz_b.shape) != shape:
+            raise ValueError('the positions of the two satellites must have the same shape, got {0} and {1}'.format(shape, tuple(xyz_b.shape)))
+        if directions is not None and tuple(directions.shape) != shape:
+            raise ValueError('directions must have shape {0}, got {1}'.format(shape, tuple(directions.shape)))
+        flat = (lambda x: x.reshape(-1, 3)) if per_epoch else (lambda x: x)
+        if directions is not None:
+            engine.check_directions(flat(directions), shape[0] * shape[1] if per_epoch else shape[0])
+        else:
+            engine.check_pairs_apart(flat(xyz_a), flat(xyz_b))
+        g = self.gravitational_acceleration(_stack_pairs(xyz_a, xyz_b), as_tensor=True)
+        l = _project_line_of_sight(g, xyz_a, xyz_b, directions)
+        return l if as_tensor else engine.to_host(l)
 
     def detrend(self, basis_functions):
         """

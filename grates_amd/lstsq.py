@@ -665,6 +665,64 @@ class NormalEquations:
         matrix._set_device(0, 0, normals)
         return cls(matrix, side, float(square_sum.item()), K * M)
 
+    @classmethod
+    def from_line_of_sight(cls, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
+                           weights=None, block_points=None):
+        """
+        Normal equations of the coefficients of degrees min_degree .. max_degree (in the order of utilities.ravel_coefficients) from
+        line-of-sight gravity differences l_i = e_i . (g(b_i) - g(a_i)) [M] of M satellite pairs at the cartesian positions xyz_a
+        [M, 3] and xyz_b [M, 3] (host arrays or device tensors; usually reduced by a reference field).  directions [M, 3] are the lines
+        of sight e (unit vectors within 1e-12); without them e = (b - a) / |b - a|, and no pair may coincide.  weights [M] (finite,
+        >= 0; default 1) are those of the observations.
+
+        The block loop of from_accelerations with At [P, Mb] from shg_los_design; the default block is the largest multiple of 256
+        pairs that keeps At within 256 MB, at least 256.  Returns NormalEquations with a one-block BlockMatrix [P, P] and the
+        right-hand side [P, 1] on the device, and observation_count = M.  Normals of the same degrees add up through
+        accumulate_normals, those of from_accelerations included: the combination of orbit and link.
+        """
+        min_degree, max_degree = int(min_degree), int(max_degree)
+        if min_degree < 0 or min_degree > max_degree:
+            raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
+        M = engine.check_pair_positions(xyz_a, xyz_b)
+        if len(differences.shape) != 1:
+            raise ValueError('differences must have shape (M,), got {0}'.format(tuple(differences.shape)))
+        if int(differences.shape[0]) != M:
+            raise ValueError('{0} pairs but {1} differences'.format(M, int(differences.shape[0])))
+        layout = engine.check_observation_weights(weights, M, 1)
+        if layout and len(weights.shape) != 1:
+            raise ValueError('weights must have shape ({0},), got {1}'.format(M, tuple(weights.shape)))
+        if directions is not None:
+            engine.check_directions(directions, M)
+        else:
+            engine.check_pairs_apart(xyz_a, xyz_b)
+        P = (max_degree + 1) ** 2 - min_degree ** 2
+        if block_points is None:
+            block_points = max(cls.DESIGN_BLOCK_BYTES // (8 * P) // 256 * 256, 256)
+        block_points = int(block_points)
+        if block_points < 1:
+            raise ValueError('block_points must be positive, got {0}'.format(block_points))
+
+        torch = engine.require_gpu()
+        a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
+        e = engine.to_device(directions) if directions is not None else None
+        if layout:
+            w = engine.to_device(weights)
+            l = l * torch.sqrt(w)[:, None]
+        normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
+        for first in range(0, M, block_points):
+            last = min(first + block_points, M)
+            At = engine.los_design_checked(max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last],
+                                           None if not layout else w[first:last], GM, R)
+            lb = l[first:last]
+            engine.gemm(At, At, transb=True, beta=1.0, out=normals)
+            engine.gemm(At, lb, beta=1.0, out=side)
+            engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
+        normals.triu_()
+        normals.add_(torch.triu(normals, 1).t())
+        matrix = BlockMatrix([0, P], [0, P])
+        matrix._set_device(0, 0, normals)
+        return cls(matrix, side, float(square_sum.item()), M)
+
     def __cholesky(self):
         """factor the matrix once; a matrix that already holds covariances cannot be factored again (ValueError, as upstream)"""
         if self.status == 'covariance_matrix' or self.status not in ('normal_matrix', 'cholesky_factor'):

@@ -523,6 +523,31 @@ int shg_gradient_design(int N, int min_degree, const double* xyz, int M, const d
                         int weight_layout, double GM, double R, double* At, int ldt, void* stream);
 int shg_gradient_design_terms(int N, int min_degree, int32_t* slot, double* factor, long long capacity);
 
+/* ------------------------------------------------------------------------------------------------
+ * Design matrix of the line-of-sight gravity difference of satellite pairs, l_i = e_i . (g(b_i) - g(a_i)) (the inter-satellite link
+ * in the acceleration approach; no reference counterpart)
+ *   At [P][ldt], transposed like shg_acceleration_design: row p is coefficient p of utilities.ravel_coefficients(., min_degree, N),
+ *   the M pairs xyz_a [M][3], xyz_b [M][3] innermost (ldt >= M; the entries from M to ldt of a row are not touched).
+ *   At[p][i] = sqrt(w_i) e_i . (d g(b_i) / d x_p - d g(a_i) / d x_p) in m/s^2.
+ *   directions == NULL: e_i = (b_i - a_i) / |b_i - a_i|, computed in the kernel as d = b - a per component,
+ *   |d| = sqrt((d_x d_x + d_y d_y) + d_z d_z), e_c = d_c / |d|.  A pair with a_i == b_i then gives NaN in its column i: callers must
+ *   not pass one (the Python layer refuses them).  Otherwise e_i = directions[i] of directions [M][3], taken as given: unit length is
+ *   not checked here.
+ *   Per pass of pairs the solid harmonics kernel of shg_acceleration_design runs on the a-points and on the b-points, in one launch
+ *   (bitwise the harmonics that call uses), into one workspace; both halves together stay within its 256 MB, so a pass holds
+ *   max(256 MB / 8 / (4 packed(N + 1)) rounded down to a multiple of 256, 256) pairs, packed(n) = (n + 1)(n + 2) / 2
+ *   (shg_los_design_pass returns this number: host only, no HIP call, -1 for N < 0 or N > 32766).  A second kernel forms, per row and
+ *   pair, the three unscaled component sums of the acceleration's table at b and at a, their difference per component, the projection
+ *   (e_x d_x + e_y d_y) + e_z d_z, then * GM / (2 R^2), then * sqrt(w) (weights [M], finite and >= 0, or NULL), and stores once.
+ *   No atomics: the entries of a pair do not depend on the other pairs of the call, and repeated calls are bitwise equal.  Swapping a
+ *   and b leaves At bitwise unchanged with directions == NULL and negates it bitwise with directions given.
+ *   Arguments are checked before the first HIP call (the rules of shg_acceleration_design: negative sizes, min_degree > N,
+ *   N > 32766, GM or R not finite, R <= 0, ldt < M; NULL xyz_a, xyz_b or At; more than 2^40 values of At); M = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_los_design(int N, int min_degree, const double* xyz_a, const double* xyz_b, const double* directions, int M, const double* weights,
+                   double GM, double R, double* At, int ldt, void* stream);
+int shg_los_design_pass(int N);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
