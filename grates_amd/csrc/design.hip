@@ -22,9 +22,14 @@
 //
 // The line-of-sight gravity difference of satellite pairs (third part) needs no table of its own: its gather kernel reads the
 // acceleration's table at the two satellites of a pair, takes the difference and projects it on the line of sight.
+//
+// The host side is one of each: d_terms is the only place that knows f-, f0, f+ (both tables are built from it), design_passes is the
+// pass driver (pass size, workspace, upload of recursion factors and table) around the launches of an entry point, and check_design
+// holds the argument checks the entry points share.
 #include "common.h"
 
 #include <cmath>
+#include <memory>
 
 namespace shg {
 
@@ -105,60 +110,15 @@ __global__ __launch_bounds__(256) void design_gather_kernel(int npts, const doub
     }
 }
 
-// terms of the rows of the acceleration's design matrix, [P][3][2] each, rows in the order of utilities.degreewise_array_index
-static void acceleration_design_table(int N, int min_degree, std::vector<int>& slot, std::vector<double>& factor) {
-    const int N1 = N + 1;
-    const size_t P = (size_t)(N + 1) * (N + 1) - (size_t)min_degree * min_degree;
-    slot.assign(P * 6, -1);
-    factor.assign(P * 6, 0.0);
-    size_t row = 0;
-    for (int n = min_degree; n <= N; ++n) {
-        const double dn = n;
-        const double base = sqrt((2.0 * dn + 1.0) / (2.0 * dn + 3.0));
-        for (int j = 0; j <= 2 * n; ++j, ++row) {
-            const int m = (j + 1) / 2;
-            const int sine = (j > 0 && j % 2 == 0) ? 1 : 0;
-            const double dm = m;
-            int* sl = &slot[row * 6];
-            double* f = &factor[row * 6];
-            // the solid harmonic of (n + 1, k) that multiplies this coefficient: the same kind (cosine | sine) in x and z, the other in y
-            auto term = [&](int c, int j2, int k, int kind, double value) {
-                if (kind == 1 && k == 0) return;                     // Ys of order 0 is zero
-                sl[c * 2 + j2] = 2 * (order_offset(N1, k) + n + 1 - k) + kind;
-                f[c * 2 + j2] = value;
-            };
-            if (m >= 1) {                                            // minus term: P_{n+1,m-1}
-                double fm = sqrt((dn - dm + 1.0) * (dn - dm + 2.0)) * base;
-                if (m == 1) fm *= sqrt(2.0);
-                term(0, 0, m - 1, sine, fm);
-                term(1, 0, m - 1, 1 - sine, sine ? fm : -fm);
-            }
-            {                                                        // plus term: P_{n+1,m+1}
-                double fp = sqrt((dn + dm + 1.0) * (dn + dm + 2.0)) * base;
-                if (m == 0) fp *= sqrt(2.0);
-                term(0, 1, m + 1, sine, -fp);
-                term(1, 1, m + 1, 1 - sine, sine ? fp : -fp);
-            }
-            const double f0 = sqrt((dn - dm + 1.0) * (dn + dm + 1.0)) * base;
-            term(2, 0, m, sine, -2.0 * f0);
-        }
-    }
-}
-
-// ---- design matrix of the gradient tensor -------------------------------------------------------------------------------------------
-// T = d^2 V / dx_c dx_d is the acceleration's map D (head of gradients.hip) applied twice, so its partial derivative with respect to
-// one coefficient is a sum of at most four terms factor * Y[slot] on the solid harmonics of degree N + 2, in units of GM / (4 R^3):
-// D_c turns the unit coefficient (n, m, kind) into at most two of degree n + 1, D_d each of those into at most two of degree n + 2,
-// and terms that meet on one slot (the order m of xx, xy and yy) are merged on the host.
-constexpr int kGradTerms = 4;
-constexpr int kGradRows = 16;                         // rows of At per workgroup of gradient_design_kernel
-
+// ---- the term map ------------------------------------------------------------------------------------------------------------------
+// One map serves every table of this file: D_c, the derivative along axis c of a single solid-harmonic coefficient (the grouping at
+// the head of acceleration.hip).  The acceleration's rows are D_c of the unit coefficient, the gradient tensor's D_d of D_c.
 struct SolidTerm {
     int n, k, kind;                                   // kind 0: cosine, 1: sine
     double f;
 };
 
-// D_c (0: x, 1: y, 2: z) of the single coefficient `in`: the terms of degree in.n + 1 (the rows of acceleration_design_table)
+// D_c (0: x, 1: y, 2: z) of the single coefficient `in`: the terms of degree in.n + 1, the minus term (order k - 1) before the plus term
 static int d_terms(int c, const SolidTerm& in, SolidTerm out[2]) {
     int count = 0;
     const int n = in.n, m = in.k, sine = in.kind;
@@ -190,6 +150,39 @@ static int d_terms(int c, const SolidTerm& in, SolidTerm out[2]) {
     return count;
 }
 
+// slot of a term in Y of degree Ny: 2 packed(n, k) + kind
+static int term_slot(int Ny, const SolidTerm& t) { return 2 * (order_offset(Ny, t.k) + t.n - t.k) + t.kind; }
+
+// the unit coefficient of row j of degree n in the order of utilities.degreewise_array_index: C_n0, C_n1, S_n1, C_n2, ...
+static SolidTerm unit_coefficient(int n, int j) { return SolidTerm{n, (j + 1) / 2, (j > 0 && j % 2 == 0) ? 1 : 0, 1.0}; }
+
+// terms of the rows of the acceleration's design matrix, [P][3][2] each (the layout design_gather_kernel<3, 2> and los_design_kernel
+// read): D_c of the unit coefficient on Y of degree N + 1, in the order of d_terms, then slot -1 and factor 0.0 (no term)
+static void acceleration_design_table(int N, int min_degree, int* slot, double* factor) {
+    size_t row = 0;
+    for (int n = min_degree; n <= N; ++n) {
+        for (int j = 0; j <= 2 * n; ++j, ++row) {
+            const SolidTerm unit = unit_coefficient(n, j);
+            for (int c = 0; c < 3; ++c) {
+                SolidTerm terms[2];
+                const int count = d_terms(c, unit, terms);
+                for (int i = 0; i < 2; ++i) {
+                    slot[(row * 3 + c) * 2 + i] = i < count ? term_slot(N + 1, terms[i]) : -1;
+                    factor[(row * 3 + c) * 2 + i] = i < count ? terms[i].f : 0.0;
+                }
+            }
+        }
+    }
+}
+
+// ---- design matrix of the gradient tensor -------------------------------------------------------------------------------------------
+// T = d^2 V / dx_c dx_d is the acceleration's map D (head of gradients.hip) applied twice, so its partial derivative with respect to
+// one coefficient is a sum of at most four terms factor * Y[slot] on the solid harmonics of degree N + 2, in units of GM / (4 R^3):
+// D_c turns the unit coefficient (n, m, kind) into at most two of degree n + 1, D_d each of those into at most two of degree n + 2,
+// and terms that meet on one slot (the order m of xx, xy and yy) are merged on the host.
+constexpr int kGradTerms = 4;
+constexpr int kGradRows = 16;                         // rows of At per workgroup of gradient_design_kernel
+
 // terms of the rows of the gradient tensor's design matrix, [P][6][kGradTerms] each (xx, xy, xz, yy, yz, zz: D_d of D_c, c <= d), rows
 // in the order of utilities.degreewise_array_index; slot = 2 packed(n + 2, k) + kind at degree N + 2, -1: no term
 static void gradient_design_table(int N, int min_degree, int* slot, double* factor) {
@@ -197,7 +190,7 @@ static void gradient_design_table(int N, int min_degree, int* slot, double* fact
     size_t row = 0;
     for (int n = min_degree; n <= N; ++n) {
         for (int j = 0; j <= 2 * n; ++j, ++row) {
-            const SolidTerm unit{n, (j + 1) / 2, (j > 0 && j % 2 == 0) ? 1 : 0, 1.0};
+            const SolidTerm unit = unit_coefficient(n, j);
             int comp = 0;
             for (int c = 0; c < 3; ++c) {
                 SolidTerm first[2];
@@ -214,7 +207,7 @@ static void gradient_design_table(int N, int min_degree, int* slot, double* fact
                         SolidTerm second[2];
                         const int n2 = d_terms(d, first[i], second);
                         for (int q = 0; q < n2; ++q) {
-                            const int s = 2 * (order_offset(N2, second[q].k) + n + 2 - second[q].k) + second[q].kind;
+                            const int s = term_slot(N2, second[q]);
                             int at = 0;
                             while (at < used && sl[at] != s) ++at;
                             if (at == used) sl[used++] = s;
@@ -302,13 +295,6 @@ __global__ __launch_bounds__(256) void gradient_design_kernel(int npts, long lon
 // the line of sight of the pair, so the gather kernel reads the terms of acceleration_design_table at two points.
 constexpr int kLosRows = 16;                          // rows of At per workgroup of los_design_kernel
 
-// pairs per pass: the harmonics of both satellites share the 256 MB of the acceleration's pass, so a pass holds half as many pairs
-// as that one holds points, in whole workgroups, at least one
-static long long los_design_pass(int N) {
-    const long long packed = packed_count(N + 1);
-    return std::max<long long>((256LL << 20) / 8 / (4 * packed) / 256 * 256, 256);
-}
-
 // Rows blockIdx.x * kLosRows ... of the transposed design matrix of the line-of-sight difference, 256 pairs per workgroup
 // (blockIdx.y): out [rows][ldt].  Y holds the solid harmonics of the pass, those of the a-points in the columns 0 .. and those of the
 // b-points in the columns `half` .. of every slot.  A lane keeps the line of sight e and sqrt(w) of its pair across the rows of the
@@ -363,216 +349,172 @@ __global__ __launch_bounds__(256) void los_design_kernel(int npairs, long long r
 
 using namespace shg;
 
-static int acceleration_design(int N, int min_degree, const double* xyz, int M, const double* weights, int wl, double GM, double R, double* At, int ldt,
-                               hipStream_t stream) {
-    const int N1 = N + 1;
-    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
-    const long long packed = packed_count(N1);
-    // points per pass: Y of a pass stays under 256 MB (the budget of the acceleration's Q), in whole workgroups, at least one
-    const long long budget = (256LL << 20) / 8 / (2 * packed) / 256 * 256;
-    const int pass = (int)std::min<long long>({std::max<long long>(budget, 256), ((long long)M + 255) / 256 * 256, 65535LL * 256});
-    const double scale = GM / (2.0 * R * R);
+// ---- host side: one pass driver and one set of checks for the three design matrices ---------------------------------------------------
+using TableBuilder = void (*)(int N, int min_degree, int* slot, double* factor);
+
+static long long design_rows(int N, int min_degree) { return (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree; }
+
+// points of one set per pass: Y [packed (n', k)][2][sets * pass] of degree Ny stays under 256 MB (the budget of the acceleration's Q),
+// in whole workgroups, at least one.  sets = 2: the two satellites of the line-of-sight design share the budget.
+static long long design_pass_points(int Ny, int sets) {
+    return std::max<long long>((256LL << 20) / 8 / (2LL * sets * packed_count(Ny)) / 256 * 256, 256);
+}
+
+// what a pass of points works with: device buffers that live until design_passes returns
+struct DesignPass {
+    int pass;                                         // points of one set per pass, the offset of the second set in a column of Y
+    size_t ldy;                                       // sets * pass
+    double2* ab;                                      // recursion factors of degree Ny, a and b of one (n', k) side by side
+    double* Y;
+    int* slot;                                        // the table of `build`, [P][entries]
+    double* factor;
+};
+
+// The scaffolding of a design matrix on the solid harmonics of degree Ny at `sets` (1 | 2) sets of M points: pass size, workspace,
+// upload of the recursion factors and of the term table (`entries` per row), a wait for the stream (the host tables go out of scope),
+// then launch(pass, p0, np) for the points p0 .. p0 + np of every pass, which enqueues the kernels of its functional.
+template <class Launch>
+static int design_passes(const char* fn, int Ny, int sets, int N, int min_degree, TableBuilder build, int entries, int M, hipStream_t stream,
+                         Launch launch) {
+    const size_t table = (size_t)design_rows(N, min_degree) * entries, packed = (size_t)packed_count(Ny);
+    DesignPass d;
+    d.pass = (int)std::min<long long>({design_pass_points(Ny, sets), ((long long)M + 255) / 256 * 256, 65535LL * 256});
+    d.ldy = (size_t)sets * d.pass;
     Workspace ws = Workspace::plain(stream);
-    double2* ab;
-    double *Y, *factor;
-    int* slot;
-    if (!ws.alloc(ab, (size_t)packed, Y, (size_t)packed * 2 * pass, factor, (size_t)P * 6, slot, (size_t)P * 6))
-        return fail(SHG_ERR_NOMEM, "shg_acceleration_design: workspace allocation failed");
-    {   // recursion factors of degree N + 1 (a and b of one (n', k) side by side) and the terms of the rows
-        std::vector<double> a, b, h(2 * (size_t)packed), f;
-        std::vector<int> sl;
-        recursion_tables(N1, a, b);
+    if (!ws.alloc(d.ab, packed, d.Y, packed * 2 * d.ldy, d.factor, table, d.slot, table))
+        return fail(SHG_ERR_NOMEM, "%s: workspace allocation failed", fn);
+    {
+        std::vector<double> a, b, h(2 * packed);
+        const std::unique_ptr<double[]> f(new double[table]);        // the builders write every entry, padding included
+        const std::unique_ptr<int[]> sl(new int[table]);
+        recursion_tables(Ny, a, b);
         for (size_t i = 0; i < a.size(); ++i) {
             h[2 * i] = a[i];
             h[2 * i + 1] = b[i];
         }
-        acceleration_design_table(N, min_degree, sl, f);
-        SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipMemcpyAsync(factor, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipMemcpyAsync(slot, sl.data(), sl.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        build(N, min_degree, sl.get(), f.get());
+        SHG_HIP(hipMemcpyAsync(d.ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(d.factor, f.get(), table * sizeof(double), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipMemcpyAsync(d.slot, sl.get(), table * sizeof(int), hipMemcpyHostToDevice, stream));
         SHG_HIP(hipStreamSynchronize(stream));
     }
-    for (int p0 = 0; p0 < M; p0 += pass) {
-        const int np = std::min(pass, M - p0);
-        hipLaunchKernelGGL(design_harmonics_kernel<false>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N1, np, xyz + (size_t)p0 * 3, nullptr, ab, R, Y,
-                           (size_t)pass, (size_t)0);
-        const double* w = wl == 0 ? nullptr : weights + (size_t)p0 * (wl == 2 ? 3 : 1);
-        hipLaunchKernelGGL((design_gather_kernel<3, 2>), dim3((unsigned)P, ceil_div(np, 256)), dim3(256), 0, stream, np, Y, (size_t)pass, slot, factor, w, wl,
-                           scale, At + p0, (size_t)ldt);
+    for (int p0 = 0; p0 < M; p0 += d.pass) {
+        launch(d, p0, std::min(d.pass, M - p0));
         SHG_HIP(hipGetLastError());
     }
     return SHG_OK;
 }
 
-// Arguments are checked before the first HIP call (the CPU tests call this without a device).
-extern "C" int shg_acceleration_design(int N, int min_degree, const double* xyz, int M, const double* weights, int weight_layout, double GM, double R,
-                                       double* At, int ldt, void* stream) {
-    const char* fn = "shg_acceleration_design";
-    SHG_REQUIRE(N >= 0 && min_degree >= 0 && M >= 0, "%s: negative size (N %d, min_degree %d, M %d)", fn, N, min_degree, M);
+// N and min_degree of a table on the solid harmonics of degree N + above (1 | 2): packed indices of that degree are ints
+static int check_design_degrees(const char* fn, int N, int min_degree, int above) {
+    SHG_REQUIRE(N >= 0 && min_degree >= 0, "%s: negative size (N %d, min_degree %d)", fn, N, min_degree);
     SHG_REQUIRE(min_degree <= N, "%s: min_degree %d above N %d", fn, min_degree, N);
-    SHG_REQUIRE(N <= 32766, "%s: N %d is too large", fn, N);
+    SHG_REQUIRE(N <= 32767 - above, "%s: N %d is too large", fn, N);
+    return SHG_OK;
+}
+
+// What the three entry points check alike, before the first HIP call (the CPU tests call them without a device): the output is
+// At [P][K][ldt].  The pointers are the caller's to check, after it has returned SHG_OK for M == 0.
+static int check_design(const char* fn, int N, int min_degree, int above, int M, int K, int weight_layout, double GM, double R, int ldt) {
+    SHG_REQUIRE(M >= 0, "%s: negative size (M %d)", fn, M);
+    if (int rc = check_design_degrees(fn, N, min_degree, above)) return rc;
     SHG_REQUIRE(weight_layout == SHG_WEIGHTS_NONE || weight_layout == SHG_WEIGHTS_POINT || weight_layout == SHG_WEIGHTS_COMPONENT,
                 "%s: weight layout %d, expected 0 (none), 1 (per point) or 2 (per component)", fn, weight_layout);
     SHG_REQUIRE(std::isfinite(GM) && std::isfinite(R) && R > 0.0, "%s: GM and R must be finite and R positive (GM %g, R %g)", fn, GM, R);
     SHG_REQUIRE(ldt >= M, "%s: ldt %d below M %d", fn, ldt, M);
-    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
-    SHG_REQUIRE(P * 3 * ldt <= (1LL << 40), "%s: output of %lld values is too large", fn, P * 3 * ldt);
+    const long long P = design_rows(N, min_degree);
+    SHG_REQUIRE(ldt == 0 || P * K <= (1LL << 40) / ldt, "%s: output of %lld x %d x %d values is too large", fn, P, K, ldt);
+    return SHG_OK;
+}
+
+extern "C" int shg_acceleration_design(int N, int min_degree, const double* xyz, int M, const double* weights, int weight_layout, double GM, double R,
+                                       double* At, int ldt, void* stream_) {
+    const char* fn = "shg_acceleration_design";
+    if (int rc = check_design(fn, N, min_degree, 1, M, 3, weight_layout, GM, R, ldt)) return rc;
     if (M == 0) return SHG_OK;
     SHG_REQUIRE(xyz && At && (weights || weight_layout == SHG_WEIGHTS_NONE), "%s: NULL pointer", fn);
-    return acceleration_design(N, min_degree, xyz, M, weights, weight_layout, GM, R, At, ldt, (hipStream_t)stream);
-}
-
-static int gradient_design(int N, int min_degree, const double* xyz, int M, const double* frames, int mask, const double* weights, int wl, double GM,
-                           double R, double* At, int ldt, hipStream_t stream) {
-    const int N2 = N + 2;
-    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
-    const long long packed = packed_count(N2);
-    const int K = __builtin_popcount((unsigned)mask);
-    // points per pass: Y of a pass stays under 256 MB, in whole workgroups, at least one (the rule of acceleration_design)
-    const long long budget = (256LL << 20) / 8 / (2 * packed) / 256 * 256;
-    const int pass = (int)std::min<long long>({std::max<long long>(budget, 256), ((long long)M + 255) / 256 * 256, 65535LL * 256});
-    const double scale = GM / (4.0 * R * R * R);
-    Workspace ws = Workspace::plain(stream);
-    double2* ab;
-    double *Y, *factor;
-    int* slot;
-    if (!ws.alloc(ab, (size_t)packed, Y, (size_t)packed * 2 * pass, factor, (size_t)P * 6 * kGradTerms, slot, (size_t)P * 6 * kGradTerms))
-        return fail(SHG_ERR_NOMEM, "shg_gradient_design: workspace allocation failed");
-    {   // recursion factors of degree N + 2 (a and b of one (n'', k) side by side) and the terms of the rows
-        std::vector<double> a, b, h(2 * (size_t)packed), f((size_t)P * 6 * kGradTerms);
-        std::vector<int> sl((size_t)P * 6 * kGradTerms);
-        recursion_tables(N2, a, b);
-        for (size_t i = 0; i < a.size(); ++i) {
-            h[2 * i] = a[i];
-            h[2 * i + 1] = b[i];
-        }
-        gradient_design_table(N, min_degree, sl.data(), f.data());
-        SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipMemcpyAsync(factor, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipMemcpyAsync(slot, sl.data(), sl.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipStreamSynchronize(stream));
-    }
-    const unsigned row_groups = (unsigned)ceil_div64(P, kGradRows);
-    for (int p0 = 0; p0 < M; p0 += pass) {
-        const int np = std::min(pass, M - p0);
-        hipLaunchKernelGGL(design_harmonics_kernel<true>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N2, np, xyz + (size_t)p0 * 3, nullptr, ab, R, Y,
-                           (size_t)pass, (size_t)0);
-        const double* w = wl == 0 ? nullptr : weights + (size_t)p0 * (wl == 2 ? K : 1);
-        const dim3 grid(row_groups, ceil_div(np, 256));
-        if (frames)
-            hipLaunchKernelGGL(gradient_design_kernel<true>, grid, dim3(256), 0, stream, np, P, Y, (size_t)pass, slot, factor, frames + (size_t)p0 * 9,
-                               mask, K, w, wl, scale, At + p0, (size_t)ldt);
-        else
-            hipLaunchKernelGGL(gradient_design_kernel<false>, grid, dim3(256), 0, stream, np, P, Y, (size_t)pass, slot, factor, nullptr, mask, K, w, wl,
-                               scale, At + p0, (size_t)ldt);
-        SHG_HIP(hipGetLastError());
-    }
-    return SHG_OK;
-}
-
-// the rules the two gradient entry points share
-static int check_gradient_degrees(const char* fn, int N, int min_degree) {
-    SHG_REQUIRE(N >= 0 && min_degree >= 0, "%s: negative size (N %d, min_degree %d)", fn, N, min_degree);
-    SHG_REQUIRE(min_degree <= N, "%s: min_degree %d above N %d", fn, min_degree, N);
-    SHG_REQUIRE(N <= 32765, "%s: N %d is too large", fn, N);
-    return SHG_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int N1 = N + 1, wl = weight_layout;
+    const unsigned P = (unsigned)design_rows(N, min_degree);
+    const double scale = GM / (2.0 * R * R);
+    return design_passes(fn, N1, 1, N, min_degree, acceleration_design_table, 3 * 2, M, stream, [&](const DesignPass& d, int p0, int np) {
+        hipLaunchKernelGGL(design_harmonics_kernel<false>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N1, np, xyz + (size_t)p0 * 3, nullptr, d.ab, R, d.Y,
+                           d.ldy, (size_t)0);
+        const double* w = wl == 0 ? nullptr : weights + (size_t)p0 * (wl == 2 ? 3 : 1);
+        hipLaunchKernelGGL((design_gather_kernel<3, 2>), dim3(P, ceil_div(np, 256)), dim3(256), 0, stream, np, d.Y, d.ldy, d.slot, d.factor, w, wl,
+                           scale, At + p0, (size_t)ldt);
+    });
 }
 
 // Host only: no HIP call.
 extern "C" int shg_gradient_design_terms(int N, int min_degree, int32_t* slot, double* factor, long long capacity) {
     const char* fn = "shg_gradient_design_terms";
-    if (int rc = check_gradient_degrees(fn, N, min_degree)) return rc;
-    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
+    if (int rc = check_design_degrees(fn, N, min_degree, 2)) return rc;
+    const long long P = design_rows(N, min_degree);
     SHG_REQUIRE(capacity >= 6 * kGradTerms * P, "%s: capacity %lld below the %lld entries of the table", fn, capacity, 6 * kGradTerms * P);
     SHG_REQUIRE(slot && factor, "%s: NULL pointer", fn);
     gradient_design_table(N, min_degree, slot, factor);
     return SHG_OK;
 }
 
-// Arguments are checked before the first HIP call (the CPU tests call this without a device).
 extern "C" int shg_gradient_design(int N, int min_degree, const double* xyz, int M, const double* frames, int components, const double* weights,
-                                   int weight_layout, double GM, double R, double* At, int ldt, void* stream) {
+                                   int weight_layout, double GM, double R, double* At, int ldt, void* stream_) {
     const char* fn = "shg_gradient_design";
-    SHG_REQUIRE(M >= 0, "%s: negative size (M %d)", fn, M);
-    if (int rc = check_gradient_degrees(fn, N, min_degree)) return rc;
     SHG_REQUIRE(components >= 1 && components <= 63, "%s: components %d, expected a set of SHG_GRAD_XX ... SHG_GRAD_ZZ (1 .. 63)", fn, components);
-    SHG_REQUIRE(weight_layout == SHG_WEIGHTS_NONE || weight_layout == SHG_WEIGHTS_POINT || weight_layout == SHG_WEIGHTS_COMPONENT,
-                "%s: weight layout %d, expected 0 (none), 1 (per point) or 2 (per component)", fn, weight_layout);
-    SHG_REQUIRE(std::isfinite(GM) && std::isfinite(R) && R > 0.0, "%s: GM and R must be finite and R positive (GM %g, R %g)", fn, GM, R);
-    SHG_REQUIRE(ldt >= M, "%s: ldt %d below M %d", fn, ldt, M);
-    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
-    const long long K = __builtin_popcount((unsigned)components);
-    SHG_REQUIRE(ldt == 0 || P * K <= (1LL << 40) / ldt, "%s: output of %lld x %lld x %d values is too large", fn, P, K, ldt);
+    const int mask = components, K = __builtin_popcount((unsigned)mask);
+    if (int rc = check_design(fn, N, min_degree, 2, M, K, weight_layout, GM, R, ldt)) return rc;
     if (M == 0) return SHG_OK;
     SHG_REQUIRE(xyz && At && (weights || weight_layout == SHG_WEIGHTS_NONE), "%s: NULL pointer", fn);
-    return gradient_design(N, min_degree, xyz, M, frames, components, weights, weight_layout, GM, R, At, ldt, (hipStream_t)stream);
-}
-
-static int los_design(int N, int min_degree, const double* xyz_a, const double* xyz_b, const double* directions, int M, const double* weights, double GM,
-                      double R, double* At, int ldt, hipStream_t stream) {
-    const int N1 = N + 1;
-    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
-    const long long packed = packed_count(N1);
-    const int pass = (int)std::min<long long>({los_design_pass(N), ((long long)M + 255) / 256 * 256, 65535LL * 256});
-    const size_t ldy = 2 * (size_t)pass;                             // a-points in the columns 0 .., b-points in the columns pass ..
-    const double scale = GM / (2.0 * R * R);
-    Workspace ws = Workspace::plain(stream);
-    double2* ab;
-    double *Y, *factor;
-    int* slot;
-    if (!ws.alloc(ab, (size_t)packed, Y, (size_t)packed * 2 * ldy, factor, (size_t)P * 6, slot, (size_t)P * 6))
-        return fail(SHG_ERR_NOMEM, "shg_los_design: workspace allocation failed");
-    {   // recursion factors of degree N + 1 and the acceleration's terms of the rows, as in acceleration_design
-        std::vector<double> a, b, h(2 * (size_t)packed), f;
-        std::vector<int> sl;
-        recursion_tables(N1, a, b);
-        for (size_t i = 0; i < a.size(); ++i) {
-            h[2 * i] = a[i];
-            h[2 * i + 1] = b[i];
-        }
-        acceleration_design_table(N, min_degree, sl, f);
-        SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipMemcpyAsync(factor, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipMemcpyAsync(slot, sl.data(), sl.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipStreamSynchronize(stream));
-    }
-    const unsigned row_groups = (unsigned)ceil_div64(P, kLosRows);
-    for (int p0 = 0; p0 < M; p0 += pass) {
-        const int np = std::min(pass, M - p0);
-        const double *xa = xyz_a + (size_t)p0 * 3, *xb = xyz_b + (size_t)p0 * 3;
-        // one launch for both satellites (blockIdx.y): the kernel's time hardly depends on the number of workgroups at these sizes
-        hipLaunchKernelGGL(design_harmonics_kernel<false>, dim3(ceil_div(np, 256), 2), dim3(256), 0, stream, N1, np, xa, xb, ab, R, Y, ldy, (size_t)pass);
-        const double* w = weights ? weights + p0 : nullptr;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int N2 = N + 2, wl = weight_layout;
+    const long long P = design_rows(N, min_degree);
+    const unsigned row_groups = (unsigned)ceil_div64(P, kGradRows);
+    const double scale = GM / (4.0 * R * R * R);
+    return design_passes(fn, N2, 1, N, min_degree, gradient_design_table, 6 * kGradTerms, M, stream, [&](const DesignPass& d, int p0, int np) {
+        hipLaunchKernelGGL(design_harmonics_kernel<true>, dim3(ceil_div(np, 256)), dim3(256), 0, stream, N2, np, xyz + (size_t)p0 * 3, nullptr, d.ab, R, d.Y,
+                           d.ldy, (size_t)0);
+        const double* w = wl == 0 ? nullptr : weights + (size_t)p0 * (wl == 2 ? K : 1);
         const dim3 grid(row_groups, ceil_div(np, 256));
-        if (directions)
-            hipLaunchKernelGGL(los_design_kernel<false>, grid, dim3(256), 0, stream, np, P, xa, xb, directions + (size_t)p0 * 3, Y, ldy, (size_t)pass, slot,
-                               factor, w, scale, At + p0, (size_t)ldt);
+        if (frames)
+            hipLaunchKernelGGL(gradient_design_kernel<true>, grid, dim3(256), 0, stream, np, P, d.Y, d.ldy, d.slot, d.factor, frames + (size_t)p0 * 9, mask,
+                               K, w, wl, scale, At + p0, (size_t)ldt);
         else
-            hipLaunchKernelGGL(los_design_kernel<true>, grid, dim3(256), 0, stream, np, P, xa, xb, nullptr, Y, ldy, (size_t)pass, slot, factor, w, scale,
+            hipLaunchKernelGGL(gradient_design_kernel<false>, grid, dim3(256), 0, stream, np, P, d.Y, d.ldy, d.slot, d.factor, nullptr, mask, K, w, wl, scale,
                                At + p0, (size_t)ldt);
-        SHG_HIP(hipGetLastError());
-    }
-    return SHG_OK;
+    });
 }
 
 // Host only: no HIP call.  Pairs per pass of shg_los_design at degree N (before the call's own M caps it), -1 for a degree it refuses.
 extern "C" int shg_los_design_pass(int N) {
     if (N < 0 || N > 32766) return -1;
-    return (int)los_design_pass(N);
+    return (int)design_pass_points(N + 1, 2);
 }
 
-// Arguments are checked before the first HIP call (the CPU tests call this without a device).
 extern "C" int shg_los_design(int N, int min_degree, const double* xyz_a, const double* xyz_b, const double* directions, int M, const double* weights,
-                              double GM, double R, double* At, int ldt, void* stream) {
+                              double GM, double R, double* At, int ldt, void* stream_) {
     const char* fn = "shg_los_design";
-    SHG_REQUIRE(N >= 0 && min_degree >= 0 && M >= 0, "%s: negative size (N %d, min_degree %d, M %d)", fn, N, min_degree, M);
-    SHG_REQUIRE(min_degree <= N, "%s: min_degree %d above N %d", fn, min_degree, N);
-    SHG_REQUIRE(N <= 32766, "%s: N %d is too large", fn, N);
-    SHG_REQUIRE(std::isfinite(GM) && std::isfinite(R) && R > 0.0, "%s: GM and R must be finite and R positive (GM %g, R %g)", fn, GM, R);
-    SHG_REQUIRE(ldt >= M, "%s: ldt %d below M %d", fn, ldt, M);
-    const long long P = (long long)(N + 1) * (N + 1) - (long long)min_degree * min_degree;
-    SHG_REQUIRE(ldt == 0 || P <= (1LL << 40) / ldt, "%s: output of %lld x %d values is too large", fn, P, ldt);
+    // weights are per pair or absent: there is no layout argument, so the layout check of check_design cannot fail here
+    if (int rc = check_design(fn, N, min_degree, 1, M, 1, weights ? SHG_WEIGHTS_POINT : SHG_WEIGHTS_NONE, GM, R, ldt)) return rc;
     if (M == 0) return SHG_OK;
     SHG_REQUIRE(xyz_a && xyz_b && At, "%s: NULL pointer", fn);
-    return los_design(N, min_degree, xyz_a, xyz_b, directions, M, weights, GM, R, At, ldt, (hipStream_t)stream);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int N1 = N + 1;
+    const long long P = design_rows(N, min_degree);
+    const unsigned row_groups = (unsigned)ceil_div64(P, kLosRows);
+    const double scale = GM / (2.0 * R * R);
+    // the acceleration's table, read at both satellites: a-points in the columns 0 .. of Y, b-points in the columns pass ..
+    return design_passes(fn, N1, 2, N, min_degree, acceleration_design_table, 3 * 2, M, stream, [&](const DesignPass& d, int p0, int np) {
+        const double *xa = xyz_a + (size_t)p0 * 3, *xb = xyz_b + (size_t)p0 * 3;
+        // one launch for both satellites (blockIdx.y): the kernel's time hardly depends on the number of workgroups at these sizes
+        hipLaunchKernelGGL(design_harmonics_kernel<false>, dim3(ceil_div(np, 256), 2), dim3(256), 0, stream, N1, np, xa, xb, d.ab, R, d.Y, d.ldy,
+                           (size_t)d.pass);
+        const double* w = weights ? weights + p0 : nullptr;
+        const dim3 grid(row_groups, ceil_div(np, 256));
+        if (directions)
+            hipLaunchKernelGGL(los_design_kernel<false>, grid, dim3(256), 0, stream, np, P, xa, xb, directions + (size_t)p0 * 3, d.Y, d.ldy, (size_t)d.pass,
+                               d.slot, d.factor, w, scale, At + p0, (size_t)ldt);
+        else
+            hipLaunchKernelGGL(los_design_kernel<true>, grid, dim3(256), 0, stream, np, P, xa, xb, nullptr, d.Y, d.ldy, (size_t)d.pass, d.slot, d.factor, w,
+                               scale, At + p0, (size_t)ldt);
+    });
 }

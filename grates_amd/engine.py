@@ -793,24 +793,40 @@ def check_observation_weights(weights, points, components=3):
     return len(shape)
 
 
+def check_degrees(min_degree, max_degree):
+    """(min_degree, max_degree) as ints, 0 <= min_degree <= max_degree; ValueError otherwise."""
+    min_degree, max_degree = int(min_degree), int(max_degree)
+    if min_degree < 0 or min_degree > max_degree:
+        raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
+    return min_degree, max_degree
+
+
+def check_positions(xyz, name='positions'):
+    """The number of points M of `name` [M, 3]; ValueError for another shape."""
+    if len(xyz.shape) != 2 or xyz.shape[1] != 3:
+        raise ValueError('{0} must have shape (M, 3), got {1}'.format(name, tuple(xyz.shape)))
+    return int(xyz.shape[0])
+
+
 def acceleration_design(max_degree, xyz, GM, R, min_degree=0, weights=None):
     """Transposed design matrix At [P, 3, M] (device) of the gravitational acceleration at the positions xyz [M, 3]: At[p, c, i] is the
     derivative of component c of g at point i with respect to coefficient p of utilities.ravel_coefficients(., min_degree, max_degree),
     P = (max_degree + 1)^2 - min_degree^2 (shg_acceleration_design).  weights [M] or [M, 3] scale the entries by sqrt(w)."""
-    min_degree, max_degree = int(min_degree), int(max_degree)
-    if min_degree < 0 or min_degree > max_degree:
-        raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
-    if len(xyz.shape) != 2 or xyz.shape[1] != 3:
-        raise ValueError('positions must have shape (M, 3), got {0}'.format(tuple(xyz.shape)))
-    M = int(xyz.shape[0])
-    layout = check_observation_weights(weights, M)
-    torch = require_gpu()
+    min_degree, max_degree = check_degrees(min_degree, max_degree)
+    layout = check_observation_weights(weights, check_positions(xyz))
     x = to_device(xyz)
-    w = to_device(weights, x.device) if layout else None
+    return acceleration_design_checked(max_degree, min_degree, x, to_device(weights, x.device) if layout else None, GM, R)
+
+
+def acceleration_design_checked(max_degree, min_degree, x, weights, GM, R):
+    """shg_acceleration_design on device tensors that acceleration_design (or NormalEquations.from_accelerations, once for all its
+    blocks) has checked: positions x [M, 3], weights [M], [M, 3] or None."""
+    torch = require_gpu()
+    M = int(x.shape[0])
     P = (max_degree + 1) ** 2 - min_degree ** 2
     out = torch.empty((P, 3, M), dtype=torch.float64, device=x.device)
-    _lib.call('shg_acceleration_design', max_degree, min_degree, _ptr(x), M, _ptr(w) if layout else None, layout, float(GM), float(R), _ptr(out),
-              M, _stream())
+    _lib.call('shg_acceleration_design', max_degree, min_degree, _ptr(x), M, None if weights is None else _ptr(weights),
+              0 if weights is None else weights.dim(), float(GM), float(R), _ptr(out), M, _stream())
     return out
 
 
@@ -858,12 +874,8 @@ def gradient_design(max_degree, xyz, GM, R, min_degree=0, frames=None, component
     utilities.ravel_coefficients(., min_degree, max_degree) (shg_gradient_design).  frames [M, 3, 3] hold the instrument axes as rows
     (None: the Earth-fixed tensor); components is a sequence of distinct names from GRADIENT_COMPONENTS in any order (None: all six),
     the output always in canonical order; weights [M] or [M, K] scale the entries by sqrt(w)."""
-    min_degree, max_degree = int(min_degree), int(max_degree)
-    if min_degree < 0 or min_degree > max_degree:
-        raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
-    if len(xyz.shape) != 2 or xyz.shape[1] != 3:
-        raise ValueError('positions must have shape (M, 3), got {0}'.format(tuple(xyz.shape)))
-    M = int(xyz.shape[0])
+    min_degree, max_degree = check_degrees(min_degree, max_degree)
+    M = check_positions(xyz)
     picked = gradient_components(components)
     layout = check_observation_weights(weights, M, len(picked))
     if frames is not None:
@@ -887,12 +899,10 @@ def gradient_design_checked(max_degree, min_degree, x, frames, picked, weights, 
 
 def check_pair_positions(xyz_a, xyz_b):
     """The positions of M satellite pairs, xyz_a [M, 3] and xyz_b [M, 3]: returns M; ValueError otherwise.  Looks at the shapes only."""
-    for name, array in (('positions of the first satellite', xyz_a), ('positions of the second satellite', xyz_b)):
-        if len(array.shape) != 2 or array.shape[1] != 3:
-            raise ValueError('{0} must have shape (M, 3), got {1}'.format(name, tuple(array.shape)))
-    if int(xyz_a.shape[0]) != int(xyz_b.shape[0]):
-        raise ValueError('{0} positions of the first satellite but {1} of the second'.format(int(xyz_a.shape[0]), int(xyz_b.shape[0])))
-    return int(xyz_a.shape[0])
+    M, second = check_positions(xyz_a, 'positions of the first satellite'), check_positions(xyz_b, 'positions of the second satellite')
+    if M != second:
+        raise ValueError('{0} positions of the first satellite but {1} of the second'.format(M, second))
+    return M
 
 
 def check_directions(directions, M):
@@ -931,9 +941,7 @@ def los_design(max_degree, xyz_a, xyz_b, GM, R, min_degree=0, directions=None, w
     utilities.ravel_coefficients(., min_degree, max_degree), P = (max_degree + 1)^2 - min_degree^2 (shg_los_design).  directions
     [M, 3] are the lines of sight e (unit vectors; None: (b - a) / |b - a|, and no pair may then coincide); weights [M] scale the
     entries by sqrt(w)."""
-    min_degree, max_degree = int(min_degree), int(max_degree)
-    if min_degree < 0 or min_degree > max_degree:
-        raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
+    min_degree, max_degree = check_degrees(min_degree, max_degree)
     M = check_pair_positions(xyz_a, xyz_b)
     layout = check_observation_weights(weights, M, 1)
     if layout and len(weights.shape) != 1:

@@ -551,6 +551,45 @@ class NormalEquations:
     DESIGN_BLOCK_BYTES = 256 << 20      # budget of one block of the transposed design matrix in from_accelerations
 
     @classmethod
+    def default_block_points(cls, parameters, components):
+        """Default block of from_accelerations (3 components), from_gradients (K) and from_line_of_sight (1): the largest multiple
+        of 256 points that keeps At [parameters, components Mb] within DESIGN_BLOCK_BYTES, at least 256."""
+        return max(cls.DESIGN_BLOCK_BYTES // (8 * components * parameters) // 256 * 256, 256)
+
+    @classmethod
+    def __check_block_points(cls, block_points, min_degree, max_degree, components):
+        """block_points of a from_* call as a positive int (None: the default); ValueError otherwise, before anything reaches the
+        device."""
+        if block_points is None:
+            block_points = cls.default_block_points((max_degree + 1) ** 2 - min_degree ** 2, components)
+        block_points = int(block_points)
+        if block_points < 1:
+            raise ValueError('block_points must be positive, got {0}'.format(block_points))
+        return block_points
+
+    @classmethod
+    def __from_design_blocks(cls, min_degree, max_degree, l, block_points, design_block):
+        """The block loop of the from_* classmethods: l [M, K] are the observations times sqrt(w) on the device, design_block(first,
+        last) the transposed design matrix [P, K, Mb] (or [P, Mb]) of the points first .. last, scaled alike.  Per block N += At At^T,
+        n += At l and l^T P l += |l|^2 on the fp64 MFMA product; both triangles of N are computed and the upper one is mirrored."""
+        torch = engine.require_gpu()
+        M, K = (int(size) for size in l.shape)
+        P = (max_degree + 1) ** 2 - min_degree ** 2
+        normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
+        for first in range(0, M, block_points):
+            last = min(first + block_points, M)
+            At = design_block(first, last).reshape(P, K * (last - first))
+            lb = l[first:last].t().reshape(-1, 1)                      # component-major, as the columns of At
+            engine.gemm(At, At, transb=True, beta=1.0, out=normals)
+            engine.gemm(At, lb, beta=1.0, out=side)
+            engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
+        normals.triu_()
+        normals.add_(torch.triu(normals, 1).t())
+        matrix = BlockMatrix([0, P], [0, P])
+        matrix._set_device(0, 0, normals)
+        return cls(matrix, side, float(square_sum.item()), K * M)
+
+    @classmethod
     def from_accelerations(cls, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
         """
         Normal equations of the coefficients of degrees min_degree .. max_degree (in the order of utilities.ravel_coefficients) from
@@ -565,42 +604,20 @@ class NormalEquations:
         Returns NormalEquations with a one-block BlockMatrix [P, P] and the right-hand side [P, 1] on the device, and
         observation_count = 3 M: components of zero weight still count as observations.
         """
-        min_degree, max_degree = int(min_degree), int(max_degree)
-        if min_degree < 0 or min_degree > max_degree:
-            raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
-        for name, array in (('positions', xyz), ('accelerations', g)):
-            if len(array.shape) != 2 or array.shape[1] != 3:
-                raise ValueError('{0} must have shape (M, 3), got {1}'.format(name, tuple(array.shape)))
-        M = int(xyz.shape[0])
-        if int(g.shape[0]) != M:
+        min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
+        M = engine.check_positions(xyz)
+        if engine.check_positions(g, 'accelerations') != M:
             raise ValueError('{0} positions but {1} accelerations'.format(M, int(g.shape[0])))
         layout = engine.check_observation_weights(weights, M)
-        P = (max_degree + 1) ** 2 - min_degree ** 2
-        if block_points is None:
-            block_points = max(cls.DESIGN_BLOCK_BYTES // (24 * P) // 256 * 256, 256)
-        block_points = int(block_points)
-        if block_points < 1:
-            raise ValueError('block_points must be positive, got {0}'.format(block_points))
+        block_points = cls.__check_block_points(block_points, min_degree, max_degree, 3)
 
         torch = engine.require_gpu()
         x, l = engine.to_device(xyz), engine.to_device(g)
+        w = engine.to_device(weights) if layout else None
         if layout:
-            w = engine.to_device(weights)
             l = l * torch.sqrt(w if layout == 2 else w[:, None])
-        normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
-        for first in range(0, M, block_points):
-            last = min(first + block_points, M)
-            At = engine.acceleration_design(max_degree, x[first:last], GM, R, min_degree, None if not layout else w[first:last])
-            At = At.reshape(P, 3 * (last - first))
-            lb = l[first:last].t().reshape(-1, 1)                      # component-major, as the columns of At
-            engine.gemm(At, At, transb=True, beta=1.0, out=normals)
-            engine.gemm(At, lb, beta=1.0, out=side)
-            engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
-        normals.triu_()
-        normals.add_(torch.triu(normals, 1).t())
-        matrix = BlockMatrix([0, P], [0, P])
-        matrix._set_device(0, 0, normals)
-        return cls(matrix, side, float(square_sum.item()), 3 * M)
+        return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.acceleration_design_checked(
+            max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R))
 
     @classmethod
     def from_gradients(cls, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
@@ -617,12 +634,8 @@ class NormalEquations:
         256 points that keeps At within 256 MB, at least 256.  Returns NormalEquations with a one-block BlockMatrix [P, P] and the
         right-hand side [P, 1] on the device, and observation_count = K M.
         """
-        min_degree, max_degree = int(min_degree), int(max_degree)
-        if min_degree < 0 or min_degree > max_degree:
-            raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
-        if len(xyz.shape) != 2 or xyz.shape[1] != 3:
-            raise ValueError('positions must have shape (M, 3), got {0}'.format(tuple(xyz.shape)))
-        M = int(xyz.shape[0])
+        min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
+        M = engine.check_positions(xyz)
         picked = engine.gradient_components(components)
         K = len(picked)
         shape = tuple(gradients.shape)
@@ -634,36 +647,18 @@ class NormalEquations:
         layout = engine.check_observation_weights(weights, M, K)
         if frames is not None:
             engine.check_frames(frames, M)
-        P = (max_degree + 1) ** 2 - min_degree ** 2
-        if block_points is None:
-            block_points = max(cls.DESIGN_BLOCK_BYTES // (8 * K * P) // 256 * 256, 256)
-        block_points = int(block_points)
-        if block_points < 1:
-            raise ValueError('block_points must be positive, got {0}'.format(block_points))
+        block_points = cls.__check_block_points(block_points, min_degree, max_degree, K)
 
         torch = engine.require_gpu()
         x, l = engine.to_device(xyz), engine.to_device(gradients)
         f = engine.to_device(frames) if frames is not None else None
         if full:
             l = torch.stack([l[:, j // 3, j % 3] for j in ((0, 1, 2, 4, 5, 8)[i] for i in picked)], dim=1)
+        w = engine.to_device(weights) if layout else None
         if layout:
-            w = engine.to_device(weights)
             l = l * torch.sqrt(w if layout == 2 else w[:, None])
-        normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
-        for first in range(0, M, block_points):
-            last = min(first + block_points, M)
-            At = engine.gradient_design_checked(max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked,
-                                                None if not layout else w[first:last], GM, R)
-            At = At.reshape(P, K * (last - first))
-            lb = l[first:last].t().reshape(-1, 1)                      # component-major, as the columns of At
-            engine.gemm(At, At, transb=True, beta=1.0, out=normals)
-            engine.gemm(At, lb, beta=1.0, out=side)
-            engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
-        normals.triu_()
-        normals.add_(torch.triu(normals, 1).t())
-        matrix = BlockMatrix([0, P], [0, P])
-        matrix._set_device(0, 0, normals)
-        return cls(matrix, side, float(square_sum.item()), K * M)
+        return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.gradient_design_checked(
+            max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last], GM, R))
 
     @classmethod
     def from_line_of_sight(cls, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
@@ -680,9 +675,7 @@ class NormalEquations:
         right-hand side [P, 1] on the device, and observation_count = M.  Normals of the same degrees add up through
         accumulate_normals, those of from_accelerations included: the combination of orbit and link.
         """
-        min_degree, max_degree = int(min_degree), int(max_degree)
-        if min_degree < 0 or min_degree > max_degree:
-            raise ValueError('min_degree {0} must lie between 0 and max_degree {1}'.format(min_degree, max_degree))
+        min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
         M = engine.check_pair_positions(xyz_a, xyz_b)
         if len(differences.shape) != 1:
             raise ValueError('differences must have shape (M,), got {0}'.format(tuple(differences.shape)))
@@ -695,33 +688,16 @@ class NormalEquations:
             engine.check_directions(directions, M)
         else:
             engine.check_pairs_apart(xyz_a, xyz_b)
-        P = (max_degree + 1) ** 2 - min_degree ** 2
-        if block_points is None:
-            block_points = max(cls.DESIGN_BLOCK_BYTES // (8 * P) // 256 * 256, 256)
-        block_points = int(block_points)
-        if block_points < 1:
-            raise ValueError('block_points must be positive, got {0}'.format(block_points))
+        block_points = cls.__check_block_points(block_points, min_degree, max_degree, 1)
 
         torch = engine.require_gpu()
         a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
         e = engine.to_device(directions) if directions is not None else None
+        w = engine.to_device(weights) if layout else None
         if layout:
-            w = engine.to_device(weights)
             l = l * torch.sqrt(w)[:, None]
-        normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
-        for first in range(0, M, block_points):
-            last = min(first + block_points, M)
-            At = engine.los_design_checked(max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last],
-                                           None if not layout else w[first:last], GM, R)
-            lb = l[first:last]
-            engine.gemm(At, At, transb=True, beta=1.0, out=normals)
-            engine.gemm(At, lb, beta=1.0, out=side)
-            engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
-        normals.triu_()
-        normals.add_(torch.triu(normals, 1).t())
-        matrix = BlockMatrix([0, P], [0, P])
-        matrix._set_device(0, 0, normals)
-        return cls(matrix, side, float(square_sum.item()), M)
+        return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.los_design_checked(
+            max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last], GM, R))
 
     def __cholesky(self):
         """factor the matrix once; a matrix that already holds covariances cannot be factored again (ValueError, as upstream)"""

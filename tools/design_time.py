@@ -52,8 +52,7 @@ def main():
     M, nmin = args.points, 2
     for N in args.degrees:
         P = (N + 1) ** 2 - nmin ** 2
-        block = max(ga.lstsq.NormalEquations.DESIGN_BLOCK_BYTES // (24 * P) // 256 * 256, 256)
-        block = min(block, M)
+        block = min(ga.lstsq.NormalEquations.default_block_points(P, 3), M)
         xyz = ga.engine.to_device(ai.scattered_positions(M, N + M))
         g = torch.from_numpy(np.random.default_rng(N).standard_normal((M, 3)) * 1e-6).to(xyz.device)
         xb = xyz[:block].contiguous()

@@ -65,7 +65,7 @@ def main():
         frames_all = ga.engine.to_device(gdi.frames(M, N))
         for label, components, framed in CASES:
             K = 6 if components is None else len(components)
-            block = min(max(ga.lstsq.NormalEquations.DESIGN_BLOCK_BYTES // (8 * K * P) // 256 * 256, 256), M)
+            block = min(ga.lstsq.NormalEquations.default_block_points(P, K), M)
             frames = frames_all if framed else None
             obs = torch.from_numpy(np.random.default_rng(N).standard_normal((M, K)) * 1e-9).to(xyz.device)
             xb, fb = xyz[:block].contiguous(), (frames[:block].contiguous() if framed else None)

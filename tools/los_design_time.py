@@ -78,7 +78,7 @@ def main():
     M, nmin = args.pairs, 2
     for N in args.degrees:
         P = (N + 1) ** 2 - nmin ** 2
-        block = min(max(ga.lstsq.NormalEquations.DESIGN_BLOCK_BYTES // (8 * P) // 256 * 256, 256), M)
+        block = min(ga.lstsq.NormalEquations.default_block_points(P, 1), M)
         a_host = ai.scattered_positions(M, N + M)
         a = ga.engine.to_device(a_host)
         b = ga.engine.to_device(a_host + li.SEPARATION * li.unit_vectors(M, N))
