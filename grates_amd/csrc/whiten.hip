@@ -1,0 +1,92 @@
+// Decorrelation of coloured observation noise (shg_whiten_rows): the banded lower-triangular W with W^T W = Sigma^-1 of a sequence
+// of scalar AR models, applied along the point axis of the rows of a matrix.
+//
+//   y[t] = sum_{k = 0 .. n} h[n][k] x[t - k],   n = min(stage[t], q, t)
+//
+// Memory-bound: one read and one write of the matrix, n + 1 FMAs per value.  A workgroup takes a tile of kTile consecutive output
+// columns of one row, stages them with the q columns in front of them in LDS (coalesced loads, every value of X is read from global
+// memory once per tile), keeps the tap row of the stationary model of the row's channel beside them, and reads the rare start-up tap
+// rows (the first q points of an arc) from global memory.  Every output is the same chain of FMAs whatever the tile, the row or the
+// call it is computed in.
+#include "common.h"
+
+namespace shg {
+
+constexpr int kWhitenThreads = 256;
+constexpr int kWhitenPerThread = 4;
+constexpr int kWhitenTile = kWhitenThreads * kWhitenPerThread;      // output columns of a work item
+constexpr int kWhitenMaxOrder = 128;
+constexpr int kWhitenBlocks = 256 * 8;                               // 8 workgroups of 4 waves fill a CU: the rest is a grid stride
+
+__global__ __launch_bounds__(kWhitenThreads) void whiten_rows_kernel(long long items, int tiles, int channels, int M, const double* __restrict__ X,
+                                                                     long long ldx, const int32_t* __restrict__ stage,
+                                                                     const double* __restrict__ taps, int q, int skip, double* __restrict__ Y,
+                                                                     long long ldy) {
+    __shared__ double xs[kWhitenTile + kWhitenMaxOrder];            // columns t0 - q .. t0 + kWhitenTile of the row
+    __shared__ double hs[kWhitenMaxOrder + 1];                      // h[q][0 .. q] of the row's channel
+    const int tid = threadIdx.x;
+    const int q1 = q + 1;
+    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+        const long long row = item / tiles;
+        const int t0 = skip + (int)(item - row * tiles) * kWhitenTile;                  // first output column of the tile: t0 < M
+        const int width = min(kWhitenTile, M - t0);
+        const double* x = X + row * ldx;
+        const double* h = taps + (size_t)(row % channels) * q1 * q1;
+        __syncthreads();                                                                 // the previous item's reads of xs / hs are done
+        for (int i = tid; i < width + q; i += kWhitenThreads) {
+            const int c = t0 - q + i;                                                    // c < M; never before column 0 of the row
+            xs[i] = c >= 0 ? x[c] : 0.0;
+        }
+        if (tid < q1) hs[tid] = h[(size_t)q * q1 + tid];
+        __syncthreads();
+        double* y = Y + row * ldy;
+#pragma unroll
+        for (int j = 0; j < kWhitenPerThread; ++j) {
+            const int i = tid + j * kWhitenThreads;
+            if (i >= width) break;
+            const int t = t0 + i;
+            const int n = min(min(max(stage[t], 0), q), t);                              // lags: inside the table and inside the row
+            const double* xt = xs + q + i;                                               // xt[-k] = x[t - k]
+            double acc;
+            if (n == q) {
+                acc = hs[0] * xt[0];
+                for (int k = 1; k <= q; ++k) acc = fma(hs[k], xt[-k], acc);
+            } else {
+                const double* hn = h + (size_t)n * q1;
+                acc = hn[0] * xt[0];
+                for (int k = 1; k <= n; ++k) acc = fma(hn[k], xt[-k], acc);
+            }
+            y[t - skip] = acc;
+        }
+    }
+}
+
+}  // namespace shg
+
+using namespace shg;
+
+extern "C" int shg_whiten_rows(long long rows, int channels, int M, const double* X, long long ldx, const int32_t* stage, const double* taps, int q,
+                               int skip, double* Y, long long ldy, void* stream_) {
+    const char* fn = "shg_whiten_rows";
+    SHG_REQUIRE(rows >= 0 && M >= 0 && ldx >= 0 && ldy >= 0, "%s: negative size (rows %lld, M %d, ldx %lld, ldy %lld)", fn, rows, M, ldx, ldy);
+    SHG_REQUIRE(channels >= 1, "%s: channels %d below 1", fn, channels);
+    SHG_REQUIRE(rows % channels == 0, "%s: rows %lld are not a multiple of channels %d", fn, rows, channels);
+    SHG_REQUIRE(q >= 0 && q <= kWhitenMaxOrder, "%s: order q %d outside 0 .. %d", fn, q, kWhitenMaxOrder);
+    SHG_REQUIRE(skip >= 0 && skip <= M, "%s: skip %d outside 0 .. M %d", fn, skip, M);
+    SHG_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
+    SHG_REQUIRE(ldy >= M - skip, "%s: ldy %lld below M - skip %d", fn, ldy, M - skip);
+    const long long limit = 1LL << 40;
+    SHG_REQUIRE((ldx == 0 || rows <= limit / ldx) && (ldy == 0 || rows <= limit / ldy), "%s: %lld rows of %lld (X) and %lld (Y) values are too large", fn,
+                rows, ldx, ldy);
+    if (rows == 0 || M == skip) return SHG_OK;
+    SHG_REQUIRE(X && stage && taps && Y, "%s: NULL pointer", fn);
+    const uintptr_t x0 = (uintptr_t)X, x1 = (uintptr_t)(X + (rows - 1) * ldx + M), y0 = (uintptr_t)Y, y1 = (uintptr_t)(Y + (rows - 1) * ldy + (M - skip));
+    SHG_REQUIRE(x1 <= y0 || y1 <= x0, "%s: X and Y overlap (the call is out of place)", fn);
+    const int tiles = (int)ceil_div64((long long)M - skip, kWhitenTile);
+    const long long items = rows * tiles;
+    const unsigned blocks = (unsigned)std::min<long long>(items, kWhitenBlocks);
+    hipLaunchKernelGGL(whiten_rows_kernel, dim3(blocks), dim3(kWhitenThreads), 0, (hipStream_t)stream_, items, tiles, channels, M, X, ldx, stage, taps, q,
+                       skip, Y, ldy);
+    SHG_HIP(hipGetLastError());
+    return SHG_OK;
+}

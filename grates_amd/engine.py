@@ -976,6 +976,40 @@ def los_design_pass(max_degree):
     return count
 
 
+def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
+    """Decorrelation along the last axis of the device tensor X [..., M] (shg_whiten_rows): Y[..., t - skip] = sum_k h[n][k] X[..., t - k]
+    for skip <= t < M with n = min(stage[t], q, t); the rows of X, all axes but the last flattened, belong to channel row % channels.
+    taps [channels, q + 1, q + 1] (float64) and stage [M] (int32) are device tensors, as lstsq.whitening_taps and lstsq.arc_stages
+    build them.  A two-dimensional X or out may be a column slice of a wider matrix (unit stride along the rows); anything else that
+    is not dense is copied.  Returns out, or a new tensor [..., M - skip]."""
+    torch = require_gpu()
+    M, skip, channels = int(X.shape[-1]), int(skip), int(channels)
+    lead = tuple(int(s) for s in X.shape[:-1])
+    if tuple(taps.shape) != (channels, taps.shape[-1], taps.shape[-1]) or taps.dtype != torch.float64 or not taps.is_contiguous():
+        raise ValueError('taps must be a dense float64 tensor of shape ({0}, q + 1, q + 1), got {1}'.format(channels, tuple(taps.shape)))
+    if tuple(stage.shape) != (M,) or stage.dtype != torch.int32 or not stage.is_contiguous():
+        raise ValueError('stage must be a dense int32 tensor of shape ({0},), got {1} {2}'.format(M, stage.dtype, tuple(stage.shape)))
+    if X.dtype != torch.float64:
+        raise ValueError('X must be float64, got {0}'.format(X.dtype))
+
+    def rows_of(t, width):
+        """(tensor, leading dimension) of t as rows of `width` columns"""
+        if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= width:
+            return t, int(t.stride(0))
+        return t.contiguous(), width
+    X, ldx = rows_of(X, M)
+    rows = 1
+    for size in lead:
+        rows *= size
+    if out is None:
+        out = torch.empty(lead + (max(M - skip, 0),), dtype=torch.float64, device=X.device)
+    elif tuple(out.shape) != lead + (M - skip,) or out.dtype != torch.float64 or rows_of(out, M - skip)[0] is not out:
+        raise ValueError('out must be a float64 tensor of shape {0}, dense or a column slice of a matrix'.format(lead + (M - skip,)))
+    _lib.call('shg_whiten_rows', rows, channels, M, _ptr(X), ldx, _ptr(stage), _ptr(taps), int(taps.shape[-1]) - 1, skip, _ptr(out),
+              rows_of(out, M - skip)[1], _stream())
+    return out
+
+
 class OrderMajorSeries:
     """A time series of coefficient sets that stays on the device between operators (the batching of TimeSeries.to_array,
     grates/gravityfield.py:964-980, in the layout the order-wise operators work on): `data` [(N+1)^2, Bpad] with the epochs fastest

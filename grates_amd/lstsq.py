@@ -169,6 +169,11 @@ class AutoregressiveModelSequence:
         return AutoregressiveModelSequence([AutoregressiveModel.from_sample(sample, order) for order in range(maximum_order + 1)])
 
     @property
+    def models(self):
+        """the AR models of orders 0 .. maximum_order, as given (no reference counterpart: whitening_taps reads them)"""
+        return tuple(self.__armodels)
+
+    @property
     def maximum_order(self):
         return self.__armodels[-1].order
 
@@ -214,6 +219,101 @@ class AutoregressiveModelSequence:
         system = self.normal_equations(epochs)
         system.compute_covariance(sparse=False)                # full inverse: block (0, k) is the covariance of lag k
         return [system.matrix[0, lag] for lag in range(maximum_lag + 1)]
+
+
+MAX_WHITENING_ORDER = 128      # of shg_whiten_rows: the halo of a tile of its kernel
+
+
+def whitening_taps(noise_model):
+    """
+    Tap rows of the decorrelation filter of scalar AR model sequences, ndarray [C, q + 1, q + 1] (host, NumPy only): row s of a
+    sequence is h[s][0] = 1 / sigma_s, h[s][k] = -phi_k / sigma_s (1 <= k <= s) from the coefficients phi and the white-noise
+    variance sigma_s^2 of its model of order s, zero beyond.  Applied with the exact start-up of an arc (order 0 for its first
+    point, order 1 for the second, ..., stationary from point q + 1 on) the rows form the lower-triangular banded W with
+    W^T W = Sigma^-1 = noise_model.normal_equations(L).
+
+    noise_model is one AutoregressiveModelSequence (shared by all components, C = 1) or a sequence of them, one per component in
+    the component order of the observations.  ValueError for a model of dimension other than 1, sequences of differing maximum
+    order, an order above 128, models that are not of orders 0, 1, ..., q, and a variance that is not finite and positive.
+    """
+    try:
+        sequences = [noise_model] if isinstance(noise_model, AutoregressiveModelSequence) else list(noise_model)
+    except TypeError:
+        sequences = []
+    if not sequences or not all(isinstance(sequence, AutoregressiveModelSequence) for sequence in sequences):
+        raise ValueError('noise_model must be an AutoregressiveModelSequence or a sequence of them, one per component')
+    orders = sorted(set(len(sequence.models) - 1 for sequence in sequences))
+    if len(orders) != 1:
+        raise ValueError('the noise models of the components differ in their maximum order: {0}'.format(orders))
+    q = orders[0]
+    if q < 0:
+        raise ValueError('a noise model without AR models')
+    if q > MAX_WHITENING_ORDER:
+        raise ValueError('maximum order {0} of the noise model above {1}'.format(q, MAX_WHITENING_ORDER))
+    taps = np.zeros((len(sequences), q + 1, q + 1))
+    for c, sequence in enumerate(sequences):
+        for s, model in enumerate(sequence.models):
+            if model.dimension != 1:
+                raise ValueError('noise model of dimension {0}: only scalar AR models (dimension 1) decorrelate an arc'.format(model.dimension))
+            if model.order != s:
+                raise ValueError('model {0} of the sequence has order {1}: expected the orders 0, 1, ..., {2}'.format(s, model.order, q))
+            variance = float(np.asarray(model.white_noise_covariance, dtype=np.float64).reshape(()))
+            if not (np.isfinite(variance) and variance > 0.0):
+                raise ValueError('white-noise variance {0} of the model of order {1} is not finite and positive'.format(variance, s))
+            sigma = np.sqrt(variance)
+            taps[c, s, 0] = 1.0 / sigma
+            for k in range(1, s + 1):
+                taps[c, s, k] = -float(np.asarray(model.coefficients[k - 1], dtype=np.float64).reshape(())) / sigma
+    return taps
+
+
+def arc_stages(arcs, count, order):
+    """
+    The AR order in use at every point of a series of `count` points in arcs, int32 ndarray [count] (host, NumPy only):
+    stage[t] = min(t - start of the arc of t, order).  arcs holds the start indices of the arcs (None: the single arc [0]); ValueError
+    unless they are integers, strictly increasing, start at 0 and stay below count.  A data gap starts a new arc.
+    """
+    count, order = int(count), int(order)
+    if count < 0 or order < 0:
+        raise ValueError('count {0} and order {1} must not be negative'.format(count, order))
+    if arcs is None:
+        starts = np.zeros(min(count, 1), dtype=np.int64)
+    else:
+        given = np.asarray(arcs)
+        if given.ndim != 1 or given.size == 0 or not (np.issubdtype(given.dtype, np.integer) or np.all(given == np.floor(given))):
+            raise ValueError('arcs must be a sequence of integer start indices')
+        starts = given.astype(np.int64)
+        if starts[0] != 0 or np.any(np.diff(starts) <= 0) or starts[-1] >= count:
+            raise ValueError('arcs must start at 0, increase strictly and stay below the {0} points'.format(count))
+    t = np.arange(count, dtype=np.int64)
+    since = t - starts[np.searchsorted(starts, t, side='right') - 1] if count else t
+    return np.minimum(since, order).astype(np.int32)
+
+
+def _whitening_tables(noise_model, arcs, count, components):
+    """(taps [C, q + 1, q + 1], stage [count]) of a from_* call or of decorrelate, on the host; ValueError before anything reaches the
+    device"""
+    taps = whitening_taps(noise_model)
+    if taps.shape[0] not in (1, components):
+        raise ValueError('{0} noise models for {1} components: expected one, or one per component'.format(taps.shape[0], components))
+    return taps, arc_stages(arcs, count, taps.shape[1] - 1)
+
+
+def decorrelate(values, noise_model, arcs=None):
+    """
+    W values along the point axis, on the device (shg_whiten_rows): values [M] or [M, K] (host array or device tensor; the result
+    has the same kind and shape), noise_model and arcs as in NormalEquations.from_accelerations.  What the normals of a whitened
+    adjustment see of the observations; residuals A x^ - l go through it the same way.
+    """
+    shape = tuple(int(size) for size in values.shape)
+    if len(shape) not in (1, 2):
+        raise ValueError('values must have shape (M,) or (M, K), got {0}'.format(shape))
+    M, K = shape[0], (shape[1] if len(shape) == 2 else 1)
+    taps, stage = _whitening_tables(noise_model, arcs, M, K)
+    torch = engine.require_gpu()
+    x = engine.to_device(values).reshape(M, K).t().contiguous()
+    y = engine.whiten_rows(x, engine.to_device(taps), torch.from_numpy(stage).to(x.device), channels=taps.shape[0])
+    return _like_input(y.t().reshape(shape).contiguous(), values)
 
 
 class BlockMatrix:
@@ -567,19 +667,43 @@ class NormalEquations:
             raise ValueError('block_points must be positive, got {0}'.format(block_points))
         return block_points
 
+    @staticmethod
+    def __check_noise_model(noise_model, arcs, points, components):
+        """noise_model= / arcs= of a from_* call: None without a model, else the host tables (taps, stage) of _whitening_tables;
+        ValueError otherwise, before anything reaches the device."""
+        if noise_model is None:
+            if arcs is not None:
+                raise ValueError('arcs are those of the noise model: pass noise_model as well')
+            return None
+        return _whitening_tables(noise_model, arcs, points, components)
+
     @classmethod
-    def __from_design_blocks(cls, min_degree, max_degree, l, block_points, design_block):
+    def __from_design_blocks(cls, min_degree, max_degree, l, block_points, design_block, whitening=None):
         """The block loop of the from_* classmethods: l [M, K] are the observations times sqrt(w) on the device, design_block(first,
         last) the transposed design matrix [P, K, Mb] (or [P, Mb]) of the points first .. last, scaled alike.  Per block N += At At^T,
-        n += At l and l^T P l += |l|^2 on the fp64 MFMA product; both triangles of N are computed and the upper one is mirrored."""
+        n += At l and l^T P l += |l|^2 on the fp64 MFMA product; both triangles of N are computed and the upper one is mirrored.
+
+        whitening = (taps, stage) of __check_noise_model: the tables go to the device once; a block [first, last) takes the
+        h = stage[first] points in front of it along (none where it starts an arc), and shg_whiten_rows turns the design matrix and
+        the observations of first - h .. last into those of W A and W l at first .. last (skip = h) in a second buffer, on which
+        the three products run unchanged."""
         torch = engine.require_gpu()
         M, K = (int(size) for size in l.shape)
         P = (max_degree + 1) ** 2 - min_degree ** 2
         normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
+        if whitening is not None:
+            halo = whitening[1]
+            taps, stage = engine.to_device(whitening[0], l.device), torch.from_numpy(halo).to(l.device)
         for first in range(0, M, block_points):
             last = min(first + block_points, M)
-            At = design_block(first, last).reshape(P, K * (last - first))
-            lb = l[first:last].t().reshape(-1, 1)                      # component-major, as the columns of At
+            if whitening is None:
+                At = design_block(first, last).reshape(P, K * (last - first))
+                lb = l[first:last].t().reshape(-1, 1)                  # component-major, as the columns of At
+            else:
+                start = first - int(halo[first])
+                whiten = dict(taps=taps, stage=stage[start:last], channels=int(taps.shape[0]), skip=first - start)
+                At = engine.whiten_rows(design_block(start, last).reshape(P * K, last - start), **whiten).reshape(P, K * (last - first))
+                lb = engine.whiten_rows(l[start:last].t().contiguous(), **whiten).reshape(-1, 1)
             engine.gemm(At, At, transb=True, beta=1.0, out=normals)
             engine.gemm(At, lb, beta=1.0, out=side)
             engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
@@ -590,7 +714,8 @@ class NormalEquations:
         return cls(matrix, side, float(square_sum.item()), K * M)
 
     @classmethod
-    def from_accelerations(cls, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
+    def from_accelerations(cls, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
+                           noise_model=None, arcs=None):
         """
         Normal equations of the coefficients of degrees min_degree .. max_degree (in the order of utilities.ravel_coefficients) from
         accelerations g [M, 3] observed at the cartesian positions xyz [M, 3] (host arrays or device tensors; g is usually reduced by
@@ -601,6 +726,17 @@ class NormalEquations:
         shg_acceleration_design, and N += At At^T, n += At (sqrt(w) g) and l^T P l += |sqrt(w) g|^2 run on the fp64 MFMA product
         (both triangles of N are computed; the upper one is mirrored at the end, so that N is exactly symmetric).
 
+        noise_model: coloured noise along the series of points.  One AutoregressiveModelSequence of dimension 1 (shared by the
+        components) or a sequence of them, one per component, of maximum order q <= 128: every arc is decorrelated with the
+        lower-triangular banded W, W^T W = Sigma^-1 = noise_model.normal_equations(arc length) (whitening_taps, shg_whiten_rows), applied
+        to the design matrix and to the observations before the three products.  arcs holds the start indices of the arcs, ascending
+        from 0 (default: one arc); nothing crosses an arc boundary, and every arc starts with the exact start-up (orders 0, 1, ...,
+        q).  A data gap is a new arc, not a zero weight: a zero weight leaves the point in the filter's history.  Weights keep their
+        meaning and scale the rows by sqrt(w) before the whitening, so the weight matrix in effect is D^1/2 W^T W D^1/2.  block_points
+        keeps its default: a block takes up to q points in front of it along as history, the whitened copy doubles the peak memory of
+        a block, and observation_count is unchanged.  noise_model=None changes nothing; arcs without it is a ValueError.
+        ColouredNoise(noise_model, arcs) offers the same for all three kinds of observation.
+
         Returns NormalEquations with a one-block BlockMatrix [P, P] and the right-hand side [P, 1] on the device, and
         observation_count = 3 M: components of zero weight still count as observations.
         """
@@ -610,6 +746,7 @@ class NormalEquations:
             raise ValueError('{0} positions but {1} accelerations'.format(M, int(g.shape[0])))
         layout = engine.check_observation_weights(weights, M)
         block_points = cls.__check_block_points(block_points, min_degree, max_degree, 3)
+        whitening = cls.__check_noise_model(noise_model, arcs, M, 3)
 
         torch = engine.require_gpu()
         x, l = engine.to_device(xyz), engine.to_device(g)
@@ -617,7 +754,7 @@ class NormalEquations:
         if layout:
             l = l * torch.sqrt(w if layout == 2 else w[:, None])
         return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.acceleration_design_checked(
-            max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R))
+            max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R), whitening)
 
     @classmethod
     def from_gradients(cls, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
@@ -633,7 +770,17 @@ class NormalEquations:
         The block loop of from_accelerations with At [P, K Mb] from shg_gradient_design; the default block is the largest multiple of
         256 points that keeps At within 256 MB, at least 256.  Returns NormalEquations with a one-block BlockMatrix [P, P] and the
         right-hand side [P, 1] on the device, and observation_count = K M.
+
+        Coloured noise: ColouredNoise(noise_model, arcs).from_gradients(the same arguments), with one scalar
+        AutoregressiveModelSequence for all K selected components or one per component in canonical order (the gradiometer's coloured
+        noise), every arc decorrelated on its own as in from_accelerations.  A data gap is a new arc, not a zero weight; block_points
+        keeps its default, the peak memory of a block doubles and observation_count is unchanged.
         """
+        return cls._gradients(None, None, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points)
+
+    @classmethod
+    def _gradients(cls, noise_model, arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points):
+        """from_gradients under a noise model (None: white noise)"""
         min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
         M = engine.check_positions(xyz)
         picked = engine.gradient_components(components)
@@ -648,6 +795,7 @@ class NormalEquations:
         if frames is not None:
             engine.check_frames(frames, M)
         block_points = cls.__check_block_points(block_points, min_degree, max_degree, K)
+        whitening = cls.__check_noise_model(noise_model, arcs, M, K)
 
         torch = engine.require_gpu()
         x, l = engine.to_device(xyz), engine.to_device(gradients)
@@ -658,7 +806,8 @@ class NormalEquations:
         if layout:
             l = l * torch.sqrt(w if layout == 2 else w[:, None])
         return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.gradient_design_checked(
-            max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last], GM, R))
+            max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last], GM, R),
+            whitening)
 
     @classmethod
     def from_line_of_sight(cls, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
@@ -674,7 +823,17 @@ class NormalEquations:
         pairs that keeps At within 256 MB, at least 256.  Returns NormalEquations with a one-block BlockMatrix [P, P] and the
         right-hand side [P, 1] on the device, and observation_count = M.  Normals of the same degrees add up through
         accumulate_normals, those of from_accelerations included: the combination of orbit and link.
+
+        Coloured noise: ColouredNoise(noise_model, arcs).from_line_of_sight(the same arguments), with one scalar
+        AutoregressiveModelSequence (the link's noise is correlated along the arc), every arc decorrelated on its own as in
+        from_accelerations.  A data gap is a new arc, not a zero weight; block_points keeps its default, the peak memory of a block
+        doubles and observation_count is unchanged.
         """
+        return cls._line_of_sight(None, None, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, block_points)
+
+    @classmethod
+    def _line_of_sight(cls, noise_model, arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, block_points):
+        """from_line_of_sight under a noise model (None: white noise)"""
         min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
         M = engine.check_pair_positions(xyz_a, xyz_b)
         if len(differences.shape) != 1:
@@ -689,6 +848,7 @@ class NormalEquations:
         else:
             engine.check_pairs_apart(xyz_a, xyz_b)
         block_points = cls.__check_block_points(block_points, min_degree, max_degree, 1)
+        whitening = cls.__check_noise_model(noise_model, arcs, M, 1)
 
         torch = engine.require_gpu()
         a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
@@ -697,7 +857,8 @@ class NormalEquations:
         if layout:
             l = l * torch.sqrt(w)[:, None]
         return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.los_design_checked(
-            max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last], GM, R))
+            max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last], GM, R),
+            whitening)
 
     def __cholesky(self):
         """factor the matrix once; a matrix that already holds covariances cannot be factored again (ValueError, as upstream)"""
@@ -781,6 +942,34 @@ class TikhonovRegularization(NormalEquations):
         for k, (lo, hi) in enumerate(zip(block_index[:-1], block_index[1:])):
             diagonal[k, k] = np.diag(weights[lo:hi])
         super().__init__(diagonal, bias, weighted_square_sum, bias.size)
+
+
+class ColouredNoise:
+    """
+    A noise model of the observations along the series of points, bound to the constructors of NormalEquations: noise_model is one
+    scalar AutoregressiveModelSequence (shared by the components) or a sequence of them, one per component, arcs the start indices of
+    the arcs (default: one arc), as NormalEquations.from_accelerations describes them.  from_accelerations, from_gradients and
+    from_line_of_sight take the arguments of the classmethods of the same name and return the NormalEquations of the decorrelated
+    observations.  The model is checked here (whitening_taps), the arcs against the number of points in every call; all of it before
+    anything reaches the device.
+    """
+
+    def __init__(self, noise_model, arcs=None):
+        whitening_taps(noise_model)
+        self.noise_model, self.arcs = noise_model, arcs
+
+    def from_accelerations(self, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
+        return NormalEquations.from_accelerations(xyz, g, min_degree, max_degree, GM, R, weights, block_points, self.noise_model, self.arcs)
+
+    def from_gradients(self, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
+                       weights=None, block_points=None):
+        return NormalEquations._gradients(self.noise_model, self.arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights,
+                                          block_points)
+
+    def from_line_of_sight(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
+                           weights=None, block_points=None):
+        return NormalEquations._line_of_sight(self.noise_model, self.arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions,
+                                              weights, block_points)
 
 
 def accumulate_normals(normal_equations, variance_factors):

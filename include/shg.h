@@ -548,6 +548,28 @@ int shg_los_design(int N, int min_degree, const double* xyz_a, const double* xyz
                    double GM, double R, double* At, int ldt, void* stream);
 int shg_los_design_pass(int N);
 
+/* ------------------------------------------------------------------------------------------------
+ * Decorrelation of coloured observation noise along the point axis (the banded lower-triangular W with W^T W = Sigma^-1 of a sequence
+ * of scalar AR models of orders 0 .. q; no reference counterpart)
+ *   X [rows][ldx] with M columns in use, row r of channel r % channels: the transposed design matrix At [P][K][ldt] of the three calls
+ *   above is rows = P K, channels = K; observations laid out [K][M] are rows = K, channels = K.
+ *   taps (device) [channels][q+1][q+1]: row s of a channel is h[s][0] = 1 / sigma_s, h[s][k] = -phi_k / sigma_s (1 <= k <= s) of its AR
+ *   model of order s, zero beyond.  stage (device) [M]: the order in use at column t, min(t - start of its arc, q).
+ *   Y[r][t - skip] = sum_{k = 0 .. n} h[n][k] X[r][t - k] for skip <= t < M, with n = min(max(stage[t], 0), q, t): the first skip
+ *   columns are read as history and not written (the halo of a block of a longer series); the entries of a row of Y from M - skip
+ *   to ldy are not touched.  The kernel never reads before column 0 of a row and never a tap outside its table, whatever stage holds.
+ *   The sum is acc = h[0] x[t], then acc = fma(h[k], x[t-k], acc) for k ascending: Y[r][t - skip] depends on x[t-n .. t], stage[t] and
+ *   the taps only, not on skip, M, the tiling or the other rows.  No atomics; repeated calls are bitwise equal, and a block whitened
+ *   with a halo of q columns is bitwise the same columns of the whole.
+ *   One workgroup per tile of 1024 columns of a row, staged through LDS with the q columns in front (one read and one write of the
+ *   matrix); a flat 64-bit index, so rows x ld may exceed 2^31.
+ *   Arguments are checked before the first HIP call (negative sizes, channels < 1, rows not a multiple of channels, q outside 0 .. 128,
+ *   skip outside 0 .. M, ldx < M, ldy < M - skip, more than 2^40 values of X or Y, NULL pointers, address ranges of X and Y that
+ *   overlap: the call is out of place); rows = 0 or M = skip returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_whiten_rows(long long rows, int channels, int M, const double* X, long long ldx, const int32_t* stage, const double* taps, int q,
+                    int skip, double* Y, long long ldy, void* stream);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
