@@ -1010,6 +1010,45 @@ def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
     return out
 
 
+def segment_products(X, Bt, seg, channels=1, out=None):
+    """Products of the rows of the device tensor X [..., M] with a basis, cut at arc boundaries (shg_segment_products):
+    S[..., s, j] = sum of X[..., t] Bt[j, row % channels, t] over seg[s] <= t < seg[s + 1]; the rows of X, all axes but the last
+    flattened, belong to channel row % channels.  Bt [u, channels, M] (float64, 1 <= u <= 16; [u, M] with channels = 1) is the basis,
+    transformed like X and transposed, seg [nseg + 1] (int32) the column indices of the boundaries, both device tensors; the kernel
+    clamps seg to 0 .. M and makes it non-decreasing.  A two-dimensional X may be a column slice of a wider matrix (unit stride along
+    the rows), and so may Bt (the same stride for all its rows); anything else that is not dense is copied.  Returns out, or a new
+    dense tensor [..., nseg, u]; every entry is written."""
+    torch = require_gpu()
+    M, channels = int(X.shape[-1]), int(channels)
+    lead = tuple(int(s) for s in X.shape[:-1])
+    if X.dtype != torch.float64:
+        raise ValueError('X must be float64, got {0}'.format(X.dtype))
+    if Bt.dim() == 2 and channels == 1:
+        Bt = Bt.unsqueeze(1)
+    if Bt.dim() != 3 or tuple(Bt.shape[1:]) != (channels, M) or Bt.dtype != torch.float64:
+        raise ValueError('Bt must be a float64 tensor of shape (u, {0}, {1}), got {2}'.format(channels, M, tuple(Bt.shape)))
+    u = int(Bt.shape[0])
+    if tuple(seg.shape) != (seg.numel(),) or seg.numel() < 1 or seg.dtype != torch.int32 or not seg.is_contiguous():
+        raise ValueError('seg must be a dense int32 tensor of shape (nseg + 1,), got {0} {1}'.format(seg.dtype, tuple(seg.shape)))
+    nseg = int(seg.numel()) - 1
+    if X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= M:
+        ldx = int(X.stride(0))
+    else:
+        X, ldx = X.contiguous(), M
+    ldb = int(Bt.stride(0) if channels == 1 else Bt.stride(1))              # rows j channels + c of Bt, one leading dimension
+    if Bt.stride(2) != 1 or ldb < M or (channels > 1 and Bt.stride(0) != channels * ldb):
+        Bt, ldb = Bt.contiguous(), M
+    rows = 1
+    for size in lead:
+        rows *= size
+    if out is None:
+        out = torch.empty(lead + (nseg, u), dtype=torch.float64, device=X.device)
+    elif tuple(out.shape) != lead + (nseg, u) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError('out must be a dense float64 tensor of shape {0}'.format(lead + (nseg, u)))
+    _lib.call('shg_segment_products', rows, channels, M, _ptr(X), ldx, _ptr(Bt), ldb, u, nseg, _ptr(seg), _ptr(out), _stream())
+    return out
+
+
 class OrderMajorSeries:
     """A time series of coefficient sets that stays on the device between operators (the batching of TimeSeries.to_array,
     grates/gravityfield.py:964-980, in the layout the order-wise operators work on): `data` [(N+1)^2, Bpad] with the epochs fastest

@@ -267,6 +267,20 @@ def whitening_taps(noise_model):
     return taps
 
 
+def _arc_starts(arcs, count):
+    """start indices of the arcs of a series of `count` points, int64 ndarray (None: the single arc [0], no arc without points);
+    ValueError unless they are integers, strictly increasing, start at 0 and stay below count"""
+    if arcs is None:
+        return np.zeros(min(count, 1), dtype=np.int64)
+    given = np.asarray(arcs)
+    if given.ndim != 1 or given.size == 0 or not (np.issubdtype(given.dtype, np.integer) or np.all(given == np.floor(given))):
+        raise ValueError('arcs must be a sequence of integer start indices')
+    starts = given.astype(np.int64)
+    if starts[0] != 0 or np.any(np.diff(starts) <= 0) or starts[-1] >= count:
+        raise ValueError('arcs must start at 0, increase strictly and stay below the {0} points'.format(count))
+    return starts
+
+
 def arc_stages(arcs, count, order):
     """
     The AR order in use at every point of a series of `count` points in arcs, int32 ndarray [count] (host, NumPy only):
@@ -276,15 +290,7 @@ def arc_stages(arcs, count, order):
     count, order = int(count), int(order)
     if count < 0 or order < 0:
         raise ValueError('count {0} and order {1} must not be negative'.format(count, order))
-    if arcs is None:
-        starts = np.zeros(min(count, 1), dtype=np.int64)
-    else:
-        given = np.asarray(arcs)
-        if given.ndim != 1 or given.size == 0 or not (np.issubdtype(given.dtype, np.integer) or np.all(given == np.floor(given))):
-            raise ValueError('arcs must be a sequence of integer start indices')
-        starts = given.astype(np.int64)
-        if starts[0] != 0 or np.any(np.diff(starts) <= 0) or starts[-1] >= count:
-            raise ValueError('arcs must start at 0, increase strictly and stay below the {0} points'.format(count))
+    starts = _arc_starts(arcs, count)
     t = np.arange(count, dtype=np.int64)
     since = t - starts[np.searchsorted(starts, t, side='right') - 1] if count else t
     return np.minimum(since, order).astype(np.int32)
@@ -314,6 +320,110 @@ def decorrelate(values, noise_model, arcs=None):
     x = engine.to_device(values).reshape(M, K).t().contiguous()
     y = engine.whiten_rows(x, engine.to_device(taps), torch.from_numpy(stage).to(x.device), channels=taps.shape[0])
     return _like_input(y.t().reshape(shape).contiguous(), values)
+
+
+MAX_ARC_PARAMETERS = 16        # of shg_segment_products: the accumulators of a wave of its kernel
+
+
+def arc_basis(arcs, count, degree=1, periods=(), times=None):
+    """
+    Basis of the parameters that last one arc, ndarray [count, u'] (host, NumPy only), for ArcParameters: the Legendre polynomials
+    P_0 .. P_degree of the arc-normalised time tau in [-1, 1] (tau = -1 at the first point of an arc, 1 at its last, 0 for an arc of one
+    point; degree=None: no polynomial columns), then cos(2 pi t / period) and sin(2 pi t / period) for every period.  t is `times`
+    [count] (finite, the periods in its unit) or else the sample index (the periods in samples).  arcs as in arc_stages.  Degree 1
+    is a bias and a drift; a period of one revolution gives the empirical once-per-revolution terms.  ValueError for arcs that
+    arc_stages refuses, a negative degree, a period that is not finite and positive, times of another shape or not finite, no column
+    at all and more than 16 columns.
+    """
+    count = int(count)
+    if count < 0:
+        raise ValueError('count {0} must not be negative'.format(count))
+    starts = _arc_starts(arcs, count)
+    if degree is not None and (int(degree) != degree or degree < 0):
+        raise ValueError('degree must be a non-negative integer or None, got {0!r}'.format(degree))
+    polynomials = 0 if degree is None else int(degree) + 1
+    periods = np.asarray(periods, dtype=np.float64).reshape(-1)
+    if not np.all(np.isfinite(periods) & (periods > 0)):
+        raise ValueError('periods must be finite and positive')
+    columns = polynomials + 2 * periods.size
+    if columns < 1 or columns > MAX_ARC_PARAMETERS:
+        raise ValueError('{0} columns of the arc basis: expected 1 .. {1}'.format(columns, MAX_ARC_PARAMETERS))
+    if times is None:
+        t = np.arange(count, dtype=np.float64)
+    else:
+        t = np.asarray(times, dtype=np.float64)
+        if t.shape != (count,) or not np.all(np.isfinite(t)):
+            raise ValueError('times must be {0} finite values'.format(count))
+    basis = np.empty((count, columns))
+    if polynomials:
+        tau = np.zeros(count)
+        for first, last in zip(starts, np.append(starts[1:], count)):
+            span = t[last - 1] - t[first]
+            if span != 0:
+                tau[first:last] = 2.0 * (t[first:last] - t[first]) / span - 1.0
+        basis[:, :polynomials] = np.polynomial.legendre.legvander(tau, polynomials - 1)
+    for i, period in enumerate(periods):
+        basis[:, polynomials + 2 * i] = np.cos(2.0 * np.pi * t / period)
+        basis[:, polynomials + 2 * i + 1] = np.sin(2.0 * np.pi * t / period)
+    return basis
+
+
+def frame_basis(basis, frames):
+    """
+    A per-axis instrument parameter seen in Earth-fixed axes, ndarray [M, 3, 3 u'] (host, NumPy only), the general form of the basis
+    of ArcParameters: basis [M, u'] (arc_basis), frames [M, 3, 3] with the instrument axes of every point as rows (as in
+    from_gradients).  Column 3 i + a of component k is basis[:, i] * frames[:, a, k]: parameter i of instrument axis a.  ValueError
+    for other shapes and for 3 u' > 16.
+    """
+    basis, frames = np.asarray(basis, dtype=np.float64), np.asarray(frames, dtype=np.float64)
+    if basis.ndim != 2 or basis.shape[1] < 1:
+        raise ValueError('basis must have shape (M, u), got {0}'.format(basis.shape))
+    if frames.shape != (basis.shape[0], 3, 3):
+        raise ValueError('frames must have shape ({0}, 3, 3), got {1}'.format(basis.shape[0], frames.shape))
+    if 3 * basis.shape[1] > MAX_ARC_PARAMETERS:
+        raise ValueError('{0} columns of the frame basis: expected at most {1}'.format(3 * basis.shape[1], MAX_ARC_PARAMETERS))
+    return np.einsum('ti,tak->tkia', basis, frames).reshape(basis.shape[0], 3, 3 * basis.shape[1])
+
+
+def _arc_reduction(G, b):
+    """Host part of the elimination of arc-wise parameters: G [units, u, u] and b [units, u] of the units (arcs, or arcs and
+    channels) -> R [units, u, u] with the columns V_keep Lambda_keep^-1/2 of numpy.linalg.eigh(G) (eigenvalues above 1e-12 of the
+    largest; zero columns for the dropped directions, all of them where the largest is not positive), R^T b [units, u] and the ranks."""
+    units, u = b.shape
+    R, ranks = np.zeros((units, u, u)), np.zeros(units, dtype=np.int64)
+    for i in range(units):
+        values, vectors = np.linalg.eigh(G[i])
+        if not values[-1] > 0.0:
+            continue
+        kept = values > 1e-12 * values[-1]
+        ranks[i] = np.count_nonzero(kept)
+        R[i][:, kept] = vectors[:, kept] / np.sqrt(values[kept])
+    return R, np.einsum('ijr,ij->ir', R, b), ranks
+
+
+class ArcElimination:
+    """
+    What NormalEquations keeps of the elimination of its arc-wise parameters (ne.arc_elimination; ArcParameters): `ranks`, the number of
+    directions eliminated per arc (ndarray [arcs], or [arcs, K] for a shared basis), and their sum `count`, by which
+    observation_count was reduced.  parameters(solution) returns the parameters y_a = R_a (R_a^T b_a - D_a^T x) that belong to a
+    solution x of the reduced system, as a host ndarray [arcs, K, u'] (shared basis) or [arcs, u], zero along the dropped
+    directions.  It needs the D_a, which ArcParameters(keep=True) retains on the device: P K u' doubles per arc (shared basis),
+    P u for the general form.
+    """
+
+    def __init__(self, ranks, R, g, shared, columns):
+        self.ranks = ranks
+        self.count = int(ranks.sum())
+        self.__R, self.__g, self.__shared, self.__columns = R, g, shared, columns
+
+    def parameters(self, solution):
+        if self.__columns is None:
+            raise ValueError('the parameters of the arcs need the eliminated columns: build with ArcParameters(keep=True)')
+        x = _dev(solution).reshape(-1, 1)
+        products = [engine.to_host(engine.gemm(D, x, transa=True)) for D in self.__columns]
+        y = self.__g - np.concatenate(products).reshape(self.__g.shape)
+        y = np.einsum('akjr,akr->akj', self.__R, y)
+        return y if self.__shared else y[:, 0]
 
 
 class BlockMatrix:
@@ -649,6 +759,8 @@ class NormalEquations:
         self.status = 'normal_matrix'
 
     DESIGN_BLOCK_BYTES = 256 << 20      # budget of one block of the transposed design matrix in from_accelerations
+    arc_elimination = None              # ArcElimination of a system built under ArcParameters
+    ARC_UPDATE_COLUMNS = 256            # columns of D that N -= D D^T waits for: the update reads and writes all of N, whatever its rank
 
     @classmethod
     def default_block_points(cls, parameters, components):
@@ -677,8 +789,20 @@ class NormalEquations:
             return None
         return _whitening_tables(noise_model, arcs, points, components)
 
+    @staticmethod
+    def __check_local(local, arcs, points, components):
+        """local= of a from_* call: None, or (ArcParameters, start indices of the arcs); ValueError for arcs that arc_stages refuses
+        and for a basis that is neither [points, u'] nor [points, components, u], before anything reaches the device."""
+        if local is None:
+            return None
+        starts = _arc_starts(arcs, points)
+        shape = local.basis.shape
+        if shape[0] != points or (len(shape) == 3 and shape[1] != components):
+            raise ValueError('the arc basis must have shape ({0}, u) or ({0}, {1}, u), got {2}'.format(points, components, shape))
+        return local, starts
+
     @classmethod
-    def __from_design_blocks(cls, min_degree, max_degree, l, block_points, design_block, whitening=None):
+    def __from_design_blocks(cls, min_degree, max_degree, l, block_points, design_block, whitening=None, local=None, root=None):
         """The block loop of the from_* classmethods: l [M, K] are the observations times sqrt(w) on the device, design_block(first,
         last) the transposed design matrix [P, K, Mb] (or [P, Mb]) of the points first .. last, scaled alike.  Per block N += At At^T,
         n += At l and l^T P l += |l|^2 on the fp64 MFMA product; both triangles of N are computed and the upper one is mirrored.
@@ -686,7 +810,16 @@ class NormalEquations:
         whitening = (taps, stage) of __check_noise_model: the tables go to the device once; a block [first, last) takes the
         h = stage[first] points in front of it along (none where it starts an arc), and shg_whiten_rows turns the design matrix and
         the observations of first - h .. last into those of W A and W l at first .. last (skip = h) in a second buffer, on which
-        the three products run unchanged."""
+        the three products run unchanged.
+
+        local = (ArcParameters, starts) of __check_local, root = sqrt(w) [M, K] (or broadcastable to it, None: 1) that l carries:
+        the parameters of the arcs are eliminated.  The basis goes the way of the design matrix (times
+        root, then W) into Bt [u, K, M], once; shg_segment_products gives G_a = B_a^T B_a and b_a = B_a^T l_a of all arcs, the host
+        R_a = V Lambda^-1/2 of the kept eigenpairs of G_a.  Per block the same call on the whitened At, with the arc boundaries
+        clipped to the block, gives the part of C_a = A_a^T B_a that lies in it; an arc that continues past the block keeps its sum
+        in the carry [P, K, u], an arc that ends gives D_a = C_a R_a, and N -= D D^T, n -= D (R^T b) run as one product each per block,
+        once ARC_UPDATE_COLUMNS columns of D are waiting (the update reads and writes all of N) and after the last block, before the
+        mirroring.  l^T P l -= |R^T b|^2 and observation_count -= sum of the ranks."""
         torch = engine.require_gpu()
         M, K = (int(size) for size in l.shape)
         P = (max_degree + 1) ** 2 - min_degree ** 2
@@ -694,6 +827,27 @@ class NormalEquations:
         if whitening is not None:
             halo = whitening[1]
             taps, stage = engine.to_device(whitening[0], l.device), torch.from_numpy(halo).to(l.device)
+        if local is not None:
+            whole = {} if whitening is None else dict(taps=taps, stage=stage, channels=int(taps.shape[0]))
+            basis = engine.to_device(local[0].basis, l.device)
+            shared = basis.dim() == 2
+            Bt = basis.t()[:, None, :].expand(-1, K, -1) if shared else basis.permute(2, 1, 0)
+            Bt = (Bt if root is None else Bt * root.expand(M, K).t()[None]).contiguous()                    # [u, K, M]
+            lt = l.t().contiguous()
+            if whitening is not None:
+                Bt, lt = engine.whiten_rows(Bt, **whole), engine.whiten_rows(lt, **whole)
+            u, Kc = int(Bt.shape[0]), (K if shared else 1)
+            bounds = np.append(local[1], M)
+            arcs = len(bounds) - 1
+            seg = torch.from_numpy(bounds.astype(np.int32)).to(l.device)
+            G = engine.segment_products(Bt, Bt, seg, channels=K).permute(2, 1, 0, 3)                       # [arcs, K, u, u]
+            b = engine.segment_products(lt, Bt, seg, channels=K).permute(1, 0, 2)                          # [arcs, K, u]
+            if not shared:
+                G, b = G.sum(1, keepdim=True), b.sum(1, keepdim=True)
+            R, g, ranks = _arc_reduction(engine.to_host(G).reshape(arcs * Kc, u, u), engine.to_host(b).reshape(arcs * Kc, u))
+            R_d, g_d = engine.to_device(R, l.device), engine.to_device(g, l.device).reshape(-1, 1)         # [arcs Kc, u, u], [arcs Kc u, 1]
+            carry, columns = _zeros((P, Kc, u)), ([] if local[0].keep else None)
+            pending, applied = [], 0                                                                        # D of finished arcs not yet subtracted
         for first in range(0, M, block_points):
             last = min(first + block_points, M)
             if whitening is None:
@@ -707,11 +861,40 @@ class NormalEquations:
             engine.gemm(At, At, transb=True, beta=1.0, out=normals)
             engine.gemm(At, lb, beta=1.0, out=side)
             engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
+            if local is not None:
+                a0, a1 = int(np.searchsorted(bounds, first, side='right')) - 1, int(np.searchsorted(bounds, last, side='left')) - 1
+                cut = (seg[a0:a1 + 2] - first).clamp_(0, last - first)                                       # arcs a0 .. a1 meet the block
+                S = engine.segment_products(At.reshape(P * K, last - first), Bt[:, :, first:last], cut, channels=K).reshape(P, K, a1 - a0 + 1, u)
+                C = S.permute(0, 2, 1, 3) if shared else S.sum(1, keepdim=True).permute(0, 2, 1, 3)          # [P, arcs of the block, Kc, u]
+                C[:, 0] += carry
+                ended = a1 - a0 + (1 if bounds[a1 + 1] <= last else 0)
+                if ended <= a1 - a0:
+                    carry = C[:, ended].clone()
+                else:
+                    carry.zero_()
+                if ended:
+                    D = torch.empty((ended * Kc, P, u), dtype=torch.float64, device=l.device)
+                    engine.gemm_ex(C[:, :ended].permute(1, 2, 0, 3).reshape(ended * Kc, P, u), R_d[a0 * Kc:(a0 + ended) * Kc], D)
+                    D = D.permute(1, 0, 2).reshape(P, ended * Kc * u)
+                    pending.append(D)
+                    if columns is not None:
+                        columns.append(D)
+                if pending and (last == M or sum(int(D.shape[1]) for D in pending) >= cls.ARC_UPDATE_COLUMNS):
+                    D = pending[0] if len(pending) == 1 else torch.cat(pending, dim=1)                       # the arcs applied .. a0 + ended
+                    engine.gemm(D, D, transb=True, alpha=-1.0, beta=1.0, out=normals)
+                    engine.gemm(D, g_d[applied * Kc * u:(a0 + ended) * Kc * u], alpha=-1.0, beta=1.0, out=side)
+                    pending, applied = [], a0 + ended
         normals.triu_()
         normals.add_(torch.triu(normals, 1).t())
         matrix = BlockMatrix([0, P], [0, P])
         matrix._set_device(0, 0, normals)
-        return cls(matrix, side, float(square_sum.item()), K * M)
+        if local is None:
+            return cls(matrix, side, float(square_sum.item()), K * M)
+        shape = (arcs, Kc) if shared else (arcs,)
+        elimination = ArcElimination(ranks.reshape(shape), R.reshape(arcs, Kc, u, u), g.reshape(arcs, Kc, u), shared, columns)
+        system = cls(matrix, side, float(square_sum.item()) - float(np.sum(g * g)), K * M - elimination.count)
+        system.arc_elimination = elimination
+        return system
 
     @classmethod
     def from_accelerations(cls, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
@@ -735,26 +918,34 @@ class NormalEquations:
         meaning and scale the rows by sqrt(w) before the whitening, so the weight matrix in effect is D^1/2 W^T W D^1/2.  block_points
         keeps its default: a block takes up to q points in front of it along as history, the whitened copy doubles the peak memory of
         a block, and observation_count is unchanged.  noise_model=None changes nothing; arcs without it is a ValueError.
-        ColouredNoise(noise_model, arcs) offers the same for all three kinds of observation.
+        ColouredNoise(noise_model, arcs) offers the same for all three kinds of observation; ArcParameters(basis, arcs, noise_model)
+        also eliminates parameters that last one arc (biases, drifts, once-per-revolution terms).
 
         Returns NormalEquations with a one-block BlockMatrix [P, P] and the right-hand side [P, 1] on the device, and
         observation_count = 3 M: components of zero weight still count as observations.
         """
+        return cls._accelerations(noise_model, arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points)
+
+    @classmethod
+    def _accelerations(cls, noise_model, arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points, local=None):
+        """from_accelerations, with the arc-wise parameters of an ArcParameters (local; its arcs are `arcs`) eliminated"""
         min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
         M = engine.check_positions(xyz)
         if engine.check_positions(g, 'accelerations') != M:
             raise ValueError('{0} positions but {1} accelerations'.format(M, int(g.shape[0])))
         layout = engine.check_observation_weights(weights, M)
         block_points = cls.__check_block_points(block_points, min_degree, max_degree, 3)
-        whitening = cls.__check_noise_model(noise_model, arcs, M, 3)
+        whitening = cls.__check_noise_model(noise_model, arcs if local is None or noise_model is not None else None, M, 3)
+        local = cls.__check_local(local, arcs, M, 3)
 
         torch = engine.require_gpu()
         x, l = engine.to_device(xyz), engine.to_device(g)
         w = engine.to_device(weights) if layout else None
+        root = torch.sqrt(w if layout == 2 else w[:, None]) if layout else None
         if layout:
-            l = l * torch.sqrt(w if layout == 2 else w[:, None])
+            l = l * root
         return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.acceleration_design_checked(
-            max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R), whitening)
+            max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R), whitening, local, root)
 
     @classmethod
     def from_gradients(cls, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
@@ -779,8 +970,8 @@ class NormalEquations:
         return cls._gradients(None, None, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points)
 
     @classmethod
-    def _gradients(cls, noise_model, arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points):
-        """from_gradients under a noise model (None: white noise)"""
+    def _gradients(cls, noise_model, arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points, local=None):
+        """from_gradients under a noise model (None: white noise), with the arc-wise parameters of an ArcParameters (local) eliminated"""
         min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
         M = engine.check_positions(xyz)
         picked = engine.gradient_components(components)
@@ -795,7 +986,8 @@ class NormalEquations:
         if frames is not None:
             engine.check_frames(frames, M)
         block_points = cls.__check_block_points(block_points, min_degree, max_degree, K)
-        whitening = cls.__check_noise_model(noise_model, arcs, M, K)
+        whitening = cls.__check_noise_model(noise_model, arcs if local is None or noise_model is not None else None, M, K)
+        local = cls.__check_local(local, arcs, M, K)
 
         torch = engine.require_gpu()
         x, l = engine.to_device(xyz), engine.to_device(gradients)
@@ -803,11 +995,12 @@ class NormalEquations:
         if full:
             l = torch.stack([l[:, j // 3, j % 3] for j in ((0, 1, 2, 4, 5, 8)[i] for i in picked)], dim=1)
         w = engine.to_device(weights) if layout else None
+        root = torch.sqrt(w if layout == 2 else w[:, None]) if layout else None
         if layout:
-            l = l * torch.sqrt(w if layout == 2 else w[:, None])
+            l = l * root
         return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.gradient_design_checked(
             max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last], GM, R),
-            whitening)
+            whitening, local, root)
 
     @classmethod
     def from_line_of_sight(cls, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
@@ -832,8 +1025,9 @@ class NormalEquations:
         return cls._line_of_sight(None, None, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, block_points)
 
     @classmethod
-    def _line_of_sight(cls, noise_model, arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, block_points):
-        """from_line_of_sight under a noise model (None: white noise)"""
+    def _line_of_sight(cls, noise_model, arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, block_points,
+                       local=None):
+        """from_line_of_sight under a noise model (None: white noise), with the arc-wise parameters of an ArcParameters (local) eliminated"""
         min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
         M = engine.check_pair_positions(xyz_a, xyz_b)
         if len(differences.shape) != 1:
@@ -848,17 +1042,19 @@ class NormalEquations:
         else:
             engine.check_pairs_apart(xyz_a, xyz_b)
         block_points = cls.__check_block_points(block_points, min_degree, max_degree, 1)
-        whitening = cls.__check_noise_model(noise_model, arcs, M, 1)
+        whitening = cls.__check_noise_model(noise_model, arcs if local is None or noise_model is not None else None, M, 1)
+        local = cls.__check_local(local, arcs, M, 1)
 
         torch = engine.require_gpu()
         a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
         e = engine.to_device(directions) if directions is not None else None
         w = engine.to_device(weights) if layout else None
+        root = torch.sqrt(w)[:, None] if layout else None
         if layout:
-            l = l * torch.sqrt(w)[:, None]
+            l = l * root
         return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.los_design_checked(
             max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last], GM, R),
-            whitening)
+            whitening, local, root)
 
     def __cholesky(self):
         """factor the matrix once; a matrix that already holds covariances cannot be factored again (ValueError, as upstream)"""
@@ -970,6 +1166,52 @@ class ColouredNoise:
                            weights=None, block_points=None):
         return NormalEquations._line_of_sight(self.noise_model, self.arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions,
                                               weights, block_points)
+
+
+class ArcParameters:
+    """
+    Parameters that last one arc (an accelerometer's bias and drift per axis, a gradiometer's bias per component, the link's empirical
+    once-per-revolution terms), estimated per arc and eliminated from the normal equations before the arcs are summed; bound to the
+    constructors of NormalEquations like ColouredNoise.  basis is [M, u'] (shared: every component of every arc has u' parameters of
+    its own, whose design matrix is the basis on the points of the arc; arc_basis) or [M, K, u] (general: every arc has one set of u
+    parameters, of which component k of point t sees basis[t, k, :]; frame_basis), u and u' at most 16.  arcs holds the start
+    indices of the arcs (default: one arc); noise_model is that of ColouredNoise, with the same arcs.  The basis goes the way of
+    the design matrix: times sqrt(w), then the arc's W.
+
+    from_accelerations, from_gradients and from_line_of_sight take the arguments of the classmethods of the same name and return the
+    NormalEquations of the coefficients alone, N = A^T A - sum_a C_a G_a^+ C_a^T with C_a = A_a^T B_a, G_a = B_a^T B_a (n and l^T P l
+    alike), with observation_count reduced by the sum of the ranks of the G_a: posterior_sigma, redundancy and
+    compute_variance_factors see the redundancy of the eliminated system.  Directions of G_a with eigenvalues at or below 1e-12 of the
+    largest are dropped (an arc shorter than u', an arc of zero weights).  ne.arc_elimination (ArcElimination) holds the ranks and,
+    with keep=True, returns the parameters of a solution; it then retains P K u' doubles per arc on the device (shared basis; P u
+    for the general form).  The shape of the basis is checked against the points and components of every call, all of it before
+    anything reaches the device.
+    """
+
+    def __init__(self, basis, arcs=None, noise_model=None, keep=True):
+        basis = np.asarray(engine.to_host(basis) if _is_tensor(basis) else basis, dtype=np.float64)
+        if basis.ndim not in (2, 3):
+            raise ValueError('the arc basis must have shape (M, u) or (M, K, u), got {0}'.format(basis.shape))
+        if not 1 <= basis.shape[-1] <= MAX_ARC_PARAMETERS:
+            raise ValueError('{0} parameters per arc: expected 1 .. {1}'.format(basis.shape[-1], MAX_ARC_PARAMETERS))
+        if not np.all(np.isfinite(basis)):
+            raise ValueError('the arc basis must be finite')
+        if noise_model is not None:
+            whitening_taps(noise_model)
+        self.basis, self.arcs, self.noise_model, self.keep = basis, arcs, noise_model, bool(keep)
+
+    def from_accelerations(self, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
+        return NormalEquations._accelerations(self.noise_model, self.arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points, self)
+
+    def from_gradients(self, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
+                       weights=None, block_points=None):
+        return NormalEquations._gradients(self.noise_model, self.arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights,
+                                          block_points, self)
+
+    def from_line_of_sight(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
+                           weights=None, block_points=None):
+        return NormalEquations._line_of_sight(self.noise_model, self.arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions,
+                                              weights, block_points, self)
 
 
 def accumulate_normals(normal_equations, variance_factors):

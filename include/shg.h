@@ -570,6 +570,30 @@ int shg_los_design_pass(int N);
 int shg_whiten_rows(long long rows, int channels, int M, const double* X, long long ldx, const int32_t* stage, const double* taps, int q,
                     int skip, double* Y, long long ldy, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Products of the rows of a matrix with a basis, cut at arc boundaries: what the elimination of arc-wise parameters needs of the
+ * transposed design matrix (C_a = A_a^T B_a; no reference counterpart)
+ *   X [rows][ldx] with M columns in use, row r of channel r % channels (the row convention of shg_whiten_rows: At [P][K][ldt] is
+ *   rows = P K, channels = K; observations laid out [K][M] are rows = K, channels = K).  Bt [u][channels][ldb]: the basis, transformed
+ *   like the design matrix and transposed, 1 <= u <= 16.  seg (device) [nseg + 1]: column indices, segment s is seg[s] .. seg[s+1] - 1.
+ *   S[r][s][j] = sum_{t = seg[s] .. seg[s+1] - 1} X[r][t] Bt[j][r % channels][t];  S [rows][nseg][u] is dense and every entry is
+ *   written, 0 for an empty segment.
+ *   Locality: S[r][s][j] depends only on X[r][seg[s] .. seg[s+1]) and on the basis values at those columns, not on rows, nseg, M, the
+ *   other segments, the position of the segment in the row or the launch geometry.  Columns outside every segment are not read.
+ *   Summation order, relative to the start of the segment: chain i of 64 is acc = 0, acc = fma(x[t], b[t], acc) over the columns
+ *   t = start + i, start + i + 64, ... ascending (an empty chain is 0); the chains are added by the butterfly v_i += v_(i ^ m) for
+ *   m = 32, 16, 8, 4, 2, 1, and entry 0 is the result.  No atomics; repeated calls are bitwise equal.
+ *   Clamping: entry i of seg is read as c_i = max over k <= i of min(max(seg[k], 0), M), so the table in effect lies in 0 .. M and
+ *   does not decrease; a wrong table gives wrong numbers, never a read outside a row.
+ *   One wave per segment of 4 rows of one channel (2 rows above u = 8; lane <-> column, coalesced): X is read from global memory
+ *   once, a basis value once per 4 (2) rows (from cache: the basis of a block is at most 16 K M doubles); a flat 64-bit index, so
+ *   rows x ldx may exceed 2^31.
+ *   Arguments are checked before the first HIP call (negative sizes, channels < 1, rows not a multiple of channels, u outside
+ *   1 .. 16, nseg < 0, ldx < M, ldb < M, more than 2^40 values of X or S, NULL pointers); rows = 0 or nseg = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_segment_products(long long rows, int channels, int M, const double* X, long long ldx, const double* Bt, long long ldb, int u, int nseg,
+                         const int32_t* seg, double* S, void* stream);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
