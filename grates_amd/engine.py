@@ -1049,6 +1049,37 @@ def segment_products(X, Bt, seg, channels=1, out=None):
     return out
 
 
+def segment_lag_products(X, seg, lags, out=None):
+    """Lagged products of the rows of the device tensor X [..., M] with themselves, cut at arc boundaries (shg_segment_lag_products):
+    S[..., s, k] = sum of X[..., t] X[..., t + k] over seg[s] <= t, t + k < seg[s + 1], for k = 0 .. lags (0 <= lags <= 128): lag 0 is
+    the square sum of a segment, lags 0 .. q its empirical autocovariance times the number of pairs.  seg [nseg + 1] (int32) holds the
+    column indices of the boundaries, a device tensor; the kernel clamps it to 0 .. M and makes it non-decreasing.  A two-dimensional
+    X may be a column slice of a wider matrix (unit stride along the rows); anything else that is not dense is copied.  Returns out,
+    or a new dense tensor [..., nseg, lags + 1]; every entry is written."""
+    torch = require_gpu()
+    M, lags = int(X.shape[-1]), int(lags)
+    lead = tuple(int(s) for s in X.shape[:-1])
+    if X.dtype != torch.float64:
+        raise ValueError('X must be float64, got {0}'.format(X.dtype))
+    if tuple(seg.shape) != (seg.numel(),) or seg.numel() < 1 or seg.dtype != torch.int32 or not seg.is_contiguous():
+        raise ValueError('seg must be a dense int32 tensor of shape (nseg + 1,), got {0} {1}'.format(seg.dtype, tuple(seg.shape)))
+    nseg = int(seg.numel()) - 1
+    if X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= M:
+        ldx = int(X.stride(0))
+    else:
+        X, ldx = X.contiguous(), M
+    rows = 1
+    for size in lead:
+        rows *= size
+    shape = lead + (nseg, max(lags, 0) + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=X.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError('out must be a dense float64 tensor of shape {0}'.format(shape))
+    _lib.call('shg_segment_lag_products', rows, M, _ptr(X), ldx, lags, nseg, _ptr(seg), _ptr(out), _stream())
+    return out
+
+
 class OrderMajorSeries:
     """A time series of coefficient sets that stays on the device between operators (the batching of TimeSeries.to_array,
     grates/gravityfield.py:964-980, in the layout the order-wise operators work on): `data` [(N+1)^2, Bpad] with the epochs fastest

@@ -401,6 +401,74 @@ def _arc_reduction(G, b):
     return R, np.einsum('ijr,ij->ir', R, b), ranks
 
 
+class _ArcSetup:
+    """what the elimination of arc-wise parameters and the post-fit pass share of an ArcParameters: see _arc_setup"""
+
+
+def _device_whitening(whitening, device):
+    """the host tables (taps, stage) of a from_* call on the device, with the host's stage table (the halo of a block) behind them;
+    None without a noise model"""
+    if whitening is None:
+        return None
+    torch = engine.require_gpu()
+    return engine.to_device(whitening[0], device), torch.from_numpy(whitening[1]).to(device), whitening[1]
+
+
+def _design_blocks(P, l, block_points, design_block, tables):
+    """The blocks of the from_* classmethods and of PostFit, one after the other: (first, last, At [P, K Mb], lb [K Mb, 1], plain, skip)
+    of the points first .. last of the observations l [M, K].  Without tables (_device_whitening) At is design_block(first, last) and lb
+    the observations, component-major as the columns of At; plain is At and skip 0.  With them a block takes the skip = stage[first]
+    points in front of it along (none where it starts an arc), shg_whiten_rows turns the design matrix and the observations of
+    first - skip .. last into those of W A and W l at first .. last in a second buffer, and plain [P, K (skip + Mb)] is the design matrix
+    as design_block gave it."""
+    M, K = (int(size) for size in l.shape)
+    for first in range(0, M, block_points):
+        last = min(first + block_points, M)
+        if tables is None:
+            At = design_block(first, last).reshape(P, K * (last - first))
+            yield first, last, At, l[first:last].t().reshape(-1, 1), At, 0      # component-major, as the columns of At
+        else:
+            taps, stage, halo = tables
+            start = first - int(halo[first])
+            whiten = dict(taps=taps, stage=stage[start:last], channels=int(taps.shape[0]), skip=first - start)
+            plain = design_block(start, last).reshape(P * K, last - start)
+            At = engine.whiten_rows(plain, **whiten).reshape(P, K * (last - first))
+            lb = engine.whiten_rows(l[start:last].t().contiguous(), **whiten).reshape(-1, 1)
+            yield first, last, At, lb, plain.reshape(P, K * (last - start)), first - start
+
+
+def _arc_setup(l, root, local, tables, plain=False):
+    """local = (ArcParameters, starts) of a from_* call, l [M, K] the observations times root = sqrt(w) [M, K] (or broadcastable to it,
+    None: 1) on the device, tables those of _device_whitening: the basis goes the way of the design matrix (times root, then W) into Bt
+    [u, K, M] (plain=True keeps the one before W as plain_Bt), once; shg_segment_products gives G_a = B_a^T B_a and b_a = B_a^T l_a of
+    all arcs (summed over the components for the general form, Kc = 1; Kc = K for a shared basis), the host R_a = V Lambda^-1/2 of the
+    kept eigenpairs of G_a, g = R^T b and the ranks (_arc_reduction).  seg holds the boundaries of the arcs on the device, bounds on
+    the host."""
+    torch = engine.require_gpu()
+    M, K = (int(size) for size in l.shape)
+    s = _ArcSetup()
+    whole = {} if tables is None else dict(taps=tables[0], stage=tables[1], channels=int(tables[0].shape[0]))
+    basis = engine.to_device(local[0].basis, l.device)
+    s.shared = shared = basis.dim() == 2
+    Bt = basis.t()[:, None, :].expand(-1, K, -1) if shared else basis.permute(2, 1, 0)
+    Bt = (Bt if root is None else Bt * root.expand(M, K).t()[None]).contiguous()                    # [u, K, M]
+    lt = l.t().contiguous()
+    s.plain_Bt = Bt if plain else None
+    if tables is not None:
+        Bt, lt = engine.whiten_rows(Bt, **whole), engine.whiten_rows(lt, **whole)
+    s.Bt, s.u, s.Kc = Bt, int(Bt.shape[0]), (K if shared else 1)
+    s.bounds = np.append(local[1], M)
+    s.arcs = len(s.bounds) - 1
+    s.seg = torch.from_numpy(s.bounds.astype(np.int32)).to(l.device)
+    G = engine.segment_products(Bt, Bt, s.seg, channels=K).permute(2, 1, 0, 3)                       # [arcs, K, u, u]
+    b = engine.segment_products(lt, Bt, s.seg, channels=K).permute(1, 0, 2)                          # [arcs, K, u]
+    if not shared:
+        G, b = G.sum(1, keepdim=True), b.sum(1, keepdim=True)
+    s.R, s.g, s.ranks = _arc_reduction(engine.to_host(G).reshape(s.arcs * s.Kc, s.u, s.u), engine.to_host(b).reshape(s.arcs * s.Kc, s.u))
+    s.R_d, s.g_d = engine.to_device(s.R, l.device), engine.to_device(s.g, l.device).reshape(-1, 1)   # [arcs Kc, u, u], [arcs Kc u, 1]
+    return s
+
+
 class ArcElimination:
     """
     What NormalEquations keeps of the elimination of its arc-wise parameters (ne.arc_elimination; ArcParameters): `ranks`, the number of
@@ -824,40 +892,14 @@ class NormalEquations:
         M, K = (int(size) for size in l.shape)
         P = (max_degree + 1) ** 2 - min_degree ** 2
         normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
-        if whitening is not None:
-            halo = whitening[1]
-            taps, stage = engine.to_device(whitening[0], l.device), torch.from_numpy(halo).to(l.device)
+        tables = _device_whitening(whitening, l.device)
         if local is not None:
-            whole = {} if whitening is None else dict(taps=taps, stage=stage, channels=int(taps.shape[0]))
-            basis = engine.to_device(local[0].basis, l.device)
-            shared = basis.dim() == 2
-            Bt = basis.t()[:, None, :].expand(-1, K, -1) if shared else basis.permute(2, 1, 0)
-            Bt = (Bt if root is None else Bt * root.expand(M, K).t()[None]).contiguous()                    # [u, K, M]
-            lt = l.t().contiguous()
-            if whitening is not None:
-                Bt, lt = engine.whiten_rows(Bt, **whole), engine.whiten_rows(lt, **whole)
-            u, Kc = int(Bt.shape[0]), (K if shared else 1)
-            bounds = np.append(local[1], M)
-            arcs = len(bounds) - 1
-            seg = torch.from_numpy(bounds.astype(np.int32)).to(l.device)
-            G = engine.segment_products(Bt, Bt, seg, channels=K).permute(2, 1, 0, 3)                       # [arcs, K, u, u]
-            b = engine.segment_products(lt, Bt, seg, channels=K).permute(1, 0, 2)                          # [arcs, K, u]
-            if not shared:
-                G, b = G.sum(1, keepdim=True), b.sum(1, keepdim=True)
-            R, g, ranks = _arc_reduction(engine.to_host(G).reshape(arcs * Kc, u, u), engine.to_host(b).reshape(arcs * Kc, u))
-            R_d, g_d = engine.to_device(R, l.device), engine.to_device(g, l.device).reshape(-1, 1)         # [arcs Kc, u, u], [arcs Kc u, 1]
+            setup = _arc_setup(l, root, local, tables)
+            Bt, seg, bounds, arcs, shared, u, Kc = setup.Bt, setup.seg, setup.bounds, setup.arcs, setup.shared, setup.u, setup.Kc
+            R, g, ranks, R_d, g_d = setup.R, setup.g, setup.ranks, setup.R_d, setup.g_d
             carry, columns = _zeros((P, Kc, u)), ([] if local[0].keep else None)
             pending, applied = [], 0                                                                        # D of finished arcs not yet subtracted
-        for first in range(0, M, block_points):
-            last = min(first + block_points, M)
-            if whitening is None:
-                At = design_block(first, last).reshape(P, K * (last - first))
-                lb = l[first:last].t().reshape(-1, 1)                  # component-major, as the columns of At
-            else:
-                start = first - int(halo[first])
-                whiten = dict(taps=taps, stage=stage[start:last], channels=int(taps.shape[0]), skip=first - start)
-                At = engine.whiten_rows(design_block(start, last).reshape(P * K, last - start), **whiten).reshape(P, K * (last - first))
-                lb = engine.whiten_rows(l[start:last].t().contiguous(), **whiten).reshape(-1, 1)
+        for first, last, At, lb, _, _ in _design_blocks(P, l, block_points, design_block, tables):
             engine.gemm(At, At, transb=True, beta=1.0, out=normals)
             engine.gemm(At, lb, beta=1.0, out=side)
             engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
@@ -927,7 +969,7 @@ class NormalEquations:
         return cls._accelerations(noise_model, arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points)
 
     @classmethod
-    def _accelerations(cls, noise_model, arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points, local=None):
+    def _accelerations(cls, noise_model, arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points, local=None, post=None):
         """from_accelerations, with the arc-wise parameters of an ArcParameters (local; its arcs are `arcs`) eliminated"""
         min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
         M = engine.check_positions(xyz)
@@ -937,6 +979,8 @@ class NormalEquations:
         block_points = cls.__check_block_points(block_points, min_degree, max_degree, 3)
         whitening = cls.__check_noise_model(noise_model, arcs if local is None or noise_model is not None else None, M, 3)
         local = cls.__check_local(local, arcs, M, 3)
+        if post is not None:
+            post._check((max_degree + 1) ** 2 - min_degree ** 2)
 
         torch = engine.require_gpu()
         x, l = engine.to_device(xyz), engine.to_device(g)
@@ -944,7 +988,8 @@ class NormalEquations:
         root = torch.sqrt(w if layout == 2 else w[:, None]) if layout else None
         if layout:
             l = l * root
-        return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.acceleration_design_checked(
+        driver = cls.__from_design_blocks if post is None else post._run                 # the normals, or the post-fit pass over the same blocks
+        return driver(min_degree, max_degree, l, block_points, lambda first, last: engine.acceleration_design_checked(
             max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R), whitening, local, root)
 
     @classmethod
@@ -970,7 +1015,8 @@ class NormalEquations:
         return cls._gradients(None, None, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points)
 
     @classmethod
-    def _gradients(cls, noise_model, arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points, local=None):
+    def _gradients(cls, noise_model, arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points, local=None,
+                   post=None):
         """from_gradients under a noise model (None: white noise), with the arc-wise parameters of an ArcParameters (local) eliminated"""
         min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
         M = engine.check_positions(xyz)
@@ -988,6 +1034,8 @@ class NormalEquations:
         block_points = cls.__check_block_points(block_points, min_degree, max_degree, K)
         whitening = cls.__check_noise_model(noise_model, arcs if local is None or noise_model is not None else None, M, K)
         local = cls.__check_local(local, arcs, M, K)
+        if post is not None:
+            post._check((max_degree + 1) ** 2 - min_degree ** 2)
 
         torch = engine.require_gpu()
         x, l = engine.to_device(xyz), engine.to_device(gradients)
@@ -998,7 +1046,8 @@ class NormalEquations:
         root = torch.sqrt(w if layout == 2 else w[:, None]) if layout else None
         if layout:
             l = l * root
-        return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.gradient_design_checked(
+        driver = cls.__from_design_blocks if post is None else post._run                 # the normals, or the post-fit pass over the same blocks
+        return driver(min_degree, max_degree, l, block_points, lambda first, last: engine.gradient_design_checked(
             max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last], GM, R),
             whitening, local, root)
 
@@ -1026,7 +1075,7 @@ class NormalEquations:
 
     @classmethod
     def _line_of_sight(cls, noise_model, arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, block_points,
-                       local=None):
+                       local=None, post=None):
         """from_line_of_sight under a noise model (None: white noise), with the arc-wise parameters of an ArcParameters (local) eliminated"""
         min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
         M = engine.check_pair_positions(xyz_a, xyz_b)
@@ -1044,6 +1093,8 @@ class NormalEquations:
         block_points = cls.__check_block_points(block_points, min_degree, max_degree, 1)
         whitening = cls.__check_noise_model(noise_model, arcs if local is None or noise_model is not None else None, M, 1)
         local = cls.__check_local(local, arcs, M, 1)
+        if post is not None:
+            post._check((max_degree + 1) ** 2 - min_degree ** 2)
 
         torch = engine.require_gpu()
         a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
@@ -1052,7 +1103,8 @@ class NormalEquations:
         root = torch.sqrt(w)[:, None] if layout else None
         if layout:
             l = l * root
-        return cls.__from_design_blocks(min_degree, max_degree, l, block_points, lambda first, last: engine.los_design_checked(
+        driver = cls.__from_design_blocks if post is None else post._run                 # the normals, or the post-fit pass over the same blocks
+        return driver(min_degree, max_degree, l, block_points, lambda first, last: engine.los_design_checked(
             max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last], GM, R),
             whitening, local, root)
 
@@ -1212,6 +1264,169 @@ class ArcParameters:
                            weights=None, block_points=None):
         return NormalEquations._line_of_sight(self.noise_model, self.arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions,
                                               weights, block_points, self)
+
+
+class PostFit:
+    """
+    What a solution says about the stochastic model it was computed under: the residuals of the observations, the square sum, the
+    redundancy and the variance factor of every arc, and the empirical covariance function of the residuals, from one more pass over
+    the blocks of the design matrix.  of_accelerations, of_gradients and of_line_of_sight take the solution
+    [P] or [P, 1] (host or device), then the arguments of NormalEquations.from_accelerations / from_gradients / from_line_of_sight with
+    the same checks, then
+
+    model   : None (white noise), the ColouredNoise or the ArcParameters the system was built with,
+    vectors : [P, S], optional: the Monte-Carlo vectors of the solved (combined) system, ne.monte_carlo_vectors.
+
+    Per block the whitened transposed design matrix At~ [P, K Mb] gives V = [x, z_1 .. z_S]^T At~ in one product on the fp64 MFMA
+    GEMM, and a thin product on the unwhitened block the unwhitened model values.  The rows are kept whole on the device, `rows`
+    [1 + S, K, M] doubles (row 0 is e~, row 1 + j the projected whitened model values of z_j): 1.3 GB for S = 100, K = 3, M = 5e5;
+    pass the vectors in groups, or drop the attribute, if that is too much.
+    Under ArcParameters the parameters of an arc are y^_a = R_a R_a^T B~_a^T (l~_a - A~_a x) with R_a as the elimination forms it, and
+    every row v of V is projected explicitly, v - B~ R R^T (B~^T v), before it is squared (shg_segment_products for the basis products,
+    shg_segment_lag_products at lags = 0 for all square sums).
+
+    whitened [M, K]         e~ = l~ - A~ x - B~ y^; its square sum is ne.residual_square_sum(x) of the system of the same arguments
+    residuals [M, K]        e^ = sqrt(w) (l - A x - B y^), not whitened: e~ = W e^
+    arc_parameters          y^ [arcs, K, u'] (shared basis) or [arcs, u] (general form), host, zero along dropped directions; None
+                            without ArcParameters.  ne.arc_elimination.parameters(x) without the kept columns: works after keep=False
+    arcs, ranks             start indices [arcs]; ranks as ArcElimination.ranks (zeros [arcs, K] without ArcParameters)
+    arc_observation_counts  n_a = K len_a - sum of the ranks of arc a
+    arc_square_sums [arcs]  Omega_a = sum over the components and points of the arc of e~^2 (host)
+
+    whitened and residuals are device tensors where the positions were, host arrays otherwise.  Without a model, and with
+    ColouredNoise(arcs=None), there is the one arc [0].
+    """
+
+    def __init__(self, solution, vectors, model, template):
+        if model is None:
+            self.__noise, self.__arcs, self.__local = None, None, None
+        elif isinstance(model, ColouredNoise):
+            self.__noise, self.__arcs, self.__local = model.noise_model, model.arcs, None
+        elif isinstance(model, ArcParameters):
+            self.__noise, self.__arcs, self.__local = model.noise_model, model.arcs, model
+        else:
+            raise ValueError('model must be None, a ColouredNoise or an ArcParameters (arcs belong to one of them), got {0!r}'.format(model))
+        self.__solution, self.__vectors, self.__template = solution, vectors, template
+
+    @classmethod
+    def of_accelerations(cls, solution, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
+                         model=None, vectors=None):
+        post = cls(solution, vectors, model, xyz)
+        return NormalEquations._accelerations(post.__noise, post.__arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points, post.__local, post)
+
+    @classmethod
+    def of_gradients(cls, solution, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
+                     weights=None, block_points=None, model=None, vectors=None):
+        post = cls(solution, vectors, model, xyz)
+        return NormalEquations._gradients(post.__noise, post.__arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights,
+                                          block_points, post.__local, post)
+
+    @classmethod
+    def of_line_of_sight(cls, solution, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
+                         weights=None, block_points=None, model=None, vectors=None):
+        post = cls(solution, vectors, model, xyz_a)
+        return NormalEquations._line_of_sight(post.__noise, post.__arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights,
+                                              block_points, post.__local, post)
+
+    def _check(self, parameters):
+        """the solution and the vectors against the number of parameters: ValueError before anything reaches the device"""
+        shape = tuple(int(size) for size in np.shape(self.__solution))
+        if shape not in ((parameters,), (parameters, 1)):
+            raise ValueError('solution must have shape ({0},) or ({0}, 1), got {1}'.format(parameters, shape))
+        if self.__vectors is not None:
+            shape = tuple(int(size) for size in np.shape(self.__vectors))
+            if len(shape) != 2 or shape[0] != parameters or shape[1] < 1:
+                raise ValueError('vectors must have shape ({0}, S), got {1}'.format(parameters, shape))
+
+    def _run(self, min_degree, max_degree, l, block_points, design_block, whitening, local, root):
+        """the pass, in place of NormalEquations.__from_design_blocks and with its arguments"""
+        torch = engine.require_gpu()
+        M, K = (int(size) for size in l.shape)
+        P = (max_degree + 1) ** 2 - min_degree ** 2
+        x = engine.to_device(self.__solution, l.device).reshape(P, 1)
+        X = x if self.__vectors is None else torch.cat((x, engine.to_device(self.__vectors, l.device)), dim=1)
+        rows = int(X.shape[1])
+        Xt = torch.empty((rows, P), dtype=torch.float64, device=l.device).copy_(X.t())                   # [1 + S, P], row stride P also for one row
+        tables = _device_whitening(whitening, l.device)
+        bounds = np.append(_arc_starts(self.__arcs, M), M)
+        arcs = len(bounds) - 1
+        V = torch.empty((rows, K, M), dtype=torch.float64, device=l.device)                             # the whitened model values of x and the z_j
+        lt, plain = torch.empty((K, M), dtype=torch.float64, device=l.device), torch.empty((K, M), dtype=torch.float64, device=l.device)
+        for first, last, At, lb, At_plain, skip in _design_blocks(P, l, block_points, design_block, tables):
+            V[:, :, first:last] = engine.gemm(Xt, At).reshape(rows, K, last - first)
+            lt[:, first:last] = lb.reshape(K, last - first)
+            if tables is None:
+                plain[:, first:last] = V[0, :, first:last]                                               # white noise: the same values
+            else:
+                plain[:, first:last] = engine.gemm(Xt[0:1], At_plain).reshape(K, skip + last - first)[:, skip:]
+        V[0] = lt - V[0]                                                                                 # l~ - A~ x
+        plain = l.t().contiguous() - plain                                                               # sqrt(w) (l - A x), dense [K, M]
+        seg = torch.from_numpy(bounds.astype(np.int32)).to(l.device)
+        self.arc_parameters, self.ranks = None, np.zeros((arcs, K), dtype=np.int64)
+        if local is not None:
+            setup = _arc_setup(l, root, local, tables, plain=True)
+            u, Kc, units = setup.u, setup.Kc, arcs * setup.Kc
+            C = engine.segment_products(V.reshape(rows * K, M), setup.Bt, seg, channels=K).reshape(rows, K, arcs, u)        # B~_a^T v
+            C = (C.permute(2, 1, 0, 3) if setup.shared else C.sum(1, keepdim=True).permute(2, 1, 0, 3)).reshape(units, rows, u).contiguous()
+            T, Y = torch.empty_like(C), torch.empty_like(C)
+            engine.gemm_ex(C, setup.R_d, T)                                                              # R^T B~^T v, as rows
+            engine.gemm_ex(T, setup.R_d, Y, transb=True)                                                 # the parameters of every row: R R^T B~^T v
+            for a in range(arcs):
+                a0, a1 = int(bounds[a]), int(bounds[a + 1])
+                Ya = Y[a * Kc:(a + 1) * Kc]                                                              # [Kc, rows, u]
+                engine.gemm_ex(Ya if setup.shared else Ya[0], setup.Bt[:, :, a0:a1].permute(1, 0, 2), V[:, :, a0:a1].permute(1, 0, 2), alpha=-1.0, beta=1.0)
+                engine.gemm_ex(Ya[:, 0:1] if setup.shared else Ya[0, 0:1], setup.plain_Bt[:, :, a0:a1].permute(1, 0, 2), plain[:, None, a0:a1], alpha=-1.0,
+                               beta=1.0)
+            y = engine.to_host(Y[:, 0]).reshape(arcs, Kc, u)
+            self.arc_parameters = y if setup.shared else y[:, 0]
+            self.ranks = setup.ranks.reshape((arcs, Kc) if setup.shared else (arcs,))
+        squares = engine.to_host(engine.segment_lag_products(V.reshape(rows * K, M), seg, 0)).reshape(rows, K, arcs)
+        self.arcs = bounds[:-1].copy()
+        self.arc_observation_counts = K * np.diff(bounds) - self.ranks.reshape(arcs, -1).sum(axis=1)
+        self.arc_square_sums = squares[0].sum(axis=0)
+        self.__traces = squares[1:].sum(axis=(0, 1)) / (rows - 1) if rows > 1 else None                   # (1 / S) sum_j |(I - Q_a Q_a^T) A~_a z_j|^2
+        self.__rows, self.__seg = plain, seg                                                              # e^ [K, M] on the device, for covariance_function
+        self.rows = V
+        self.whitened = _like_input(V[0].t().contiguous(), self.__template)
+        self.residuals = _like_input(plain.t().contiguous(), self.__template)
+        self.__solution = self.__vectors = None
+        return self
+
+    def arc_redundancies(self, variance_factor=1.0):
+        """r_a = n_a - (1 / S) sum_j |(I - Q_a Q_a^T) A~_a z_j|^2 / variance_factor [arcs]: the estimator of NormalEquations.redundancy,
+        restricted to the arc.  ValueError without vectors."""
+        if self.__traces is None:
+            raise ValueError('the redundancies of the arcs need the Monte-Carlo vectors: pass vectors=ne.monte_carlo_vectors')
+        return self.arc_observation_counts - self.__traces / variance_factor
+
+    def arc_variance_factors(self, variance_factor=1.0):
+        """Omega_a / r_a [arcs], the arc-wise form of compute_variance_factors; nan where r_a <= 0"""
+        redundancies = self.arc_redundancies(variance_factor)
+        usable = redundancies > 0
+        return np.where(usable, self.arc_square_sums / np.where(usable, redundancies, 1.0), np.nan)
+
+    def covariance_function(self, maximum_lag, per_component=False, biased=True):
+        """
+        Empirical covariance function of the unwhitened residuals, c_k = sum_a sum_t e^[t] e^[t + k] / d_k over the pairs inside an arc
+        (one call of shg_segment_lag_products), k = 0 .. maximum_lag <= 128.  biased=True: d_k = d_0 = sum_a len_a, positive
+        semi-definite by construction; biased=False: d_k = sum_a max(len_a - k, 0).  The components are pooled into one function
+        (K d_k in the divisor), or per_component=True gives one function each.  Returns what
+        AutoregressiveModelSequence.from_covariance_function takes, a list of [1, 1] arrays, or a list of K such lists.  ValueError
+        for a maximum_lag outside 0 .. 128 and, with biased=False, for a lag no arc is long enough for.
+        """
+        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_WHITENING_ORDER:
+            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_WHITENING_ORDER, maximum_lag))
+        q = int(maximum_lag)
+        lengths = np.diff(np.append(self.arcs, int(self.__rows.shape[1])))
+        pairs = np.array([np.maximum(lengths - k, 0).sum() for k in range(q + 1)], dtype=np.float64)
+        if biased:
+            pairs[:] = pairs[0]
+        elif not np.all(pairs > 0):
+            raise ValueError('no arc is longer than {0} points: no pair at lag {1}'.format(int(lengths.max()), int(np.argmin(pairs > 0))))
+        sums = engine.to_host(engine.segment_lag_products(self.__rows, self.__seg, q)).sum(axis=1)       # [K, q + 1]
+        if per_component:
+            return [[np.array([[value]]) for value in row / pairs] for row in sums]
+        return [np.array([[value]]) for value in sums.sum(axis=0) / (sums.shape[0] * pairs)]
 
 
 def accumulate_normals(normal_equations, variance_factors):

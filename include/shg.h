@@ -594,6 +594,30 @@ int shg_whiten_rows(long long rows, int channels, int M, const double* X, long l
 int shg_segment_products(long long rows, int channels, int M, const double* X, long long ldx, const double* Bt, long long ldb, int u, int nseg,
                          const int32_t* seg, double* S, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Lagged products of the rows of a matrix with themselves, cut at arc boundaries: the square sums per arc (lag 0) and the empirical
+ * autocovariance (lags 0 .. q) of post-fit residuals (no reference counterpart)
+ *   X [rows][ldx] with M columns in use.  seg (device) [nseg + 1]: column indices, segment s is seg[s] .. seg[s+1] - 1.  0 <= lags <= 128.
+ *   S[r][s][k] = sum over t with seg[s] <= t and t + k < seg[s+1] of X[r][t] X[r][t + k], k = 0 .. lags;  S [rows][nseg][lags + 1] is
+ *   dense and every entry is written, 0 where the segment has k columns or fewer.
+ *   Locality: S[r][s][k] depends only on X[r][seg[s] .. seg[s+1]) and on k, not on rows, nseg, M, lags, the other segments, the
+ *   position of the segment in the row or the launch geometry.  Columns outside every segment and the padding from M to ldx are not
+ *   read.
+ *   Summation order, relative to the start of the segment: chain i of 64 is acc = 0, acc = fma(x[t], x[t + k], acc) over
+ *   t = start + i, start + i + 64, ... ascending while t + k < end (an empty chain is 0); the chains are added by the butterfly
+ *   v_i += v_(i ^ m) for m = 32, 16, 8, 4, 2, 1, and entry 0 is the result.  No atomics; repeated calls are bitwise equal.
+ *   Clamping: entry i of seg is read as c_i = max over k <= i of min(max(seg[k], 0), M), so the table in effect lies in 0 .. M and
+ *   does not decrease; a wrong table gives wrong numbers, never a read outside a row.
+ *   lags = 0: one wave per segment of 4 consecutive rows (lane <-> column, coalesced), X is read from global memory once.  lags > 0:
+ *   one workgroup of 4 waves per segment of a row, in tiles of 1024 columns staged in LDS with the `lags` columns behind them; wave w
+ *   holds the lags w G .. w G + G - 1, G the smallest of 1, 2, 4, 8, 16, 33 with 4 G > lags.  A flat 64-bit index, so rows x ldx may
+ *   exceed 2^31.
+ *   Arguments are checked before the first HIP call (negative sizes, lags outside 0 .. 128, nseg < 0, ldx < M, more than 2^40 values
+ *   of X or S, NULL pointers); rows = 0 or nseg = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_segment_lag_products(long long rows, int M, const double* X, long long ldx, int lags, int nseg, const int32_t* seg, double* S,
+                             void* stream);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
