@@ -401,72 +401,193 @@ def _arc_reduction(G, b):
     return R, np.einsum('ijr,ij->ir', R, b), ranks
 
 
-class _ArcSetup:
-    """what the elimination of arc-wise parameters and the post-fit pass share of an ArcParameters: see _arc_setup"""
+class _Observations:
+    """The observations of one from_* or of_* call.  The constructors below, one per kind, run the checks of their kind on the host and
+    fill the degrees, P, M, K and the layout of the weights (engine.check_observation_weights).  to_device, after every other check of
+    the call, fills l [M, K], the observations times root, root = sqrt(w) [M, K] or [M, 1] (None without weights) and design_block(first,
+    last), the transposed design matrix [P, K, Mb] (or [P, Mb]) of the points first .. last, scaled alike; upload() is the kind's part of
+    it: from the weights on the device, or None, it returns (l [M, K], design_block)."""
+
+    def __init__(self, min_degree, max_degree, M, K, weights, layout, upload):
+        self.min_degree, self.max_degree, self.P = min_degree, max_degree, (max_degree + 1) ** 2 - min_degree ** 2
+        self.M, self.K, self.weights, self.layout = M, K, weights, layout
+        self.__upload = upload
+        self.l = self.root = self.design_block = None
+
+    def to_device(self):
+        torch = engine.require_gpu()
+        w = engine.to_device(self.weights) if self.layout else None
+        l, self.design_block = self.__upload(w)
+        self.root = torch.sqrt(w if self.layout == 2 else w[:, None]) if self.layout else None
+        self.l = l * self.root if self.layout else l
 
 
-def _device_whitening(whitening, device):
-    """the host tables (taps, stage) of a from_* call on the device, with the host's stage table (the halo of a block) behind them;
-    None without a noise model"""
-    if whitening is None:
-        return None
-    torch = engine.require_gpu()
-    return engine.to_device(whitening[0], device), torch.from_numpy(whitening[1]).to(device), whitening[1]
+def _acceleration_observations(xyz, g, min_degree, max_degree, GM, R, weights):
+    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
+    M = engine.check_positions(xyz)
+    if engine.check_positions(g, 'accelerations') != M:
+        raise ValueError('{0} positions but {1} accelerations'.format(M, int(g.shape[0])))
+    layout = engine.check_observation_weights(weights, M)
+
+    def upload(w):
+        x, l = engine.to_device(xyz), engine.to_device(g)
+        return l, lambda first, last: engine.acceleration_design_checked(
+            max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R)
+    return _Observations(min_degree, max_degree, M, 3, weights, layout, upload)
 
 
-def _design_blocks(P, l, block_points, design_block, tables):
+def _gradient_observations(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights):
+    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
+    M = engine.check_positions(xyz)
+    picked = engine.gradient_components(components)
+    K = len(picked)
+    shape = tuple(gradients.shape)
+    full = len(shape) == 3 and shape[1:] == (3, 3)
+    if not full and (len(shape) != 2 or shape[1] != K):
+        raise ValueError('gradients must have shape (M, {0}) or (M, 3, 3), got {1}'.format(K, shape))
+    if shape[0] != M:
+        raise ValueError('{0} positions but {1} gradients'.format(M, shape[0]))
+    layout = engine.check_observation_weights(weights, M, K)
+    if frames is not None:
+        engine.check_frames(frames, M)
+
+    def upload(w):
+        x, l = engine.to_device(xyz), engine.to_device(gradients)
+        f = engine.to_device(frames) if frames is not None else None
+        if full:
+            l = l.reshape(M, 9)[:, [(0, 1, 2, 4, 5, 8)[i] for i in picked]]                              # the selected upper-triangle entries
+        return l, lambda first, last: engine.gradient_design_checked(
+            max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last], GM, R)
+    return _Observations(min_degree, max_degree, M, K, weights, layout, upload)
+
+
+def _los_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights):
+    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
+    M = engine.check_pair_positions(xyz_a, xyz_b)
+    if len(differences.shape) != 1:
+        raise ValueError('differences must have shape (M,), got {0}'.format(tuple(differences.shape)))
+    if int(differences.shape[0]) != M:
+        raise ValueError('{0} pairs but {1} differences'.format(M, int(differences.shape[0])))
+    layout = engine.check_observation_weights(weights, M, 1)
+    if layout and len(weights.shape) != 1:
+        raise ValueError('weights must have shape ({0},), got {1}'.format(M, tuple(weights.shape)))
+    if directions is not None:
+        engine.check_directions(directions, M)
+    else:
+        engine.check_pairs_apart(xyz_a, xyz_b)
+
+    def upload(w):
+        a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
+        e = engine.to_device(directions) if directions is not None else None
+        return l, lambda first, last: engine.los_design_checked(
+            max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last], GM, R)
+    return _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
+
+
+class _StochasticModel:
+    """The stochastic model of one from_* or of_* call beyond the weights: noise_model and arcs as NormalEquations.from_accelerations
+    takes them, parameters an ArcParameters or None; of(model) reads them from None, a ColouredNoise or an ArcParameters.  check(M, K)
+    fills whitening = (taps, stage) of _whitening_tables on the host (None without a noise model) and starts, the start indices of the
+    arcs; to_device the device's taps and stage (None without one) and halo, the host's stage table: what a block takes along in front."""
+
+    def __init__(self, noise_model=None, arcs=None, parameters=None):
+        self.noise_model, self.arcs, self.parameters = noise_model, arcs, parameters
+        self.whitening = self.starts = self.taps = self.stage = self.halo = None
+
+    @classmethod
+    def of(cls, model):
+        if isinstance(model, _BoundModel):
+            return cls(model.noise_model, model.arcs, model if isinstance(model, ArcParameters) else None)
+        if model is None:
+            return cls()
+        raise ValueError('model must be None, a ColouredNoise or an ArcParameters (arcs belong to one of them), got {0!r}'.format(model))
+
+    def check(self, M, K):
+        """ValueError for what _whitening_tables refuses, arcs that belong to nothing and a basis that is neither [M, u'] nor [M, K, u]"""
+        if self.noise_model is not None:
+            self.whitening = _whitening_tables(self.noise_model, self.arcs, M, K)
+        elif self.arcs is not None and self.parameters is None:
+            raise ValueError('arcs are those of the noise model: pass noise_model as well')
+        self.starts = _arc_starts(self.arcs, M)
+        if self.parameters is not None:
+            shape = self.parameters.basis.shape
+            if shape[0] != M or (len(shape) == 3 and shape[1] != K):
+                raise ValueError('the arc basis must have shape ({0}, u) or ({0}, {1}, u), got {2}'.format(M, K, shape))
+
+    def to_device(self, device):
+        if self.whitening is not None:
+            torch = engine.require_gpu()
+            self.taps, self.stage, self.halo = engine.to_device(self.whitening[0], device), torch.from_numpy(self.whitening[1]).to(device), self.whitening[1]
+
+    def whiten(self, X, start=0, skip=0):
+        """W along the last axis of X [..., n], which holds the points start .. start + n; the first skip of them are history only"""
+        return engine.whiten_rows(X, taps=self.taps, stage=self.stage[start:start + int(X.shape[-1])], channels=int(self.taps.shape[0]), skip=skip)
+
+
+def _prepare(observations, model, block_points, fit=None):
+    """Every from_* and of_* call between the checks of its observations and its pass: block_points as a positive int (None: the default),
+    the model, the solution and the vectors of a PostFit, every ValueError before anything reaches the device; then the uploads."""
+    block_points = int(NormalEquations.default_block_points(observations.P, observations.K) if block_points is None else block_points)
+    if block_points < 1:
+        raise ValueError('block_points must be positive, got {0}'.format(block_points))
+    model.check(observations.M, observations.K)
+    if fit is not None:
+        fit._check(observations.P)
+    observations.to_device()
+    model.to_device(observations.l.device)
+    return block_points
+
+
+def _design_blocks(observations, model, block_points):
     """The blocks of the from_* classmethods and of PostFit, one after the other: (first, last, At [P, K Mb], lb [K Mb, 1], plain, skip)
-    of the points first .. last of the observations l [M, K].  Without tables (_device_whitening) At is design_block(first, last) and lb
-    the observations, component-major as the columns of At; plain is At and skip 0.  With them a block takes the skip = stage[first]
+    of the points first .. last of the observations l [M, K].  Without a noise model At is design_block(first, last) and lb the
+    observations, component-major as the columns of At; plain is At and skip 0.  With one a block takes the skip = stage[first]
     points in front of it along (none where it starts an arc), shg_whiten_rows turns the design matrix and the observations of
     first - skip .. last into those of W A and W l at first .. last in a second buffer, and plain [P, K (skip + Mb)] is the design matrix
     as design_block gave it."""
-    M, K = (int(size) for size in l.shape)
+    P, M, K, l = observations.P, observations.M, observations.K, observations.l
     for first in range(0, M, block_points):
         last = min(first + block_points, M)
-        if tables is None:
-            At = design_block(first, last).reshape(P, K * (last - first))
+        if model.taps is None:
+            At = observations.design_block(first, last).reshape(P, K * (last - first))
             yield first, last, At, l[first:last].t().reshape(-1, 1), At, 0      # component-major, as the columns of At
         else:
-            taps, stage, halo = tables
-            start = first - int(halo[first])
-            whiten = dict(taps=taps, stage=stage[start:last], channels=int(taps.shape[0]), skip=first - start)
-            plain = design_block(start, last).reshape(P * K, last - start)
-            At = engine.whiten_rows(plain, **whiten).reshape(P, K * (last - first))
-            lb = engine.whiten_rows(l[start:last].t().contiguous(), **whiten).reshape(-1, 1)
+            start = first - int(model.halo[first])
+            plain = observations.design_block(start, last).reshape(P * K, last - start)
+            At = model.whiten(plain, start, first - start).reshape(P, K * (last - first))
+            lb = model.whiten(l[start:last].t().contiguous(), start, first - start).reshape(-1, 1)
             yield first, last, At, lb, plain.reshape(P, K * (last - start)), first - start
 
 
-def _arc_setup(l, root, local, tables, plain=False):
-    """local = (ArcParameters, starts) of a from_* call, l [M, K] the observations times root = sqrt(w) [M, K] (or broadcastable to it,
-    None: 1) on the device, tables those of _device_whitening: the basis goes the way of the design matrix (times root, then W) into Bt
-    [u, K, M] (plain=True keeps the one before W as plain_Bt), once; shg_segment_products gives G_a = B_a^T B_a and b_a = B_a^T l_a of
-    all arcs (summed over the components for the general form, Kc = 1; Kc = K for a shared basis), the host R_a = V Lambda^-1/2 of the
-    kept eigenpairs of G_a, g = R^T b and the ranks (_arc_reduction).  seg holds the boundaries of the arcs on the device, bounds on
-    the host."""
-    torch = engine.require_gpu()
-    M, K = (int(size) for size in l.shape)
-    s = _ArcSetup()
-    whole = {} if tables is None else dict(taps=tables[0], stage=tables[1], channels=int(tables[0].shape[0]))
-    basis = engine.to_device(local[0].basis, l.device)
-    s.shared = shared = basis.dim() == 2
-    Bt = basis.t()[:, None, :].expand(-1, K, -1) if shared else basis.permute(2, 1, 0)
-    Bt = (Bt if root is None else Bt * root.expand(M, K).t()[None]).contiguous()                    # [u, K, M]
-    lt = l.t().contiguous()
-    s.plain_Bt = Bt if plain else None
-    if tables is not None:
-        Bt, lt = engine.whiten_rows(Bt, **whole), engine.whiten_rows(lt, **whole)
-    s.Bt, s.u, s.Kc = Bt, int(Bt.shape[0]), (K if shared else 1)
-    s.bounds = np.append(local[1], M)
-    s.arcs = len(s.bounds) - 1
-    s.seg = torch.from_numpy(s.bounds.astype(np.int32)).to(l.device)
-    G = engine.segment_products(Bt, Bt, s.seg, channels=K).permute(2, 1, 0, 3)                       # [arcs, K, u, u]
-    b = engine.segment_products(lt, Bt, s.seg, channels=K).permute(1, 0, 2)                          # [arcs, K, u]
-    if not shared:
-        G, b = G.sum(1, keepdim=True), b.sum(1, keepdim=True)
-    s.R, s.g, s.ranks = _arc_reduction(engine.to_host(G).reshape(s.arcs * s.Kc, s.u, s.u), engine.to_host(b).reshape(s.arcs * s.Kc, s.u))
-    s.R_d, s.g_d = engine.to_device(s.R, l.device), engine.to_device(s.g, l.device).reshape(-1, 1)   # [arcs Kc, u, u], [arcs Kc u, 1]
-    return s
+class _ArcSetup:
+    """What the elimination of arc-wise parameters and the post-fit pass share of an ArcParameters, from observations and a model on the
+    device.  The basis goes the way of the design matrix (times root, then W) into Bt [u, K, M] (plain=True keeps the one before W as
+    plain_Bt), once; shg_segment_products gives G_a = B_a^T B_a and b_a = B_a^T l_a of all arcs (summed over the components for the general
+    form, Kc = 1; Kc = K for a shared basis), the host R_a = V Lambda^-1/2 of the kept eigenpairs of G_a, g = R^T b and the ranks
+    (_arc_reduction; R_d and g_d on the device).  seg holds the boundaries of the arcs on the device, bounds on the host."""
+
+    def __init__(self, observations, model, plain=False):
+        torch = engine.require_gpu()
+        l, root, M, K = observations.l, observations.root, observations.M, observations.K
+        basis = engine.to_device(model.parameters.basis, l.device)
+        self.shared = basis.dim() == 2
+        Bt = basis.t()[:, None, :].expand(-1, K, -1) if self.shared else basis.permute(2, 1, 0)
+        Bt = (Bt if root is None else Bt * root.expand(M, K).t()[None]).contiguous()                    # [u, K, M]
+        lt = l.t().contiguous()
+        self.plain_Bt = Bt if plain else None
+        if model.taps is not None:
+            Bt, lt = model.whiten(Bt), model.whiten(lt)
+        self.Bt, self.u, self.Kc = Bt, int(Bt.shape[0]), (K if self.shared else 1)
+        self.bounds = np.append(model.starts, M)
+        self.arcs = len(self.bounds) - 1
+        self.seg = torch.from_numpy(self.bounds.astype(np.int32)).to(l.device)
+        G = engine.segment_products(Bt, Bt, self.seg, channels=K).permute(2, 1, 0, 3)                    # [arcs, K, u, u]
+        b = engine.segment_products(lt, Bt, self.seg, channels=K).permute(1, 0, 2)                       # [arcs, K, u]
+        if not self.shared:
+            G, b = G.sum(1, keepdim=True), b.sum(1, keepdim=True)
+        units = self.arcs * self.Kc
+        self.R, self.g, self.ranks = _arc_reduction(engine.to_host(G).reshape(units, self.u, self.u), engine.to_host(b).reshape(units, self.u))
+        self.R_d, self.g_d = engine.to_device(self.R, l.device), engine.to_device(self.g, l.device).reshape(-1, 1)
 
 
 class ArcElimination:
@@ -492,6 +613,59 @@ class ArcElimination:
         y = self.__g - np.concatenate(products).reshape(self.__g.shape)
         y = np.einsum('akjr,akr->akj', self.__R, y)
         return y if self.__shared else y[:, 0]
+
+
+class _ArcSweep:
+    """The elimination of the arc-wise parameters over the blocks of one from_* call, on its normals and
+    right-hand side.  block(first, last, At): shg_segment_products on the whitened At, with the arc boundaries clipped to the block, gives
+    the part of C_a = A_a^T B_a that lies in it; an arc that continues past the block keeps its sum in the carry [P, Kc, u], an arc that
+    ends gives D_a = C_a R_a, and N -= D D^T, n -= D (R^T b) run as one product each once `update_columns` columns of D are waiting (the
+    update reads and writes all of N); flush() applies the rest after the last block, before the mirroring.  keep retains every D."""
+
+    def __init__(self, observations, model, normals, side, update_columns):
+        self.setup, self.normals, self.side, self.update_columns = _ArcSetup(observations, model), normals, side, update_columns
+        self.carry = _zeros((observations.P, self.setup.Kc, self.setup.u))
+        self.columns = [] if model.parameters.keep else None
+        self.pending, self.applied, self.finished = [], 0, 0                                              # D of finished arcs not yet subtracted
+
+    def block(self, first, last, At):
+        torch = engine.require_gpu()
+        s, P = self.setup, int(At.shape[0])
+        K, Kc, u = int(s.Bt.shape[1]), s.Kc, s.u
+        a0, a1 = int(np.searchsorted(s.bounds, first, side='right')) - 1, int(np.searchsorted(s.bounds, last, side='left')) - 1
+        cut = (s.seg[a0:a1 + 2] - first).clamp_(0, last - first)                                         # arcs a0 .. a1 meet the block
+        S = engine.segment_products(At.reshape(P * K, last - first), s.Bt[:, :, first:last], cut, channels=K).reshape(P, K, a1 - a0 + 1, u)
+        C = S.permute(0, 2, 1, 3) if s.shared else S.sum(1, keepdim=True).permute(0, 2, 1, 3)            # [P, arcs of the block, Kc, u]
+        C[:, 0] += self.carry
+        ended = a1 - a0 + (1 if s.bounds[a1 + 1] <= last else 0)
+        if ended <= a1 - a0:
+            self.carry = C[:, ended].clone()
+        else:
+            self.carry.zero_()
+        if ended:
+            D = torch.empty((ended * Kc, P, u), dtype=torch.float64, device=At.device)
+            engine.gemm_ex(C[:, :ended].permute(1, 2, 0, 3).reshape(ended * Kc, P, u), s.R_d[a0 * Kc:(a0 + ended) * Kc], D)
+            D = D.permute(1, 0, 2).reshape(P, ended * Kc * u)
+            self.pending.append(D)
+            if self.columns is not None:
+                self.columns.append(D)
+        self.finished = a0 + ended
+        if sum(int(D.shape[1]) for D in self.pending) >= self.update_columns:
+            self.flush()
+
+    def flush(self):
+        if self.pending:
+            torch = engine.require_gpu()
+            width = self.setup.Kc * self.setup.u
+            D = self.pending[0] if len(self.pending) == 1 else torch.cat(self.pending, dim=1)            # the arcs applied .. finished
+            engine.gemm(D, D, transb=True, alpha=-1.0, beta=1.0, out=self.normals)
+            engine.gemm(D, self.setup.g_d[self.applied * width:self.finished * width], alpha=-1.0, beta=1.0, out=self.side)
+            self.pending, self.applied = [], self.finished
+
+    def result(self):
+        s = self.setup
+        shape = (s.arcs, s.Kc) if s.shared else (s.arcs,)
+        return ArcElimination(s.ranks.reshape(shape), s.R.reshape(s.arcs, s.Kc, s.u, s.u), s.g.reshape(s.arcs, s.Kc, s.u), s.shared, self.columns)
 
 
 class BlockMatrix:
@@ -837,105 +1011,33 @@ class NormalEquations:
         return max(cls.DESIGN_BLOCK_BYTES // (8 * components * parameters) // 256 * 256, 256)
 
     @classmethod
-    def __check_block_points(cls, block_points, min_degree, max_degree, components):
-        """block_points of a from_* call as a positive int (None: the default); ValueError otherwise, before anything reaches the
-        device."""
-        if block_points is None:
-            block_points = cls.default_block_points((max_degree + 1) ** 2 - min_degree ** 2, components)
-        block_points = int(block_points)
-        if block_points < 1:
-            raise ValueError('block_points must be positive, got {0}'.format(block_points))
-        return block_points
-
-    @staticmethod
-    def __check_noise_model(noise_model, arcs, points, components):
-        """noise_model= / arcs= of a from_* call: None without a model, else the host tables (taps, stage) of _whitening_tables;
-        ValueError otherwise, before anything reaches the device."""
-        if noise_model is None:
-            if arcs is not None:
-                raise ValueError('arcs are those of the noise model: pass noise_model as well')
-            return None
-        return _whitening_tables(noise_model, arcs, points, components)
-
-    @staticmethod
-    def __check_local(local, arcs, points, components):
-        """local= of a from_* call: None, or (ArcParameters, start indices of the arcs); ValueError for arcs that arc_stages refuses
-        and for a basis that is neither [points, u'] nor [points, components, u], before anything reaches the device."""
-        if local is None:
-            return None
-        starts = _arc_starts(arcs, points)
-        shape = local.basis.shape
-        if shape[0] != points or (len(shape) == 3 and shape[1] != components):
-            raise ValueError('the arc basis must have shape ({0}, u) or ({0}, {1}, u), got {2}'.format(points, components, shape))
-        return local, starts
-
-    @classmethod
-    def __from_design_blocks(cls, min_degree, max_degree, l, block_points, design_block, whitening=None, local=None, root=None):
-        """The block loop of the from_* classmethods: l [M, K] are the observations times sqrt(w) on the device, design_block(first,
-        last) the transposed design matrix [P, K, Mb] (or [P, Mb]) of the points first .. last, scaled alike.  Per block N += At At^T,
-        n += At l and l^T P l += |l|^2 on the fp64 MFMA product; both triangles of N are computed and the upper one is mirrored.
-
-        whitening = (taps, stage) of __check_noise_model: the tables go to the device once; a block [first, last) takes the
-        h = stage[first] points in front of it along (none where it starts an arc), and shg_whiten_rows turns the design matrix and
-        the observations of first - h .. last into those of W A and W l at first .. last (skip = h) in a second buffer, on which
-        the three products run unchanged.
-
-        local = (ArcParameters, starts) of __check_local, root = sqrt(w) [M, K] (or broadcastable to it, None: 1) that l carries:
-        the parameters of the arcs are eliminated.  The basis goes the way of the design matrix (times
-        root, then W) into Bt [u, K, M], once; shg_segment_products gives G_a = B_a^T B_a and b_a = B_a^T l_a of all arcs, the host
-        R_a = V Lambda^-1/2 of the kept eigenpairs of G_a.  Per block the same call on the whitened At, with the arc boundaries
-        clipped to the block, gives the part of C_a = A_a^T B_a that lies in it; an arc that continues past the block keeps its sum
-        in the carry [P, K, u], an arc that ends gives D_a = C_a R_a, and N -= D D^T, n -= D (R^T b) run as one product each per block,
-        once ARC_UPDATE_COLUMNS columns of D are waiting (the update reads and writes all of N) and after the last block, before the
-        mirroring.  l^T P l -= |R^T b|^2 and observation_count -= sum of the ranks."""
+    def _normals(cls, observations, model, block_points):
+        """Every from_* behind the checks of its observations (an _Observations) under a _StochasticModel.  Per block of _design_blocks
+        N += At At^T, n += At l and l^T P l += |l|^2 on the fp64 MFMA product; both triangles of N are computed and the upper one is
+        mirrored.  Under ArcParameters the parameters of the arcs are eliminated block by block (_ArcSetup, _ArcSweep), with
+        l^T P l -= |R^T b|^2 and observation_count -= sum of the ranks."""
+        block_points = _prepare(observations, model, block_points)
         torch = engine.require_gpu()
-        M, K = (int(size) for size in l.shape)
-        P = (max_degree + 1) ** 2 - min_degree ** 2
+        P = observations.P
         normals, side, square_sum = _zeros((P, P)), _zeros((P, 1)), _zeros((1, 1))
-        tables = _device_whitening(whitening, l.device)
-        if local is not None:
-            setup = _arc_setup(l, root, local, tables)
-            Bt, seg, bounds, arcs, shared, u, Kc = setup.Bt, setup.seg, setup.bounds, setup.arcs, setup.shared, setup.u, setup.Kc
-            R, g, ranks, R_d, g_d = setup.R, setup.g, setup.ranks, setup.R_d, setup.g_d
-            carry, columns = _zeros((P, Kc, u)), ([] if local[0].keep else None)
-            pending, applied = [], 0                                                                        # D of finished arcs not yet subtracted
-        for first, last, At, lb, _, _ in _design_blocks(P, l, block_points, design_block, tables):
+        sweep = _ArcSweep(observations, model, normals, side, cls.ARC_UPDATE_COLUMNS) if model.parameters is not None else None
+        for first, last, At, lb, _, _ in _design_blocks(observations, model, block_points):
             engine.gemm(At, At, transb=True, beta=1.0, out=normals)
             engine.gemm(At, lb, beta=1.0, out=side)
             engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
-            if local is not None:
-                a0, a1 = int(np.searchsorted(bounds, first, side='right')) - 1, int(np.searchsorted(bounds, last, side='left')) - 1
-                cut = (seg[a0:a1 + 2] - first).clamp_(0, last - first)                                       # arcs a0 .. a1 meet the block
-                S = engine.segment_products(At.reshape(P * K, last - first), Bt[:, :, first:last], cut, channels=K).reshape(P, K, a1 - a0 + 1, u)
-                C = S.permute(0, 2, 1, 3) if shared else S.sum(1, keepdim=True).permute(0, 2, 1, 3)          # [P, arcs of the block, Kc, u]
-                C[:, 0] += carry
-                ended = a1 - a0 + (1 if bounds[a1 + 1] <= last else 0)
-                if ended <= a1 - a0:
-                    carry = C[:, ended].clone()
-                else:
-                    carry.zero_()
-                if ended:
-                    D = torch.empty((ended * Kc, P, u), dtype=torch.float64, device=l.device)
-                    engine.gemm_ex(C[:, :ended].permute(1, 2, 0, 3).reshape(ended * Kc, P, u), R_d[a0 * Kc:(a0 + ended) * Kc], D)
-                    D = D.permute(1, 0, 2).reshape(P, ended * Kc * u)
-                    pending.append(D)
-                    if columns is not None:
-                        columns.append(D)
-                if pending and (last == M or sum(int(D.shape[1]) for D in pending) >= cls.ARC_UPDATE_COLUMNS):
-                    D = pending[0] if len(pending) == 1 else torch.cat(pending, dim=1)                       # the arcs applied .. a0 + ended
-                    engine.gemm(D, D, transb=True, alpha=-1.0, beta=1.0, out=normals)
-                    engine.gemm(D, g_d[applied * Kc * u:(a0 + ended) * Kc * u], alpha=-1.0, beta=1.0, out=side)
-                    pending, applied = [], a0 + ended
+            if sweep is not None:
+                sweep.block(first, last, At)
+        if sweep is not None:
+            sweep.flush()
         normals.triu_()
         normals.add_(torch.triu(normals, 1).t())
         matrix = BlockMatrix([0, P], [0, P])
         matrix._set_device(0, 0, normals)
-        if local is None:
-            return cls(matrix, side, float(square_sum.item()), K * M)
-        shape = (arcs, Kc) if shared else (arcs,)
-        elimination = ArcElimination(ranks.reshape(shape), R.reshape(arcs, Kc, u, u), g.reshape(arcs, Kc, u), shared, columns)
-        system = cls(matrix, side, float(square_sum.item()) - float(np.sum(g * g)), K * M - elimination.count)
-        system.arc_elimination = elimination
+        system = cls(matrix, side, float(square_sum.item()), observations.K * observations.M)
+        if sweep is not None:
+            system.arc_elimination = sweep.result()
+            system.observation_square_sum -= float(np.sum(sweep.setup.g * sweep.setup.g))
+            system.observation_count -= system.arc_elimination.count
         return system
 
     @classmethod
@@ -966,31 +1068,8 @@ class NormalEquations:
         Returns NormalEquations with a one-block BlockMatrix [P, P] and the right-hand side [P, 1] on the device, and
         observation_count = 3 M: components of zero weight still count as observations.
         """
-        return cls._accelerations(noise_model, arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points)
-
-    @classmethod
-    def _accelerations(cls, noise_model, arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points, local=None, post=None):
-        """from_accelerations, with the arc-wise parameters of an ArcParameters (local; its arcs are `arcs`) eliminated"""
-        min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
-        M = engine.check_positions(xyz)
-        if engine.check_positions(g, 'accelerations') != M:
-            raise ValueError('{0} positions but {1} accelerations'.format(M, int(g.shape[0])))
-        layout = engine.check_observation_weights(weights, M)
-        block_points = cls.__check_block_points(block_points, min_degree, max_degree, 3)
-        whitening = cls.__check_noise_model(noise_model, arcs if local is None or noise_model is not None else None, M, 3)
-        local = cls.__check_local(local, arcs, M, 3)
-        if post is not None:
-            post._check((max_degree + 1) ** 2 - min_degree ** 2)
-
-        torch = engine.require_gpu()
-        x, l = engine.to_device(xyz), engine.to_device(g)
-        w = engine.to_device(weights) if layout else None
-        root = torch.sqrt(w if layout == 2 else w[:, None]) if layout else None
-        if layout:
-            l = l * root
-        driver = cls.__from_design_blocks if post is None else post._run                 # the normals, or the post-fit pass over the same blocks
-        return driver(min_degree, max_degree, l, block_points, lambda first, last: engine.acceleration_design_checked(
-            max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R), whitening, local, root)
+        observations = _acceleration_observations(xyz=xyz, g=g, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
+        return cls._normals(observations, _StochasticModel(noise_model, arcs), block_points)
 
     @classmethod
     def from_gradients(cls, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
@@ -1012,44 +1091,9 @@ class NormalEquations:
         noise), every arc decorrelated on its own as in from_accelerations.  A data gap is a new arc, not a zero weight; block_points
         keeps its default, the peak memory of a block doubles and observation_count is unchanged.
         """
-        return cls._gradients(None, None, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points)
-
-    @classmethod
-    def _gradients(cls, noise_model, arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, block_points, local=None,
-                   post=None):
-        """from_gradients under a noise model (None: white noise), with the arc-wise parameters of an ArcParameters (local) eliminated"""
-        min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
-        M = engine.check_positions(xyz)
-        picked = engine.gradient_components(components)
-        K = len(picked)
-        shape = tuple(gradients.shape)
-        full = len(shape) == 3 and shape[1:] == (3, 3)
-        if not full and (len(shape) != 2 or shape[1] != K):
-            raise ValueError('gradients must have shape (M, {0}) or (M, 3, 3), got {1}'.format(K, shape))
-        if shape[0] != M:
-            raise ValueError('{0} positions but {1} gradients'.format(M, shape[0]))
-        layout = engine.check_observation_weights(weights, M, K)
-        if frames is not None:
-            engine.check_frames(frames, M)
-        block_points = cls.__check_block_points(block_points, min_degree, max_degree, K)
-        whitening = cls.__check_noise_model(noise_model, arcs if local is None or noise_model is not None else None, M, K)
-        local = cls.__check_local(local, arcs, M, K)
-        if post is not None:
-            post._check((max_degree + 1) ** 2 - min_degree ** 2)
-
-        torch = engine.require_gpu()
-        x, l = engine.to_device(xyz), engine.to_device(gradients)
-        f = engine.to_device(frames) if frames is not None else None
-        if full:
-            l = torch.stack([l[:, j // 3, j % 3] for j in ((0, 1, 2, 4, 5, 8)[i] for i in picked)], dim=1)
-        w = engine.to_device(weights) if layout else None
-        root = torch.sqrt(w if layout == 2 else w[:, None]) if layout else None
-        if layout:
-            l = l * root
-        driver = cls.__from_design_blocks if post is None else post._run                 # the normals, or the post-fit pass over the same blocks
-        return driver(min_degree, max_degree, l, block_points, lambda first, last: engine.gradient_design_checked(
-            max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last], GM, R),
-            whitening, local, root)
+        observations = _gradient_observations(xyz=xyz, gradients=gradients, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, frames=frames,
+                                              components=components, weights=weights)
+        return cls._normals(observations, _StochasticModel(), block_points)
 
     @classmethod
     def from_line_of_sight(cls, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
@@ -1071,42 +1115,9 @@ class NormalEquations:
         from_accelerations.  A data gap is a new arc, not a zero weight; block_points keeps its default, the peak memory of a block
         doubles and observation_count is unchanged.
         """
-        return cls._line_of_sight(None, None, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, block_points)
-
-    @classmethod
-    def _line_of_sight(cls, noise_model, arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, block_points,
-                       local=None, post=None):
-        """from_line_of_sight under a noise model (None: white noise), with the arc-wise parameters of an ArcParameters (local) eliminated"""
-        min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
-        M = engine.check_pair_positions(xyz_a, xyz_b)
-        if len(differences.shape) != 1:
-            raise ValueError('differences must have shape (M,), got {0}'.format(tuple(differences.shape)))
-        if int(differences.shape[0]) != M:
-            raise ValueError('{0} pairs but {1} differences'.format(M, int(differences.shape[0])))
-        layout = engine.check_observation_weights(weights, M, 1)
-        if layout and len(weights.shape) != 1:
-            raise ValueError('weights must have shape ({0},), got {1}'.format(M, tuple(weights.shape)))
-        if directions is not None:
-            engine.check_directions(directions, M)
-        else:
-            engine.check_pairs_apart(xyz_a, xyz_b)
-        block_points = cls.__check_block_points(block_points, min_degree, max_degree, 1)
-        whitening = cls.__check_noise_model(noise_model, arcs if local is None or noise_model is not None else None, M, 1)
-        local = cls.__check_local(local, arcs, M, 1)
-        if post is not None:
-            post._check((max_degree + 1) ** 2 - min_degree ** 2)
-
-        torch = engine.require_gpu()
-        a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
-        e = engine.to_device(directions) if directions is not None else None
-        w = engine.to_device(weights) if layout else None
-        root = torch.sqrt(w)[:, None] if layout else None
-        if layout:
-            l = l * root
-        driver = cls.__from_design_blocks if post is None else post._run                 # the normals, or the post-fit pass over the same blocks
-        return driver(min_degree, max_degree, l, block_points, lambda first, last: engine.los_design_checked(
-            max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last], GM, R),
-            whitening, local, root)
+        observations = _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
+                                         directions=directions, weights=weights)
+        return cls._normals(observations, _StochasticModel(), block_points)
 
     def __cholesky(self):
         """factor the matrix once; a matrix that already holds covariances cannot be factored again (ValueError, as upstream)"""
@@ -1192,7 +1203,27 @@ class TikhonovRegularization(NormalEquations):
         super().__init__(diagonal, bias, weighted_square_sum, bias.size)
 
 
-class ColouredNoise:
+class _BoundModel:
+    """the from_* of ColouredNoise and ArcParameters: the arguments of the classmethods of NormalEquations, the normals under this model"""
+
+    def from_accelerations(self, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
+        observations = _acceleration_observations(xyz=xyz, g=g, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
+        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+
+    def from_gradients(self, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
+                       weights=None, block_points=None):
+        observations = _gradient_observations(xyz=xyz, gradients=gradients, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, frames=frames,
+                                              components=components, weights=weights)
+        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+
+    def from_line_of_sight(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
+                           weights=None, block_points=None):
+        observations = _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
+                                         directions=directions, weights=weights)
+        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+
+
+class ColouredNoise(_BoundModel):
     """
     A noise model of the observations along the series of points, bound to the constructors of NormalEquations: noise_model is one
     scalar AutoregressiveModelSequence (shared by the components) or a sequence of them, one per component, arcs the start indices of
@@ -1206,21 +1237,8 @@ class ColouredNoise:
         whitening_taps(noise_model)
         self.noise_model, self.arcs = noise_model, arcs
 
-    def from_accelerations(self, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
-        return NormalEquations.from_accelerations(xyz, g, min_degree, max_degree, GM, R, weights, block_points, self.noise_model, self.arcs)
 
-    def from_gradients(self, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
-                       weights=None, block_points=None):
-        return NormalEquations._gradients(self.noise_model, self.arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights,
-                                          block_points)
-
-    def from_line_of_sight(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
-                           weights=None, block_points=None):
-        return NormalEquations._line_of_sight(self.noise_model, self.arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions,
-                                              weights, block_points)
-
-
-class ArcParameters:
+class ArcParameters(_BoundModel):
     """
     Parameters that last one arc (an accelerometer's bias and drift per axis, a gradiometer's bias per component, the link's empirical
     once-per-revolution terms), estimated per arc and eliminated from the normal equations before the arcs are summed; bound to the
@@ -1251,19 +1269,6 @@ class ArcParameters:
         if noise_model is not None:
             whitening_taps(noise_model)
         self.basis, self.arcs, self.noise_model, self.keep = basis, arcs, noise_model, bool(keep)
-
-    def from_accelerations(self, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
-        return NormalEquations._accelerations(self.noise_model, self.arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points, self)
-
-    def from_gradients(self, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
-                       weights=None, block_points=None):
-        return NormalEquations._gradients(self.noise_model, self.arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights,
-                                          block_points, self)
-
-    def from_line_of_sight(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
-                           weights=None, block_points=None):
-        return NormalEquations._line_of_sight(self.noise_model, self.arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions,
-                                              weights, block_points, self)
 
 
 class PostFit:
@@ -1298,35 +1303,30 @@ class PostFit:
     """
 
     def __init__(self, solution, vectors, model, template):
-        if model is None:
-            self.__noise, self.__arcs, self.__local = None, None, None
-        elif isinstance(model, ColouredNoise):
-            self.__noise, self.__arcs, self.__local = model.noise_model, model.arcs, None
-        elif isinstance(model, ArcParameters):
-            self.__noise, self.__arcs, self.__local = model.noise_model, model.arcs, model
-        else:
-            raise ValueError('model must be None, a ColouredNoise or an ArcParameters (arcs belong to one of them), got {0!r}'.format(model))
-        self.__solution, self.__vectors, self.__template = solution, vectors, template
+        self.__model, self.__solution, self.__vectors, self.__template = _StochasticModel.of(model), solution, vectors, template
 
     @classmethod
     def of_accelerations(cls, solution, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
                          model=None, vectors=None):
-        post = cls(solution, vectors, model, xyz)
-        return NormalEquations._accelerations(post.__noise, post.__arcs, xyz, g, min_degree, max_degree, GM, R, weights, block_points, post.__local, post)
+        fit = cls(solution, vectors, model, xyz)
+        observations = _acceleration_observations(xyz=xyz, g=g, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
+        return fit._pass(observations, fit.__model, block_points)
 
     @classmethod
     def of_gradients(cls, solution, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
                      weights=None, block_points=None, model=None, vectors=None):
-        post = cls(solution, vectors, model, xyz)
-        return NormalEquations._gradients(post.__noise, post.__arcs, xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights,
-                                          block_points, post.__local, post)
+        fit = cls(solution, vectors, model, xyz)
+        observations = _gradient_observations(xyz=xyz, gradients=gradients, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, frames=frames,
+                                              components=components, weights=weights)
+        return fit._pass(observations, fit.__model, block_points)
 
     @classmethod
     def of_line_of_sight(cls, solution, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
                          weights=None, block_points=None, model=None, vectors=None):
-        post = cls(solution, vectors, model, xyz_a)
-        return NormalEquations._line_of_sight(post.__noise, post.__arcs, xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights,
-                                              block_points, post.__local, post)
+        fit = cls(solution, vectors, model, xyz_a)
+        observations = _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
+                                         directions=directions, weights=weights)
+        return fit._pass(observations, fit.__model, block_points)
 
     def _check(self, parameters):
         """the solution and the vectors against the number of parameters: ValueError before anything reaches the device"""
@@ -1338,24 +1338,23 @@ class PostFit:
             if len(shape) != 2 or shape[0] != parameters or shape[1] < 1:
                 raise ValueError('vectors must have shape ({0}, S), got {1}'.format(parameters, shape))
 
-    def _run(self, min_degree, max_degree, l, block_points, design_block, whitening, local, root):
-        """the pass, in place of NormalEquations.__from_design_blocks and with its arguments"""
+    def _pass(self, observations, model, block_points):
+        """the pass over the blocks of NormalEquations._normals, with its arguments; returns self"""
+        block_points = _prepare(observations, model, block_points, self)
         torch = engine.require_gpu()
-        M, K = (int(size) for size in l.shape)
-        P = (max_degree + 1) ** 2 - min_degree ** 2
+        l, M, K, P = observations.l, observations.M, observations.K, observations.P
         x = engine.to_device(self.__solution, l.device).reshape(P, 1)
         X = x if self.__vectors is None else torch.cat((x, engine.to_device(self.__vectors, l.device)), dim=1)
         rows = int(X.shape[1])
         Xt = torch.empty((rows, P), dtype=torch.float64, device=l.device).copy_(X.t())                   # [1 + S, P], row stride P also for one row
-        tables = _device_whitening(whitening, l.device)
-        bounds = np.append(_arc_starts(self.__arcs, M), M)
+        bounds = np.append(model.starts, M)
         arcs = len(bounds) - 1
         V = torch.empty((rows, K, M), dtype=torch.float64, device=l.device)                             # the whitened model values of x and the z_j
         lt, plain = torch.empty((K, M), dtype=torch.float64, device=l.device), torch.empty((K, M), dtype=torch.float64, device=l.device)
-        for first, last, At, lb, At_plain, skip in _design_blocks(P, l, block_points, design_block, tables):
+        for first, last, At, lb, At_plain, skip in _design_blocks(observations, model, block_points):
             V[:, :, first:last] = engine.gemm(Xt, At).reshape(rows, K, last - first)
             lt[:, first:last] = lb.reshape(K, last - first)
-            if tables is None:
+            if model.taps is None:
                 plain[:, first:last] = V[0, :, first:last]                                               # white noise: the same values
             else:
                 plain[:, first:last] = engine.gemm(Xt[0:1], At_plain).reshape(K, skip + last - first)[:, skip:]
@@ -1363,8 +1362,8 @@ class PostFit:
         plain = l.t().contiguous() - plain                                                               # sqrt(w) (l - A x), dense [K, M]
         seg = torch.from_numpy(bounds.astype(np.int32)).to(l.device)
         self.arc_parameters, self.ranks = None, np.zeros((arcs, K), dtype=np.int64)
-        if local is not None:
-            setup = _arc_setup(l, root, local, tables, plain=True)
+        if model.parameters is not None:
+            setup = _ArcSetup(observations, model, plain=True)
             u, Kc, units = setup.u, setup.Kc, arcs * setup.Kc
             C = engine.segment_products(V.reshape(rows * K, M), setup.Bt, seg, channels=K).reshape(rows, K, arcs, u)        # B~_a^T v
             C = (C.permute(2, 1, 0, 3) if setup.shared else C.sum(1, keepdim=True).permute(2, 1, 0, 3)).reshape(units, rows, u).contiguous()
@@ -1389,7 +1388,7 @@ class PostFit:
         self.rows = V
         self.whitened = _like_input(V[0].t().contiguous(), self.__template)
         self.residuals = _like_input(plain.t().contiguous(), self.__template)
-        self.__solution = self.__vectors = None
+        self.__solution = self.__vectors = self.__model = None
         return self
 
     def arc_redundancies(self, variance_factor=1.0):

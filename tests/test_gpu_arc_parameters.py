@@ -219,8 +219,9 @@ def test_reduced_normals_of_accelerations(block_points, noise):
     assert elimination.ranks.shape == (3, 3) and np.array_equal(elimination.ranks, np.full((3, 3), 4))
     assert _same(_build_accelerations(block_points, noise), ne)                                    # two runs are bitwise equal
     assert _same(_build_accelerations(block_points, noise, keep=False), ne)
-    internal = ga.lstsq.NormalEquations._accelerations(model if noise else None, ARCS, xyz, obs, 0, NA, di.GM, di.R, w, block_points,
-                                                       ga.lstsq.ArcParameters(basis))
+    internal = ga.lstsq.NormalEquations._normals(
+        ga.lstsq._acceleration_observations(xyz=xyz, g=obs, min_degree=0, max_degree=NA, GM=di.GM, R=di.R, weights=w),
+        ga.lstsq._StochasticModel(model if noise else None, ARCS, ga.lstsq.ArcParameters(basis)), block_points)
     assert _same(internal, ne)                                                                     # the bound form is the internal path
     plain = ga.lstsq.NormalEquations.from_accelerations(xyz, obs, 0, NA, di.GM, di.R, weights=w, block_points=block_points,
                                                         noise_model=model if noise else None, arcs=ARCS if noise else None)

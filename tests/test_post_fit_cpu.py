@@ -149,6 +149,34 @@ def test_signatures():
     assert list(inspect.signature(ga.engine.segment_lag_products).parameters) == ['X', 'seg', 'lags', 'out']
 
 
+def test_signatures_of_all_twelve_entry_points():
+    """the parameter lists of from_* (NormalEquations, ColouredNoise, ArcParameters) and of_* (PostFit) and of the three constructors,
+    written out: names, order and defaults"""
+    empty, GM, R = inspect.Parameter.empty, 3.9860044150e+14, 6.3781363000e+06
+    tail = [('weights', None), ('block_points', None)]
+    kinds = {'accelerations': [('xyz', empty), ('g', empty), ('min_degree', empty), ('max_degree', empty), ('GM', GM), ('R', R)] + tail,
+             'gradients': [('xyz', empty), ('gradients', empty), ('min_degree', empty), ('max_degree', empty), ('GM', GM), ('R', R), ('frames', None),
+                           ('components', None)] + tail,
+             'line_of_sight': [('xyz_a', empty), ('xyz_b', empty), ('differences', empty), ('min_degree', empty), ('max_degree', empty), ('GM', GM), ('R', R),
+                               ('directions', None)] + tail}
+
+    def listed(function):
+        return [(prm.name, prm.default) for prm in inspect.signature(function).parameters.values()]
+    lstsq = ga.lstsq
+    checked = 0
+    for kind, plain in kinds.items():
+        extra = [('noise_model', None), ('arcs', None)] if kind == 'accelerations' else []
+        assert listed(getattr(lstsq.NormalEquations, 'from_' + kind)) == plain + extra
+        assert listed(getattr(lstsq.ColouredNoise, 'from_' + kind)) == [('self', empty)] + plain
+        assert listed(getattr(lstsq.ArcParameters, 'from_' + kind)) == [('self', empty)] + plain
+        assert listed(getattr(lstsq.PostFit, 'of_' + kind)) == [('solution', empty)] + plain + [('model', None), ('vectors', None)]
+        checked += 4
+    assert checked == 12
+    assert listed(lstsq.PostFit.__init__) == [('self', empty), ('solution', empty), ('vectors', empty), ('model', empty), ('template', empty)]
+    assert listed(lstsq.ColouredNoise.__init__) == [('self', empty), ('noise_model', empty), ('arcs', None)]
+    assert listed(lstsq.ArcParameters.__init__) == [('self', empty), ('basis', empty), ('arcs', None), ('noise_model', None), ('keep', True)]
+
+
 # ---- the host references against each other ------------------------------------------------------------------------------------------------
 def test_exact_lag_products_against_a_plain_loop():
     rng = np.random.default_rng(2901)
