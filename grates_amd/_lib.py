@@ -57,6 +57,7 @@ PROTOTYPES = {
     'shg_covprop_points': [ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
     'shg_degree_scale': [c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
     'shg_orderwise_filter': [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
+    'shg_orderwise_filter_info': [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
     'shg_order_major_pack': [c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p],
     'shg_order_major_unpack': [c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_void_p],
     'shg_orderwise_filter_om': [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_void_p],
@@ -149,6 +150,13 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise ImportError('libshg.so not found at {0}: build it with `make -C grates_amd/csrc` or '
                           '`python -c "import __graft_entry__ as g; g.build()"`. There is no CPU fallback.'.format(LIB_PATH))
+    # libshg works on torch's tensors and streams, so it must bind to the HIP runtime torch brings along: torch first.  A host-only query
+    # (engine.orderwise_filter_info, gemm_route, ...) made before the first tensor would otherwise load libshg against the system's
+    # runtime, and every later launch fails with "no ROCm-capable device is detected".
+    try:
+        import torch  # noqa: F401
+    except ImportError:
+        pass
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in PROTOTYPES.items():
         fn = getattr(lib, name)            # AttributeError if the symbol is not exported

@@ -231,6 +231,17 @@ static int orderwise_plane(int N, int G) {
     return rows + ((1 + 16 / G - rows) % 16 + 16) % 16;
 }
 
+// Orders per workgroup of the block kernel for degree N: as many as the LDS stage allows (8: degree <= 143, 4: <= 295, 2: <= 599), 0
+// where not even two fit; every wave holds the results of its (order, row tile) units in registers.  `lds`: dynamic LDS bytes of the launch.
+static int orderwise_group(int N, size_t* lds) {
+    auto bytes = [&](int G) { return (size_t)G * orderwise_plane(N, G) * sizeof(double); };
+    auto fits = [&](int G) { return bytes(G) <= 160 * 1024 && ceil_div(G * ceil_div(N + 1, 16), kOwWaves) <= kOwMaxUnits; };
+    const int want = SHG_FILT_GROUP;
+    const int G = (want == 0 || want == 8) && fits(8) ? 8 : (want == 0 || want == 4) && fits(4) ? 4 : fits(2) ? 2 : 0;
+    if (lds) *lds = G ? bytes(G) : 0;
+    return G;
+}
+
 template <int G>
 static int launch_orderwise(int Nb, int N, int B, const double* blocks, const long long* block_off, const double* in, double* out, hipStream_t stream) {
     const int plane = orderwise_plane(N, G);
@@ -254,6 +265,8 @@ constexpr int kSeriesMinEpochs = 64;
 // LDS of order_major_kernel: one row of the reference arrays for 16 epochs (above 64 KB the launch needs the opt-in attribute)
 constexpr size_t kOrderMajorMaxLds = 160 * 1024;
 static size_t order_major_lds_bytes(int N) { return (size_t)16 * (N + 2) * sizeof(double); }
+// the batch entry point goes through the order-major layout: many epochs, and only where the row stage of the layout kernels fits the LDS
+static bool orderwise_via_series(int N, int B) { return SHG_FILT_VIA_SERIES && B >= kSeriesMinEpochs && order_major_lds_bytes(N) <= kOrderMajorMaxLds; }
 extern "C" int shg_order_major_pack(const double* anm, int N, int B, double* om, int Bpad, void* stream_);
 extern "C" int shg_order_major_unpack(const double* om, int N, int B, int Bpad, double* anm, void* stream_);
 extern "C" int shg_orderwise_filter_om(const double* blocks_packed, const int64_t* block_off, int Nb, int N, const double* om_in, int B, int Bpad,
@@ -271,30 +284,40 @@ extern "C" int shg_orderwise_filter(const double* blocks_packed, const int64_t* 
     // Batches of many epochs go through the order-major layout (below): pack 14 us + one product per block on whole matrices 30 us +
     // unpack 12 us at d/o 120 and 240 epochs, against 63 us for the kernel that gathers from and scatters to the reference layout --
     // the same products in the same order, bit-identical results.
-    if (SHG_FILT_VIA_SERIES && B >= kSeriesMinEpochs) {
+    if (orderwise_via_series(N, B)) {
         const int Bpad = round_up(B, 32);
         const size_t bytes = (size_t)(N + 1) * (N + 1) * Bpad * sizeof(double);
         ScratchLease lease(stream);
         double* om_in = (double*)lease.get(kScratchSeriesIn, bytes);
         double* om_out = (double*)lease.get(kScratchSeriesOut, bytes);
-        // (only where the row stage of the layout kernels fits the LDS; whatever fails on this way, the block kernel below still serves)
-        if (om_in && om_out && order_major_lds_bytes(N) <= kOrderMajorMaxLds) {
+        // (whatever fails on this way, the block kernel below still serves)
+        if (om_in && om_out) {
             int rc = shg_order_major_pack(anm_in, N, B, om_in, Bpad, stream_);
             if (!rc) rc = shg_orderwise_filter_om(blocks_packed, block_off, Nb, N, om_in, B, Bpad, om_out, stream_);
             if (!rc) rc = shg_order_major_unpack(om_out, N, B, Bpad, anm_out, stream_);
             if (!rc) return rc;
         }
     }
-    // orders per workgroup: as many as the LDS stage allows (8: degree <= 143, 4: <= 295, 2: <= 591); every wave holds the results of
-    // its (order, row tile) units in registers
-    auto fits = [&](int G) {
-        return (size_t)G * orderwise_plane(N, G) * sizeof(double) <= 160 * 1024 && ceil_div(G * ceil_div(N + 1, 16), kOwWaves) <= kOwMaxUnits;
-    };
-    const int want = SHG_FILT_GROUP;
-    if ((want == 0 || want == 8) && fits(8)) return launch_orderwise<8>(Nb, N, B, blocks_packed, off, anm_in, anm_out, stream);
-    if ((want == 0 || want == 4) && fits(4)) return launch_orderwise<4>(Nb, N, B, blocks_packed, off, anm_in, anm_out, stream);
-    if (fits(2)) return launch_orderwise<2>(Nb, N, B, blocks_packed, off, anm_in, anm_out, stream);
-    return fail(SHG_ERR_UNSUPPORTED, "shg_orderwise_filter: degree %d exceeds the LDS staging of the block kernel (max degree 591)", N);
+    switch (orderwise_group(N, nullptr)) {
+        case 8: return launch_orderwise<8>(Nb, N, B, blocks_packed, off, anm_in, anm_out, stream);
+        case 4: return launch_orderwise<4>(Nb, N, B, blocks_packed, off, anm_in, anm_out, stream);
+        case 2: return launch_orderwise<2>(Nb, N, B, blocks_packed, off, anm_in, anm_out, stream);
+    }
+    return fail(SHG_ERR_UNSUPPORTED, "shg_orderwise_filter: degree %d exceeds the LDS staging of the block kernel (max degree 599)", N);
+}
+
+// Host-only query of the dispatch above (touches no device): which[0] = 1 if a batch of B epochs of degree N goes through the order-major
+// layout, [1] = orders per workgroup G of the block kernel for degree N (0: it refuses), [2] = dynamic LDS bytes of that launch,
+// [3] = epochs per workgroup of the block kernel.
+extern "C" int shg_orderwise_filter_info(int N, int B, int which[4]) {
+    SHG_REQUIRE(N >= 0 && B >= 0, "shg_orderwise_filter_info: negative size");
+    SHG_REQUIRE(which, "shg_orderwise_filter_info: NULL pointer");
+    size_t lds = 0;
+    which[0] = orderwise_via_series(N, B) ? 1 : 0;
+    which[1] = orderwise_group(N, &lds);
+    which[2] = (int)lds;
+    which[3] = kOwEpochs;
+    return SHG_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

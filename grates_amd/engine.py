@@ -1197,6 +1197,15 @@ def orderwise_filter(blocks_packed, block_offsets, block_max_degree, anm):
     return out
 
 
+def orderwise_filter_info(N, B):
+    """{'via_series', 'group', 'lds_bytes', 'epochs_per_workgroup'}: the kernels `orderwise_filter` takes for B epochs of degree N -- whether the
+    batch goes through the order-major layout, and the orders per workgroup (8, 4, 2; 0: refused) and LDS bytes of the kernel on the reference
+    layout.  A host-side query: no GPU needed."""
+    arr = (ctypes.c_int * 4)()
+    _lib.call('shg_orderwise_filter_info', int(N), int(B), arr)
+    return {'via_series': bool(arr[0]), 'group': int(arr[1]), 'lds_bytes': int(arr[2]), 'epochs_per_workgroup': int(arr[3])}
+
+
 def ddk_blocks(normal_blocks, weights):
     """W_k = (N_k + diag(w[m:]))^-1 N_k for a list of order-wise normal blocks (host ndarrays) -> list of ndarrays."""
     torch = require_gpu()

@@ -205,6 +205,10 @@ int shg_degree_scale(const double* w /* [N+1] device */, int N, int nfirst, cons
 int shg_orderwise_filter(const double* blocks_packed, const int64_t* block_off, int Nb, int N,
                          const double* anm_in, int B, double* anm_out, void* stream);
 int shg_dense_filter(const double* W, int P, const double* X, int T, double* Y, void* stream);
+/* Which kernels shg_orderwise_filter takes for B epochs of degree N (host only, no device call): which[0] = 1 if the batch goes through
+ * the order-major layout (pack, shg_orderwise_filter_om, unpack), [1] = orders per workgroup of the kernel on the reference layout
+ * (8, 4 or 2; 0: the degree exceeds its LDS stage and it refuses), [2] = dynamic LDS bytes of that launch, [3] = its epochs per workgroup. */
+int shg_orderwise_filter_info(int N, int B, int which[4]);
 
 /* Order-major series: a time series of coefficient sets kept on the device between operators -- the batching the reference does with
  * TimeSeries.to_array (grates/gravityfield.py:964-980), in the layout the order-wise operators want:
