@@ -213,6 +213,26 @@ inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ inline int order_offset(int N, int m) { return m * (N + 1) - (m * (m - 1)) / 2; }
 __host__ __device__ inline int packed_count(int N) { return (N + 1) * (N + 2) / 2; }
 
+// Factors of the derivative map D of the solid harmonics (gravity_points.hip, design.hip), of the input coefficient (n, m): f- goes with
+// P_{n+1,m-1} (m >= 1), f0 with P_{n+1,m}, f+ with P_{n+1,m+1}; f- of order 1 and f+ of order 0 carry the reference's extra sqrt(2).
+__host__ __device__ inline double d_factor_base(double dn) { return sqrt((2.0 * dn + 1.0) / (2.0 * dn + 3.0)); }
+__host__ __device__ inline double d_factor_minus(int n, int m) {
+    const double dn = n, dm = m;
+    double f = sqrt((dn - dm + 1.0) * (dn - dm + 2.0)) * d_factor_base(dn);
+    if (m == 1) f *= sqrt(2.0);
+    return f;
+}
+__host__ __device__ inline double d_factor_zero(int n, int m) {
+    const double dn = n, dm = m;
+    return sqrt((dn - dm + 1.0) * (dn + dm + 1.0)) * d_factor_base(dn);
+}
+__host__ __device__ inline double d_factor_plus(int n, int m) {
+    const double dn = n, dm = m;
+    double f = sqrt((dn + dm + 1.0) * (dn + dm + 2.0)) * d_factor_base(dn);
+    if (m == 0) f *= sqrt(2.0);
+    return f;
+}
+
 // Exchange between the lanes 2q and 2q+1 that turns "4 rows x 1 column per lane" into "2 rows x 2 adjacent columns per lane":
 //   even lanes: lo = x (own),                  hi = x of the odd neighbour
 //   odd lanes:  lo = y of the even neighbour,  hi = y (own)

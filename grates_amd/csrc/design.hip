@@ -1,8 +1,8 @@
-// Design matrix of the gravitational acceleration at points: the partial derivatives of g (acceleration.hip) with respect to the
+// Design matrix of the gravitational acceleration at points: the partial derivatives of g (gravity_points.hip) with respect to the
 // coefficients, transposed, At [P][3][ldt] with the points innermost and the rows in the degree-wise order of
 // utilities.ravel_coefficients (C_n0, C_n1, S_n1, C_n2, ... for n = min_degree .. N).
 //
-// g is linear in the coefficients and the grouping at the head of acceleration.hip gives every column directly.  With the solid
+// g is linear in the coefficients and the grouping at the head of gravity_points.hip gives every column directly.  With the solid
 // harmonics of degree n' = n + 1,
 //   Yc_{n'k} = (R/r)^(n'+1) P_{n'k} cos(k lon)      Ys_{n'k} = (R/r)^(n'+1) P_{n'k} sin(k lon),
 // and the factors f-, f0, f+ of (n, m) (f- of order 1 and f+ of order 0 carry the reference's extra sqrt(2)), in units of GM / (2 R^2):
@@ -11,7 +11,7 @@
 //   d g_z / d C_nm = -2 f0 Yc_{n+1,m}                       d g_z / d S_nm = -2 f0 Ys_{n+1,m}
 // (the minus terms exist for m >= 1 only).  No sum over degrees: an entry is one or two products.
 //
-// Two kernels per pass of points: design_harmonics_kernel runs the column recursion of acceleration_points_kernel once per point and
+// Two kernels per pass of points: design_harmonics_kernel runs the column recursion of solid_points_kernel once per point and
 // writes Y [packed (n', k)][2][ldy] of degree N + 1 to a workspace; design_gather_kernel forms every row of At from at most two
 // entries of Y per component, following a host-built table of (slot of Y, factor) terms.  The table is all the gather kernel knows
 // about the acceleration: another linear functional of the solid harmonics is another table.
@@ -23,9 +23,9 @@
 // The line-of-sight gravity difference of satellite pairs (third part) needs no table of its own: its gather kernel reads the
 // acceleration's table at the two satellites of a pair, takes the difference and projects it on the line of sight.
 //
-// The host side is one of each: d_terms is the only place that knows f-, f0, f+ (both tables are built from it), design_passes is the
-// pass driver (pass size, workspace, upload of recursion factors and table) around the launches of an entry point, and check_design
-// holds the argument checks the entry points share.
+// The host side is one of each: d_terms is the only host code that uses f-, f0, f+ (both tables are built from it; the formulas
+// themselves are in common.h, shared with the forward kernels), design_passes is the pass driver (pass size, workspace, upload of
+// recursion factors and table) around the launches of an entry point, and check_design holds the argument checks the entry points share.
 #include "common.h"
 
 #include <cmath>
@@ -34,9 +34,9 @@
 namespace shg {
 
 // 256 lanes = 256 points.  (r, colatitude, longitude) come from xyz as grid.cartesian2spherical computes them (the operation order of
-// acceleration_points_kernel), (R/r)^(n'+1) is carried along the degree loop.  The recursion factors a, b of one (n', k) lie side by
+// solid_points_kernel), (R/r)^(n'+1) is carried along the degree loop.  The recursion factors a, b of one (n', k) lie side by
 // side and are read with wave-uniform addresses: no LDS, whatever the degree.  kDirect takes cos and sin of the colatitude straight from
-// xyz (t = z / r, s = rho / r: the form of gradients_points_kernel, exact next to the axis) instead of the reference's
+// xyz (t = z / r, s = rho / r: the gradient tensor's form, exact next to the axis) instead of the reference's
 // s = sqrt(1 - t^2), which the acceleration and its design matrix follow.  A launch with gridDim.y = 2 runs two sets of npts points,
 // xyz and xyz_second, and writes the second set's harmonics to the columns `second` .. of Y (the two satellites of the line-of-sight
 // design); with gridDim.y = 1 neither is looked at.
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void design_gather_kernel(int npts, const doub
 
 // ---- the term map ------------------------------------------------------------------------------------------------------------------
 // One map serves every table of this file: D_c, the derivative along axis c of a single solid-harmonic coefficient (the grouping at
-// the head of acceleration.hip).  The acceleration's rows are D_c of the unit coefficient, the gradient tensor's D_d of D_c.
+// the head of gravity_points.hip).  The acceleration's rows are D_c of the unit coefficient, the gradient tensor's D_d of D_c.
 struct SolidTerm {
     int n, k, kind;                                   // kind 0: cosine, 1: sine
     double f;
@@ -122,27 +122,22 @@ struct SolidTerm {
 static int d_terms(int c, const SolidTerm& in, SolidTerm out[2]) {
     int count = 0;
     const int n = in.n, m = in.k, sine = in.kind;
-    const double dn = n, dm = m;
-    const double base = sqrt((2.0 * dn + 1.0) / (2.0 * dn + 3.0));
     auto put = [&](int k, int kind, double value) {
         if (kind == 1 && k == 0) return;                             // Ys of order 0 is zero
         out[count++] = SolidTerm{n + 1, k, kind, in.f * value};
     };
     if (c == 2) {
-        const double f0 = sqrt((dn - dm + 1.0) * (dn + dm + 1.0)) * base;
-        put(m, sine, -2.0 * f0);
+        put(m, sine, -2.0 * d_factor_zero(n, m));
         return count;
     }
     if (m >= 1) {                                                    // minus term: P_{n+1,m-1}
-        double fm = sqrt((dn - dm + 1.0) * (dn - dm + 2.0)) * base;
-        if (m == 1) fm *= sqrt(2.0);
+        const double fm = d_factor_minus(n, m);
         if (c == 0)
             put(m - 1, sine, fm);
         else
             put(m - 1, 1 - sine, sine ? fm : -fm);
     }
-    double fp = sqrt((dn + dm + 1.0) * (dn + dm + 2.0)) * base;      // plus term: P_{n+1,m+1}
-    if (m == 0) fp *= sqrt(2.0);
+    const double fp = d_factor_plus(n, m);                           // plus term: P_{n+1,m+1}
     if (c == 0)
         put(m + 1, sine, -fp);
     else
@@ -176,8 +171,8 @@ static void acceleration_design_table(int N, int min_degree, int* slot, double* 
 }
 
 // ---- design matrix of the gradient tensor -------------------------------------------------------------------------------------------
-// T = d^2 V / dx_c dx_d is the acceleration's map D (head of gradients.hip) applied twice, so its partial derivative with respect to
-// one coefficient is a sum of at most four terms factor * Y[slot] on the solid harmonics of degree N + 2, in units of GM / (4 R^3):
+// T = d^2 V / dx_c dx_d is the acceleration's map D (head of gravity_points.hip) applied twice, so its partial derivative with respect
+// to one coefficient is a sum of at most four terms factor * Y[slot] on the solid harmonics of degree N + 2, in units of GM / (4 R^3):
 // D_c turns the unit coefficient (n, m, kind) into at most two of degree n + 1, D_d each of those into at most two of degree n + 2,
 // and terms that meet on one slot (the order m of xx, xy and yy) are merged on the host.
 constexpr int kGradTerms = 4;

@@ -1,0 +1,402 @@
+// Gravitational acceleration g and gradient tensor T = d^2 V / dx_c dx_d at arbitrary points (g replaces grates/gravityfield.py:423-481,
+// three per-order Legendre tables of degree N + 1 per point and a dgemv per component and order; the reference has no T).
+//
+// The reference sums, per coefficient order m, P_{n+1,m-1} f-, P_{n+1,m} f0 and P_{n+1,m+1} f+ times (R/r)^(n+2).  Regrouped by the
+// Legendre function (n', k), n' = n + 1 = 0 .. N + 1, each Cartesian component c is a point synthesis of degree N + 1:
+//   g_c = GM / (2 R^2) sum_{n', k} (R/r)^(n'+1) P_{n'k} (cos(k lon) A^c_{n'k} + sin(k lon) B^c_{n'k}),    (A^c, B^c) = D_c(C, S)
+// where D_c reads the orders k + 1 (C-, S-), k - 1 (C+, S+) and k (C0, S0) of degree n and writes (n + 1, k):
+//   x: A = f- C- - f+ C+    B = f- S- - f+ S+        y: A = f- S- + f+ S+    B = -(f- C- + f+ C+)        z: A = -2 f0 C0    B = -2 f0 S0
+// (the factors are d_factor_minus / _zero / _plus of common.h).  D works on any solid-harmonic coefficient set, so applying it to
+// (A^c, B^c) differentiates once more: with (A^cd, B^cd) = D_d(D_c(C, S)) of degree N + 2,
+//   T_cd = dg_c / dx_d = GM / (4 R^3) sum_{n'', k} (R/r)^(n''+1) P_{n''k} (cos(k lon) A^cd_{n''k} + sin(k lon) B^cd_{n''k}).
+// Both are one computation with two parameterisations (Acceleration, Gradients below): a combine kernel forms the 2 C numbers A/B of
+// the C components (x, y, z or xx, xy, xz, yy, yz, zz) per (n', k) of degree Nq = N + 1 or N + 2 and epoch once per call (the
+// gradients' composition fused: the three first-derivative sets it needs are formed in registers), and solid_points_kernel runs one
+// column recursion per point and (n', k) for all components and every epoch of a pass.  xx, yy and zz each come from their own
+// combination: the trace is a check, not an identity.
+#include "common.h"
+
+#include <climits>
+#include <cmath>
+
+namespace shg {
+
+// Q [pass][packed (n', k) of degree Nq][2 C][EP]: A/B of the C components of EP consecutive epochs.
+// Coefficient source: the reference layout anm [B][N+1][N+1] (om == nullptr) or an order-major series om [(N+1)^2][Bpad].
+struct CoefSource {
+    const double* anm;
+    const double* om;
+    int N, B, Bpad;
+    __device__ double cos_coef(int b, int n, int m) const {
+        if (om) return om[(size_t)(om_first_row(m == 0 ? 0 : 2 * m - 1) + n - m) * Bpad + b];
+        return anm[((size_t)b * (N + 1) + n) * (N + 1) + m];
+    }
+    __device__ double sin_coef(int b, int n, int m) const {         // m >= 1
+        if (om) return om[(size_t)(om_first_row(2 * m) + n - m) * Bpad + b];
+        return anm[((size_t)b * (N + 1) + m - 1) * (N + 1) + n];
+    }
+    // first row of slot s (0: order 0 cosine, 2m - 1: order m cosine, 2m: order m sine): engine.order_major_first_row
+    __device__ int om_first_row(int s) const {
+        if (s == 0) return 0;
+        const int m = (s + 1) >> 1;
+        const int cos_row = (N + 1) + 2 * ((m - 1) * (N + 1) - m * (m - 1) / 2);
+        return (s & 1) ? cos_row : cos_row + (N + 1 - m);
+    }
+};
+
+// The inputs of D at output (np, k): the pairs (C, S) of orders k + 1 (minus), k - 1 (plus) and k (zero) of degree np - 1 with their
+// factors.  A factor is zero where its term does not exist; the sine of an order-0 input is never read.
+struct DTerms {
+    double fm, fp, f0;
+    double cm, sm, cp, sp, c0, s0;
+};
+
+__device__ inline void d_factors(int np, int k, DTerms& t) {
+    t.fm = t.fp = t.f0 = 0.0;
+    t.cm = t.sm = t.cp = t.sp = t.c0 = t.s0 = 0.0;
+    if (np < 1) return;
+    const int n = np - 1;
+    if (np >= k + 2) t.fm = d_factor_minus(n, k + 1);
+    if (k >= 1) t.fp = d_factor_plus(n, k - 1);
+    if (np >= k + 1) t.f0 = d_factor_zero(n, k);
+}
+
+// D_c of the terms: (A, B) of component c (0: x, 1: y, 2: z)
+__device__ inline void d_apply(int c, const DTerms& t, double& A, double& B) {
+    if (c == 0) {
+        A = t.fm * t.cm - t.fp * t.cp;
+        B = t.fm * t.sm - t.fp * t.sp;
+    } else if (c == 1) {
+        A = t.fm * t.sm + t.fp * t.sp;
+        B = -(t.fm * t.cm + t.fp * t.cp);
+    } else {
+        A = -2.0 * (t.f0 * t.c0);
+        B = -2.0 * (t.f0 * t.s0);
+    }
+}
+
+// first-derivative coefficients (A^c, B^c) [3][2] of degree n1 <= N + 1 and order k1 <= n1 of epoch b: D_c of the source
+__device__ inline void first_derivative(const CoefSource& src, int b, int n1, int k1, double F[3][2]) {
+    DTerms t;
+    d_factors(n1, k1, t);
+    const int n = n1 - 1;
+    if (n1 >= k1 + 2) {
+        t.cm = src.cos_coef(b, n, k1 + 1);
+        t.sm = src.sin_coef(b, n, k1 + 1);
+    }
+    if (k1 >= 1) {
+        t.cp = src.cos_coef(b, n, k1 - 1);
+        t.sp = k1 >= 2 ? src.sin_coef(b, n, k1 - 1) : 0.0;
+    }
+    if (n1 >= k1 + 1) {
+        t.c0 = src.cos_coef(b, n, k1);
+        t.s0 = k1 >= 1 ? src.sin_coef(b, n, k1) : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d_apply(c, t, F[c][0], F[c][1]);
+}
+
+// The thread of a combine kernel: one per (n', k, epoch slot e) of `passes` passes of EP epochs starting at epoch b_first.  q is
+// where its numbers go, EP apart; epochs b past B get zeros.
+struct CombineSlot {
+    int k, np, b;
+    double* q;
+};
+
+__device__ inline bool combine_slot(int Nq, int numbers, int EP, int b_first, int passes, double* Q, CombineSlot& s) {
+    const long long per_pass = (long long)packed_count(Nq) * EP;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= per_pass * passes) return false;
+    const int pass = (int)(idx / per_pass);
+    const long long rem = idx - pass * per_pass;
+    const int e = (int)(rem % EP);
+    const int p = (int)(rem / EP);
+    int k = 0;                                                       // packed index p -> (k, n'): order_offset(Nq, k) <= p
+    while (k < Nq && order_offset(Nq, k + 1) <= p) ++k;
+    s.k = k;
+    s.np = k + (p - order_offset(Nq, k));
+    s.b = b_first + pass * EP + e;
+    s.q = Q + (size_t)pass * per_pass * numbers + (size_t)p * numbers * EP + e;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void acceleration_combine_kernel(CoefSource src, int EP, int b_first, int passes, double* __restrict__ Q) {
+    CombineSlot s;
+    if (!combine_slot(src.N + 1, 6, EP, b_first, passes, Q, s)) return;
+    double F[3][2] = {};
+    if (s.b < src.B && s.np >= 1) first_derivative(src, s.b, s.np, s.k, F);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) s.q[j * EP] = F[j / 2][j % 2];
+}
+
+__global__ __launch_bounds__(256) void gradients_combine_kernel(CoefSource src, int EP, int b_first, int passes, double* __restrict__ Q) {
+    CombineSlot s;
+    if (!combine_slot(src.N + 2, 12, EP, b_first, passes, Q, s)) return;
+    const int np = s.np, k = s.k, b = s.b;
+    double out[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) out[j] = 0.0;
+    if (b < src.B && np >= 1) {
+        DTerms t;
+        d_factors(np, k, t);
+        const int n1 = np - 1;                                       // degree of the first-derivative sets read
+        double Fm[3][2] = {}, Fp[3][2] = {}, F0[3][2] = {};
+        if (np >= k + 2) first_derivative(src, b, n1, k + 1, Fm);
+        if (k >= 1) first_derivative(src, b, n1, k - 1, Fp);
+        if (np >= k + 1) first_derivative(src, b, n1, k, F0);
+        int j = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            DTerms tc = t;
+            tc.cm = Fm[c][0];
+            tc.sm = Fm[c][1];
+            tc.cp = Fp[c][0];
+            tc.sp = k >= 2 ? Fp[c][1] : 0.0;                         // the order-0 sine of the first derivative is never read
+            tc.c0 = F0[c][0];
+            tc.s0 = k >= 1 ? F0[c][1] : 0.0;
+#pragma unroll
+            for (int d = c; d < 3; ++d, j += 2) d_apply(d, tc, out[j], out[j + 1]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 12; ++j) s.q[j * EP] = out[j];
+}
+
+// degrees per LDS stage of a point kernel with C components and EP epochs: 64, or 32 where 64 would take more than 24 KB (3 x 16: 25 KB
+// for 32 degrees with a and b; 6 x 4: 24 KB for 64; 6 workgroups per CU either way)
+constexpr int stage_degrees(int C, int EP) { return 64 * 2 * C * EP * 8 > (24 << 10) ? 32 : 64; }
+
+// 256 lanes = 256 points x EP epochs (grid.y = pass), C components each.  Per order k the 2 C coefficients of every epoch are staged in
+// LDS in chunks of kDegrees degrees, together with the recursion factors a, b of degree Nq; the degree loop reads them as LDS
+// broadcasts, so any degree fits.  r and the longitude come from xyz as grid.cartesian2spherical computes them, and so does the
+// colatitude unless kDirect; (R/r)^(n'+1) is carried along the degree loop.  C = 3 writes g [b][pt][3]; C = 6 (xx, xy, xz, yy, yz, zz)
+// writes T [b][pt][3][3], each off-diagonal value twice.
+template <int C, int EP, int kDegrees, bool kDirect>
+__global__ __launch_bounds__(256) void solid_points_kernel(int Nq, int npts, int B, const double* __restrict__ xyz, long long xyz_pass_stride,
+                                                           const double* __restrict__ ab, const double* __restrict__ Q, double R, double scale,
+                                                           double* __restrict__ out) {
+    constexpr int kStride = 2 * C * EP;                              // doubles per (n', k) in Q and in the stage
+    __shared__ __attribute__((aligned(16))) double stage[kDegrees * kStride];
+    __shared__ __attribute__((aligned(16))) double abs_[kDegrees * 2];
+    const int tid = threadIdx.x;
+    const int pt = blockIdx.x * 256 + tid;
+    const int pass = blockIdx.y;
+    const bool ok = pt < npts;
+    const double* xp = xyz + pass * xyz_pass_stride + (size_t)(ok ? pt : 0) * 3;
+    const double x = xp[0], y = xp[1], z = xp[2];
+    const double r = sqrt((x * x + y * y) + z * z);                  // np.sum over axis 1: ((x^2 + y^2) + z^2)
+    const double lam = atan2(y, x);
+    const double u = R / r;
+    double t, s;
+    if constexpr (kDirect) {
+        // cos and sin of the colatitude straight from xyz: s = sqrt(1 - t^2), the reference's form, is 0 within 1.5e-8 rad of the
+        // axis, where T_xz = 3 GM x z / r^5 is still up to 2e-8 of max|T|
+        t = z / r;
+        s = sqrt(x * x + y * y) / r;
+    } else {
+        const double th = atan2(sqrt(x * x + y * y), z);
+        t = cos(th);
+        s = sqrt(1.0 - t * t);
+    }
+    const double* Qp = Q + (size_t)pass * packed_count(Nq) * kStride;
+    double acc[C][EP];
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int e = 0; e < EP; ++e) acc[c][e] = 0.0;
+    double pmm = 1.0, rk = u;                                        // rk = (R/r)^(k+1)
+    for (int k = 0; k <= Nq; ++k) {
+        if (k == 1)
+            pmm = sqrt(3.0) * s;
+        else if (k >= 2)
+            pmm = sqrt((2.0 * k + 1.0) / (2.0 * k)) * s * pmm;
+        if (k >= 1) rk *= u;
+        double sk, ck;
+        sincos((double)k * lam, &sk, &ck);
+        double p1 = pmm, p2 = 0.0, rad = rk;
+        const int off = order_offset(Nq, k);
+        for (int n0 = k; n0 <= Nq; n0 += kDegrees) {
+            const int cnt = min(kDegrees, Nq + 1 - n0);
+            __syncthreads();                                         // the previous chunk has been consumed
+            {
+                const double2* src = reinterpret_cast<const double2*>(Qp + (size_t)(off + n0 - k) * kStride);
+                double2* dst = reinterpret_cast<double2*>(stage);
+                for (int i = tid; i < cnt * kStride / 2; i += 256) dst[i] = src[i];
+                const double2* sab = reinterpret_cast<const double2*>(ab + (size_t)(off + n0 - k) * 2);
+                double2* dab = reinterpret_cast<double2*>(abs_);
+                for (int i = tid; i < cnt; i += 256) dab[i] = sab[i];
+            }
+            __syncthreads();
+            for (int j = 0; j < cnt; ++j) {
+                const int n = n0 + j;
+                if (n > k) {
+                    const double p = (abs_[2 * j] * t) * p1 - abs_[2 * j + 1] * p2;
+                    p2 = p1;
+                    p1 = p;
+                }
+                const double pk = p1 * rad;
+                rad *= u;
+                const double yc = pk * ck, ys = pk * sk;
+                const double* q = stage + j * kStride;
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+#pragma unroll
+                    for (int e = 0; e < EP; ++e) {
+                        acc[c][e] = fma(yc, q[(2 * c) * EP + e], acc[c][e]);
+                        acc[c][e] = fma(ys, q[(2 * c + 1) * EP + e], acc[c][e]);
+                    }
+            }
+        }
+    }
+    if (ok) {
+#pragma unroll
+        for (int e = 0; e < EP; ++e) {
+            const int b = pass * EP + e;
+            if (b < B) {
+                if constexpr (C == 3) {
+                    double* o = out + ((size_t)b * npts + pt) * 3;
+                    o[0] = acc[0][e] * scale;
+                    o[1] = acc[1][e] * scale;
+                    o[2] = acc[2][e] * scale;
+                } else {
+                    const double xx = acc[0][e] * scale, xy = acc[1][e] * scale, xz = acc[2][e] * scale;
+                    const double yy = acc[3][e] * scale, yz = acc[4][e] * scale, zz = acc[5][e] * scale;
+                    double* o = out + ((size_t)b * npts + pt) * 9;
+                    o[0] = xx;
+                    o[1] = xy;
+                    o[2] = xz;
+                    o[3] = xy;
+                    o[4] = yy;
+                    o[5] = yz;
+                    o[6] = xz;
+                    o[7] = yz;
+                    o[8] = zz;
+                }
+            }
+        }
+    }
+}
+
+// The two functionals.  kOffset: Nq = N + kOffset; kComponents: C of the kernels (2 C numbers per (n', k) in Q); kValues: values per
+// point and epoch; kMaxEP: epochs per pass with shared points are the smallest of 1, 4, 16 that holds all epochs, kMaxEP at most.
+struct Acceleration {
+    static constexpr int kOffset = 1, kComponents = 3, kValues = 3, kMaxEP = 16;
+    static constexpr bool kDirect = false;                           // the reference's s = sqrt(1 - t^2): its consumers depend on it
+    static constexpr bool kCheckQ = false;
+    static constexpr auto kCombine = acceleration_combine_kernel;
+    static constexpr const char* kNoWorkspace = "shg_acceleration_points: workspace allocation failed";
+    static double scale(double GM, double R) { return GM / (2.0 * R * R); }
+};
+
+struct Gradients {
+    // 12 EP accumulators: EP = 4 already holds 48 doubles, EP = 8 would spill or fall to one wave per SIMD
+    static constexpr int kOffset = 2, kComponents = 6, kValues = 9, kMaxEP = 4;
+    static constexpr bool kDirect = true;
+    static constexpr bool kCheckQ = true;                            // the point kernel indexes one pass of Q with int
+    static constexpr auto kCombine = gradients_combine_kernel;
+    static constexpr const char* kNoWorkspace = "shg_gravitational_gradients_points: workspace allocation failed";
+    static double scale(double GM, double R) { return GM / (4.0 * R * R * R); }
+};
+
+}  // namespace shg
+
+using namespace shg;
+
+template <class F>
+static int solid_points(int N, const double* xyz, int M, int layout, CoefSource src, double GM, double R, double* out, hipStream_t stream) {
+    constexpr int C = F::kComponents;
+    const int Nq = N + F::kOffset, B = src.B;
+    // epochs per pass: per-epoch points take one epoch per pass (each pass has its own points)
+    const int EP = layout == SHG_POINTS_PER_EPOCH ? 1 : std::min(B <= 1 ? 1 : B <= 4 ? 4 : 16, F::kMaxEP);
+    const int passes = ceil_div(B, EP);
+    const long long per_pass = (long long)packed_count(Nq) * 2 * C * EP;      // doubles of Q per pass
+    // passes per group: Q of a group stays under 256 MB (and under 65535 passes per launch)
+    const int group = (int)std::max<long long>(1, std::min<long long>({(long long)passes, (256LL << 20) / 8 / per_pass, 65535LL}));
+    const double scale = F::scale(GM, R);
+    {
+        Workspace ws = Workspace::plain(stream);
+        double *ab, *Q;
+        if (!ws.alloc(ab, (size_t)packed_count(Nq) * 2, Q, (size_t)group * per_pass)) return fail(SHG_ERR_NOMEM, F::kNoWorkspace);
+        {   // recursion factors of degree Nq, a and b of one (n', k) side by side (staged together)
+            std::vector<double> a, b, h(2 * (size_t)packed_count(Nq));
+            recursion_tables(Nq, a, b);
+            for (size_t i = 0; i < a.size(); ++i) {
+                h[2 * i] = a[i];
+                h[2 * i + 1] = b[i];
+            }
+            SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+            SHG_HIP(hipStreamSynchronize(stream));
+        }
+        for (int p0 = 0; p0 < passes; p0 += group) {
+            const int np = std::min(group, passes - p0);
+            const long long threads = (long long)packed_count(Nq) * EP * np;
+            hipLaunchKernelGGL(F::kCombine, dim3((unsigned)ceil_div64(threads, 256)), dim3(256), 0, stream, src, EP, p0 * EP, np, Q);
+            const long long stride = layout == SHG_POINTS_PER_EPOCH ? 3LL * M : 0;
+            const double* x0 = xyz + (size_t)p0 * stride;
+            double* o0 = out + (size_t)p0 * EP * M * F::kValues;
+            const int Bg = std::min(B - p0 * EP, np * EP);
+            const dim3 grid(ceil_div(M, 256), np);
+            auto launch = [&](auto ep) {
+                constexpr int kEP = decltype(ep)::value;
+                hipLaunchKernelGGL((solid_points_kernel<C, kEP, stage_degrees(C, kEP), F::kDirect>), grid, dim3(256), 0, stream, Nq, M, Bg, x0, stride, ab,
+                                   Q, R, scale, o0);
+            };
+            if (EP == 1)
+                launch(std::integral_constant<int, 1>());
+            else if (EP == 4)
+                launch(std::integral_constant<int, 4>());
+            else if constexpr (F::kMaxEP == 16)
+                launch(std::integral_constant<int, 16>());
+            SHG_HIP(hipGetLastError());
+        }
+    }
+    SHG_HIP(hipGetLastError());
+    return SHG_OK;
+}
+
+// Arguments are checked before the first HIP call (the CPU tests call these without a device).
+template <class F>
+static int check_points(const char* fn, int N, const double* xyz, int M, int layout, const void* coef, int B, double GM, double R, double* out) {
+    SHG_REQUIRE(N >= 0 && M >= 0 && B >= 0, "%s: negative size (N %d, M %d, B %d)", fn, N, M, B);
+    SHG_REQUIRE(layout == SHG_POINTS_SHARED || layout == SHG_POINTS_PER_EPOCH, "%s: layout %d, expected 0 (shared points) or 1 (points per epoch)", fn,
+                layout);
+    SHG_REQUIRE(std::isfinite(GM) && std::isfinite(R) && R > 0.0, "%s: GM and R must be finite and R positive (GM %g, R %g)", fn, GM, R);
+    const long long values = (long long)F::kValues * M * B;
+    SHG_REQUIRE(values <= (1LL << 40), "%s: output of %lld values is too large", fn, values);
+    if constexpr (F::kCheckQ) {
+        const long long q_pass = (long long)(N + F::kOffset + 1) * (N + F::kOffset + 2) / 2 * 2 * F::kComponents * F::kMaxEP;
+        SHG_REQUIRE(q_pass <= INT_MAX, "%s: degree %d is too large (a pass of Q holds %lld values)", fn, N, q_pass);
+    }
+    if (M > 0 && B > 0) SHG_REQUIRE(xyz && coef && out, "%s: NULL pointer", fn);
+    return SHG_OK;
+}
+
+extern "C" int shg_acceleration_points(int N, const double* xyz, int M, int layout, const double* anm, int B, double GM, double R, double* g,
+                                       void* stream) {
+    if (int rc = check_points<Acceleration>("shg_acceleration_points", N, xyz, M, layout, anm, B, GM, R, g)) return rc;
+    if (M == 0 || B == 0) return SHG_OK;
+    return solid_points<Acceleration>(N, xyz, M, layout, CoefSource{anm, nullptr, N, B, 0}, GM, R, g, (hipStream_t)stream);
+}
+
+extern "C" int shg_acceleration_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM, double R, double* g,
+                                          void* stream) {
+    if (int rc = check_points<Acceleration>("shg_acceleration_points_om", N, xyz, M, layout, om, B, GM, R, g)) return rc;
+    SHG_REQUIRE(Bpad >= B, "shg_acceleration_points_om: Bpad %d below B %d", Bpad, B);
+    if (M == 0 || B == 0) return SHG_OK;
+    return solid_points<Acceleration>(N, xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, g, (hipStream_t)stream);
+}
+
+extern "C" int shg_gravitational_gradients_points(int N, const double* xyz, int M, int layout, const double* anm, int B, double GM, double R, double* T,
+                                                  void* stream) {
+    if (int rc = check_points<Gradients>("shg_gravitational_gradients_points", N, xyz, M, layout, anm, B, GM, R, T)) return rc;
+    if (M == 0 || B == 0) return SHG_OK;
+    return solid_points<Gradients>(N, xyz, M, layout, CoefSource{anm, nullptr, N, B, 0}, GM, R, T, (hipStream_t)stream);
+}
+
+extern "C" int shg_gravitational_gradients_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM, double R,
+                                                     double* T, void* stream) {
+    if (int rc = check_points<Gradients>("shg_gravitational_gradients_points_om", N, xyz, M, layout, om, B, GM, R, T)) return rc;
+    SHG_REQUIRE(Bpad >= B, "shg_gravitational_gradients_points_om: Bpad %d below B %d", Bpad, B);
+    if (M == 0 || B == 0) return SHG_OK;
+    return solid_points<Gradients>(N, xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, T, (hipStream_t)stream);
+}

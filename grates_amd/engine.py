@@ -722,10 +722,8 @@ def check_acceleration_points(xyz, epochs):
     raise ValueError('positions must have shape (M, 3) or ({0}, M, 3), got {1}'.format(epochs, shape))
 
 
-def acceleration_points(max_degree, xyz, coefficients, GM, R):
-    """Gravitational acceleration g [B, M, 3] (device, m/s^2) of the fields `coefficients` -- a batch [B, N+1, N+1] or an
-    OrderMajorSeries, read in its own layout -- with constants GM and R at the positions xyz [M, 3] (shared by all fields) or
-    [B, M, 3] (per field) (shg_acceleration_points / shg_acceleration_points_om)."""
+def _functional_points(stem, tail, max_degree, xyz, coefficients, GM, R):
+    """out [B, M, *tail] of the point functional shg_<stem> (a batch) / shg_<stem>_om (an OrderMajorSeries)."""
     torch = require_gpu()
     om = isinstance(coefficients, OrderMajorSeries)
     if not om:
@@ -738,41 +736,28 @@ def acceleration_points(max_degree, xyz, coefficients, GM, R):
     per_epoch = check_acceleration_points(xyz, B)
     x = to_device(xyz, coefficients.data.device if om else coefficients.device)
     M = int(x.shape[-2])
-    out = torch.empty((B, M, 3), dtype=torch.float64, device=x.device)
+    out = torch.empty((B, M) + tail, dtype=torch.float64, device=x.device)
     layout = 1 if per_epoch else 0
     if om:
-        _lib.call('shg_acceleration_points_om', int(max_degree), _ptr(x), M, layout, _ptr(coefficients.data), B, coefficients.padded_epochs,
+        _lib.call('shg_' + stem + '_om', int(max_degree), _ptr(x), M, layout, _ptr(coefficients.data), B, coefficients.padded_epochs,
                   float(GM), float(R), _ptr(out), _stream())
     else:
-        _lib.call('shg_acceleration_points', int(max_degree), _ptr(x), M, layout, _ptr(coefficients), B, float(GM), float(R), _ptr(out), _stream())
+        _lib.call('shg_' + stem, int(max_degree), _ptr(x), M, layout, _ptr(coefficients), B, float(GM), float(R), _ptr(out), _stream())
     return out
+
+
+def acceleration_points(max_degree, xyz, coefficients, GM, R):
+    """Gravitational acceleration g [B, M, 3] (device, m/s^2) of the fields `coefficients` -- a batch [B, N+1, N+1] or an
+    OrderMajorSeries, read in its own layout -- with constants GM and R at the positions xyz [M, 3] (shared by all fields) or
+    [B, M, 3] (per field) (shg_acceleration_points / shg_acceleration_points_om)."""
+    return _functional_points('acceleration_points', (3,), max_degree, xyz, coefficients, GM, R)
 
 
 def gravitational_gradients_points(max_degree, xyz, coefficients, GM, R):
     """Gravitational gradient tensor T [B, M, 3, 3] (device, s^-2), T[b, m, c, d] = d g_c / d x_d, of the fields `coefficients` -- a
     batch [B, N+1, N+1] or an OrderMajorSeries, read in its own layout -- with constants GM and R at the positions xyz [M, 3] (shared
     by all fields) or [B, M, 3] (per field) (shg_gravitational_gradients_points / shg_gravitational_gradients_points_om)."""
-    torch = require_gpu()
-    om = isinstance(coefficients, OrderMajorSeries)
-    if not om:
-        coefficients = to_device(coefficients)
-        if coefficients.dim() != 3 or coefficients.shape[1] != coefficients.shape[2] or coefficients.shape[1] != max_degree + 1:
-            raise ValueError('coefficient batch must have shape (B, {0}, {0}), got {1}'.format(max_degree + 1, tuple(coefficients.shape)))
-    elif coefficients.max_degree != max_degree:
-        raise ValueError('the series holds degrees up to {0}, not {1}'.format(coefficients.max_degree, max_degree))
-    B = coefficients.epochs if om else int(coefficients.shape[0])
-    per_epoch = check_acceleration_points(xyz, B)
-    x = to_device(xyz, coefficients.data.device if om else coefficients.device)
-    M = int(x.shape[-2])
-    out = torch.empty((B, M, 3, 3), dtype=torch.float64, device=x.device)
-    layout = 1 if per_epoch else 0
-    if om:
-        _lib.call('shg_gravitational_gradients_points_om', int(max_degree), _ptr(x), M, layout, _ptr(coefficients.data), B,
-                  coefficients.padded_epochs, float(GM), float(R), _ptr(out), _stream())
-    else:
-        _lib.call('shg_gravitational_gradients_points', int(max_degree), _ptr(x), M, layout, _ptr(coefficients), B, float(GM), float(R),
-                  _ptr(out), _stream())
-    return out
+    return _functional_points('gravitational_gradients_points', (3, 3), max_degree, xyz, coefficients, GM, R)
 
 
 def check_observation_weights(weights, points, components=3):

@@ -654,6 +654,23 @@ class TimeSeries:
             out.append(g)
         return out
 
+    def _functional_at_points(self, engine_function, field_method, xyz, as_tensor):
+        """A point functional of every epoch, [T, M, ...]: one `engine_function` call on the device series or, with a common GM and R,
+        on the coefficient batch; else the method named `field_method` of every field, with its own constants."""
+        per_epoch = engine.check_acceleration_points(xyz, len(self))
+        if self.__series is not None:
+            GM, R = self._constants()
+            out = engine_function(self.__series.max_degree, xyz, self.__series, GM, R)
+        else:
+            fields = self.__data
+            if all(d.GM == fields[0].GM and d.R == fields[0].R for d in fields):
+                batch = self.to_coefficient_batch()
+                out = engine_function(batch.shape[-1] - 1, xyz, batch, fields[0].GM, fields[0].R)
+            else:
+                import torch
+                out = torch.stack([getattr(d, field_method)(xyz[k] if per_epoch else xyz, as_tensor=True) for k, d in enumerate(fields)])
+        return out if as_tensor else engine.to_host(out)
+
     def gravitational_acceleration(self, xyz, as_tensor=False):
         """
         Gravitational acceleration [m/s^2] of every epoch, [T, M, 3], at the positions xyz: [M, 3] for all epochs (a grid at altitude)
@@ -661,19 +678,7 @@ class TimeSeries:
         (shg_acceleration_points); a device series is read in its own order-major layout and never leaves the device.  Fields with
         different GM or R take one call each.  Returns an ndarray, or the float64 device tensor with as_tensor=True.
         """
-        per_epoch = engine.check_acceleration_points(xyz, len(self))
-        if self.__series is not None:
-            GM, R = self._constants()
-            g = engine.acceleration_points(self.__series.max_degree, xyz, self.__series, GM, R)
-        else:
-            fields = self.__data
-            if all(d.GM == fields[0].GM and d.R == fields[0].R for d in fields):
-                batch = self.to_coefficient_batch()
-                g = engine.acceleration_points(batch.shape[-1] - 1, xyz, batch, fields[0].GM, fields[0].R)
-            else:
-                import torch
-                g = torch.stack([d.gravitational_acceleration(xyz[k] if per_epoch else xyz, as_tensor=True) for k, d in enumerate(fields)])
-        return g if as_tensor else engine.to_host(g)
+        return self._functional_at_points(engine.acceleration_points, 'gravitational_acceleration', xyz, as_tensor)
 
     def gravitational_gradients(self, xyz, as_tensor=False):
         """
@@ -683,19 +688,7 @@ class TimeSeries:
         device; fields with different GM or R take one call each.  There is no host implementation.  Returns an ndarray, or the float64
         device tensor with as_tensor=True.
         """
-        per_epoch = engine.check_acceleration_points(xyz, len(self))
-        if self.__series is not None:
-            GM, R = self._constants()
-            T = engine.gravitational_gradients_points(self.__series.max_degree, xyz, self.__series, GM, R)
-        else:
-            fields = self.__data
-            if all(d.GM == fields[0].GM and d.R == fields[0].R for d in fields):
-                batch = self.to_coefficient_batch()
-                T = engine.gravitational_gradients_points(batch.shape[-1] - 1, xyz, batch, fields[0].GM, fields[0].R)
-            else:
-                import torch
-                T = torch.stack([d.gravitational_gradients(xyz[k] if per_epoch else xyz, as_tensor=True) for k, d in enumerate(fields)])
-        return T if as_tensor else engine.to_host(T)
+        return self._functional_at_points(engine.gravitational_gradients_points, 'gravitational_gradients', xyz, as_tensor)
 
     def line_of_sight_acceleration(self, xyz_a, xyz_b, directions=None, as_tensor=False):
         """
