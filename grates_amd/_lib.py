@@ -120,6 +120,14 @@ PROTOTYPES = {
     'shg_los_design': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p, ctypes.c_double, ctypes.c_double,
                        c_double_p, ctypes.c_int, ctypes.c_void_p],
     'shg_los_design_pass': [ctypes.c_int],
+    'shg_potential_points': [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                             c_double_p, ctypes.c_void_p],
+    'shg_potential_points_om': [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                ctypes.c_double, c_double_p, ctypes.c_void_p],
+    'shg_potential_design': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_double, ctypes.c_double, c_double_p,
+                             ctypes.c_int, ctypes.c_void_p],
+    'shg_potential_difference_design': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, ctypes.c_double,
+                                        ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_void_p],
     'shg_whiten_rows': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, c_double_p, ctypes.c_int,
                         ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p],
     'shg_segment_products': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, c_double_p, ctypes.c_longlong, ctypes.c_int,

@@ -23,6 +23,9 @@
 // The line-of-sight gravity difference of satellite pairs (third part) needs no table of its own: its gather kernel reads the
 // acceleration's table at the two satellites of a pair, takes the difference and projects it on the line of sight.
 //
+// The potential and the potential difference of satellite pairs (fourth part, the energy-balance observations) need no gather at
+// all: an entry is one solid harmonic of degree N, which potential_design_kernel stores straight from the recursion to its row.
+//
 // The host side is one of each: d_terms is the only host code that uses f-, f0, f+ (both tables are built from it; the formulas
 // themselves are in common.h, shared with the forward kernels), design_passes is the pass driver (pass size, workspace, upload of
 // recursion factors and table) around the launches of an entry point, and check_design holds the argument checks the entry points share.
@@ -340,6 +343,99 @@ __global__ __launch_bounds__(256) void los_design_kernel(int npairs, long long r
     }
 }
 
+// ---- design matrices of the potential and of the potential difference of satellite pairs ------------------------------------------------
+// dV / dC_nm = GM / R Yc_nm and dV / dS_nm = GM / R Ys_nm on the solid harmonics of degree N itself: an entry is one harmonic, so
+// there is nothing to gather and no table.  The kernel stores every harmonic straight to its row.
+constexpr int kPotLanes = 64;                         // points per workgroup: one wave, whose store covers 64 consecutive doubles of a row
+constexpr int kPotOrders = 4;                         // orders per workgroup (blockIdx.y)
+
+// The column recursion of design_harmonics_kernel<false> at one point, in its operation order, one call per step.
+struct SolidColumn {
+    double t, s, u, lam, pmm, rk;                     // rk = (R/r)^(k+1)
+    double p1, p2, rad, ck, sk;
+    __device__ void start(const double* xp, double R) {
+        const double x = xp[0], y = xp[1], z = xp[2];
+        const double r = sqrt((x * x + y * y) + z * z);
+        const double th = atan2(sqrt(x * x + y * y), z);
+        lam = atan2(y, x);
+        u = R / r;
+        t = cos(th);
+        s = sqrt(1.0 - t * t);
+        pmm = 1.0;
+        rk = u;
+    }
+    // on to order k (every order from 0 in turn); live: the degrees of this order follow
+    __device__ void order(int k, bool live) {
+        if (k == 1)
+            pmm = sqrt(3.0) * s;
+        else if (k >= 2)
+            pmm = sqrt((2.0 * k + 1.0) / (2.0 * k)) * s * pmm;
+        if (k >= 1) rk *= u;
+        if (live) {
+            sincos((double)k * lam, &sk, &ck);
+            p1 = pmm;
+            p2 = 0.0;
+            rad = rk;
+        }
+    }
+    // degree n of order k (every degree from k in turn), f = (a, b) of (n, k): Yc and Ys
+    __device__ void degree(int n, int k, double2 f, double& yc, double& ys) {
+        if (n > k) {
+            const double p = (f.x * t) * p1 - f.y * p2;
+            p2 = p1;
+            p1 = p;
+        }
+        const double pk = p1 * rad;
+        rad *= u;
+        yc = pk * ck;
+        ys = pk * sk;
+    }
+};
+
+// out [P][ldt], transposed: the rows of the orders blockIdx.y * kPotOrders ... at the 64 points (pairs) blockIdx.x * 64 ...  One lane
+// is one point; kPairs runs the recursions at a and at b in lockstep and stores Y(b) - Y(a).  The orders below the workgroup's first
+// only carry the sectoral seed and (R/r)^(k+1) along, so every workgroup sees the values of the one-pass recursion.  Degrees below
+// min_degree are computed and not stored; row(n, k) = n^2 - min_degree^2 + (0 | 2k - 1 cosine | 2k sine).  An entry is
+// (Y * scale) * sqrt(w) (w NULL: 1).  No workspace but the recursion factors ab of degree N, read with wave-uniform addresses.
+template <bool kPairs>
+__global__ __launch_bounds__(kPotLanes) void potential_design_kernel(int N, int min_degree, int npts, const double* __restrict__ xyz_a,
+                                                                     const double* __restrict__ xyz_b, const double2* __restrict__ ab,
+                                                                     const double* __restrict__ w, double R, double scale, double* __restrict__ out,
+                                                                     size_t ldt) {
+    constexpr int kSets = kPairs ? 2 : 1;
+    const int pt = blockIdx.x * kPotLanes + threadIdx.x;
+    const bool ok = pt < npts;
+    const size_t at = (size_t)(ok ? pt : 0);
+    SolidColumn c[kSets];
+    c[0].start(xyz_a + at * 3, R);
+    if (kPairs) c[kSets - 1].start(xyz_b + at * 3, R);
+    const double sw = w ? sqrt(w[at]) : 1.0;
+    const int k0 = blockIdx.y * kPotOrders, k1 = min(k0 + kPotOrders - 1, N);
+    const long long below = (long long)min_degree * min_degree;
+    for (int k = 0; k <= k1; ++k) {
+        const bool live = k >= k0;
+#pragma unroll
+        for (int i = 0; i < kSets; ++i) c[i].order(k, live);
+        if (!live) continue;
+        const int off = order_offset(N, k);
+        for (int n = k; n <= N; ++n) {
+            const double2 f = ab[off + n - k];
+            double yc[kSets], ys[kSets];
+#pragma unroll
+            for (int i = 0; i < kSets; ++i) c[i].degree(n, k, f, yc[i], ys[i]);
+            if (ok && n >= min_degree) {
+                const double vc = kPairs ? yc[kSets - 1] - yc[0] : yc[0];
+                double* o = out + (size_t)((long long)n * n - below + (k == 0 ? 0 : 2 * k - 1)) * ldt + pt;
+                o[0] = (vc * scale) * sw;
+                if (k >= 1) {
+                    const double vs = kPairs ? ys[kSets - 1] - ys[0] : ys[0];
+                    o[ldt] = (vs * scale) * sw;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace shg
 
 using namespace shg;
@@ -512,4 +608,48 @@ extern "C" int shg_los_design(int N, int min_degree, const double* xyz_a, const 
             hipLaunchKernelGGL(los_design_kernel<true>, grid, dim3(256), 0, stream, np, P, xa, xb, nullptr, d.Y, d.ldy, (size_t)d.pass, d.slot, d.factor, w,
                                scale, At + p0, (size_t)ldt);
     });
+}
+
+// The potential's two design matrices behind their checks: the recursion factors of degree N are the only workspace, and one launch
+// covers all points (no Y, no table, no passes).
+template <bool kPairs>
+static int potential_design(const char* fn, int N, int min_degree, const double* xyz_a, const double* xyz_b, int M, const double* weights, double GM,
+                            double R, double* At, int ldt, hipStream_t stream) {
+    const size_t packed = (size_t)packed_count(N);
+    Workspace ws = Workspace::plain(stream);
+    double2* ab;
+    if (!ws.alloc(ab, packed)) return fail(SHG_ERR_NOMEM, "%s: workspace allocation failed", fn);
+    {
+        std::vector<double> a, b, h(2 * packed);
+        recursion_tables(N, a, b);
+        for (size_t i = 0; i < a.size(); ++i) {
+            h[2 * i] = a[i];
+            h[2 * i + 1] = b[i];
+        }
+        SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipStreamSynchronize(stream));
+    }
+    hipLaunchKernelGGL(potential_design_kernel<kPairs>, dim3(ceil_div(M, kPotLanes), ceil_div(N + 1, kPotOrders)), dim3(kPotLanes), 0, stream, N, min_degree,
+                       M, xyz_a, xyz_b, ab, weights, R, GM / R, At, (size_t)ldt);
+    SHG_HIP(hipGetLastError());
+    return SHG_OK;
+}
+
+extern "C" int shg_potential_design(int N, int min_degree, const double* xyz, int M, const double* weights, double GM, double R, double* At, int ldt,
+                                    void* stream) {
+    const char* fn = "shg_potential_design";
+    // weights are per point or absent, as in shg_los_design: the layout check of check_design cannot fail here
+    if (int rc = check_design(fn, N, min_degree, 0, M, 1, weights ? SHG_WEIGHTS_POINT : SHG_WEIGHTS_NONE, GM, R, ldt)) return rc;
+    if (M == 0) return SHG_OK;
+    SHG_REQUIRE(xyz && At, "%s: NULL pointer", fn);
+    return potential_design<false>(fn, N, min_degree, xyz, nullptr, M, weights, GM, R, At, ldt, (hipStream_t)stream);
+}
+
+extern "C" int shg_potential_difference_design(int N, int min_degree, const double* xyz_a, const double* xyz_b, int M, const double* weights, double GM,
+                                               double R, double* At, int ldt, void* stream) {
+    const char* fn = "shg_potential_difference_design";
+    if (int rc = check_design(fn, N, min_degree, 0, M, 1, weights ? SHG_WEIGHTS_POINT : SHG_WEIGHTS_NONE, GM, R, ldt)) return rc;
+    if (M == 0) return SHG_OK;
+    SHG_REQUIRE(xyz_a && xyz_b && At, "%s: NULL pointer", fn);
+    return potential_design<true>(fn, N, min_degree, xyz_a, xyz_b, M, weights, GM, R, At, ldt, (hipStream_t)stream);
 }

@@ -14,6 +14,10 @@
 // gradients' composition fused: the three first-derivative sets it needs are formed in registers), and solid_points_kernel runs one
 // column recursion per point and (n', k) for all components and every epoch of a pass.  xx, yy and zz each come from their own
 // combination: the trace is a check, not an identity.
+//
+// The potential itself is the zeroth member of the family (Potential below): no D at all, the coefficients are the (C, S) of (n, k),
+//   V = GM / R sum_{n, k} (R/r)^(n+1) P_{nk} (cos(k lon) C_{nk} + sin(k lon) S_{nk}),
+// a point synthesis of degree N with one component.
 #include "common.h"
 
 #include <climits>
@@ -162,15 +166,25 @@ __global__ __launch_bounds__(256) void gradients_combine_kernel(CoefSource src, 
     for (int j = 0; j < 12; ++j) s.q[j * EP] = out[j];
 }
 
+// the zeroth member: (A, B) = (C, S) of (n, k) itself, the sine of order 0 zero
+__global__ __launch_bounds__(256) void potential_combine_kernel(CoefSource src, int EP, int b_first, int passes, double* __restrict__ Q) {
+    CombineSlot s;
+    if (!combine_slot(src.N, 2, EP, b_first, passes, Q, s)) return;
+    const bool live = s.b < src.B;
+    s.q[0] = live ? src.cos_coef(s.b, s.np, s.k) : 0.0;
+    s.q[EP] = live && s.k >= 1 ? src.sin_coef(s.b, s.np, s.k) : 0.0;
+}
+
 // degrees per LDS stage of a point kernel with C components and EP epochs: 64, or 32 where 64 would take more than 24 KB (3 x 16: 25 KB
-// for 32 degrees with a and b; 6 x 4: 24 KB for 64; 6 workgroups per CU either way)
+// for 32 degrees with a and b; 6 x 4: 24 KB for 64; 6 workgroups per CU either way; 1 x 16: 16 KB for 64, 1 x 1: 1 KB, two doubles per
+// degree, which the double2 copies of the staging still cover exactly)
 constexpr int stage_degrees(int C, int EP) { return 64 * 2 * C * EP * 8 > (24 << 10) ? 32 : 64; }
 
 // 256 lanes = 256 points x EP epochs (grid.y = pass), C components each.  Per order k the 2 C coefficients of every epoch are staged in
 // LDS in chunks of kDegrees degrees, together with the recursion factors a, b of degree Nq; the degree loop reads them as LDS
 // broadcasts, so any degree fits.  r and the longitude come from xyz as grid.cartesian2spherical computes them, and so does the
-// colatitude unless kDirect; (R/r)^(n'+1) is carried along the degree loop.  C = 3 writes g [b][pt][3]; C = 6 (xx, xy, xz, yy, yz, zz)
-// writes T [b][pt][3][3], each off-diagonal value twice.
+// colatitude unless kDirect; (R/r)^(n'+1) is carried along the degree loop.  C = 1 writes V [b][pt]; C = 3 writes g [b][pt][3]; C = 6
+// (xx, xy, xz, yy, yz, zz) writes T [b][pt][3][3], each off-diagonal value twice.
 template <int C, int EP, int kDegrees, bool kDirect>
 __global__ __launch_bounds__(256) void solid_points_kernel(int Nq, int npts, int B, const double* __restrict__ xyz, long long xyz_pass_stride,
                                                            const double* __restrict__ ab, const double* __restrict__ Q, double R, double scale,
@@ -253,7 +267,9 @@ __global__ __launch_bounds__(256) void solid_points_kernel(int Nq, int npts, int
         for (int e = 0; e < EP; ++e) {
             const int b = pass * EP + e;
             if (b < B) {
-                if constexpr (C == 3) {
+                if constexpr (C == 1) {
+                    out[(size_t)b * npts + pt] = acc[0][e] * scale;
+                } else if constexpr (C == 3) {
                     double* o = out + ((size_t)b * npts + pt) * 3;
                     o[0] = acc[0][e] * scale;
                     o[1] = acc[1][e] * scale;
@@ -277,7 +293,7 @@ __global__ __launch_bounds__(256) void solid_points_kernel(int Nq, int npts, int
     }
 }
 
-// The two functionals.  kOffset: Nq = N + kOffset; kComponents: C of the kernels (2 C numbers per (n', k) in Q); kValues: values per
+// The three functionals.  kOffset: Nq = N + kOffset; kComponents: C of the kernels (2 C numbers per (n', k) in Q); kValues: values per
 // point and epoch; kMaxEP: epochs per pass with shared points are the smallest of 1, 4, 16 that holds all epochs, kMaxEP at most.
 struct Acceleration {
     static constexpr int kOffset = 1, kComponents = 3, kValues = 3, kMaxEP = 16;
@@ -286,6 +302,18 @@ struct Acceleration {
     static constexpr auto kCombine = acceleration_combine_kernel;
     static constexpr const char* kNoWorkspace = "shg_acceleration_points: workspace allocation failed";
     static double scale(double GM, double R) { return GM / (2.0 * R * R); }
+};
+
+struct Potential {
+    // EP = 16 is 16 accumulators: 120 VGPRs, no spills, 4 waves per SIMD, a 64-degree stage of 17 KB.  EP = 32 also compiles without
+    // spills (151 VGPRs) but falls to 3 waves and a 32-degree stage (twice the barriers) to halve a recursion that is already a
+    // sixteenth of the loop: 16 stays
+    static constexpr int kOffset = 0, kComponents = 1, kValues = 1, kMaxEP = 16;
+    static constexpr bool kDirect = false;                           // the reference's colatitude form, as the acceleration uses
+    static constexpr bool kCheckQ = false;
+    static constexpr auto kCombine = potential_combine_kernel;
+    static constexpr const char* kNoWorkspace = "shg_potential_points: workspace allocation failed";
+    static double scale(double GM, double R) { return GM / R; }
 };
 
 struct Gradients {
@@ -399,4 +427,18 @@ extern "C" int shg_gravitational_gradients_points_om(int N, const double* xyz, i
     SHG_REQUIRE(Bpad >= B, "shg_gravitational_gradients_points_om: Bpad %d below B %d", Bpad, B);
     if (M == 0 || B == 0) return SHG_OK;
     return solid_points<Gradients>(N, xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, T, (hipStream_t)stream);
+}
+
+extern "C" int shg_potential_points(int N, const double* xyz, int M, int layout, const double* anm, int B, double GM, double R, double* V, void* stream) {
+    if (int rc = check_points<Potential>("shg_potential_points", N, xyz, M, layout, anm, B, GM, R, V)) return rc;
+    if (M == 0 || B == 0) return SHG_OK;
+    return solid_points<Potential>(N, xyz, M, layout, CoefSource{anm, nullptr, N, B, 0}, GM, R, V, (hipStream_t)stream);
+}
+
+extern "C" int shg_potential_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM, double R, double* V,
+                                       void* stream) {
+    if (int rc = check_points<Potential>("shg_potential_points_om", N, xyz, M, layout, om, B, GM, R, V)) return rc;
+    SHG_REQUIRE(Bpad >= B, "shg_potential_points_om: Bpad %d below B %d", Bpad, B);
+    if (M == 0 || B == 0) return SHG_OK;
+    return solid_points<Potential>(N, xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, V, (hipStream_t)stream);
 }

@@ -760,6 +760,13 @@ def gravitational_gradients_points(max_degree, xyz, coefficients, GM, R):
     return _functional_points('gravitational_gradients_points', (3, 3), max_degree, xyz, coefficients, GM, R)
 
 
+def potential_points(max_degree, xyz, coefficients, GM, R):
+    """Gravitational potential V [B, M] (device, m^2/s^2) of the fields `coefficients` -- a batch [B, N+1, N+1] or an
+    OrderMajorSeries, read in its own layout -- with constants GM and R at the positions xyz [M, 3] (shared by all fields) or
+    [B, M, 3] (per field) (shg_potential_points / shg_potential_points_om)."""
+    return _functional_points('potential_points', (), max_degree, xyz, coefficients, GM, R)
+
+
 def check_observation_weights(weights, points, components=3):
     """The layout of the weights of `points` observed positions with `components` observed values each: None (returns 0), w [M] per
     point (1) or w [M, components] per component (2), finite and >= 0; ValueError otherwise.  Host arrays are checked on the host,
@@ -959,6 +966,61 @@ def los_design_pass(max_degree):
     if count < 0:
         raise ValueError('max_degree {0} is out of range'.format(max_degree))
     return count
+
+
+def check_point_weights(weights, M):
+    """Weights of observations with one value per point (pair): None (returns 0) or w [M], finite and >= 0 (returns 1); ValueError
+    otherwise."""
+    layout = check_observation_weights(weights, M, 1)
+    if layout and len(weights.shape) != 1:
+        raise ValueError('weights must have shape ({0},), got {1}'.format(M, tuple(weights.shape)))
+    return layout
+
+
+def potential_design(max_degree, xyz, GM, R, min_degree=0, weights=None):
+    """Transposed design matrix At [P, M] (device) of the gravitational potential at the positions xyz [M, 3]: At[p, i] is the
+    derivative of V at point i with respect to coefficient p of utilities.ravel_coefficients(., min_degree, max_degree),
+    P = (max_degree + 1)^2 - min_degree^2 (shg_potential_design).  weights [M] scale the entries by sqrt(w)."""
+    min_degree, max_degree = check_degrees(min_degree, max_degree)
+    layout = check_point_weights(weights, check_positions(xyz))
+    x = to_device(xyz)
+    return potential_design_checked(max_degree, min_degree, x, to_device(weights, x.device) if layout else None, GM, R)
+
+
+def potential_design_checked(max_degree, min_degree, x, weights, GM, R):
+    """shg_potential_design on device tensors that potential_design (or NormalEquations.from_potentials, once for all its blocks) has
+    checked: positions x [M, 3], weights [M] or None."""
+    torch = require_gpu()
+    M = int(x.shape[0])
+    P = (max_degree + 1) ** 2 - min_degree ** 2
+    out = torch.empty((P, M), dtype=torch.float64, device=x.device)
+    _lib.call('shg_potential_design', max_degree, min_degree, _ptr(x), M, None if weights is None else _ptr(weights), float(GM), float(R), _ptr(out),
+              M, _stream())
+    return out
+
+
+def potential_difference_design(max_degree, xyz_a, xyz_b, GM, R, min_degree=0, weights=None):
+    """Transposed design matrix At [P, M] (device) of the potential difference of the satellite pairs xyz_a [M, 3], xyz_b [M, 3]:
+    At[p, i] is the derivative of V(b_i) - V(a_i) with respect to coefficient p of utilities.ravel_coefficients(., min_degree,
+    max_degree) (shg_potential_difference_design).  A pair with a == b is legal and gives a zero column; weights [M] scale the entries
+    by sqrt(w)."""
+    min_degree, max_degree = check_degrees(min_degree, max_degree)
+    layout = check_point_weights(weights, check_pair_positions(xyz_a, xyz_b))
+    a = to_device(xyz_a)
+    return potential_difference_design_checked(max_degree, min_degree, a, to_device(xyz_b, a.device), to_device(weights, a.device) if layout else None,
+                                               GM, R)
+
+
+def potential_difference_design_checked(max_degree, min_degree, a, b, weights, GM, R):
+    """shg_potential_difference_design on device tensors that potential_difference_design (or
+    NormalEquations.from_potential_differences, once for all its blocks) has checked: positions a, b [M, 3], weights [M] or None."""
+    torch = require_gpu()
+    M = int(a.shape[0])
+    P = (max_degree + 1) ** 2 - min_degree ** 2
+    out = torch.empty((P, M), dtype=torch.float64, device=a.device)
+    _lib.call('shg_potential_difference_design', max_degree, min_degree, _ptr(a), _ptr(b), M, None if weights is None else _ptr(weights), float(GM),
+              float(R), _ptr(out), M, _stream())
+    return out
 
 
 def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
@@ -1308,8 +1370,9 @@ def gemm_ex_args(A, B, out, transa=False, transb=False):
     if tuple(out.shape[-2:]) != (M, N):
         raise ValueError('gemm_ex: output must be ({0}, {1})'.format(M, N))
     stride = lambda t: t.stride(0) if t.dim() == 3 and t.shape[0] > 1 else 0      # noqa: E731
-    return (bool(transa), bool(transb), M, N, K, A, max(A.stride(-2), 1), stride(A), B, max(B.stride(-2), 1), stride(B),
-            out, max(out.stride(-2), 1), stride(out), batch)
+    # a single row is never stepped over: torch leaves the stride of an axis of size 1 arbitrary (1 for the transpose of a column)
+    ld = lambda t: max(t.stride(-2), 1) if t.shape[-2] > 1 else max(t.stride(-2), t.shape[-1], 1)      # noqa: E731
+    return (bool(transa), bool(transb), M, N, K, A, ld(A), stride(A), B, ld(B), stride(B), out, ld(out), stride(out), batch)
 
 
 def gemm_ex(A, B, out, transa=False, transb=False, alpha=1.0, beta=0.0, flags=0):

@@ -304,6 +304,31 @@ class PotentialCoefficients:
         l = _project_line_of_sight(g, xyz_a, xyz_b, directions)
         return l if as_tensor else engine.to_host(l)
 
+    def gravitational_potential(self, xyz, as_tensor=False):
+        """
+        Gravitational potential V [m^2/s^2] at cartesian positions xyz (M, 3): [M], the functional whose gradient is
+        gravitational_acceleration.  There is no host implementation: the GPU kernel (shg_potential_points) always computes it.  It is
+        the observation of the energy-balance approach, known up to one constant per arc (lstsq.ArcParameters with
+        lstsq.arc_basis(arcs, M, degree=0)); the centrifugal potential and the dissipative integrals of the energy equation are the
+        caller's reduction.  Returns an ndarray, or the float64 device tensor with as_tensor=True; xyz may be an ndarray or a device
+        tensor.
+        """
+        engine.check_positions(xyz)
+        V = engine.potential_points(self.max_degree, xyz, self.anm[np.newaxis, :, :], self.GM, self.R)[0]
+        return V if as_tensor else engine.to_host(V)
+
+    def potential_difference(self, xyz_a, xyz_b, as_tensor=False):
+        """
+        Potential difference V(b_i) - V(a_i) [m^2/s^2] of M satellite pairs at the cartesian positions xyz_a (M, 3) and xyz_b (M, 3):
+        [M], the inter-satellite observation of the energy-balance approach.  Pairs may coincide (their difference is zero).  One call
+        of the GPU potential kernel (shg_potential_points) on the stacked 2 M points, then the difference in torch.  Returns an
+        ndarray, or the float64 device tensor with as_tensor=True.
+        """
+        M = engine.check_pair_positions(xyz_a, xyz_b)
+        V = self.gravitational_potential(_stack_pairs(xyz_a, xyz_b), as_tensor=True)
+        d = V[M:] - V[:M]
+        return d if as_tensor else engine.to_host(d)
+
 
 def _host_legendre_per_order(max_degree, order, colat):
     """Host NumPy per-order Legendre recursion (formulas of grates/utilities.py:62-115, 138-151) for the few
@@ -371,6 +396,34 @@ def line_of_sight_design_matrix(xyz_a, xyz_b, min_degree, max_degree, GM=3.98600
     block by block); the transposition here is a copy meant for modest sizes.
     """
     A = engine.los_design(max_degree, xyz_a, xyz_b, GM, R, min_degree, directions, weights).t().contiguous()
+    return A if as_tensor else engine.to_host(A)
+
+
+def potential_design_matrix(xyz, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, as_tensor=False):
+    """
+    Design matrix A [M, P] of the gravitational potential at the cartesian positions xyz (M, 3) with respect to the coefficients of
+    degrees min_degree .. max_degree: one row per point, the columns follow utilities.ravel_coefficients, so that
+    ``A @ ravel_coefficients(anm, min_degree, max_degree)`` equals ``gravitational_potential(xyz)`` of a field without coefficients
+    below min_degree.  weights (M,) scale the rows by sqrt(w).  Always computed on the GPU (shg_potential_design); returns an ndarray,
+    or the float64 device tensor with as_tensor=True.  The kernel builds the transposed matrix (engine.potential_design, what
+    NormalEquations.from_potentials accumulates block by block); the transposition here is a copy meant for modest sizes.
+    """
+    A = engine.potential_design(max_degree, xyz, GM, R, min_degree, weights).t().contiguous()
+    return A if as_tensor else engine.to_host(A)
+
+
+def potential_difference_design_matrix(xyz_a, xyz_b, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, as_tensor=False):
+    """
+    Design matrix A [M, P] of the potential difference V(b_i) - V(a_i) of M satellite pairs at the cartesian positions xyz_a (M, 3) and
+    xyz_b (M, 3) with respect to the coefficients of degrees min_degree .. max_degree: one row per pair, the columns follow
+    utilities.ravel_coefficients, so that ``A @ ravel_coefficients(anm, min_degree, max_degree)`` equals
+    ``potential_difference(xyz_a, xyz_b)`` of a field without coefficients below min_degree.  Swapping the satellites negates the
+    matrix bitwise; a pair with both satellites at one position is legal and gives a zero row.  weights (M,) scale the rows by sqrt(w).
+    Always computed on the GPU (shg_potential_difference_design); returns an ndarray, or the float64 device tensor with as_tensor=True.
+    The kernel builds the transposed matrix (engine.potential_difference_design, what NormalEquations.from_potential_differences
+    accumulates block by block); the transposition here is a copy meant for modest sizes.
+    """
+    A = engine.potential_difference_design(max_degree, xyz_a, xyz_b, GM, R, min_degree, weights).t().contiguous()
     return A if as_tensor else engine.to_host(A)
 
 
@@ -712,6 +765,30 @@ class TimeSeries:
         g = self.gravitational_acceleration(_stack_pairs(xyz_a, xyz_b), as_tensor=True)
         l = _project_line_of_sight(g, xyz_a, xyz_b, directions)
         return l if as_tensor else engine.to_host(l)
+
+    def gravitational_potential(self, xyz, as_tensor=False):
+        """
+        Gravitational potential [m^2/s^2] of every epoch, [T, M], at the positions xyz: [M, 3] for all epochs or [T, M, 3] (points of
+        their own per epoch).  Branches as gravitational_acceleration does: one GPU call for all epochs (shg_potential_points); a
+        device series is read in its own order-major layout and never leaves the device; fields with different GM or R take one call
+        each.  There is no host implementation.  Returns an ndarray, or the float64 device tensor with as_tensor=True.
+        """
+        return self._functional_at_points(engine.potential_points, 'gravitational_potential', xyz, as_tensor)
+
+    def potential_difference(self, xyz_a, xyz_b, as_tensor=False):
+        """
+        Potential difference [m^2/s^2] of every epoch, [T, M], d[t, i] = V_t(b_i) - V_t(a_i), of M satellite pairs at the positions
+        xyz_a and xyz_b: both [M, 3] for all epochs or both [T, M, 3] (pairs of their own per epoch).  One gravitational_potential call
+        on the stacked 2 M points, then the difference in torch.  Returns an ndarray, or the float64 device tensor with as_tensor=True.
+        """
+        engine.check_acceleration_points(xyz_a, len(self))
+        shape = tuple(xyz_a.shape)
+        if tuple(xyz_b.shape) != shape:
+            raise ValueError('the positions of the two satellites must have the same shape, got {0} and {1}'.format(shape, tuple(xyz_b.shape)))
+        V = self.gravitational_potential(_stack_pairs(xyz_a, xyz_b), as_tensor=True)
+        M = shape[-2]
+        d = V[:, M:] - V[:, :M]
+        return d if as_tensor else engine.to_host(d)
 
     def detrend(self, basis_functions):
         """

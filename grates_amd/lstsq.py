@@ -484,6 +484,39 @@ def _los_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, 
     return _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
 
 
+def _check_scalar_observations(values, M, name, unit):
+    """one observed value per point (pair): `name` [M]"""
+    if len(values.shape) != 1:
+        raise ValueError('{0} must have shape (M,), got {1}'.format(name, tuple(values.shape)))
+    if int(values.shape[0]) != M:
+        raise ValueError('{0} {1} but {2} {3}'.format(M, unit, int(values.shape[0]), name))
+
+
+def _potential_observations(xyz, potentials, min_degree, max_degree, GM, R, weights):
+    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
+    M = engine.check_positions(xyz)
+    _check_scalar_observations(potentials, M, 'potentials', 'positions')
+    layout = engine.check_point_weights(weights, M)
+
+    def upload(w):
+        x, l = engine.to_device(xyz), engine.to_device(potentials).reshape(-1, 1)
+        return l, lambda first, last: engine.potential_design_checked(max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R)
+    return _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
+
+
+def _potential_difference_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights):
+    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
+    M = engine.check_pair_positions(xyz_a, xyz_b)
+    _check_scalar_observations(differences, M, 'differences', 'pairs')
+    layout = engine.check_point_weights(weights, M)
+
+    def upload(w):
+        a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
+        return l, lambda first, last: engine.potential_difference_design_checked(
+            max_degree, min_degree, a[first:last], b[first:last], None if w is None else w[first:last], GM, R)
+    return _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
+
+
 class _StochasticModel:
     """The stochastic model of one from_* or of_* call beyond the weights: noise_model and arcs as NormalEquations.from_accelerations
     takes them, parameters an ArcParameters or None; of(model) reads them from None, a ColouredNoise or an ArcParameters.  check(M, K)
@@ -645,7 +678,7 @@ class _ArcSweep:
         if ended:
             D = torch.empty((ended * Kc, P, u), dtype=torch.float64, device=At.device)
             engine.gemm_ex(C[:, :ended].permute(1, 2, 0, 3).reshape(ended * Kc, P, u), s.R_d[a0 * Kc:(a0 + ended) * Kc], D)
-            D = D.permute(1, 0, 2).reshape(P, ended * Kc * u)
+            D = D.permute(1, 0, 2).reshape(P, ended * Kc * u).contiguous()                               # u = 1: the reshape alone is a strided view
             self.pending.append(D)
             if self.columns is not None:
                 self.columns.append(D)
@@ -1119,6 +1152,45 @@ class NormalEquations:
                                          directions=directions, weights=weights)
         return cls._normals(observations, _StochasticModel(), block_points)
 
+    @classmethod
+    def from_potentials(cls, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
+        """
+        Normal equations of the coefficients of degrees min_degree .. max_degree (in the order of utilities.ravel_coefficients) from
+        the gravitational potential V [M] observed at the cartesian positions xyz [M, 3] (host arrays or device tensors; usually
+        reduced by a reference field): the observation of the energy-balance approach, the kinetic energy of a satellite less the
+        terms the caller has removed (the centrifugal potential and the dissipative integrals of the energy equation are the caller's
+        reduction and no part of this).  weights [M] (finite, >= 0; default 1) are those of the observations.
+
+        The energy integral leaves one unknown constant per arc: ArcParameters(arc_basis(arcs, M, degree=0), arcs).from_potentials(the
+        same arguments) estimates and eliminates it; use min_degree >= 1 there, the constant of an arc and C_00 are hardly separable.
+        ColouredNoise(noise_model, arcs).from_potentials decorrelates every arc with one scalar AutoregressiveModelSequence.
+
+        The block loop of from_accelerations with At [P, Mb] from shg_potential_design; the default block is the largest multiple of
+        256 points that keeps At within 256 MB, at least 256.  Returns NormalEquations with a one-block BlockMatrix [P, P] and the
+        right-hand side [P, 1] on the device, and observation_count = M.  Normals of the same degrees add up through accumulate_normals.
+        """
+        observations = _potential_observations(xyz=xyz, potentials=potentials, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
+        return cls._normals(observations, _StochasticModel(), block_points)
+
+    @classmethod
+    def from_potential_differences(cls, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None,
+                                   block_points=None):
+        """
+        Normal equations of the coefficients of degrees min_degree .. max_degree (in the order of utilities.ravel_coefficients) from
+        potential differences V(b_i) - V(a_i) [M] of M satellite pairs at the cartesian positions xyz_a [M, 3] and xyz_b [M, 3] (host
+        arrays or device tensors; usually reduced by a reference field): the inter-satellite observation of the energy-balance approach,
+        from the range-rate of the pair, with the caller's reductions as in from_potentials.  Pairs may coincide (a zero row).  weights
+        [M] (finite, >= 0; default 1) are those of the observations.  ArcParameters and ColouredNoise bind it as they bind
+        from_potentials.
+
+        The block loop of from_accelerations with At [P, Mb] from shg_potential_difference_design; the default block as in
+        from_potentials.  Returns NormalEquations with a one-block BlockMatrix [P, P] and the right-hand side [P, 1] on the device, and
+        observation_count = M.
+        """
+        observations = _potential_difference_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree,
+                                                          max_degree=max_degree, GM=GM, R=R, weights=weights)
+        return cls._normals(observations, _StochasticModel(), block_points)
+
     def __cholesky(self):
         """factor the matrix once; a matrix that already holds covariances cannot be factored again (ValueError, as upstream)"""
         if self.status == 'covariance_matrix' or self.status not in ('normal_matrix', 'cholesky_factor'):
@@ -1220,6 +1292,16 @@ class _BoundModel:
                            weights=None, block_points=None):
         observations = _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
                                          directions=directions, weights=weights)
+        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+
+    def from_potentials(self, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
+        observations = _potential_observations(xyz=xyz, potentials=potentials, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
+        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+
+    def from_potential_differences(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None,
+                                   block_points=None):
+        observations = _potential_difference_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree,
+                                                          max_degree=max_degree, GM=GM, R=R, weights=weights)
         return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
 
 
@@ -1326,6 +1408,21 @@ class PostFit:
         fit = cls(solution, vectors, model, xyz_a)
         observations = _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
                                          directions=directions, weights=weights)
+        return fit._pass(observations, fit.__model, block_points)
+
+    @classmethod
+    def of_potentials(cls, solution, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
+                      model=None, vectors=None):
+        fit = cls(solution, vectors, model, xyz)
+        observations = _potential_observations(xyz=xyz, potentials=potentials, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
+        return fit._pass(observations, fit.__model, block_points)
+
+    @classmethod
+    def of_potential_differences(cls, solution, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06,
+                                 weights=None, block_points=None, model=None, vectors=None):
+        fit = cls(solution, vectors, model, xyz_a)
+        observations = _potential_difference_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree,
+                                                          max_degree=max_degree, GM=GM, R=R, weights=weights)
         return fit._pass(observations, fit.__model, block_points)
 
     def _check(self, parameters):

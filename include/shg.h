@@ -553,6 +553,50 @@ int shg_los_design(int N, int min_degree, const double* xyz_a, const double* xyz
 int shg_los_design_pass(int N);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gravitational potential at points (the zeroth member beside shg_acceleration_points and shg_gravitational_gradients_points; the
+ * reference reaches it only as a grid synthesis with kernel 'potential')
+ *   V [B][M] (m^2/s^2), V = GM / R sum_{n,k} (R/r)^(n+1) P_nk (C_nk cos(k lon) + S_nk sin(k lon)), of the fields anm [B][N+1][N+1]
+ *   (one GM and R for all) at the Cartesian positions xyz:
+ *     layout SHG_POINTS_SHARED     xyz [M][3], the same points for every field
+ *     layout SHG_POINTS_PER_EPOCH  xyz [B][M][3], points of their own for every field
+ *   A point synthesis of degree N with one component, by the point kernel of shg_acceleration_points (the same column recursion, the
+ *   colatitude from atan2 as there), up to 16 epochs per pass.  No atomics: a field's result does not depend on the other fields of
+ *   the call or on the layout, and repeated calls are bitwise equal.  Points at the poles and below R are fine; r = 0 is not.
+ *   The centrifugal potential and the dissipative integrals of the energy equation are not part of V: they are the caller's reduction.
+ *   shg_potential_points_om  the same from an order-major series om [(N+1)^2][Bpad] (shg_order_major_pack), Bpad >= B.
+ *   Arguments are checked before the first HIP call (the rules of shg_acceleration_points); nothing to do (M = 0 or B = 0) returns 0 at
+ *   once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_potential_points(int N, const double* xyz, int M, int layout, const double* anm, int B, double GM, double R, double* V,
+                         void* stream);
+int shg_potential_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM, double R,
+                            double* V, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Design matrices of the energy-balance observations: the potential at points, and the potential difference V(b_i) - V(a_i) of
+ * satellite pairs (the partial derivatives of shg_potential_points with respect to the coefficients; no reference counterpart)
+ *   At [P][ldt], transposed like shg_acceleration_design: row p is coefficient p of utilities.ravel_coefficients(., min_degree, N),
+ *   the M points xyz [M][3] (pairs xyz_a [M][3], xyz_b [M][3]) innermost (ldt >= M; the entries from M to ldt of a row are not
+ *   touched).  For a field without coefficients below min_degree, sum_p At[p][i] x_p = V[i] of shg_potential_points (V(b_i) - V(a_i)).
+ *   An entry is one solid harmonic of degree N, d V / d C_nm = GM / R Yc_nm and d V / d S_nm = GM / R Ys_nm: one kernel runs the
+ *   column recursion of shg_acceleration_design's harmonics (the same operation order, at degree N) with one lane per point, at both
+ *   satellites of a pair in lockstep, and stores every value straight to row n^2 - min_degree^2 + (0 | 2k - 1 cosine | 2k sine).  No
+ *   workspace beyond the recursion factors, no passes of points.
+ *     shg_potential_design             At[p][i] = (Y_p(x_i) * GM / R) * sqrt(w_i), in that order
+ *     shg_potential_difference_design  At[p][i] = ((Y_p(b_i) - Y_p(a_i)) * GM / R) * sqrt(w_i): swapping a and b negates At bitwise, and
+ *                                      a pair with a_i == b_i gives an exactly zero column i (nothing divides by the separation: such
+ *                                      pairs are legal)
+ *   weights [M], finite and >= 0, or NULL.  No atomics: the entries of a point do not depend on the other points of the call, and
+ *   repeated calls are bitwise equal.  Points at the poles and below R are fine; r = 0 is not.
+ *   Arguments are checked before the first HIP call (the rules of shg_acceleration_design with N <= 32767: negative sizes,
+ *   min_degree > N, GM or R not finite, R <= 0, ldt < M; NULL positions or At; more than 2^40 values of At); M = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_potential_design(int N, int min_degree, const double* xyz, int M, const double* weights, double GM, double R, double* At, int ldt,
+                         void* stream);
+int shg_potential_difference_design(int N, int min_degree, const double* xyz_a, const double* xyz_b, int M, const double* weights, double GM,
+                                    double R, double* At, int ldt, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decorrelation of coloured observation noise along the point axis (the banded lower-triangular W with W^T W = Sigma^-1 of a sequence
  * of scalar AR models of orders 0 .. q; no reference counterpart)
  *   X [rows][ldx] with M columns in use, row r of channel r % channels: the transposed design matrix At [P][K][ldt] of the three calls
