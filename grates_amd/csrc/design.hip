@@ -11,10 +11,11 @@
 //   d g_z / d C_nm = -2 f0 Yc_{n+1,m}                       d g_z / d S_nm = -2 f0 Ys_{n+1,m}
 // (the minus terms exist for m >= 1 only).  No sum over degrees: an entry is one or two products.
 //
-// Two kernels per pass of points: design_harmonics_kernel runs the column recursion of solid_points_kernel once per point and
-// writes Y [packed (n', k)][2][ldy] of degree N + 1 to a workspace; design_gather_kernel forms every row of At from at most two
-// entries of Y per component, following a host-built table of (slot of Y, factor) terms.  The table is all the gather kernel knows
-// about the acceleration: another linear functional of the solid harmonics is another table.
+// Two kernels per pass of points: design_harmonics_kernel runs the column recursion of the forward kernel (SolidColumn of solid.h,
+// the one definition both sides share) once per point and writes Y [packed (n', k)][2][ldy] of degree N + 1 to a workspace;
+// design_gather_kernel forms every row of At from at most two entries of Y per component, following a host-built table of (slot of
+// Y, factor) terms.  The table is all the gather kernel knows about the acceleration: another linear functional of the solid
+// harmonics is another table.
 //
 // The design matrix of the gradient tensor (second half of this file) is that other table, of at most four terms on Y of degree N + 2,
 // with a gather kernel of its own that rotates the six entries of a point into a per-point instrument frame and keeps only the
@@ -29,20 +30,18 @@
 // The host side is one of each: d_terms is the only host code that uses f-, f0, f+ (both tables are built from it; the formulas
 // themselves are in common.h, shared with the forward kernels), design_passes is the pass driver (pass size, workspace, upload of
 // recursion factors and table) around the launches of an entry point, and check_design holds the argument checks the entry points share.
-#include "common.h"
+#include "solid.h"
 
 #include <cmath>
 #include <memory>
 
 namespace shg {
 
-// 256 lanes = 256 points.  (r, colatitude, longitude) come from xyz as grid.cartesian2spherical computes them (the operation order of
-// solid_points_kernel), (R/r)^(n'+1) is carried along the degree loop.  The recursion factors a, b of one (n', k) lie side by
-// side and are read with wave-uniform addresses: no LDS, whatever the degree.  kDirect takes cos and sin of the colatitude straight from
-// xyz (t = z / r, s = rho / r: the gradient tensor's form, exact next to the axis) instead of the reference's
-// s = sqrt(1 - t^2), which the acceleration and its design matrix follow.  A launch with gridDim.y = 2 runs two sets of npts points,
-// xyz and xyz_second, and writes the second set's harmonics to the columns `second` .. of Y (the two satellites of the line-of-sight
-// design); with gridDim.y = 1 neither is looked at.
+// 256 lanes = 256 points, each running SolidColumn<kDirect> (solid.h: kDirect is the gradient tensor's form of the colatitude, exact
+// next to the axis; the acceleration and its design matrix follow the reference's).  The recursion factors a, b of one (n', k) lie
+// side by side and are read with wave-uniform addresses: no LDS, whatever the degree.  A launch with gridDim.y = 2 runs two sets of
+// npts points, xyz and xyz_second, and writes the second set's harmonics to the columns `second` .. of Y (the two satellites of the
+// line-of-sight design); with gridDim.y = 1 neither is looked at.
 template <bool kDirect>
 __global__ __launch_bounds__(256) void design_harmonics_kernel(int N1, int npts, const double* __restrict__ xyz, const double* __restrict__ xyz_second,
                                                                const double2* __restrict__ ab, double R, double* __restrict__ Y_first, size_t ldy,
@@ -51,38 +50,18 @@ __global__ __launch_bounds__(256) void design_harmonics_kernel(int N1, int npts,
     const bool ok = pt < npts;
     // blockIdx.y = 1 (the line-of-sight design only): a second set of npts points, whose harmonics go to the columns `second` ..
     double* __restrict__ Y = blockIdx.y ? Y_first + second : Y_first;
-    const double* xp = (blockIdx.y ? xyz_second : xyz) + (size_t)(ok ? pt : 0) * 3;
-    const double x = xp[0], y = xp[1], z = xp[2];
-    const double r = sqrt((x * x + y * y) + z * z);                  // np.sum over axis 1: ((x^2 + y^2) + z^2)
-    const double th = atan2(sqrt(x * x + y * y), z);
-    const double lam = atan2(y, x);
-    const double u = R / r;
-    const double t = kDirect ? z / r : cos(th);
-    const double s = kDirect ? sqrt(x * x + y * y) / r : sqrt(1.0 - t * t);
-    double pmm = 1.0, rk = u;                                        // rk = (R/r)^(k+1)
+    SolidColumn<kDirect> col;
+    col.start((blockIdx.y ? xyz_second : xyz) + (size_t)(ok ? pt : 0) * 3, R);
     for (int k = 0; k <= N1; ++k) {
-        if (k == 1)
-            pmm = sqrt(3.0) * s;
-        else if (k >= 2)
-            pmm = sqrt((2.0 * k + 1.0) / (2.0 * k)) * s * pmm;
-        if (k >= 1) rk *= u;
-        double sk, ck;
-        sincos((double)k * lam, &sk, &ck);
-        double p1 = pmm, p2 = 0.0, rad = rk;
+        col.order(k);
         const int off = order_offset(N1, k);
         for (int n = k; n <= N1; ++n) {
-            if (n > k) {
-                const double2 f = ab[off + n - k];
-                const double p = (f.x * t) * p1 - f.y * p2;
-                p2 = p1;
-                p1 = p;
-            }
-            const double pk = p1 * rad;
-            rad *= u;
+            double yc, ys;
+            col.degree(n, k, ab + off + n - k, yc, ys);
             if (ok) {
                 double* yo = Y + (size_t)(off + n - k) * 2 * ldy + pt;
-                yo[0] = pk * ck;
-                yo[ldy] = pk * sk;
+                yo[0] = yc;
+                yo[ldy] = ys;
             }
         }
     }
@@ -349,49 +328,6 @@ __global__ __launch_bounds__(256) void los_design_kernel(int npairs, long long r
 constexpr int kPotLanes = 64;                         // points per workgroup: one wave, whose store covers 64 consecutive doubles of a row
 constexpr int kPotOrders = 4;                         // orders per workgroup (blockIdx.y)
 
-// The column recursion of design_harmonics_kernel<false> at one point, in its operation order, one call per step.
-struct SolidColumn {
-    double t, s, u, lam, pmm, rk;                     // rk = (R/r)^(k+1)
-    double p1, p2, rad, ck, sk;
-    __device__ void start(const double* xp, double R) {
-        const double x = xp[0], y = xp[1], z = xp[2];
-        const double r = sqrt((x * x + y * y) + z * z);
-        const double th = atan2(sqrt(x * x + y * y), z);
-        lam = atan2(y, x);
-        u = R / r;
-        t = cos(th);
-        s = sqrt(1.0 - t * t);
-        pmm = 1.0;
-        rk = u;
-    }
-    // on to order k (every order from 0 in turn); live: the degrees of this order follow
-    __device__ void order(int k, bool live) {
-        if (k == 1)
-            pmm = sqrt(3.0) * s;
-        else if (k >= 2)
-            pmm = sqrt((2.0 * k + 1.0) / (2.0 * k)) * s * pmm;
-        if (k >= 1) rk *= u;
-        if (live) {
-            sincos((double)k * lam, &sk, &ck);
-            p1 = pmm;
-            p2 = 0.0;
-            rad = rk;
-        }
-    }
-    // degree n of order k (every degree from k in turn), f = (a, b) of (n, k): Yc and Ys
-    __device__ void degree(int n, int k, double2 f, double& yc, double& ys) {
-        if (n > k) {
-            const double p = (f.x * t) * p1 - f.y * p2;
-            p2 = p1;
-            p1 = p;
-        }
-        const double pk = p1 * rad;
-        rad *= u;
-        yc = pk * ck;
-        ys = pk * sk;
-    }
-};
-
 // out [P][ldt], transposed: the rows of the orders blockIdx.y * kPotOrders ... at the 64 points (pairs) blockIdx.x * 64 ...  One lane
 // is one point; kPairs runs the recursions at a and at b in lockstep and stores Y(b) - Y(a).  The orders below the workgroup's first
 // only carry the sectoral seed and (R/r)^(k+1) along, so every workgroup sees the values of the one-pass recursion.  Degrees below
@@ -406,7 +342,7 @@ __global__ __launch_bounds__(kPotLanes) void potential_design_kernel(int N, int 
     const int pt = blockIdx.x * kPotLanes + threadIdx.x;
     const bool ok = pt < npts;
     const size_t at = (size_t)(ok ? pt : 0);
-    SolidColumn c[kSets];
+    SolidColumn<false> c[kSets];                                     // the reference's colatitude form, as the forward potential uses
     c[0].start(xyz_a + at * 3, R);
     if (kPairs) c[kSets - 1].start(xyz_b + at * 3, R);
     const double sw = w ? sqrt(w[at]) : 1.0;
@@ -422,7 +358,7 @@ __global__ __launch_bounds__(kPotLanes) void potential_design_kernel(int N, int 
             const double2 f = ab[off + n - k];
             double yc[kSets], ys[kSets];
 #pragma unroll
-            for (int i = 0; i < kSets; ++i) c[i].degree(n, k, f, yc[i], ys[i]);
+            for (int i = 0; i < kSets; ++i) c[i].degree(n, k, &f, yc[i], ys[i]);
             if (ok && n >= min_degree) {
                 const double vc = kPairs ? yc[kSets - 1] - yc[0] : yc[0];
                 double* o = out + (size_t)((long long)n * n - below + (k == 0 ? 0 : 2 * k - 1)) * ldt + pt;
@@ -462,8 +398,8 @@ struct DesignPass {
 };
 
 // The scaffolding of a design matrix on the solid harmonics of degree Ny at `sets` (1 | 2) sets of M points: pass size, workspace,
-// upload of the recursion factors and of the term table (`entries` per row), a wait for the stream (the host tables go out of scope),
-// then launch(pass, p0, np) for the points p0 .. p0 + np of every pass, which enqueues the kernels of its functional.
+// upload of the recursion factors (solid.h) and of the term table (`entries` per row), a wait for the stream (the host table goes out
+// of scope), then launch(pass, p0, np) for the points p0 .. p0 + np of every pass, which enqueues the kernels of its functional.
 template <class Launch>
 static int design_passes(const char* fn, int Ny, int sets, int N, int min_degree, TableBuilder build, int entries, int M, hipStream_t stream,
                          Launch launch) {
@@ -472,22 +408,20 @@ static int design_passes(const char* fn, int Ny, int sets, int N, int min_degree
     d.pass = (int)std::min<long long>({design_pass_points(Ny, sets), ((long long)M + 255) / 256 * 256, 65535LL * 256});
     d.ldy = (size_t)sets * d.pass;
     Workspace ws = Workspace::plain(stream);
-    if (!ws.alloc(d.ab, packed, d.Y, packed * 2 * d.ldy, d.factor, table, d.slot, table))
-        return fail(SHG_ERR_NOMEM, "%s: workspace allocation failed", fn);
+    if (!ws.alloc(d.Y, packed * 2 * d.ldy, d.factor, table, d.slot, table)) return fail(SHG_ERR_NOMEM, "%s: workspace allocation failed", fn);
     {
-        std::vector<double> a, b, h(2 * packed);
         const std::unique_ptr<double[]> f(new double[table]);        // the builders write every entry, padding included
         const std::unique_ptr<int[]> sl(new int[table]);
-        recursion_tables(Ny, a, b);
-        for (size_t i = 0; i < a.size(); ++i) {
-            h[2 * i] = a[i];
-            h[2 * i + 1] = b[i];
-        }
-        build(N, min_degree, sl.get(), f.get());
-        SHG_HIP(hipMemcpyAsync(d.ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        build(N, min_degree, sl.get(), f.get());                     // before anything waits: the stream may still be busy with the caller's
         SHG_HIP(hipMemcpyAsync(d.factor, f.get(), table * sizeof(double), hipMemcpyHostToDevice, stream));
         SHG_HIP(hipMemcpyAsync(d.slot, sl.get(), table * sizeof(int), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipStreamSynchronize(stream));
+        // the recursion factors last (built on the host while the two copies run): upload_solid_factors ends in a wait for the stream,
+        // which is the one wait of a call and covers the two copies above as well; f and sl depend on that wait.  With the wait in
+        // front of the table, NormalEquations.from_gradients lost 5 to 8 % (profiles/solid_fold_time.txt, table 4)
+        if (int rc = upload_solid_factors(fn, ws, Ny, stream, d.ab)) {
+            (void)hipStreamSynchronize(stream);                      // f and sl must outlive their copies on this path too
+            return rc;
+        }
     }
     for (int p0 = 0; p0 < M; p0 += d.pass) {
         launch(d, p0, std::min(d.pass, M - p0));
@@ -610,25 +544,18 @@ extern "C" int shg_los_design(int N, int min_degree, const double* xyz_a, const 
     });
 }
 
-// The potential's two design matrices behind their checks: the recursion factors of degree N are the only workspace, and one launch
-// covers all points (no Y, no table, no passes).
+// The potential's two design matrices: the checks they share with the others, then one launch that covers all points (no Y, no
+// table, no passes; the recursion factors of degree N are the only workspace).  Weights are per point or absent, as in shg_los_design:
+// the layout check of check_design cannot fail here.
 template <bool kPairs>
 static int potential_design(const char* fn, int N, int min_degree, const double* xyz_a, const double* xyz_b, int M, const double* weights, double GM,
                             double R, double* At, int ldt, hipStream_t stream) {
-    const size_t packed = (size_t)packed_count(N);
+    if (int rc = check_design(fn, N, min_degree, 0, M, 1, weights ? SHG_WEIGHTS_POINT : SHG_WEIGHTS_NONE, GM, R, ldt)) return rc;
+    if (M == 0) return SHG_OK;
+    SHG_REQUIRE(xyz_a && (xyz_b || !kPairs) && At, "%s: NULL pointer", fn);
     Workspace ws = Workspace::plain(stream);
     double2* ab;
-    if (!ws.alloc(ab, packed)) return fail(SHG_ERR_NOMEM, "%s: workspace allocation failed", fn);
-    {
-        std::vector<double> a, b, h(2 * packed);
-        recursion_tables(N, a, b);
-        for (size_t i = 0; i < a.size(); ++i) {
-            h[2 * i] = a[i];
-            h[2 * i + 1] = b[i];
-        }
-        SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        SHG_HIP(hipStreamSynchronize(stream));
-    }
+    if (int rc = upload_solid_factors(fn, ws, N, stream, ab)) return rc;
     hipLaunchKernelGGL(potential_design_kernel<kPairs>, dim3(ceil_div(M, kPotLanes), ceil_div(N + 1, kPotOrders)), dim3(kPotLanes), 0, stream, N, min_degree,
                        M, xyz_a, xyz_b, ab, weights, R, GM / R, At, (size_t)ldt);
     SHG_HIP(hipGetLastError());
@@ -637,19 +564,10 @@ static int potential_design(const char* fn, int N, int min_degree, const double*
 
 extern "C" int shg_potential_design(int N, int min_degree, const double* xyz, int M, const double* weights, double GM, double R, double* At, int ldt,
                                     void* stream) {
-    const char* fn = "shg_potential_design";
-    // weights are per point or absent, as in shg_los_design: the layout check of check_design cannot fail here
-    if (int rc = check_design(fn, N, min_degree, 0, M, 1, weights ? SHG_WEIGHTS_POINT : SHG_WEIGHTS_NONE, GM, R, ldt)) return rc;
-    if (M == 0) return SHG_OK;
-    SHG_REQUIRE(xyz && At, "%s: NULL pointer", fn);
-    return potential_design<false>(fn, N, min_degree, xyz, nullptr, M, weights, GM, R, At, ldt, (hipStream_t)stream);
+    return potential_design<false>("shg_potential_design", N, min_degree, xyz, nullptr, M, weights, GM, R, At, ldt, (hipStream_t)stream);
 }
 
 extern "C" int shg_potential_difference_design(int N, int min_degree, const double* xyz_a, const double* xyz_b, int M, const double* weights, double GM,
                                                double R, double* At, int ldt, void* stream) {
-    const char* fn = "shg_potential_difference_design";
-    if (int rc = check_design(fn, N, min_degree, 0, M, 1, weights ? SHG_WEIGHTS_POINT : SHG_WEIGHTS_NONE, GM, R, ldt)) return rc;
-    if (M == 0) return SHG_OK;
-    SHG_REQUIRE(xyz_a && xyz_b && At, "%s: NULL pointer", fn);
-    return potential_design<true>(fn, N, min_degree, xyz_a, xyz_b, M, weights, GM, R, At, ldt, (hipStream_t)stream);
+    return potential_design<true>("shg_potential_difference_design", N, min_degree, xyz_a, xyz_b, M, weights, GM, R, At, ldt, (hipStream_t)stream);
 }

@@ -12,13 +12,13 @@
 // Both are one computation with two parameterisations (Acceleration, Gradients below): a combine kernel forms the 2 C numbers A/B of
 // the C components (x, y, z or xx, xy, xz, yy, yz, zz) per (n', k) of degree Nq = N + 1 or N + 2 and epoch once per call (the
 // gradients' composition fused: the three first-derivative sets it needs are formed in registers), and solid_points_kernel runs one
-// column recursion per point and (n', k) for all components and every epoch of a pass.  xx, yy and zz each come from their own
-// combination: the trace is a check, not an identity.
+// column recursion per point and (n', k), SolidColumn of solid.h, which the design matrices run too, for all components and every
+// epoch of a pass.  xx, yy and zz each come from their own combination: the trace is a check, not an identity.
 //
 // The potential itself is the zeroth member of the family (Potential below): no D at all, the coefficients are the (C, S) of (n, k),
 //   V = GM / R sum_{n, k} (R/r)^(n+1) P_{nk} (cos(k lon) C_{nk} + sin(k lon) S_{nk}),
 // a point synthesis of degree N with one component.
-#include "common.h"
+#include "solid.h"
 
 #include <climits>
 #include <cmath>
@@ -182,52 +182,29 @@ constexpr int stage_degrees(int C, int EP) { return 64 * 2 * C * EP * 8 > (24 <<
 
 // 256 lanes = 256 points x EP epochs (grid.y = pass), C components each.  Per order k the 2 C coefficients of every epoch are staged in
 // LDS in chunks of kDegrees degrees, together with the recursion factors a, b of degree Nq; the degree loop reads them as LDS
-// broadcasts, so any degree fits.  r and the longitude come from xyz as grid.cartesian2spherical computes them, and so does the
-// colatitude unless kDirect; (R/r)^(n'+1) is carried along the degree loop.  C = 1 writes V [b][pt]; C = 3 writes g [b][pt][3]; C = 6
-// (xx, xy, xz, yy, yz, zz) writes T [b][pt][3][3], each off-diagonal value twice.
+// broadcasts, so any degree fits.  The recursion itself is SolidColumn<kDirect> (solid.h).  C = 1 writes V [b][pt]; C = 3 writes
+// g [b][pt][3]; C = 6 (xx, xy, xz, yy, yz, zz) writes T [b][pt][3][3], each off-diagonal value twice.
 template <int C, int EP, int kDegrees, bool kDirect>
 __global__ __launch_bounds__(256) void solid_points_kernel(int Nq, int npts, int B, const double* __restrict__ xyz, long long xyz_pass_stride,
-                                                           const double* __restrict__ ab, const double* __restrict__ Q, double R, double scale,
+                                                           const double2* __restrict__ ab, const double* __restrict__ Q, double R, double scale,
                                                            double* __restrict__ out) {
     constexpr int kStride = 2 * C * EP;                              // doubles per (n', k) in Q and in the stage
     __shared__ __attribute__((aligned(16))) double stage[kDegrees * kStride];
-    __shared__ __attribute__((aligned(16))) double abs_[kDegrees * 2];
+    __shared__ double2 abs_[kDegrees];
     const int tid = threadIdx.x;
     const int pt = blockIdx.x * 256 + tid;
     const int pass = blockIdx.y;
     const bool ok = pt < npts;
-    const double* xp = xyz + pass * xyz_pass_stride + (size_t)(ok ? pt : 0) * 3;
-    const double x = xp[0], y = xp[1], z = xp[2];
-    const double r = sqrt((x * x + y * y) + z * z);                  // np.sum over axis 1: ((x^2 + y^2) + z^2)
-    const double lam = atan2(y, x);
-    const double u = R / r;
-    double t, s;
-    if constexpr (kDirect) {
-        // cos and sin of the colatitude straight from xyz: s = sqrt(1 - t^2), the reference's form, is 0 within 1.5e-8 rad of the
-        // axis, where T_xz = 3 GM x z / r^5 is still up to 2e-8 of max|T|
-        t = z / r;
-        s = sqrt(x * x + y * y) / r;
-    } else {
-        const double th = atan2(sqrt(x * x + y * y), z);
-        t = cos(th);
-        s = sqrt(1.0 - t * t);
-    }
+    SolidColumn<kDirect> col;
+    col.start(xyz + pass * xyz_pass_stride + (size_t)(ok ? pt : 0) * 3, R);
     const double* Qp = Q + (size_t)pass * packed_count(Nq) * kStride;
     double acc[C][EP];
 #pragma unroll
     for (int c = 0; c < C; ++c)
 #pragma unroll
         for (int e = 0; e < EP; ++e) acc[c][e] = 0.0;
-    double pmm = 1.0, rk = u;                                        // rk = (R/r)^(k+1)
     for (int k = 0; k <= Nq; ++k) {
-        if (k == 1)
-            pmm = sqrt(3.0) * s;
-        else if (k >= 2)
-            pmm = sqrt((2.0 * k + 1.0) / (2.0 * k)) * s * pmm;
-        if (k >= 1) rk *= u;
-        double sk, ck;
-        sincos((double)k * lam, &sk, &ck);
-        double p1 = pmm, p2 = 0.0, rad = rk;
+        col.order(k);
         const int off = order_offset(Nq, k);
         for (int n0 = k; n0 <= Nq; n0 += kDegrees) {
             const int cnt = min(kDegrees, Nq + 1 - n0);
@@ -236,21 +213,12 @@ __global__ __launch_bounds__(256) void solid_points_kernel(int Nq, int npts, int
                 const double2* src = reinterpret_cast<const double2*>(Qp + (size_t)(off + n0 - k) * kStride);
                 double2* dst = reinterpret_cast<double2*>(stage);
                 for (int i = tid; i < cnt * kStride / 2; i += 256) dst[i] = src[i];
-                const double2* sab = reinterpret_cast<const double2*>(ab + (size_t)(off + n0 - k) * 2);
-                double2* dab = reinterpret_cast<double2*>(abs_);
-                for (int i = tid; i < cnt; i += 256) dab[i] = sab[i];
+                for (int i = tid; i < cnt; i += 256) abs_[i] = ab[off + n0 - k + i];
             }
             __syncthreads();
             for (int j = 0; j < cnt; ++j) {
-                const int n = n0 + j;
-                if (n > k) {
-                    const double p = (abs_[2 * j] * t) * p1 - abs_[2 * j + 1] * p2;
-                    p2 = p1;
-                    p1 = p;
-                }
-                const double pk = p1 * rad;
-                rad *= u;
-                const double yc = pk * ck, ys = pk * sk;
+                double yc, ys;
+                col.degree(n0 + j, k, abs_ + j, yc, ys);
                 const double* q = stage + j * kStride;
 #pragma unroll
                 for (int c = 0; c < C; ++c)
@@ -300,19 +268,19 @@ struct Acceleration {
     static constexpr bool kDirect = false;                           // the reference's s = sqrt(1 - t^2): its consumers depend on it
     static constexpr bool kCheckQ = false;
     static constexpr auto kCombine = acceleration_combine_kernel;
-    static constexpr const char* kNoWorkspace = "shg_acceleration_points: workspace allocation failed";
+    static constexpr const char* kName = "shg_acceleration_points";             // of the out-of-memory message, both layouts
     static double scale(double GM, double R) { return GM / (2.0 * R * R); }
 };
 
 struct Potential {
-    // EP = 16 is 16 accumulators: 120 VGPRs, no spills, 4 waves per SIMD, a 64-degree stage of 17 KB.  EP = 32 also compiles without
+    // EP = 16 is 16 accumulators: 118 VGPRs, no spills, 4 waves per SIMD, a 64-degree stage of 17 KB.  EP = 32 also compiles without
     // spills (151 VGPRs) but falls to 3 waves and a 32-degree stage (twice the barriers) to halve a recursion that is already a
     // sixteenth of the loop: 16 stays
     static constexpr int kOffset = 0, kComponents = 1, kValues = 1, kMaxEP = 16;
     static constexpr bool kDirect = false;                           // the reference's colatitude form, as the acceleration uses
     static constexpr bool kCheckQ = false;
     static constexpr auto kCombine = potential_combine_kernel;
-    static constexpr const char* kNoWorkspace = "shg_potential_points: workspace allocation failed";
+    static constexpr const char* kName = "shg_potential_points";
     static double scale(double GM, double R) { return GM / R; }
 };
 
@@ -322,7 +290,7 @@ struct Gradients {
     static constexpr bool kDirect = true;
     static constexpr bool kCheckQ = true;                            // the point kernel indexes one pass of Q with int
     static constexpr auto kCombine = gradients_combine_kernel;
-    static constexpr const char* kNoWorkspace = "shg_gravitational_gradients_points: workspace allocation failed";
+    static constexpr const char* kName = "shg_gravitational_gradients_points";
     static double scale(double GM, double R) { return GM / (4.0 * R * R * R); }
 };
 
@@ -343,18 +311,10 @@ static int solid_points(int N, const double* xyz, int M, int layout, CoefSource 
     const double scale = F::scale(GM, R);
     {
         Workspace ws = Workspace::plain(stream);
-        double *ab, *Q;
-        if (!ws.alloc(ab, (size_t)packed_count(Nq) * 2, Q, (size_t)group * per_pass)) return fail(SHG_ERR_NOMEM, F::kNoWorkspace);
-        {   // recursion factors of degree Nq, a and b of one (n', k) side by side (staged together)
-            std::vector<double> a, b, h(2 * (size_t)packed_count(Nq));
-            recursion_tables(Nq, a, b);
-            for (size_t i = 0; i < a.size(); ++i) {
-                h[2 * i] = a[i];
-                h[2 * i + 1] = b[i];
-            }
-            SHG_HIP(hipMemcpyAsync(ab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-            SHG_HIP(hipStreamSynchronize(stream));
-        }
+        double2* ab;
+        double* Q;
+        if (int rc = upload_solid_factors(F::kName, ws, Nq, stream, ab)) return rc;
+        if (!ws.alloc(Q, (size_t)group * per_pass)) return fail(SHG_ERR_NOMEM, "%s: workspace allocation failed", F::kName);
         for (int p0 = 0; p0 < passes; p0 += group) {
             const int np = std::min(group, passes - p0);
             const long long threads = (long long)packed_count(Nq) * EP * np;
@@ -399,46 +359,41 @@ static int check_points(const char* fn, int N, const double* xyz, int M, int lay
     return SHG_OK;
 }
 
+// An entry point behind its checks.  The reference layout has no padding (its source says Bpad = B), so only a series can fail the
+// Bpad check.
+template <class F>
+static int points_entry(const char* fn, const double* xyz, int M, int layout, CoefSource src, double GM, double R, double* out, void* stream) {
+    if (int rc = check_points<F>(fn, src.N, xyz, M, layout, src.om ? src.om : src.anm, src.B, GM, R, out)) return rc;
+    SHG_REQUIRE(src.Bpad >= src.B, "%s: Bpad %d below B %d", fn, src.Bpad, src.B);
+    if (M == 0 || src.B == 0) return SHG_OK;
+    return solid_points<F>(src.N, xyz, M, layout, src, GM, R, out, (hipStream_t)stream);
+}
+
 extern "C" int shg_acceleration_points(int N, const double* xyz, int M, int layout, const double* anm, int B, double GM, double R, double* g,
                                        void* stream) {
-    if (int rc = check_points<Acceleration>("shg_acceleration_points", N, xyz, M, layout, anm, B, GM, R, g)) return rc;
-    if (M == 0 || B == 0) return SHG_OK;
-    return solid_points<Acceleration>(N, xyz, M, layout, CoefSource{anm, nullptr, N, B, 0}, GM, R, g, (hipStream_t)stream);
+    return points_entry<Acceleration>("shg_acceleration_points", xyz, M, layout, CoefSource{anm, nullptr, N, B, B}, GM, R, g, stream);
 }
 
 extern "C" int shg_acceleration_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM, double R, double* g,
                                           void* stream) {
-    if (int rc = check_points<Acceleration>("shg_acceleration_points_om", N, xyz, M, layout, om, B, GM, R, g)) return rc;
-    SHG_REQUIRE(Bpad >= B, "shg_acceleration_points_om: Bpad %d below B %d", Bpad, B);
-    if (M == 0 || B == 0) return SHG_OK;
-    return solid_points<Acceleration>(N, xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, g, (hipStream_t)stream);
+    return points_entry<Acceleration>("shg_acceleration_points_om", xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, g, stream);
 }
 
 extern "C" int shg_gravitational_gradients_points(int N, const double* xyz, int M, int layout, const double* anm, int B, double GM, double R, double* T,
                                                   void* stream) {
-    if (int rc = check_points<Gradients>("shg_gravitational_gradients_points", N, xyz, M, layout, anm, B, GM, R, T)) return rc;
-    if (M == 0 || B == 0) return SHG_OK;
-    return solid_points<Gradients>(N, xyz, M, layout, CoefSource{anm, nullptr, N, B, 0}, GM, R, T, (hipStream_t)stream);
+    return points_entry<Gradients>("shg_gravitational_gradients_points", xyz, M, layout, CoefSource{anm, nullptr, N, B, B}, GM, R, T, stream);
 }
 
 extern "C" int shg_gravitational_gradients_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM, double R,
                                                      double* T, void* stream) {
-    if (int rc = check_points<Gradients>("shg_gravitational_gradients_points_om", N, xyz, M, layout, om, B, GM, R, T)) return rc;
-    SHG_REQUIRE(Bpad >= B, "shg_gravitational_gradients_points_om: Bpad %d below B %d", Bpad, B);
-    if (M == 0 || B == 0) return SHG_OK;
-    return solid_points<Gradients>(N, xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, T, (hipStream_t)stream);
+    return points_entry<Gradients>("shg_gravitational_gradients_points_om", xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, T, stream);
 }
 
 extern "C" int shg_potential_points(int N, const double* xyz, int M, int layout, const double* anm, int B, double GM, double R, double* V, void* stream) {
-    if (int rc = check_points<Potential>("shg_potential_points", N, xyz, M, layout, anm, B, GM, R, V)) return rc;
-    if (M == 0 || B == 0) return SHG_OK;
-    return solid_points<Potential>(N, xyz, M, layout, CoefSource{anm, nullptr, N, B, 0}, GM, R, V, (hipStream_t)stream);
+    return points_entry<Potential>("shg_potential_points", xyz, M, layout, CoefSource{anm, nullptr, N, B, B}, GM, R, V, stream);
 }
 
 extern "C" int shg_potential_points_om(int N, const double* xyz, int M, int layout, const double* om, int B, int Bpad, double GM, double R, double* V,
                                        void* stream) {
-    if (int rc = check_points<Potential>("shg_potential_points_om", N, xyz, M, layout, om, B, GM, R, V)) return rc;
-    SHG_REQUIRE(Bpad >= B, "shg_potential_points_om: Bpad %d below B %d", Bpad, B);
-    if (M == 0 || B == 0) return SHG_OK;
-    return solid_points<Potential>(N, xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, V, (hipStream_t)stream);
+    return points_entry<Potential>("shg_potential_points_om", xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, V, stream);
 }

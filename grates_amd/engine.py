@@ -800,6 +800,13 @@ def check_positions(xyz, name='positions'):
     return int(xyz.shape[0])
 
 
+def _design_output(max_degree, min_degree, x, *components):
+    """(M, At): the number of positions x [M, 3] and the empty transposed design matrix At [P, *components, M] on their device."""
+    torch = require_gpu()
+    M = int(x.shape[0])
+    return M, torch.empty(((max_degree + 1) ** 2 - min_degree ** 2,) + components + (M,), dtype=torch.float64, device=x.device)
+
+
 def acceleration_design(max_degree, xyz, GM, R, min_degree=0, weights=None):
     """Transposed design matrix At [P, 3, M] (device) of the gravitational acceleration at the positions xyz [M, 3]: At[p, c, i] is the
     derivative of component c of g at point i with respect to coefficient p of utilities.ravel_coefficients(., min_degree, max_degree),
@@ -813,10 +820,7 @@ def acceleration_design(max_degree, xyz, GM, R, min_degree=0, weights=None):
 def acceleration_design_checked(max_degree, min_degree, x, weights, GM, R):
     """shg_acceleration_design on device tensors that acceleration_design (or NormalEquations.from_accelerations, once for all its
     blocks) has checked: positions x [M, 3], weights [M], [M, 3] or None."""
-    torch = require_gpu()
-    M = int(x.shape[0])
-    P = (max_degree + 1) ** 2 - min_degree ** 2
-    out = torch.empty((P, 3, M), dtype=torch.float64, device=x.device)
+    M, out = _design_output(max_degree, min_degree, x, 3)
     _lib.call('shg_acceleration_design', max_degree, min_degree, _ptr(x), M, None if weights is None else _ptr(weights),
               0 if weights is None else weights.dim(), float(GM), float(R), _ptr(out), M, _stream())
     return out
@@ -880,10 +884,7 @@ def gradient_design(max_degree, xyz, GM, R, min_degree=0, frames=None, component
 def gradient_design_checked(max_degree, min_degree, x, frames, picked, weights, GM, R):
     """shg_gradient_design on device tensors that gradient_design (or NormalEquations.from_gradients, once for all its blocks) has
     checked: positions x [M, 3], frames [M, 3, 3] or None, the ascending component positions `picked`, weights [M], [M, K] or None."""
-    torch = require_gpu()
-    M, K = int(x.shape[0]), len(picked)
-    P = (max_degree + 1) ** 2 - min_degree ** 2
-    out = torch.empty((P, K, M), dtype=torch.float64, device=x.device)
+    M, out = _design_output(max_degree, min_degree, x, len(picked))
     _lib.call('shg_gradient_design', max_degree, min_degree, _ptr(x), M, None if frames is None else _ptr(frames), sum(1 << j for j in picked),
               None if weights is None else _ptr(weights), 0 if weights is None else weights.dim(), float(GM), float(R), _ptr(out), M, _stream())
     return out
@@ -935,9 +936,7 @@ def los_design(max_degree, xyz_a, xyz_b, GM, R, min_degree=0, directions=None, w
     entries by sqrt(w)."""
     min_degree, max_degree = check_degrees(min_degree, max_degree)
     M = check_pair_positions(xyz_a, xyz_b)
-    layout = check_observation_weights(weights, M, 1)
-    if layout and len(weights.shape) != 1:
-        raise ValueError('weights must have shape ({0},), got {1}'.format(M, tuple(weights.shape)))
+    layout = check_point_weights(weights, M)
     if directions is not None:
         check_directions(directions, M)
     else:
@@ -950,10 +949,7 @@ def los_design(max_degree, xyz_a, xyz_b, GM, R, min_degree=0, directions=None, w
 def los_design_checked(max_degree, min_degree, a, b, directions, weights, GM, R):
     """shg_los_design on device tensors that los_design (or NormalEquations.from_line_of_sight, once for all its blocks) has checked:
     positions a, b [M, 3], directions [M, 3] or None, weights [M] or None."""
-    torch = require_gpu()
-    M = int(a.shape[0])
-    P = (max_degree + 1) ** 2 - min_degree ** 2
-    out = torch.empty((P, M), dtype=torch.float64, device=a.device)
+    M, out = _design_output(max_degree, min_degree, a)
     _lib.call('shg_los_design', max_degree, min_degree, _ptr(a), _ptr(b), None if directions is None else _ptr(directions), M,
               None if weights is None else _ptr(weights), float(GM), float(R), _ptr(out), M, _stream())
     return out
@@ -990,10 +986,7 @@ def potential_design(max_degree, xyz, GM, R, min_degree=0, weights=None):
 def potential_design_checked(max_degree, min_degree, x, weights, GM, R):
     """shg_potential_design on device tensors that potential_design (or NormalEquations.from_potentials, once for all its blocks) has
     checked: positions x [M, 3], weights [M] or None."""
-    torch = require_gpu()
-    M = int(x.shape[0])
-    P = (max_degree + 1) ** 2 - min_degree ** 2
-    out = torch.empty((P, M), dtype=torch.float64, device=x.device)
+    M, out = _design_output(max_degree, min_degree, x)
     _lib.call('shg_potential_design', max_degree, min_degree, _ptr(x), M, None if weights is None else _ptr(weights), float(GM), float(R), _ptr(out),
               M, _stream())
     return out
@@ -1014,10 +1007,7 @@ def potential_difference_design(max_degree, xyz_a, xyz_b, GM, R, min_degree=0, w
 def potential_difference_design_checked(max_degree, min_degree, a, b, weights, GM, R):
     """shg_potential_difference_design on device tensors that potential_difference_design (or
     NormalEquations.from_potential_differences, once for all its blocks) has checked: positions a, b [M, 3], weights [M] or None."""
-    torch = require_gpu()
-    M = int(a.shape[0])
-    P = (max_degree + 1) ** 2 - min_degree ** 2
-    out = torch.empty((P, M), dtype=torch.float64, device=a.device)
+    M, out = _design_output(max_degree, min_degree, a)
     _lib.call('shg_potential_difference_design', max_degree, min_degree, _ptr(a), _ptr(b), M, None if weights is None else _ptr(weights), float(GM),
               float(R), _ptr(out), M, _stream())
     return out
