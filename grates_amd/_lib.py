@@ -128,6 +128,9 @@ PROTOTYPES = {
                              ctypes.c_int, ctypes.c_void_p],
     'shg_potential_difference_design': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, ctypes.c_double,
                                         ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_void_p],
+    'shg_rbf_design': [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int,
+                       c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_void_p],
+    'shg_rbf_design_info': [ctypes.POINTER(ctypes.c_int)],
     'shg_whiten_rows': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, c_double_p, ctypes.c_int,
                         ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p],
     'shg_segment_products': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, c_double_p, ctypes.c_longlong, ctypes.c_int,

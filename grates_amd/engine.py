@@ -1013,6 +1013,79 @@ def potential_difference_design_checked(max_degree, min_degree, a, b, weights, G
     return out
 
 
+RBF_KINDS = ('acceleration', 'line_of_sight', 'potential', 'potential_difference')      # position: the kind of shg_rbf_design
+
+
+def rbf_design_info():
+    """(nodes per workgroup, nodes a lane runs side by side, points per workgroup, most nodes of one call) of shg_rbf_design: the seams
+    of its launch geometry (host only, no HIP call)."""
+    arr = (ctypes.c_int * 4)()
+    _lib.call('shg_rbf_design_info', arr)
+    return tuple(int(v) for v in arr)
+
+
+def rbf_node_table(basis):
+    """What shg_rbf_design reads of a gravityfield.RadialBasisFunctions, built on the host once per basis and kept on it: the degree
+    factors k_n [N + 1] (host; ValueError for an anisotropic K) and the nodes [J, 4] on the device, the unit vector of (geocentric
+    colatitude, longitude) of every nodal point on the ellipsoid of its point distribution and R / r_j.  The table follows the nodal
+    points at the time of the first call: a basis whose points change afterwards is a new basis (copy())."""
+    cached = getattr(basis, '_rbf_node_table', None)
+    if cached is None or cached[2] != float(basis.R):
+        from . import utilities
+        points = basis.point_distribution
+        shape = np.ascontiguousarray(basis.degree_factors, dtype=np.float64)
+        colat = utilities.colatitude(points.latitude, points.semimajor_axis, points.flattening)
+        radius = utilities.geocentric_radius(points.latitude, points.semimajor_axis, points.flattening)
+        lon = np.asarray(points.longitude, dtype=np.float64)
+        nodes = np.stack((np.sin(colat) * np.cos(lon), np.sin(colat) * np.sin(lon), np.cos(colat), basis.R / radius), axis=1)
+        cached = basis._rbf_node_table = (shape, to_device(np.ascontiguousarray(nodes.reshape(-1, 4))), float(basis.R))
+    return cached[:2]
+
+
+def rbf_design(kind, basis, xyz, xyz_b=None, directions=None, weights=None):
+    """Transposed design matrix At [J, K, M] (acceleration, K = 3) or [J, M] (device) of the observations `kind` (one of RBF_KINDS) with
+    respect to the node values of the isotropic gravityfield.RadialBasisFunctions `basis`: At[j, ..., i] is the derivative of the
+    observation at point (pair) i with respect to value j (shg_rbf_design).  xyz [M, 3] are the points, or the first satellites of the
+    pair kinds, whose second satellites are xyz_b [M, 3]; directions [M, 3] are the lines of sight of 'line_of_sight' (None:
+    (b - a) / |b - a|, and no pair may then coincide); weights [M] (or [M, 3], acceleration only) scale the entries by sqrt(w).  The
+    columns equal those of the spherical harmonic design matrix of the basis's band times basis.to_potential_coefficients_matrix()."""
+    if kind not in RBF_KINDS:
+        raise ValueError('unknown kind {0!r}: expected one of {1}'.format(kind, RBF_KINDS))
+    pairs = kind in ('line_of_sight', 'potential_difference')
+    if pairs:
+        if xyz_b is None:
+            raise ValueError('{0} needs the positions of the second satellite'.format(kind))
+        M = check_pair_positions(xyz, xyz_b)
+    else:
+        M = check_positions(xyz)
+    layout = check_observation_weights(weights, M) if kind == 'acceleration' else check_point_weights(weights, M)
+    if kind == 'line_of_sight':
+        if directions is not None:
+            check_directions(directions, M)
+        else:
+            check_pairs_apart(xyz, xyz_b)
+    rbf_node_table(basis)                                            # an anisotropic K is refused before anything else reaches the device
+    a = to_device(xyz)
+    return rbf_design_checked(kind, basis, a, to_device(xyz_b, a.device) if pairs else None,
+                              to_device(directions, a.device) if kind == 'line_of_sight' and directions is not None else None,
+                              to_device(weights, a.device) if layout else None)
+
+
+def rbf_design_checked(kind, basis, a, b, directions, weights):
+    """shg_rbf_design on device tensors that rbf_design (or a NormalEquations.from_*(basis=...), once for all its blocks) has checked:
+    positions a [M, 3], b [M, 3] or None, directions [M, 3] or None, weights [M], [M, 3] or None."""
+    torch = require_gpu()
+    shape, nodes = rbf_node_table(basis)
+    if nodes.device != a.device:
+        nodes = nodes.to(a.device)
+    J, M = int(nodes.shape[0]), int(a.shape[0])
+    out = torch.empty((J, 3, M) if kind == 'acceleration' else (J, M), dtype=torch.float64, device=a.device)
+    _lib.call('shg_rbf_design', RBF_KINDS.index(kind), int(basis.max_degree), int(basis.min_degree), _host_ptr(shape), _ptr(nodes), J, _ptr(a),
+              None if b is None else _ptr(b), None if directions is None else _ptr(directions), M, None if weights is None else _ptr(weights),
+              0 if weights is None else weights.dim(), float(basis.GM), float(basis.R), _ptr(out), M, _stream())
+    return out
+
+
 def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
     """Decorrelation along the last axis of the device tensor X [..., M] (shg_whiten_rows): Y[..., t - skip] = sum_k h[n][k] X[..., t - k]
     for skip <= t < M with n = min(stage[t], q, t); the rows of X, all axes but the last flattened, belong to channel row % channels.

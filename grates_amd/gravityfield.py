@@ -1101,6 +1101,92 @@ class RadialBasisFunctions:
         from .grid import GeographicGrid
         return self.to_potential_coefficients().to_grid(GeographicGrid() if grid is None else grid, kernel)
 
+    # ---- the node values as parameters (no reference counterpart): what the design matrices of engine.rbf_design need of the basis ----
+
+    min_degree = property(lambda self: self.__min_degree, doc='first degree of the modelled band (read-only)')
+    max_degree = property(lambda self: self.__max_degree, doc='last degree of the modelled band (read-only)')
+    shape_factors = property(lambda self: self.__K.copy(), doc='a copy of K [N+1, N+1] in the coefficient layout (read-only)')
+
+    @property
+    def degree_factors(self):
+        """k_n [N+1] of an isotropic basis: every C slot K[n, 0..n] and every S slot K[m-1, n] of degree n holds the same bits, and k_n
+        is that value.  ValueError otherwise: the closed Legendre sums of the design matrices (rbf_acceleration_design_matrix,
+        NormalEquations.from_*(basis=...)) exist for isotropic shapes only."""
+        K, N = np.ascontiguousarray(self.__K, dtype=np.float64), self.__max_degree
+        if K.shape != (N + 1, N + 1):
+            raise ValueError('shape factors of shape {0} do not hold degrees 0 .. {1}'.format(K.shape, N))
+        k = np.ascontiguousarray(np.diagonal(K), dtype=np.float64).copy()      # C_nn
+        for n in range(N + 1):
+            if np.any(K[n, :n + 1].view(np.int64) != k[n:n + 1].view(np.int64)) or np.any(K[:n, n].view(np.int64) != k[n:n + 1].view(np.int64)):
+                raise ValueError('the shape factors of degree {0} differ between its orders: design matrices with respect to the node values exist for '
+                                 'isotropic shapes only; anisotropic shapes go through to_potential_coefficients_matrix'.format(n))
+        return k
+
+    def __functional(self, kind, xyz, xyz_b, directions, as_tensor):
+        """design blocks of engine.rbf_design times the node values on engine.gemm: [M] or [M, 3]"""
+        At = engine.rbf_design(kind, self, xyz, xyz_b, directions)
+        v = engine.to_device(np.ascontiguousarray(self.values, dtype=float), At.device).reshape(-1, 1)
+        rows = At.reshape(At.shape[0], -1)
+        out = engine.gemm(rows, v, transa=True).reshape(At.shape[1:])
+        out = out.t().contiguous() if kind == 'acceleration' else out
+        return out if as_tensor else engine.to_host(out)
+
+    def gravitational_acceleration(self, xyz, as_tensor=False):
+        """Gravitational acceleration [m/s^2] of the band min_degree .. max_degree at cartesian positions xyz (M, 3): [M, 3], the design
+        matrix of the node values (shg_rbf_design) times `values`.  Isotropic shape factors only.  Returns an ndarray, or the float64
+        device tensor with as_tensor=True."""
+        return self.__functional('acceleration', xyz, None, None, as_tensor)
+
+    def gravitational_potential(self, xyz, as_tensor=False):
+        """Gravitational potential [m^2/s^2] of the band at cartesian positions xyz (M, 3): [M]; see gravitational_acceleration."""
+        return self.__functional('potential', xyz, None, None, as_tensor)
+
+    def line_of_sight_acceleration(self, xyz_a, xyz_b, directions=None, as_tensor=False):
+        """Line-of-sight gravity difference e_i . (g(b_i) - g(a_i)) [m/s^2] of M satellite pairs: [M]; directions as in
+        PotentialCoefficients.line_of_sight_acceleration; see gravitational_acceleration."""
+        return self.__functional('line_of_sight', xyz_a, xyz_b, directions, as_tensor)
+
+    def potential_difference(self, xyz_a, xyz_b, as_tensor=False):
+        """Potential difference V(b_i) - V(a_i) [m^2/s^2] of M satellite pairs: [M]; see gravitational_acceleration."""
+        return self.__functional('potential_difference', xyz_a, xyz_b, None, as_tensor)
+
+
+def rbf_acceleration_design_matrix(basis, xyz, weights=None, as_tensor=False):
+    """
+    Design matrix A [3 M, J] of the gravitational acceleration at the cartesian positions xyz (M, 3) with respect to the J node values
+    of the isotropic RadialBasisFunctions `basis`: row 3 i + c is component c at point i, so that ``A @ basis.values`` equals
+    ``basis.gravitational_acceleration(xyz).ravel()``, and A equals acceleration_design_matrix of the basis's band times
+    ``basis.to_potential_coefficients_matrix()``.  Always computed on the GPU (shg_rbf_design: a closed Legendre sum per point and
+    node); weights (M,) per point or (M, 3) per component scale the rows by sqrt(w).  Returns an ndarray, or the float64 device tensor
+    with as_tensor=True.  The kernel builds the transposed matrix (engine.rbf_design, what NormalEquations.from_accelerations(...,
+    basis=basis) accumulates block by block); the transposition here is a copy meant for modest sizes.
+    """
+    At = engine.rbf_design('acceleration', basis, xyz, weights=weights)
+    A = At.permute(2, 1, 0).reshape(3 * At.shape[2], At.shape[0])
+    return A if as_tensor else engine.to_host(A)
+
+
+def rbf_line_of_sight_design_matrix(basis, xyz_a, xyz_b, directions=None, weights=None, as_tensor=False):
+    """Design matrix A [M, J] of the line-of-sight gravity difference of M satellite pairs with respect to the node values of `basis`:
+    one row per pair, directions and weights (M,) as in line_of_sight_design_matrix; see rbf_acceleration_design_matrix."""
+    A = engine.rbf_design('line_of_sight', basis, xyz_a, xyz_b, directions, weights).t().contiguous()
+    return A if as_tensor else engine.to_host(A)
+
+
+def rbf_potential_design_matrix(basis, xyz, weights=None, as_tensor=False):
+    """Design matrix A [M, J] of the gravitational potential at xyz (M, 3) with respect to the node values of `basis`: one row per
+    point, weights (M,); see rbf_acceleration_design_matrix."""
+    A = engine.rbf_design('potential', basis, xyz, weights=weights).t().contiguous()
+    return A if as_tensor else engine.to_host(A)
+
+
+def rbf_potential_difference_design_matrix(basis, xyz_a, xyz_b, weights=None, as_tensor=False):
+    """Design matrix A [M, J] of the potential difference V(b_i) - V(a_i) of M satellite pairs with respect to the node values of
+    `basis`: one row per pair (swapping the satellites negates it bitwise, a pair at one position gives a zero row), weights (M,);
+    see rbf_acceleration_design_matrix."""
+    A = engine.rbf_design('potential_difference', basis, xyz_a, xyz_b, weights=weights).t().contiguous()
+    return A if as_tensor else engine.to_host(A)
+
 
 # -------------------------------------------------------------------------------------------------------
 # reference fields (grates/gravityfield.py:1474-1574)

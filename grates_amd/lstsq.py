@@ -422,7 +422,20 @@ class _Observations:
         self.l = l * self.root if self.layout else l
 
 
-def _acceleration_observations(xyz, g, min_degree, max_degree, GM, R, weights):
+def _node_parameters(observations, basis, GM, R):
+    """The observations of a call with basis=...: the parameters are the node values of the gravityfield.RadialBasisFunctions `basis`
+    instead of the coefficients, so P is its node count; the degrees and constants of the call must be the basis's (ValueError
+    otherwise, as for an anisotropic basis: all of it on the host).  Returns the observations."""
+    for name, given, own in (('min_degree', observations.min_degree, int(basis.min_degree)), ('max_degree', observations.max_degree, int(basis.max_degree)),
+                             ('GM', float(GM), float(basis.GM)), ('R', float(R), float(basis.R))):
+        if given != own:
+            raise ValueError('{0} of the call is {1!r} but the basis has {2!r}: pass the values of the basis'.format(name, given, own))
+    basis.degree_factors
+    observations.P = int(basis.point_distribution.longitude.size)
+    return observations
+
+
+def _acceleration_observations(xyz, g, min_degree, max_degree, GM, R, weights, basis=None):
     min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
     M = engine.check_positions(xyz)
     if engine.check_positions(g, 'accelerations') != M:
@@ -431,9 +444,12 @@ def _acceleration_observations(xyz, g, min_degree, max_degree, GM, R, weights):
 
     def upload(w):
         x, l = engine.to_device(xyz), engine.to_device(g)
+        if basis is not None:
+            return l, lambda first, last: engine.rbf_design_checked('acceleration', basis, x[first:last], None, None, None if w is None else w[first:last])
         return l, lambda first, last: engine.acceleration_design_checked(
             max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R)
-    return _Observations(min_degree, max_degree, M, 3, weights, layout, upload)
+    observations = _Observations(min_degree, max_degree, M, 3, weights, layout, upload)
+    return observations if basis is None else _node_parameters(observations, basis, GM, R)
 
 
 def _gradient_observations(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights):
@@ -461,7 +477,7 @@ def _gradient_observations(xyz, gradients, min_degree, max_degree, GM, R, frames
     return _Observations(min_degree, max_degree, M, K, weights, layout, upload)
 
 
-def _los_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights):
+def _los_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, basis=None):
     min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
     M = engine.check_pair_positions(xyz_a, xyz_b)
     if len(differences.shape) != 1:
@@ -479,9 +495,13 @@ def _los_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, 
     def upload(w):
         a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
         e = engine.to_device(directions) if directions is not None else None
+        if basis is not None:
+            return l, lambda first, last: engine.rbf_design_checked(
+                'line_of_sight', basis, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last])
         return l, lambda first, last: engine.los_design_checked(
             max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last], GM, R)
-    return _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
+    observations = _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
+    return observations if basis is None else _node_parameters(observations, basis, GM, R)
 
 
 def _check_scalar_observations(values, M, name, unit):
@@ -492,7 +512,7 @@ def _check_scalar_observations(values, M, name, unit):
         raise ValueError('{0} {1} but {2} {3}'.format(M, unit, int(values.shape[0]), name))
 
 
-def _potential_observations(xyz, potentials, min_degree, max_degree, GM, R, weights):
+def _potential_observations(xyz, potentials, min_degree, max_degree, GM, R, weights, basis=None):
     min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
     M = engine.check_positions(xyz)
     _check_scalar_observations(potentials, M, 'potentials', 'positions')
@@ -500,11 +520,14 @@ def _potential_observations(xyz, potentials, min_degree, max_degree, GM, R, weig
 
     def upload(w):
         x, l = engine.to_device(xyz), engine.to_device(potentials).reshape(-1, 1)
+        if basis is not None:
+            return l, lambda first, last: engine.rbf_design_checked('potential', basis, x[first:last], None, None, None if w is None else w[first:last])
         return l, lambda first, last: engine.potential_design_checked(max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R)
-    return _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
+    observations = _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
+    return observations if basis is None else _node_parameters(observations, basis, GM, R)
 
 
-def _potential_difference_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights):
+def _potential_difference_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights, basis=None):
     min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
     M = engine.check_pair_positions(xyz_a, xyz_b)
     _check_scalar_observations(differences, M, 'differences', 'pairs')
@@ -512,9 +535,13 @@ def _potential_difference_observations(xyz_a, xyz_b, differences, min_degree, ma
 
     def upload(w):
         a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
+        if basis is not None:
+            return l, lambda first, last: engine.rbf_design_checked(
+                'potential_difference', basis, a[first:last], b[first:last], None, None if w is None else w[first:last])
         return l, lambda first, last: engine.potential_difference_design_checked(
             max_degree, min_degree, a[first:last], b[first:last], None if w is None else w[first:last], GM, R)
-    return _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
+    observations = _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
+    return observations if basis is None else _node_parameters(observations, basis, GM, R)
 
 
 class _StochasticModel:
@@ -1353,6 +1380,75 @@ class ArcParameters(_BoundModel):
         self.basis, self.arcs, self.noise_model, self.keep = basis, arcs, noise_model, bool(keep)
 
 
+class RadialBasisParameters:
+    """
+    The node values of an isotropic gravityfield.RadialBasisFunctions as the parameters of a least-squares problem, bound to the
+    constructors of NormalEquations and of PostFit like ColouredNoise and ArcParameters: a regional solution (a basin, an ice sheet,
+    mascon-like nodes) from the observations the spherical harmonic route takes.  basis gives the nodal points, the shape factors
+    (degree_factors: ValueError for an anisotropic K), the band min_degree .. max_degree, GM and R, so the calls take none of them;
+    model is None (white noise), a ColouredNoise or an ArcParameters, as PostFit takes it.
+
+    from_accelerations, from_line_of_sight, from_potentials and from_potential_differences take the observations, weights and
+    block_points of the classmethods of the same name and return NormalEquations [J, J] of the J node values: the block loop of
+    NormalEquations.from_accelerations with At [J, K Mb] from shg_rbf_design (a closed Legendre sum per point and node; neither the
+    spherical harmonic design matrix nor to_potential_coefficients_matrix is formed), whitening, arc elimination and the products
+    unchanged; the default block is default_block_points(J, K).  ``basis.values = engine.to_host(ne.solve())[:, 0]`` and
+    ``basis.to_grid(...)`` close the chain.  of_accelerations ... of_potential_differences take the solution [J] first and vectors
+    [J, S] last and return the PostFit of that solution under the model.  The gradient tensor is not offered: it needs second
+    derivatives of the kernel.  Every check runs before anything reaches the device.
+    """
+
+    def __init__(self, basis, model=None):
+        _StochasticModel.of(model)
+        basis.degree_factors
+        self.basis, self.model = basis, model
+
+    def __band(self):
+        basis = self.basis
+        return dict(min_degree=basis.min_degree, max_degree=basis.max_degree, GM=basis.GM, R=basis.R, basis=basis)
+
+    def __accelerations(self, xyz, g, weights):
+        return _acceleration_observations(xyz=xyz, g=g, weights=weights, **self.__band())
+
+    def __line_of_sight(self, xyz_a, xyz_b, differences, directions, weights):
+        return _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights, **self.__band())
+
+    def __potentials(self, xyz, potentials, weights):
+        return _potential_observations(xyz=xyz, potentials=potentials, weights=weights, **self.__band())
+
+    def __potential_differences(self, xyz_a, xyz_b, differences, weights):
+        return _potential_difference_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, weights=weights, **self.__band())
+
+    def __normals(self, observations, block_points):
+        return NormalEquations._normals(observations, _StochasticModel.of(self.model), block_points)
+
+    def from_accelerations(self, xyz, g, weights=None, block_points=None):
+        return self.__normals(self.__accelerations(xyz, g, weights), block_points)
+
+    def from_line_of_sight(self, xyz_a, xyz_b, differences, directions=None, weights=None, block_points=None):
+        return self.__normals(self.__line_of_sight(xyz_a, xyz_b, differences, directions, weights), block_points)
+
+    def from_potentials(self, xyz, potentials, weights=None, block_points=None):
+        return self.__normals(self.__potentials(xyz, potentials, weights), block_points)
+
+    def from_potential_differences(self, xyz_a, xyz_b, differences, weights=None, block_points=None):
+        return self.__normals(self.__potential_differences(xyz_a, xyz_b, differences, weights), block_points)
+
+    def of_accelerations(self, solution, xyz, g, weights=None, block_points=None, vectors=None):
+        return PostFit._of_observations(solution, vectors, self.model, xyz, lambda: self.__accelerations(xyz, g, weights), block_points)
+
+    def of_line_of_sight(self, solution, xyz_a, xyz_b, differences, directions=None, weights=None, block_points=None, vectors=None):
+        return PostFit._of_observations(solution, vectors, self.model, xyz_a,
+                                        lambda: self.__line_of_sight(xyz_a, xyz_b, differences, directions, weights), block_points)
+
+    def of_potentials(self, solution, xyz, potentials, weights=None, block_points=None, vectors=None):
+        return PostFit._of_observations(solution, vectors, self.model, xyz, lambda: self.__potentials(xyz, potentials, weights), block_points)
+
+    def of_potential_differences(self, solution, xyz_a, xyz_b, differences, weights=None, block_points=None, vectors=None):
+        return PostFit._of_observations(solution, vectors, self.model, xyz_a,
+                                        lambda: self.__potential_differences(xyz_a, xyz_b, differences, weights), block_points)
+
+
 class PostFit:
     """
     What a solution says about the stochastic model it was computed under: the residuals of the observations, the square sum, the
@@ -1424,6 +1520,12 @@ class PostFit:
         observations = _potential_difference_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree,
                                                           max_degree=max_degree, GM=GM, R=R, weights=weights)
         return fit._pass(observations, fit.__model, block_points)
+
+    @classmethod
+    def _of_observations(cls, solution, vectors, model, template, build, block_points):
+        """an of_* call on the observations that build() returns (the record of another parameterisation: RadialBasisParameters)"""
+        fit = cls(solution, vectors, model, template)
+        return fit._pass(build(), fit.__model, block_points)
 
     def _check(self, parameters):
         """the solution and the vectors against the number of parameters: ValueError before anything reaches the device"""

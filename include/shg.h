@@ -597,6 +597,41 @@ int shg_potential_difference_design(int N, int min_degree, const double* xyz_a, 
                                     double R, double* At, int ldt, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Design matrices with respect to the node values of isotropic radial basis functions (gravityfield.RadialBasisFunctions; the
+ * reference can only convert that representation, nothing estimates it)
+ *   At [J][K][ldt], transposed like shg_acceleration_design: row j is node j, the M points (pairs) innermost (ldt >= M; the entries
+ *   from M to ldt of a row are not touched).  nodes (device) [J][4]: the unit vector e_j of node j and R / r_j.  shape (host) [N + 1]:
+ *   the shape factor k_n of every degree; degrees below min_degree are not read and count as zero.  With, for a point x = r xh,
+ *   t = xh . e_j, q = (R / r)(R / r_j) and d_n = k_n (2n + 1),
+ *     V_j(x)      = GM / R sum_n d_n q^(n+1) P_n(t)
+ *     grad V_j(x) = GM / (R r) [ -S_r xh + S_t (e_j - t xh) ],  S_r = sum_n (n + 1) d_n q^(n+1) P_n(t),  S_t = sum_n d_n q^(n+1) P'_n(t)
+ *   (P_n the unnormalised Legendre polynomials, P_n = (2n-1)/n t P_{n-1} - (n-1)/n P_{n-2}, P'_n = P'_{n-2} + (2n-1) P_{n-1}); these
+ *   are the columns of the spherical harmonic design matrices of degrees min_degree .. N times to_potential_coefficients_matrix.
+ *     kind SHG_RBF_ACCELERATION          K = 3  At[j][c][i] = d g_c(x_i) / d v_j; weights NONE, POINT w [M] or COMPONENT w [M][3]
+ *     kind SHG_RBF_LINE_OF_SIGHT         K = 1  At[j][i] = e_i . (grad V_j(b_i) - grad V_j(a_i)), the difference per component first,
+ *                                               then (e_x d_x + e_y d_y) + e_z d_z; e_i = directions[i] as given, or with directions ==
+ *                                               NULL (b_i - a_i) / |b_i - a_i| as shg_los_design forms it (NaN for a_i == b_i)
+ *     kind SHG_RBF_POTENTIAL             K = 1  At[j][i] = V_j(x_i)
+ *     kind SHG_RBF_POTENTIAL_DIFFERENCE  K = 1  At[j][i] = V_j(b_i) - V_j(a_i): swapping a and b negates At bitwise, a_i == b_i gives an
+ *                                               exactly zero column i
+ *   The single-point kinds read xyz_a only (xyz_b and directions are not looked at); the three kinds with K = 1 take weights NONE or
+ *   POINT w [M].  Every entry is (value * scale) * sqrt(w) with scale = GM / R or GM / (R r), the weight last: a weighted matrix is
+ *   bitwise the unweighted one times sqrt(w).  One kernel, one lane per point and 256 points per workgroup, a tile of nodes per
+ *   workgroup, the recursion of several nodes side by side in a lane (shg_rbf_design_info, host only: which = {nodes per tile, nodes
+ *   side by side, points per workgroup, most nodes of a call}); no workspace but the table of N + 1 degrees, no fma, no atomics: an
+ *   entry depends on its point and its node only, not on M, J, ldt or the place in the batch, and repeated calls are bitwise equal.
+ *   The rows of a pair kind are made of the values the single-point kind computes at the two satellites.  r = 0 is not allowed.
+ *   Arguments are checked before the first HIP call (kind outside 0 .. 3, negative sizes, min_degree > N, N > 32767, more nodes than
+ *   one call takes, a weight layout the kind does not have, GM or R not finite, R <= 0, ldt < M, more than 2^40 values of At; NULL
+ *   shape, nodes, xyz_a, At or weights that are due; NULL xyz_b for a pair kind); M = 0 or J = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+enum { SHG_RBF_ACCELERATION = 0, SHG_RBF_LINE_OF_SIGHT = 1, SHG_RBF_POTENTIAL = 2, SHG_RBF_POTENTIAL_DIFFERENCE = 3 };
+int shg_rbf_design(int kind, int N, int min_degree, const double* shape, const double* nodes, int J, const double* xyz_a, const double* xyz_b,
+                   const double* directions, int M, const double* weights, int weight_layout, double GM, double R, double* At, int ldt,
+                   void* stream);
+int shg_rbf_design_info(int which[4]);
+
+/* ------------------------------------------------------------------------------------------------
  * Decorrelation of coloured observation noise along the point axis (the banded lower-triangular W with W^T W = Sigma^-1 of a sequence
  * of scalar AR models of orders 0 .. q; no reference counterpart)
  *   X [rows][ldx] with M columns in use, row r of channel r % channels: the transposed design matrix At [P][K][ldt] of the three calls
