@@ -1086,6 +1086,41 @@ def rbf_design_checked(kind, basis, a, b, directions, weights):
     return out
 
 
+def rbf_gradient_design(basis, xyz, frames=None, components=None, weights=None):
+    """Transposed design matrix At [J, K, M] (device) of the gravitational gradient tensor at the positions xyz [M, 3] with respect to
+    the node values of the isotropic gravityfield.RadialBasisFunctions `basis`: At[j, k, i] is the derivative of the k-th selected
+    component of T' = F T F^T at point i with respect to value j (shg_rbf_gradient_design).  frames, components and weights as in
+    gradient_design: frames [M, 3, 3] hold the instrument axes as rows (None: the Earth-fixed tensor), components is a sequence of
+    distinct names from GRADIENT_COMPONENTS (None: all six), the output always in canonical order, weights [M] or [M, K] scale the
+    entries by sqrt(w).  The columns equal those of gradient_design of the basis's band times
+    basis.to_potential_coefficients_matrix()."""
+    M = check_positions(xyz)
+    picked = gradient_components(components)
+    layout = check_observation_weights(weights, M, len(picked))
+    if frames is not None:
+        check_frames(frames, M)
+    rbf_node_table(basis)                                            # an anisotropic K is refused before anything else reaches the device
+    x = to_device(xyz)
+    return rbf_gradient_design_checked(basis, x, None if frames is None else to_device(frames, x.device), picked,
+                                       to_device(weights, x.device) if layout else None)
+
+
+def rbf_gradient_design_checked(basis, x, frames, picked, weights):
+    """shg_rbf_gradient_design on device tensors that rbf_gradient_design (or RadialBasisParameters.from_gradients, once for all its
+    blocks) has checked: positions x [M, 3], frames [M, 3, 3] or None, the ascending component positions `picked`, weights [M], [M, K]
+    or None."""
+    torch = require_gpu()
+    shape, nodes = rbf_node_table(basis)
+    if nodes.device != x.device:
+        nodes = nodes.to(x.device)
+    J, M = int(nodes.shape[0]), int(x.shape[0])
+    out = torch.empty((J, len(picked), M), dtype=torch.float64, device=x.device)
+    _lib.call('shg_rbf_gradient_design', int(basis.max_degree), int(basis.min_degree), _host_ptr(shape), _ptr(nodes), J, _ptr(x), M,
+              None if frames is None else _ptr(frames), sum(1 << j for j in picked), None if weights is None else _ptr(weights),
+              0 if weights is None else weights.dim(), float(basis.GM), float(basis.R), _ptr(out), M, _stream())
+    return out
+
+
 def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
     """Decorrelation along the last axis of the device tensor X [..., M] (shg_whiten_rows): Y[..., t - skip] = sum_k h[n][k] X[..., t - k]
     for skip <= t < M with n = min(stage[t], q, t); the rows of X, all axes but the last flattened, belong to channel row % channels.

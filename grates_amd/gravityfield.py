@@ -1150,6 +1150,19 @@ class RadialBasisFunctions:
         """Potential difference V(b_i) - V(a_i) [m^2/s^2] of M satellite pairs: [M]; see gravitational_acceleration."""
         return self.__functional('potential_difference', xyz_a, xyz_b, None, as_tensor)
 
+    def gravitational_gradients(self, xyz, as_tensor=False):
+        """Gravitational gradient tensor d^2 V / dx_i dx_j [s^-2] of the band at cartesian positions xyz (M, 3), in their Earth-fixed
+        frame: [M, 3, 3], as PotentialCoefficients.gravitational_gradients; the six entries of the design matrix of the node values
+        (shg_rbf_gradient_design) times `values`, filled symmetrically: T[k] equals its transpose bit for bit.  See
+        gravitational_acceleration."""
+        At = engine.rbf_gradient_design(self, xyz)                                                        # [J, 6, M]
+        torch = engine.require_gpu()
+        v = engine.to_device(np.ascontiguousarray(self.values, dtype=float), At.device).reshape(-1, 1)
+        six = engine.gemm(At.reshape(At.shape[0], -1), v, transa=True).reshape(6, At.shape[2])
+        index = torch.tensor([0, 1, 2, 1, 3, 4, 2, 4, 5], device=At.device)
+        out = six[index].t().reshape(At.shape[2], 3, 3).contiguous()
+        return out if as_tensor else engine.to_host(out)
+
 
 def rbf_acceleration_design_matrix(basis, xyz, weights=None, as_tensor=False):
     """
@@ -1163,6 +1176,16 @@ def rbf_acceleration_design_matrix(basis, xyz, weights=None, as_tensor=False):
     """
     At = engine.rbf_design('acceleration', basis, xyz, weights=weights)
     A = At.permute(2, 1, 0).reshape(3 * At.shape[2], At.shape[0])
+    return A if as_tensor else engine.to_host(A)
+
+
+def rbf_gradient_design_matrix(basis, xyz, frames=None, components=None, weights=None, as_tensor=False):
+    """Design matrix A [K M, J] of the gravitational gradient tensor at xyz (M, 3) with respect to the node values of `basis`: row
+    K i + j is the j-th selected component at point i; frames (M, 3, 3), components and weights (M,) or (M, K) as in
+    gradient_design_matrix, whose matrix of the basis's band times ``basis.to_potential_coefficients_matrix()`` this equals
+    (shg_rbf_gradient_design: the closed Hessian of the Legendre sum per point and node); see rbf_acceleration_design_matrix."""
+    At = engine.rbf_gradient_design(basis, xyz, frames, components, weights)
+    A = At.permute(2, 1, 0).reshape(At.shape[1] * At.shape[2], At.shape[0])
     return A if as_tensor else engine.to_host(A)
 
 

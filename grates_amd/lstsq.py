@@ -452,7 +452,7 @@ def _acceleration_observations(xyz, g, min_degree, max_degree, GM, R, weights, b
     return observations if basis is None else _node_parameters(observations, basis, GM, R)
 
 
-def _gradient_observations(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights):
+def _gradient_observations(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, basis=None):
     min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
     M = engine.check_positions(xyz)
     picked = engine.gradient_components(components)
@@ -472,9 +472,13 @@ def _gradient_observations(xyz, gradients, min_degree, max_degree, GM, R, frames
         f = engine.to_device(frames) if frames is not None else None
         if full:
             l = l.reshape(M, 9)[:, [(0, 1, 2, 4, 5, 8)[i] for i in picked]]                              # the selected upper-triangle entries
+        if basis is not None:
+            return l, lambda first, last: engine.rbf_gradient_design_checked(
+                basis, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last])
         return l, lambda first, last: engine.gradient_design_checked(
             max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last], GM, R)
-    return _Observations(min_degree, max_degree, M, K, weights, layout, upload)
+    observations = _Observations(min_degree, max_degree, M, K, weights, layout, upload)
+    return observations if basis is None else _node_parameters(observations, basis, GM, R)
 
 
 def _los_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, basis=None):
@@ -1388,14 +1392,14 @@ class RadialBasisParameters:
     (degree_factors: ValueError for an anisotropic K), the band min_degree .. max_degree, GM and R, so the calls take none of them;
     model is None (white noise), a ColouredNoise or an ArcParameters, as PostFit takes it.
 
-    from_accelerations, from_line_of_sight, from_potentials and from_potential_differences take the observations, weights and
-    block_points of the classmethods of the same name and return NormalEquations [J, J] of the J node values: the block loop of
-    NormalEquations.from_accelerations with At [J, K Mb] from shg_rbf_design (a closed Legendre sum per point and node; neither the
+    from_accelerations, from_gradients, from_line_of_sight, from_potentials and from_potential_differences take the observations,
+    weights and block_points of the classmethods of the same name (from_gradients also frames and components) and return
+    NormalEquations [J, J] of the J node values: the block loop of NormalEquations.from_accelerations with At [J, K Mb] from
+    shg_rbf_design or, for the gradient tensor, shg_rbf_gradient_design (a closed Legendre sum per point and node; neither the
     spherical harmonic design matrix nor to_potential_coefficients_matrix is formed), whitening, arc elimination and the products
     unchanged; the default block is default_block_points(J, K).  ``basis.values = engine.to_host(ne.solve())[:, 0]`` and
     ``basis.to_grid(...)`` close the chain.  of_accelerations ... of_potential_differences take the solution [J] first and vectors
-    [J, S] last and return the PostFit of that solution under the model.  The gradient tensor is not offered: it needs second
-    derivatives of the kernel.  Every check runs before anything reaches the device.
+    [J, S] last and return the PostFit of that solution under the model.  Every check runs before anything reaches the device.
     """
 
     def __init__(self, basis, model=None):
@@ -1409,6 +1413,9 @@ class RadialBasisParameters:
 
     def __accelerations(self, xyz, g, weights):
         return _acceleration_observations(xyz=xyz, g=g, weights=weights, **self.__band())
+
+    def __gradients(self, xyz, gradients, frames, components, weights):
+        return _gradient_observations(xyz=xyz, gradients=gradients, frames=frames, components=components, weights=weights, **self.__band())
 
     def __line_of_sight(self, xyz_a, xyz_b, differences, directions, weights):
         return _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights, **self.__band())
@@ -1425,6 +1432,9 @@ class RadialBasisParameters:
     def from_accelerations(self, xyz, g, weights=None, block_points=None):
         return self.__normals(self.__accelerations(xyz, g, weights), block_points)
 
+    def from_gradients(self, xyz, gradients, frames=None, components=None, weights=None, block_points=None):
+        return self.__normals(self.__gradients(xyz, gradients, frames, components, weights), block_points)
+
     def from_line_of_sight(self, xyz_a, xyz_b, differences, directions=None, weights=None, block_points=None):
         return self.__normals(self.__line_of_sight(xyz_a, xyz_b, differences, directions, weights), block_points)
 
@@ -1436,6 +1446,10 @@ class RadialBasisParameters:
 
     def of_accelerations(self, solution, xyz, g, weights=None, block_points=None, vectors=None):
         return PostFit._of_observations(solution, vectors, self.model, xyz, lambda: self.__accelerations(xyz, g, weights), block_points)
+
+    def of_gradients(self, solution, xyz, gradients, frames=None, components=None, weights=None, block_points=None, vectors=None):
+        return PostFit._of_observations(solution, vectors, self.model, xyz,
+                                        lambda: self.__gradients(xyz, gradients, frames, components, weights), block_points)
 
     def of_line_of_sight(self, solution, xyz_a, xyz_b, differences, directions=None, weights=None, block_points=None, vectors=None):
         return PostFit._of_observations(solution, vectors, self.model, xyz_a,

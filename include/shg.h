@@ -632,6 +632,29 @@ int shg_rbf_design(int kind, int N, int min_degree, const double* shape, const d
 int shg_rbf_design_info(int which[4]);
 
 /* ------------------------------------------------------------------------------------------------
+ * Design matrix of the gravitational gradient tensor with respect to the node values of isotropic radial basis functions
+ *   At [J][K][ldt], the layout of shg_gradient_design with the nodes of shg_rbf_design as rows: At[j][k][i] is the derivative of the
+ *   k-th selected component of T' = F_i T F_i^T at point i with respect to node value j (ldt >= M; the entries from M to ldt of a row
+ *   are not touched).  shape, nodes, N and min_degree as in shg_rbf_design; frames, components, weights and weight_layout as in
+ *   shg_gradient_design (frames NULL: the Earth-fixed tensor; components a set of SHG_GRAD_* bits, rows in ascending bit order;
+ *   weights NONE, POINT w [M] or COMPONENT w [M][K]).  With the notation of shg_rbf_design and tau = e_j - t xh,
+ *     Hess V_j(x) = GM / (R r^2) [ S_rr xh xh^T - (S_r + t S_t)(I - xh xh^T) - (S_rt + S_t)(xh tau^T + tau xh^T) + S_tt tau tau^T ]
+ *     S_rr = sum_n (n + 1)(n + 2) d_n q^(n+1) P_n(t),  S_rt = sum_n (n + 1) d_n q^(n+1) P'_n(t),  S_tt = sum_n d_n q^(n+1) P''_n(t)
+ *   (P''_n = P''_{n-2} + (2n-1) P'_{n-1}): symmetric by construction, trace-free degree by degree, regular above a node and antipodal
+ *   to it (tau = 0; nothing divides by a sine).  These are the columns of shg_gradient_design of degrees min_degree .. N times
+ *   to_potential_coefficients_matrix.  The rotation is that of shg_gradient_design, T f_b once per needed b, then f_a . (T f_b), exact
+ *   for identity frames; every entry is (value * scale) * sqrt(w) with scale = GM / (R r^2).  The launch geometry is that of
+ *   shg_rbf_design (shg_rbf_design_info: the same node tile, nodes side by side in a lane and points per workgroup);
+ *   no workspace but the table of N + 1 degrees, no fma, no atomics: an entry depends on its point, its frame and its node only, not
+ *   on M, J, ldt, the component set or the place in the batch, and repeated calls are bitwise equal.  r = 0 is not allowed.
+ *   Every argument is checked before the first HIP call (components outside 1 .. 63; N, min_degree, J or M < 0; min_degree > N;
+ *   N > 32767; J above the nodes one call takes; an unknown weight layout; GM or R not finite, R <= 0; ldt < M; more than 2^40 values
+ *   of At; NULL shape, nodes, xyz, At or weights that are due); M = 0 or J = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_rbf_gradient_design(int N, int min_degree, const double* shape, const double* nodes, int J, const double* xyz, int M, const double* frames,
+                            int components, const double* weights, int weight_layout, double GM, double R, double* At, int ldt, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decorrelation of coloured observation noise along the point axis (the banded lower-triangular W with W^T W = Sigma^-1 of a sequence
  * of scalar AR models of orders 0 .. q; no reference counterpart)
  *   X [rows][ldx] with M columns in use, row r of channel r % channels: the transposed design matrix At [P][K][ldt] of the three calls
