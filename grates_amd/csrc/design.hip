@@ -30,6 +30,7 @@
 // The host side is one of each: d_terms is the only host code that uses f-, f0, f+ (both tables are built from it; the formulas
 // themselves are in common.h, shared with the forward kernels), design_passes is the pass driver (pass size, workspace, upload of
 // recursion factors and table) around the launches of an entry point, and check_design holds the argument checks the entry points share.
+#include "observe.h"
 #include "solid.h"
 
 #include <cmath>
@@ -199,10 +200,9 @@ static void gradient_design_table(int N, int min_degree, int* slot, double* fact
 
 // Rows blockIdx.x * kGradRows ... of the transposed design matrix of the gradient tensor, 256 points per workgroup (blockIdx.y):
 // out [rows][K][ldt] with the K components of `mask` (bit j: component j of xx, xy, xz, yy, yz, zz) in ascending order.  A lane keeps
-// the frame of its point (kFrames: F [3][3], row a = instrument axis a) and the square roots of its weights across the rows of the
-// workgroup; per row it forms the six Earth-fixed entries from the table (wave-uniform slots and factors), then
-// T'_ab = f_a . (T f_b) for the selected components (T f_b once per b, from the six entries), scales by `scale` and by sqrt(w)
-// (wl 0: none, 1: w [npts], 2: w [npts][K]) and stores.
+// the frame of its point and the square roots of its weights across the rows of the workgroup (FrameTensor of observe.h, shared with
+// the radial basis functions: wl 0: none, 1: w [npts], 2: w [npts][K]); per row it forms the six Earth-fixed entries from the table
+// (wave-uniform slots and factors) and hands them to FrameTensor::store, which rotates, scales by `scale` and by sqrt(w) and stores.
 template <bool kFrames>
 __global__ __launch_bounds__(256) void gradient_design_kernel(int npts, long long rows, const double* __restrict__ Y, size_t ldy,
                                                               const int* __restrict__ slot, const double* __restrict__ factor,
@@ -210,24 +210,8 @@ __global__ __launch_bounds__(256) void gradient_design_kernel(int npts, long lon
                                                               double scale, double* __restrict__ out, size_t ldt) {
     const int pt = blockIdx.y * 256 + threadIdx.x;
     if (pt >= npts) return;
-    double F[3][3];
-    if (kFrames) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) F[i / 3][i % 3] = frames[(size_t)pt * 9 + i];
-    }
-    double sw[6];
-    {
-        const double wp = wl == 1 ? sqrt(w[pt]) : 1.0;
-        int k = 0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            sw[j] = wp;
-            if ((mask >> j) & 1) {
-                if (wl == 2) sw[j] = sqrt(w[(size_t)pt * K + k]);
-                ++k;
-            }
-        }
-    }
+    FrameTensor<kFrames> tensor;
+    tensor.start(frames, mask, K, w, wl, (size_t)pt);
     const size_t row0 = (size_t)blockIdx.x * kGradRows;
     const size_t row1 = min((unsigned long long)(row0 + kGradRows), (unsigned long long)rows);
     for (size_t row = row0; row < row1; ++row) {
@@ -242,28 +226,7 @@ __global__ __launch_bounds__(256) void gradient_design_kernel(int npts, long lon
             }
             t[c] = v;
         }
-        double u[3][3] = {};                                         // u[b] = T f_b
-        if (kFrames) {
-            const int need[3] = {mask & 1, mask & (2 | 8), mask & (4 | 16 | 32)};
-#pragma unroll
-            for (int b = 0; b < 3; ++b)
-                if (need[b]) {
-                    u[b][0] = (t[0] * F[b][0] + t[1] * F[b][1]) + t[2] * F[b][2];
-                    u[b][1] = (t[1] * F[b][0] + t[3] * F[b][1]) + t[4] * F[b][2];
-                    u[b][2] = (t[2] * F[b][0] + t[4] * F[b][1]) + t[5] * F[b][2];
-                }
-        }
-        double* o = out + row * K * ldt + pt;
-        int j = 0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = a; b < 3; ++b, ++j)
-                if ((mask >> j) & 1) {
-                    const double v = kFrames ? (F[a][0] * u[b][0] + F[a][1] * u[b][1]) + F[a][2] * u[b][2] : t[j];
-                    *o = (v * scale) * sw[j];
-                    o += ldt;
-                }
+        tensor.store(t, mask, scale, out + row * K * ldt + pt, ldt);
     }
 }
 
@@ -275,8 +238,8 @@ constexpr int kLosRows = 16;                          // rows of At per workgrou
 // Rows blockIdx.x * kLosRows ... of the transposed design matrix of the line-of-sight difference, 256 pairs per workgroup
 // (blockIdx.y): out [rows][ldt].  Y holds the solid harmonics of the pass, those of the a-points in the columns 0 .. and those of the
 // b-points in the columns `half` .. of every slot.  A lane keeps the line of sight e and sqrt(w) of its pair across the rows of the
-// workgroup.  kUnit: e = (b - a) / |b - a| from the positions, |d| = sqrt((dx^2 + dy^2) + dz^2) and one division per component;
-// otherwise e = directions [npairs][3] as given.  Per row (wave-uniform slots and factors) the unscaled component sums at b and at a,
+// workgroup.  kUnit: e = (b - a) / |b - a| from the positions, otherwise e = directions [npairs][3] as given (line_of_sight of
+// observe.h, shared with the radial basis functions).  Per row (wave-uniform slots and factors) the unscaled component sums at b and at a,
 // their difference per component, the projection (e_x d_x + e_y d_y) + e_z d_z, then * scale, then * sqrt(w), one store.
 template <bool kUnit>
 __global__ __launch_bounds__(256) void los_design_kernel(int npairs, long long rows, const double* __restrict__ xyz_a, const double* __restrict__ xyz_b,
@@ -286,16 +249,7 @@ __global__ __launch_bounds__(256) void los_design_kernel(int npairs, long long r
     const int pt = blockIdx.y * 256 + threadIdx.x;
     if (pt >= npairs) return;
     double e[3];
-    if (kUnit) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) e[c] = xyz_b[(size_t)pt * 3 + c] - xyz_a[(size_t)pt * 3 + c];
-        const double len = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) e[c] = e[c] / len;
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) e[c] = directions[(size_t)pt * 3 + c];
-    }
+    line_of_sight(kUnit, xyz_a, xyz_b, directions, (size_t)pt, e);
     const double sw = w ? sqrt(w[pt]) : 1.0;
     const double* Ya = Y + pt;
     const double* Yb = Y + half + pt;

@@ -864,6 +864,17 @@ def check_frames(frames, points):
         raise ValueError('frames must have orthonormal rows: |F F^T - I| is {0:.3g}, above {1:g}'.format(defect, FRAME_TOLERANCE))
 
 
+def _check_gradient_observations(xyz, frames, components, weights):
+    """(picked, layout): what gradient_design and rbf_gradient_design check alike, in this order: the positions, the components (their
+    ascending positions `picked`), the weights (their layout) and the frames; ValueError otherwise."""
+    M = check_positions(xyz)
+    picked = gradient_components(components)
+    layout = check_observation_weights(weights, M, len(picked))
+    if frames is not None:
+        check_frames(frames, M)
+    return picked, layout
+
+
 def gradient_design(max_degree, xyz, GM, R, min_degree=0, frames=None, components=None, weights=None):
     """Transposed design matrix At [P, K, M] (device) of the gravitational gradient tensor at the positions xyz [M, 3]: At[p, k, i] is
     the derivative of the k-th selected component of T' = F T F^T at point i with respect to coefficient p of
@@ -871,11 +882,7 @@ def gradient_design(max_degree, xyz, GM, R, min_degree=0, frames=None, component
     (None: the Earth-fixed tensor); components is a sequence of distinct names from GRADIENT_COMPONENTS in any order (None: all six),
     the output always in canonical order; weights [M] or [M, K] scale the entries by sqrt(w)."""
     min_degree, max_degree = check_degrees(min_degree, max_degree)
-    M = check_positions(xyz)
-    picked = gradient_components(components)
-    layout = check_observation_weights(weights, M, len(picked))
-    if frames is not None:
-        check_frames(frames, M)
+    picked, layout = _check_gradient_observations(xyz, frames, components, weights)
     x = to_device(xyz)
     return gradient_design_checked(max_degree, min_degree, x, None if frames is None else to_device(frames, x.device), picked,
                                    to_device(weights, x.device) if layout else None, GM, R)
@@ -1042,6 +1049,17 @@ def rbf_node_table(basis):
     return cached[:2]
 
 
+def _rbf_design_output(basis, x, *components):
+    """(shape, nodes, J, M, At): the node table of the basis (rbf_node_table) with the nodes on the device of the positions x [M, 3],
+    the numbers of nodes and positions and the empty transposed design matrix At [J, *components, M] on that device."""
+    torch = require_gpu()
+    shape, nodes = rbf_node_table(basis)
+    if nodes.device != x.device:
+        nodes = nodes.to(x.device)
+    J, M = int(nodes.shape[0]), int(x.shape[0])
+    return shape, nodes, J, M, torch.empty((J,) + components + (M,), dtype=torch.float64, device=x.device)
+
+
 def rbf_design(kind, basis, xyz, xyz_b=None, directions=None, weights=None):
     """Transposed design matrix At [J, K, M] (acceleration, K = 3) or [J, M] (device) of the observations `kind` (one of RBF_KINDS) with
     respect to the node values of the isotropic gravityfield.RadialBasisFunctions `basis`: At[j, ..., i] is the derivative of the
@@ -1074,12 +1092,7 @@ def rbf_design(kind, basis, xyz, xyz_b=None, directions=None, weights=None):
 def rbf_design_checked(kind, basis, a, b, directions, weights):
     """shg_rbf_design on device tensors that rbf_design (or a NormalEquations.from_*(basis=...), once for all its blocks) has checked:
     positions a [M, 3], b [M, 3] or None, directions [M, 3] or None, weights [M], [M, 3] or None."""
-    torch = require_gpu()
-    shape, nodes = rbf_node_table(basis)
-    if nodes.device != a.device:
-        nodes = nodes.to(a.device)
-    J, M = int(nodes.shape[0]), int(a.shape[0])
-    out = torch.empty((J, 3, M) if kind == 'acceleration' else (J, M), dtype=torch.float64, device=a.device)
+    shape, nodes, J, M, out = _rbf_design_output(basis, a, *((3,) if kind == 'acceleration' else ()))
     _lib.call('shg_rbf_design', RBF_KINDS.index(kind), int(basis.max_degree), int(basis.min_degree), _host_ptr(shape), _ptr(nodes), J, _ptr(a),
               None if b is None else _ptr(b), None if directions is None else _ptr(directions), M, None if weights is None else _ptr(weights),
               0 if weights is None else weights.dim(), float(basis.GM), float(basis.R), _ptr(out), M, _stream())
@@ -1094,11 +1107,7 @@ def rbf_gradient_design(basis, xyz, frames=None, components=None, weights=None):
     distinct names from GRADIENT_COMPONENTS (None: all six), the output always in canonical order, weights [M] or [M, K] scale the
     entries by sqrt(w).  The columns equal those of gradient_design of the basis's band times
     basis.to_potential_coefficients_matrix()."""
-    M = check_positions(xyz)
-    picked = gradient_components(components)
-    layout = check_observation_weights(weights, M, len(picked))
-    if frames is not None:
-        check_frames(frames, M)
+    picked, layout = _check_gradient_observations(xyz, frames, components, weights)
     rbf_node_table(basis)                                            # an anisotropic K is refused before anything else reaches the device
     x = to_device(xyz)
     return rbf_gradient_design_checked(basis, x, None if frames is None else to_device(frames, x.device), picked,
@@ -1109,12 +1118,7 @@ def rbf_gradient_design_checked(basis, x, frames, picked, weights):
     """shg_rbf_gradient_design on device tensors that rbf_gradient_design (or RadialBasisParameters.from_gradients, once for all its
     blocks) has checked: positions x [M, 3], frames [M, 3, 3] or None, the ascending component positions `picked`, weights [M], [M, K]
     or None."""
-    torch = require_gpu()
-    shape, nodes = rbf_node_table(basis)
-    if nodes.device != x.device:
-        nodes = nodes.to(x.device)
-    J, M = int(nodes.shape[0]), int(x.shape[0])
-    out = torch.empty((J, len(picked), M), dtype=torch.float64, device=x.device)
+    shape, nodes, J, M, out = _rbf_design_output(basis, x, len(picked))
     _lib.call('shg_rbf_gradient_design', int(basis.max_degree), int(basis.min_degree), _host_ptr(shape), _ptr(nodes), J, _ptr(x), M,
               None if frames is None else _ptr(frames), sum(1 << j for j in picked), None if weights is None else _ptr(weights),
               0 if weights is None else weights.dim(), float(basis.GM), float(basis.R), _ptr(out), M, _stream())

@@ -1,6 +1,6 @@
 """Seeded inputs of the fixture of the gradient-tensor design matrix with respect to the node values of radial basis functions
 (tests/golden/make_golden_rbf_gradients.py -> g30_rbf_gradients.npz) and of the tests that replay it, with a float64 NumPy
-restatement of RbfHessianChain (grates_amd/csrc/rbf.h) and rbf_gradient_design_kernel (rbf.hip) in the kernel's operation order: the
+restatement of RbfChain<2> (grates_amd/csrc/rbf.h), RbfGradient (rbf.hip) and FrameTensor (observe.h) in the kernel's operation order: the
 chain, the closed Hessian, the rotation into the instrument frames, the scaling and the weights.  The kernel has no transcendental
 function, so the restatement reproduces it bit for bit.  Needs NumPy only; the basis, the nodes and the points are rbf_inputs'."""
 
@@ -64,9 +64,9 @@ def bias_indicator():
     return B
 
 
-# ---- the restatement of RbfHessianChain and rbf_gradient_design_kernel ---------------------------------------------------------------
+# ---- the restatement of RbfChain<2>, RbfGradient and FrameTensor ---------------------------------------------------------------------------
 def degree_table(k, min_degree, dtype=np.float64):
-    """(alpha, beta, gamma, d, e, h) [N + 1] each, as rbf_degree_table builds them for RbfDegree2: h = (n + 2) e"""
+    """(alpha, beta, gamma, d, e, h) [N + 1] each, as rbf_degree_table builds them for RbfDegree<2>: h = (n + 2) e"""
     k = np.asarray(k, dtype=dtype)
     n = np.arange(k.size).astype(dtype)
     one, two = dtype(1.0), dtype(2.0)
@@ -80,7 +80,7 @@ def degree_table(k, min_degree, dtype=np.float64):
 
 
 def hessians(xyz, nodes, k, min_degree, GM=GM, R=R, dtype=np.float64):
-    """(T [M, J, 6], scale [M]): the six unscaled Earth-fixed entries xx, xy, xz, yy, yz, zz of RbfHessianChain.finish for every (point,
+    """(T [M, J, 6], scale [M]): the six unscaled Earth-fixed entries xx, xy, xz, yy, yz, zz of RbfChain<2>.finish for every (point,
     node) pair and GM / (R r^2) as the kernel forms it.  dtype=np.longdouble runs the same operations in extended precision (the
     inputs are the float64 values, converted exactly)."""
     alpha, beta, gamma, d, e, h = degree_table(k, min_degree, dtype)

@@ -129,7 +129,7 @@ def project(e, gb, ga):
 
 # ---- the restatement of rbf.h ------------------------------------------------------------------------------------------------------
 def degree_table(k, min_degree):
-    """(alpha, beta, gamma, d, e) [N + 1] each, as rbf_degree_table builds them"""
+    """(alpha, beta, gamma, d, e) [N + 1] each, as rbf_degree_table builds them for RbfDegree<1>"""
     n = np.arange(k.size, dtype=float)
     safe = np.maximum(n, 1.0)
     alpha = np.where(n > 0, (2.0 * n - 1.0) / safe, 0.0)
@@ -140,7 +140,7 @@ def degree_table(k, min_degree):
 
 
 def chains(xyz, nodes, k, min_degree, GM=GM, R=R):
-    """(V [M, J], g [M, J, 3]): RbfPoint, RbfChain and the scaling of rbf_design_kernel for every (point, node) pair"""
+    """(V [M, J], g [M, J, 3]): RbfPoint, RbfChain<1> and the scaling of RbfObservation (rbf.hip) for every (point, node) pair"""
     alpha, beta, gamma, d, e = degree_table(k, min_degree)
     x, y, z = xyz[:, 0], xyz[:, 1], xyz[:, 2]
     r = np.sqrt((x * x + y * y) + z * z)

@@ -64,7 +64,7 @@ def test_design_matrices_match_the_reference(golden, tag):
         restated = np.abs(A - ri.restatement(kind, ri.node_table(data['lon_' + tag], data['lat_' + tag]), data['k_' + tag], min_degree, a, b, e)).max()
         print('{0} {1}: {2:.2e} of max|A| (bound {3:.2e}); 1 mm off the axis {4:.2e} (bound {5:.2e}); {6:.2e} from the restatement'.format(
             tag, kind, off_axis, bound, axis, axis_bound, restated / float(scales[kind])))
-        if not (off_axis <= bound and axis <= axis_bound):
+        if not (off_axis <= bound and axis <= axis_bound and restated == 0.0):     # the kernel follows the restatement to the last bit
             failures.append(kind)
     assert not failures
 

@@ -1,6 +1,6 @@
 """Acceleration design matrix with respect to the node values of radial basis functions, direct against composed, event-timed
 (DESIGN.md section 4.19).
-    python3 tools/rbf_design_time.py [--repeats R] [--output profiles/rbf_design_time.txt]
+    python3 tools/rbf_design_time.py [--repeats R] [--kinds KIND ...] [--output profiles/rbf_design_time.txt]
 At each size (band 2 .. N, J scattered nodes on GRS80 with flat shape factors, M scattered points), for the acceleration kind:
   direct    engine.rbf_design_checked (one shg_rbf_design call, without the Python checks: the Legendre sum of every (point, node)
             pair), with its fp64 operations (15 per degree and pair: 10 multiplications and 5 additions, none fused) over the time,
@@ -8,6 +8,9 @@ At each size (band 2 .. N, J scattered nodes on GRS80 with flat shape factors, M
   composed  what the package offered before: engine.acceleration_design_checked of the block (At_sh [P][3][M]), then
             engine.gemm with F^T = to_potential_coefficients_matrix()^T resident on the device (F^T At_sh, 2 (3 M) P J flop)
   F         forming F itself (to_potential_coefficients_matrix, host result), once per basis: not part of `composed`
+--kinds names the kinds of engine.RBF_KINDS to time (default: acceleration).  The other three get a `direct` line each, the time of
+one engine.rbf_design_checked call and the bytes of At [J][M] it writes; the pair kinds run at b = a + 220 km along seeded unit vectors,
+the line of sight with those vectors as directions.  There is no composed route for them here.
 Warm-up 2 calls, median of R (default 10).  Prints one line per measurement and a JSON summary line, and writes both to --output."""
 import argparse
 import json
@@ -48,6 +51,7 @@ def median_ms(fn, repeats, warmup=2):
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument('--repeats', type=int, default=10)
+    parser.add_argument('--kinds', nargs='+', choices=ga.engine.RBF_KINDS, default=['acceleration'])
     parser.add_argument('--output', default=os.path.join(ROOT, 'profiles', 'rbf_design_time.txt'))
     args = parser.parse_args()
     ga.engine.require_gpu()
@@ -71,6 +75,20 @@ def main():
         Ft = ga.engine.to_device(np.ascontiguousarray(F.T))                         # [J, P]
         report('F        band {0}..{1:3d} J {2:5d}: {3:9.1f} ms once per basis (wall clock, host result), {4:.2f} GB resident'.format(
             nmin, N, J, f_ms, 8.0 * P * J / 1e9))
+
+        for kind in args.kinds:
+            if kind == 'acceleration':
+                continue
+            d = np.random.default_rng(N + M + 1).standard_normal((M, 3))
+            d = ga.engine.to_device(d / np.sqrt(np.sum(d * d, axis=1))[:, None])
+            b = x + ri.SEPARATION * d if kind in ('line_of_sight', 'potential_difference') else None
+            e = d if kind == 'line_of_sight' else None
+            ms = median_ms(lambda: ga.engine.rbf_design_checked(kind, basis, x, b, e, None), args.repeats)
+            rows.append({'degree': N, 'nodes': J, 'points': M, 'what': 'direct ' + kind, 'ms': ms, 'gbytes_per_s': 8.0 * J * M / ms / 1e6})
+            report('direct   band {0}..{1:3d} J {2:5d} M {3:5d} {4}: {5:9.3f} ms  {6:7.1f} GB/s written'.format(nmin, N, J, M, kind, ms,
+                                                                                                          rows[-1]['gbytes_per_s']))
+        if 'acceleration' not in args.kinds:
+            continue
 
         direct = ga.engine.rbf_design_checked('acceleration', basis, x, None, None, None)
         ms = median_ms(lambda: ga.engine.rbf_design_checked('acceleration', basis, x, None, None, None), args.repeats)
