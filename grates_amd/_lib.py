@@ -133,6 +133,10 @@ PROTOTYPES = {
     'shg_rbf_design_info': [ctypes.POINTER(ctypes.c_int)],
     'shg_rbf_gradient_design': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
                                 c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_void_p],
+    'shg_rbf_surface': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
+                        ctypes.c_int, ctypes.c_void_p],
+    'shg_rbf_surface_info': [ctypes.POINTER(ctypes.c_int)],
+    'shg_column_dots': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
     'shg_whiten_rows': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, c_double_p, ctypes.c_int,
                         ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p],
     'shg_segment_products': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, c_double_p, ctypes.c_longlong, ctypes.c_int,

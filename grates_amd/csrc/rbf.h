@@ -3,7 +3,8 @@
 // shg_rbf_gradient_design).  The start, the recursions of P_n and P'_n and the sums S_r and S_t are the same statements for both
 // orders; the second order adds P''_n and three sums and drops V_j.  The family is tested bit for bit against itself (pairs against
 // single points, one batch size against another, a subset of tensor components against all six): that holds because the operations
-// below, and their order, exist once.
+// below, and their order, exist once.  RbfSurfaceChain at the end is the small chain of the surface synthesis (shg_rbf_surface): the
+// same recursion of P_n, a running power of R / r_j and one sum, with a factor per point and degree in the place of d_n.
 #pragma once
 
 #include "common.h"
@@ -156,6 +157,37 @@ struct RbfChain {
                 const double k = c == d ? 1.0 - xx : -xx;
                 T[j] = ((s.srr * xx - b * k) - m * (pt.xh[c] * ta[d] + ta[c] * pt.xh[d])) + s.stt * (ta[c] * ta[d]);
             }
+    }
+};
+
+// The sum of the surface synthesis (shg_rbf_surface) for one (grid point, node) pair, with t = e_i . e_j and u = R / r_j:
+//   s = sum_{n = min_degree .. N} c_n u^(n+1) P_n(t),      c_n = kn[i][n] d_n, formed once per lane and degree and shared by its chains.
+// P_n by the recursion of RbfChain with the same alpha and beta, u^(n+1) as a running product, no derivative, no fma.  start takes
+// degree 0 with c0 = c_0 (0.0 for a band that starts above it), advance steps a degree below the band without its term, step a degree
+// of the band: un *= u, w = un * p, s = s + c * w, in that order.
+struct RbfSurfaceChain {
+    double t, u, un;                                  // un = u^(n+1)
+    double p1, p2;                                    // P_n, P_{n-1} after the step of degree n
+    double s;
+    __device__ void start(const double* xh, const double* node, double c0) {
+        t = (xh[0] * node[0] + xh[1] * node[1]) + xh[2] * node[2];
+        u = node[3];
+        un = u;
+        p1 = 1.0;
+        p2 = 0.0;
+        s = c0 * un;
+    }
+    __device__ double advance(double alpha, double beta) {
+        const double p = (alpha * t) * p1 - beta * p2;
+        p2 = p1;
+        p1 = p;
+        un *= u;
+        return p;
+    }
+    __device__ void step(double alpha, double beta, double c) {
+        const double p = advance(alpha, beta);
+        const double w = un * p;
+        s = s + c * w;
     }
 };
 

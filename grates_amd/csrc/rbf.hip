@@ -21,6 +21,10 @@
 //   potential difference   K = 1        V(b_i) - V(a_i)
 //   gradient tensor        K = 1 .. 6   the selected components of F_i Hess V(x_i) F_i^T            RbfGradient, shg_rbf_gradient_design
 // so a pair's row is, bit for bit, made of what the single-point kinds compute at its two satellites.
+//
+// The way back from node values to maps is here as well: the surface synthesis St [J][ldt] of a grid's points (rbf_surface_kernel,
+// shg_rbf_surface: the same sum with the surface factors of the functional per point and degree) and the column dot products that
+// turn St and C St into the formal errors of a map (column_dots_kernel, shg_column_dots).
 #include "observe.h"
 #include "rbf.h"
 
@@ -160,6 +164,78 @@ __global__ __launch_bounds__(256) void rbf_sweep_kernel(int N, int J, int M, con
     }
 }
 
+// ---- the surface synthesis of the node values (shg_rbf_surface) ---------------------------------------------------------------------------
+constexpr int kRbfSurfaceUnroll = 4;                  // nodes a lane runs side by side: 6 doubles a chain, 70 VGPRs and 7 waves per SIMD at 4 chains
+static_assert(kRbfTile % kRbfSurfaceUnroll == 0, "a tile is a whole number of groups");
+
+// St[j][i] = sum_{n = min_degree .. N} kn[n][i] d_n u_j^(n+1) P_n(e_i . e_j): the launch geometry of rbf_sweep_kernel, one lane per grid
+// point, 256 per workgroup (blockIdx.x), the nodes blockIdx.y * kRbfTile ... per workgroup, kRbfSurfaceUnroll chains (RbfSurfaceChain)
+// side by side in a lane.  The factor of the point is per degree, so it cannot sit in the wave-uniform table: the lane loads its own
+// kn[n][i] (degree-major, consecutive lanes consecutive doubles), one degree ahead of its use, and forms c_n = kn[n][i] d_n once for its
+// chains.  The rows of kn below max(min_degree, 1) are not read, row 0 only by a band that starts there.  The last group of a tile
+// repeats its last node instead of branching inside the degree loop; the repeats are not stored.
+__global__ __launch_bounds__(256) void rbf_surface_kernel(int N, int min_degree, int J, int M, const RbfDegree<1>* __restrict__ tab,
+                                                          const double* __restrict__ nodes, const double* __restrict__ points,
+                                                          const double* __restrict__ kn, size_t ldk, double* __restrict__ St, size_t ldt) {
+    constexpr int kUnroll = kRbfSurfaceUnroll;
+    const int pt = blockIdx.x * 256 + threadIdx.x;
+    if (pt >= M) return;
+    const double xh[3] = {points[(size_t)pt * 3], points[(size_t)pt * 3 + 1], points[(size_t)pt * 3 + 2]};
+    const double* kp = kn + pt;
+    const int first = max(min_degree, 1);             // the first degree that takes a step with its term
+    const double c0 = min_degree == 0 ? kp[0] * tab[0].d : 0.0;
+
+    const int j0 = blockIdx.y * kRbfTile, j1 = min(j0 + kRbfTile, J);
+    for (int jb = j0; jb < j1; jb += kUnroll) {
+        RbfSurfaceChain ch[kUnroll];
+#pragma unroll
+        for (int i = 0; i < kUnroll; ++i) ch[i].start(xh, nodes + (size_t)min(jb + i, j1 - 1) * 4, c0);
+        for (int n = 1; n < first; ++n) {
+            const RbfDegree<1> f = tab[n];
+#pragma unroll
+            for (int i = 0; i < kUnroll; ++i) ch[i].advance(f.alpha, f.beta);
+        }
+        double ahead = first <= N ? kp[(size_t)first * ldk] : 0.0;
+        for (int n = first; n <= N; ++n) {
+            const RbfDegree<1> f = tab[n];
+            const double c = ahead * f.d;
+            ahead = kp[(size_t)min(n + 1, N) * ldk];
+#pragma unroll
+            for (int i = 0; i < kUnroll; ++i) ch[i].step(f.alpha, f.beta, c);
+        }
+#pragma unroll
+        for (int i = 0; i < kUnroll; ++i) {
+            if (jb + i >= j1) break;
+            St[(size_t)(jb + i) * ldt + pt] = ch[i].s;
+        }
+    }
+}
+
+// ---- column dot products (shg_column_dots) -------------------------------------------------------------------------------------------------
+constexpr int kDotLanes = 64;                         // columns per workgroup: one lane per column, many workgroups for a block of a few thousand
+constexpr int kDotSums = 8;                           // partial sums of a column, loads in flight per operand
+
+// out[i] = sum_r X[r][i] Y[r][i]: row r goes to partial sum r % kDotSums in ascending order, every product rounded before it is added,
+// and the partial sums close as ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)).  The order is a function of `rows` alone.
+__global__ __launch_bounds__(kDotLanes) void column_dots_kernel(int rows, int cols, const double* __restrict__ X, size_t ldx, const double* __restrict__ Y,
+                                                                size_t ldy, double* __restrict__ out) {
+    const int c = blockIdx.x * kDotLanes + threadIdx.x;
+    if (c >= cols) return;
+    const double *x = X + c, *y = Y + c;
+    double a[kDotSums];
+#pragma unroll
+    for (int k = 0; k < kDotSums; ++k) a[k] = 0.0;
+    int r = 0;
+    for (; r + kDotSums <= rows; r += kDotSums) {
+#pragma unroll
+        for (int k = 0; k < kDotSums; ++k) a[k] = a[k] + x[(size_t)(r + k) * ldx] * y[(size_t)(r + k) * ldy];
+    }
+#pragma unroll
+    for (int k = 0; k < kDotSums; ++k)
+        if (r + k < rows) a[k] = a[k] + x[(size_t)(r + k) * ldx] * y[(size_t)(r + k) * ldy];
+    out[c] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+}
+
 }  // namespace shg
 
 using namespace shg;
@@ -206,18 +282,23 @@ static int check_rbf_output(const RbfCall& c, int K) {
     return SHG_OK;
 }
 
-// The call itself, after every check: the table of degrees of the functional's order, built on the host and uploaded to a workspace
-// of the stream, then the sweep over all (point, node) pairs.
+// The table of degrees of one order, built on the host and uploaded to a workspace of the call's stream.
+template <int kOrder>
+static int rbf_upload_degrees(const RbfCall& c, Workspace& ws, RbfDegree<kOrder>*& tab) {
+    if (!ws.alloc(tab, (size_t)c.N + 1)) return fail(SHG_ERR_NOMEM, "%s: workspace allocation failed", c.fn);
+    std::vector<RbfDegree<kOrder>> h((size_t)c.N + 1);
+    rbf_degree_table(c.N, c.min_degree, c.shape, h.data());
+    SHG_HIP(hipMemcpyAsync(tab, h.data(), h.size() * sizeof(RbfDegree<kOrder>), hipMemcpyHostToDevice, c.stream));
+    SHG_HIP(hipStreamSynchronize(c.stream));                         // the one wait of a call: the host table goes out of scope
+    return SHG_OK;
+}
+
+// The call itself, after every check: the table of degrees of the functional's order, then the sweep over all (point, node) pairs.
 template <class Functional>
 static int rbf_sweep(const RbfCall& c, const Functional& fn) {
-    using Degree = RbfDegree<Functional::kOrder>;
     Workspace ws = Workspace::plain(c.stream);
-    Degree* tab;
-    if (!ws.alloc(tab, (size_t)c.N + 1)) return fail(SHG_ERR_NOMEM, "%s: workspace allocation failed", c.fn);
-    std::vector<Degree> h((size_t)c.N + 1);
-    rbf_degree_table(c.N, c.min_degree, c.shape, h.data());
-    SHG_HIP(hipMemcpyAsync(tab, h.data(), h.size() * sizeof(Degree), hipMemcpyHostToDevice, c.stream));
-    SHG_HIP(hipStreamSynchronize(c.stream));                         // the one wait of a call: the host table goes out of scope
+    RbfDegree<Functional::kOrder>* tab;
+    if (int rc = rbf_upload_degrees(c, ws, tab)) return rc;
     hipLaunchKernelGGL(rbf_sweep_kernel<Functional>, dim3(ceil_div(c.M, 256), ceil_div(c.J, kRbfTile)), dim3(256), 0, c.stream, c.N, c.J, c.M, tab, c.nodes,
                        fn, c.GM / c.R, c.R, c.At, (size_t)c.ldt);
     SHG_HIP(hipGetLastError());
@@ -264,4 +345,43 @@ extern "C" int shg_rbf_gradient_design(int N, int min_degree, const double* shap
     SHG_REQUIRE(shape && nodes && xyz && At && (weights || weight_layout == SHG_WEIGHTS_NONE), "%s: NULL pointer", c.fn);
     if (frames) return rbf_sweep(c, RbfGradient<true>{xyz, frames, weights, mask, K, weight_layout});
     return rbf_sweep(c, RbfGradient<false>{xyz, nullptr, weights, mask, K, weight_layout});
+}
+
+// Host only: no HIP call.
+extern "C" int shg_rbf_surface_info(int which[4]) {
+    SHG_REQUIRE(which, "shg_rbf_surface_info: NULL pointer");
+    which[0] = kRbfTile;
+    which[1] = kRbfSurfaceUnroll;
+    which[2] = 256;                                                  // points per workgroup
+    which[3] = 65535 * kRbfTile;                                     // the most nodes of one call
+    return SHG_OK;
+}
+
+extern "C" int shg_rbf_surface(int N, int min_degree, const double* shape, const double* nodes, int J, const double* points, const double* kn, int ldk, int M,
+                               double* St, int ldt, void* stream) {
+    const RbfCall c{"shg_rbf_surface", N, min_degree, shape, nodes, J, M, 0.0, 0.0, St, ldt, (hipStream_t)stream};
+    if (int rc = check_rbf_sizes(c)) return rc;
+    SHG_REQUIRE(ldk >= M, "%s: ldk %d below M %d", c.fn, ldk, M);
+    SHG_REQUIRE(ldt >= M, "%s: ldt %d below M %d", c.fn, ldt, M);
+    SHG_REQUIRE(ldt == 0 || (long long)J <= (1LL << 40) / ldt, "%s: output of %d x %d values is too large", c.fn, J, ldt);
+    if (M == 0 || J == 0) return SHG_OK;
+    SHG_REQUIRE(shape && nodes && points && kn && St, "%s: NULL pointer", c.fn);
+    Workspace ws = Workspace::plain(c.stream);
+    RbfDegree<1>* tab;
+    if (int rc = rbf_upload_degrees(c, ws, tab)) return rc;
+    hipLaunchKernelGGL(rbf_surface_kernel, dim3(ceil_div(M, 256), ceil_div(J, kRbfTile)), dim3(256), 0, c.stream, N, min_degree, J, M, tab, nodes, points, kn,
+                       (size_t)ldk, St, (size_t)ldt);
+    SHG_HIP(hipGetLastError());
+    return SHG_OK;
+}
+
+extern "C" int shg_column_dots(int rows, int cols, const double* X, int ldx, const double* Y, int ldy, double* out, void* stream) {
+    SHG_REQUIRE(rows >= 0 && cols >= 0, "shg_column_dots: negative size (rows %d, cols %d)", rows, cols);
+    SHG_REQUIRE(ldx >= cols && ldy >= cols, "shg_column_dots: leading dimensions %d and %d below the %d columns", ldx, ldy, cols);
+    if (cols == 0) return SHG_OK;
+    SHG_REQUIRE(out && ((X && Y) || rows == 0), "shg_column_dots: NULL pointer");
+    hipLaunchKernelGGL(column_dots_kernel, dim3(ceil_div(cols, kDotLanes)), dim3(kDotLanes), 0, (hipStream_t)stream, rows, cols, X, (size_t)ldx, Y,
+                       (size_t)ldy, out);
+    SHG_HIP(hipGetLastError());
+    return SHG_OK;
 }

@@ -1125,6 +1125,76 @@ def rbf_gradient_design_checked(basis, x, frames, picked, weights):
     return out
 
 
+def rbf_surface_info():
+    """(nodes per workgroup, nodes a lane runs side by side, points per workgroup, most nodes of one call) of shg_rbf_surface: the seams
+    of its launch geometry (host only, no HIP call)."""
+    arr = (ctypes.c_int * 4)()
+    _lib.call('shg_rbf_surface_info', arr)
+    return tuple(int(v) for v in arr)
+
+
+def rbf_surface_tables(grid, kernel, basis):
+    """(points [M, 3], kn_t [N + 1, M]) on the device: what shg_rbf_surface reads of the M points of `grid` for the functional `kernel`
+    (a name of kernel.get_kernel) and the band and constants of the gravityfield.RadialBasisFunctions `basis`.  points are the unit
+    vectors of (geocentric colatitude, longitude) of the grid points on the grid's ellipsoid; kn_t is gravityfield.surface_factors with
+    GM and R of the basis, degree-major -- the colatitudes and factors the spherical harmonic route of the grid uses, bit for bit --
+    with the rows below basis.min_degree set to zero on the host.  The pair is cached by content like the point tables of to_grid
+    (cached_point_tables: the factors of 25600 points at d/o 60 are 10 ms of NumPy, more than the kernels of a map need): callers read
+    the tensors and do not write to them."""
+    def build():
+        colat, lon, kn = grid._point_tables(kernel, int(basis.max_degree), basis.GM, basis.R)
+        lon = np.asarray(lon, dtype=np.float64)
+        kn_t = np.ascontiguousarray(np.asarray(kn, dtype=np.float64).T)
+        kn_t[:int(basis.min_degree)] = 0.0
+        return np.stack((np.sin(colat) * np.cos(lon), np.sin(colat) * np.sin(lon), np.cos(colat)), axis=1), kn_t
+    tag = ('rbf_surface', str(kernel), int(basis.min_degree), float(basis.GM), float(basis.R), float(grid.semimajor_axis), float(grid.flattening))
+    return cached_point_tables(int(basis.max_degree), grid.latitude, grid.longitude, tag, build)
+
+
+def _rows_of_doubles(t, name):
+    """the row stride of a float64 device tensor [rows, columns] whose last dimension is contiguous"""
+    torch = require_gpu()
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1)):
+        raise ValueError('{0} must be a two-dimensional float64 device tensor with a contiguous last dimension'.format(name))
+    return max(int(t.stride(0)), int(t.shape[1]), 1) if t.shape[0] > 1 else max(int(t.shape[1]), 1)
+
+
+def rbf_surface(basis, points, kn_t):
+    """Transposed surface synthesis matrix St [J, M] (device) of the isotropic gravityfield.RadialBasisFunctions `basis` at the points
+    of rbf_surface_tables (or a block of them: points[a:b] and kn_t[:, a:b], whose row stride is honoured): St[j, i] is the value at
+    point i for a unit value at node j (shg_rbf_surface).  The columns of St^T equal those of the grid's synthesis matrix of the
+    basis's band times basis.to_potential_coefficients_matrix()."""
+    torch = require_gpu()
+    shape, nodes = rbf_node_table(basis)
+    ldk = _rows_of_doubles(kn_t, 'kn_t')
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float64 and points.dim() == 2 and points.shape[1] == 3
+            and points.is_contiguous()):
+        raise ValueError('points must be a contiguous float64 device tensor of shape (M, 3)')
+    J, M = int(nodes.shape[0]), int(points.shape[0])
+    if tuple(kn_t.shape) != (int(basis.max_degree) + 1, M):
+        raise ValueError('kn_t of shape {0} does not hold degrees 0 .. {1} of {2} points'.format(tuple(kn_t.shape), int(basis.max_degree), M))
+    if nodes.device != points.device:
+        nodes = nodes.to(points.device)
+    out = torch.empty((J, M), dtype=torch.float64, device=points.device)
+    _lib.call('shg_rbf_surface', int(basis.max_degree), int(basis.min_degree), _host_ptr(shape), _ptr(nodes), J, _ptr(points), _ptr(kn_t), ldk, M,
+              _ptr(out), M, _stream())
+    return out
+
+
+def column_dots(X, Y):
+    """out [cols] (device) with out[i] = sum_r X[r, i] Y[r, i] for float64 device tensors X, Y [rows, cols] (row strides are honoured):
+    the diagonal of X^T Y without the product (shg_column_dots).  The order of the sum depends on the number of rows alone: a column
+    gives the same bits in any batch, at any position and in every call."""
+    torch = require_gpu()
+    ldx, ldy = _rows_of_doubles(X, 'X'), _rows_of_doubles(Y, 'Y')
+    if tuple(X.shape) != tuple(Y.shape) or X.device != Y.device:
+        raise ValueError('column_dots: X {0} and Y {1} must have one shape and one device'.format(tuple(X.shape), tuple(Y.shape)))
+    rows, cols = int(X.shape[0]), int(X.shape[1])
+    out = torch.empty((cols,), dtype=torch.float64, device=X.device)
+    _lib.call('shg_column_dots', rows, cols, _ptr(X), ldx, _ptr(Y), ldy, _ptr(out), _stream())
+    return out
+
+
 def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
     """Decorrelation along the last axis of the device tensor X [..., M] (shg_whiten_rows): Y[..., t - skip] = sum_k h[n][k] X[..., t - k]
     for skip <= t < M with n = min(stage[t], q, t); the rows of X, all axes but the last flattened, belong to channel row % channels.

@@ -1163,6 +1163,109 @@ class RadialBasisFunctions:
         out = six[index].t().reshape(At.shape[2], 3, 3).contiguous()
         return out if as_tensor else engine.to_host(out)
 
+    # ---- from node values to maps (no reference counterpart): the surface synthesis S [M, J] of a grid's points,
+    #      S[i, j] the value at point i of the functional `kernel` for a unit value at node j, in blocks of points (engine.rbf_surface)
+
+    def __surface_blocks(self, grid, kernel, block_points=None, covariance_matrix=None):
+        """The host checks that the surface methods share, in this order -- the kernel name, block_points, the shape of the covariance
+        matrix, an anisotropic K (engine.rbf_node_table: nothing has reached the device before it) -- then (points, kn_t, blocks): the
+        tables of engine.rbf_surface_tables and the slices of the points, block_points each (None: St and C St of a block together
+        stay near 1 GB)."""
+        _kernel.get_kernel(kernel)
+        if block_points is not None and block_points < 1:
+            raise ValueError('block_points must be positive, got {0}'.format(block_points))
+        J = self.point_distribution.size
+        if covariance_matrix is not None and tuple(covariance_matrix.shape) != (J, J):
+            raise ValueError('covariance matrix must have shape ({0}, {0}) for {0} nodes, got {1}'.format(J, tuple(covariance_matrix.shape)))
+        engine.rbf_node_table(self)
+        points, kn_t = engine.rbf_surface_tables(grid, kernel, self)
+        M = int(points.shape[0])
+        step = max((1 << 30) // (16 * max(J, 1)), 1) if block_points is None else int(block_points)
+        return points, kn_t, [slice(start, min(start + step, M)) for start in range(0, M, step)]
+
+    def __node_values(self, values):
+        """(values [T, J] as a host array or device tensor, whether they came as one vector): checked on the host"""
+        v = self.values if values is None else values
+        if not hasattr(v, 'shape'):
+            v = np.asarray(v, dtype=float)
+        J = self.point_distribution.size
+        if len(v.shape) not in (1, 2) or v.shape[-1] != J:
+            raise ValueError('values must have shape ({0},) or (T, {0}) for {0} nodes, got {1}'.format(J, tuple(v.shape)))
+        return (v.reshape(1, J), True) if len(v.shape) == 1 else (v, False)
+
+    def surface_matrix(self, grid, kernel='ewh', as_tensor=False):
+        """S [M, J]: row i is grid point i in the grid's point order, so that ``S @ values`` is the functional `kernel` on the grid; equal
+        to ``grid.synthesis_matrix(min_degree, max_degree, kernel, GM, R) @ to_potential_coefficients_matrix()`` at O(N) instead of
+        O(N^2) per entry (shg_rbf_surface: a closed Legendre sum per point and node).  Isotropic shape factors only; any Grid.  The
+        kernel builds the transposed matrix; the transposition here is a copy meant for modest sizes.  Returns an ndarray, or the
+        float64 device tensor with as_tensor=True."""
+        points, kn_t, _ = self.__surface_blocks(grid, kernel)
+        S = engine.rbf_surface(self, points, kn_t).t().contiguous()
+        return S if as_tensor else engine.to_host(S)
+
+    def synthesize(self, grid, kernel='ewh', values=None, as_tensor=False, block_points=None):
+        """The functional `kernel` of the node values on the points of `grid`: [M], or [T, M] for a series `values` [T, J] of solutions in
+        one pass (default: self.values).  Works through blocks of block_points points (shg_rbf_surface, then engine.gemm), so S is never
+        whole in memory.  The grid is not modified.  Returns an ndarray, or the float64 device tensor with as_tensor=True."""
+        v, single = self.__node_values(values)
+        points, kn_t, blocks = self.__surface_blocks(grid, kernel, block_points)
+        torch = engine.require_gpu()
+        v = engine.to_device(v, points.device)
+        out = torch.empty((v.shape[0], points.shape[0]), dtype=torch.float64, device=points.device)
+        for block in blocks:
+            engine.gemm(v, engine.rbf_surface(self, points[block], kn_t[:, block]), out=out[:, block])
+        out = out[0] if single else out
+        return out if as_tensor else engine.to_host(out)
+
+    def covariance_propagation(self, grid, covariance_matrix, kernel='ewh', as_tensor=False, block_points=None):
+        """Standard deviations [M] of the functional `kernel` on the points of `grid`, sqrt(diag(S C S^T)), from the covariance matrix C
+        [J, J] of the node values (host array or device tensor, read in full).  Per block of points T = C St on engine.gemm, then the
+        column dot products of St and T (engine.column_dots) and the square root, without a clamp (as Grid.covariance_propagation) and
+        without an [M, M] product.  The grid is not modified."""
+        points, kn_t, blocks = self.__surface_blocks(grid, kernel, block_points, covariance_matrix)
+        torch = engine.require_gpu()
+        C = covariance_matrix
+        if not (isinstance(C, torch.Tensor) and C.is_cuda and C.dtype == torch.float64 and C.is_contiguous()):
+            C = engine.to_device(C, points.device)
+        out = torch.empty((points.shape[0],), dtype=torch.float64, device=points.device)
+        for block in blocks:
+            St = engine.rbf_surface(self, points[block], kn_t[:, block])
+            out[block] = torch.sqrt(engine.column_dots(St, engine.gemm(C, St)))
+        return out if as_tensor else engine.to_host(out)
+
+    def basin_functionals(self, grid, masks, kernel='ewh', as_tensor=False):
+        """F [B, J]: the area-weighted means over the masks (one [M] or a stack [B, M] of bool arrays or tensors, B <= 64) of the
+        functional `kernel` on `grid` as row vectors on the node values, ``(area * mask) @ S / sum(area * mask)``, accumulated per block
+        of points with engine.gemm; weights as in Grid.basin_functionals (ones for a grid without areas), an empty mask gives NaN."""
+        m = grid._mask_stack(masks)
+        points, kn_t, blocks = self.__surface_blocks(grid, kernel)
+        torch = engine.require_gpu()
+        m = m.to(points.device)
+        weighted = (m.t().to(torch.float64) * grid._point_weights(points.device)[:, None]).contiguous()             # [M, B]
+        F = torch.zeros((m.shape[0], self.point_distribution.size), dtype=torch.float64, device=points.device)
+        for block in blocks:
+            engine.gemm(weighted[block], engine.rbf_surface(self, points[block], kn_t[:, block]), transa=True, transb=True, beta=1.0, out=F)
+        F = F / weighted.sum(dim=0)[:, None]
+        return F if as_tensor else engine.to_host(F)
+
+    def basin_averages(self, grid, masks, kernel='ewh', values=None):
+        """Basin means [B], or [T, B] for a series `values` [T, J] (default: self.values): basin_functionals times the values (float64
+        device tensor, as Grid.basin_averages)."""
+        v, single = self.__node_values(values)
+        F = self.basin_functionals(grid, masks, kernel, as_tensor=True)
+        out = engine.gemm(engine.to_device(v, F.device), F, transb=True)
+        return out[0] if single else out
+
+    def basin_covariance(self, grid, covariance_matrix, masks, kernel='ewh'):
+        """Covariance of the basin means, F C F^T [B, B] (float64 device tensor, exactly symmetric) with F = basin_functionals(...) and
+        the covariance matrix C [J, J] of the node values, of which ONLY THE UPPER TRIANGLE IS READ (engine.basin_covariance, at most 64
+        masks); the basin standard deviations are sqrt(diag)."""
+        grid._mask_stack(masks)
+        J = self.point_distribution.size
+        if tuple(covariance_matrix.shape) != (J, J):
+            raise ValueError('covariance matrix must have shape ({0}, {0}) for {0} nodes, got {1}'.format(J, tuple(covariance_matrix.shape)))
+        return engine.basin_covariance(self.basin_functionals(grid, masks, kernel, as_tensor=True), covariance_matrix)
+
 
 def rbf_acceleration_design_matrix(basis, xyz, weights=None, as_tensor=False):
     """

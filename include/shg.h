@@ -655,6 +655,38 @@ int shg_rbf_gradient_design(int N, int min_degree, const double* shape, const do
                             int components, const double* weights, int weight_layout, double GM, double R, double* At, int ldt, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Surface synthesis of the node values of isotropic radial basis functions (no reference counterpart)
+ *   St [J][ldt], transposed with the points innermost (the layout of shg_rbf_design: St viewed as [J, M] is a gemm operand as it
+ *   stands; ldt >= M, the entries from M to ldt of a row are not touched):
+ *     St[j][i] = sum_{n = min_degree .. N} kn[n][i] d_n u_j^(n+1) P_n(e_i . e_j),     d_n = k_n (2n + 1),  u_j = R / r_j
+ *   the value at grid point i of the functional whose surface factors are kn, for a unit value at node j.  shape [N + 1] (host), nodes
+ *   [J][4] (device), N and min_degree as in shg_rbf_design; points [M][3] (device) are the unit vectors e_i of the grid points; kn
+ *   [N + 1][ldk] (device, ldk >= M) is DEGREE-MAJOR with the points innermost, kn[n][i] = (1 / k_n(r_i, theta_i)) (R / r_i)^(n+1) GM / R
+ *   of gravityfield.surface_factors.  The rows of kn below max(min_degree, 1) are never read, row 0 only when min_degree is 0: an
+ *   inverse kernel coefficient that is not finite at degree 0 or 1 does not reach a band that starts at 2.
+ *   One kernel with the launch geometry of shg_rbf_design (shg_rbf_surface_info, host only: which = {nodes per tile, nodes side by
+ *   side in a lane, points per workgroup, most nodes of a call}); P_n by the recursion of shg_rbf_design, u^(n+1) as a running
+ *   product, c = kn[n][i] d_n once per lane and degree, then s = s + c (u^(n+1) P_n); no workspace but the table of N + 1 degrees, no
+ *   fma, no atomics, no LDS: an entry depends on its point and its node only, not on M, J, ldk, ldt or the place in the batch, and
+ *   repeated calls are bitwise equal.  Arguments are checked before the first HIP call (N, min_degree, J or M < 0; min_degree > N;
+ *   N > 32767; J above the nodes one call takes; ldk < M; ldt < M; more than 2^40 values of St; NULL shape, nodes, points, kn or St);
+ *   M = 0 or J = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_rbf_surface(int N, int min_degree, const double* shape, const double* nodes, int J, const double* points, const double* kn, int ldk, int M,
+                    double* St, int ldt, void* stream);
+int shg_rbf_surface_info(int which[4]);
+
+/* ------------------------------------------------------------------------------------------------
+ * Column dot products: out[i] = sum_r X[r][i] Y[r][i] for X [rows][ldx], Y [rows][ldy] (device, ldx, ldy >= cols), out [cols]
+ *   The diagonal of X^T Y without the product: with X = St and Y = C St of shg_rbf_surface, diag(S C S^T).  One lane per column; row r
+ *   goes to partial sum r % 8 of its column in ascending order, every product rounded before it is added (no fma), and the eight sums
+ *   close as ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)): the order depends on `rows` alone, not on cols, the launch or the
+ *   position of the column, no atomics -- two calls, or a column computed within any batch, give the same bits.  rows = 0 gives zeros.
+ *   Checked before the first HIP call: negative sizes, ldx or ldy < cols, NULL out, NULL X or Y with rows > 0; cols = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_column_dots(int rows, int cols, const double* X, int ldx, const double* Y, int ldy, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decorrelation of coloured observation noise along the point axis (the banded lower-triangular W with W^T W = Sigma^-1 of a sequence
  * of scalar AR models of orders 0 .. q; no reference counterpart)
  *   X [rows][ldx] with M columns in use, row r of channel r % channels: the transposed design matrix At [P][K][ldt] of the three calls
