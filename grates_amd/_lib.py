@@ -22,6 +22,10 @@ class ShgError(RuntimeError):
         self.status = status
 
 
+# the arguments of the shg_*_points_at family behind the fields: run_first, run_begin (host), runs, weights, W, GM, R, out, stream
+_POINTS_AT_TAIL = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p,
+                   ctypes.c_void_p]
+
 # name -> argument types (all functions return int, except the two string getters)
 PROTOTYPES = {
     'shg_plan_create': [ctypes.POINTER(c_plan_p), ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int],
@@ -124,6 +128,13 @@ PROTOTYPES = {
                              c_double_p, ctypes.c_void_p],
     'shg_potential_points_om': [ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                 ctypes.c_double, c_double_p, ctypes.c_void_p],
+    'shg_acceleration_points_at': [ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int] + _POINTS_AT_TAIL,
+    'shg_acceleration_points_at_om': [ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int] + _POINTS_AT_TAIL,
+    'shg_potential_points_at': [ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int] + _POINTS_AT_TAIL,
+    'shg_potential_points_at_om': [ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int] + _POINTS_AT_TAIL,
+    'shg_gravitational_gradients_points_at': [ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int] + _POINTS_AT_TAIL,
+    'shg_gravitational_gradients_points_at_om': [ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int] + _POINTS_AT_TAIL,
+    'shg_points_at_set_workspace_limit': [ctypes.c_longlong],
     'shg_potential_design': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_double, ctypes.c_double, c_double_p,
                              ctypes.c_int, ctypes.c_void_p],
     'shg_potential_difference_design': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, ctypes.c_double,

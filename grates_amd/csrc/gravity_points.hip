@@ -180,6 +180,25 @@ __global__ __launch_bounds__(256) void potential_combine_kernel(CoefSource src, 
 // degree, which the double2 copies of the staging still cover exactly)
 constexpr int stage_degrees(int C, int EP) { return 64 * 2 * C * EP * 8 > (24 << 10) ? 32 : 64; }
 
+// The values of one point and field: C = 1 V, C = 3 g [3], C = 6 (xx, xy, xz, yy, yz, zz) T [3][3], each off-diagonal value twice.
+template <int C>
+__device__ inline void store_values(double* o, const double (&v)[C]) {
+    if constexpr (C == 6) {
+        o[0] = v[0];
+        o[1] = v[1];
+        o[2] = v[2];
+        o[3] = v[1];
+        o[4] = v[3];
+        o[5] = v[4];
+        o[6] = v[2];
+        o[7] = v[4];
+        o[8] = v[5];
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) o[c] = v[c];
+    }
+}
+
 // 256 lanes = 256 points x EP epochs (grid.y = pass), C components each.  Per order k the 2 C coefficients of every epoch are staged in
 // LDS in chunks of kDegrees degrees, together with the recursion factors a, b of degree Nq; the degree loop reads them as LDS
 // broadcasts, so any degree fits.  The recursion itself is SolidColumn<kDirect> (solid.h).  C = 1 writes V [b][pt]; C = 3 writes
@@ -235,29 +254,98 @@ __global__ __launch_bounds__(256) void solid_points_kernel(int Nq, int npts, int
         for (int e = 0; e < EP; ++e) {
             const int b = pass * EP + e;
             if (b < B) {
-                if constexpr (C == 1) {
-                    out[(size_t)b * npts + pt] = acc[0][e] * scale;
-                } else if constexpr (C == 3) {
-                    double* o = out + ((size_t)b * npts + pt) * 3;
-                    o[0] = acc[0][e] * scale;
-                    o[1] = acc[1][e] * scale;
-                    o[2] = acc[2][e] * scale;
-                } else {
-                    const double xx = acc[0][e] * scale, xy = acc[1][e] * scale, xz = acc[2][e] * scale;
-                    const double yy = acc[3][e] * scale, yz = acc[4][e] * scale, zz = acc[5][e] * scale;
-                    double* o = out + ((size_t)b * npts + pt) * 9;
-                    o[0] = xx;
-                    o[1] = xy;
-                    o[2] = xz;
-                    o[3] = xy;
-                    o[4] = yy;
-                    o[5] = yz;
-                    o[6] = xz;
-                    o[7] = yz;
-                    o[8] = zz;
+                double v[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[c] = acc[c][e] * scale;
+                store_values<C>(out + ((size_t)b * npts + pt) * (C == 6 ? 9 : C), v);
+            }
+        }
+    }
+}
+
+// A workgroup of solid_points_at_kernel: `count` <= 256 consecutive points from `begin` whose window starts at field `field` of Q.
+struct AtTile {
+    int field, begin, count;
+};
+
+// Every point at its own fields: out[i] = scale sum_{j < W} weights[i][j] S(field first_i + j, x_i), S the unscaled sums of
+// solid_points_kernel.  One workgroup per tile, one lane per point.  Q [field][packed (n', k) of degree Nq][2 C] holds every field
+// once; the window is swept in chunks of E fields: per order and kDegrees degrees the chunk's numbers are staged in LDS, transposed to
+// the [2 C][E] of solid_points_kernel's stage, and the degree loop is that kernel's, so acc[c][e] is bitwise its value of the field.
+// Slots past W are staged as zeros and weighted with zero.  After a sweep the E weights of the point are loaded and res[c] takes
+// one fma per field, fields ascending from 0.0; the column restarts for the next chunk.  One plain store per value, after the
+// product with scale.
+template <int C, int E, int kDegrees, bool kDirect>
+__global__ __launch_bounds__(256) void solid_points_at_kernel(int Nq, int W, const AtTile* __restrict__ tiles, const double* __restrict__ xyz,
+                                                              const double2* __restrict__ ab, const double* __restrict__ Q,
+                                                              const double* __restrict__ weights, double R, double scale, double* __restrict__ out) {
+    constexpr int kNumbers = 2 * C;                                  // doubles per (n', k) and field in Q
+    constexpr int kStride = kNumbers * E;                            // doubles per (n', k) in the stage
+    __shared__ __attribute__((aligned(16))) double stage[kDegrees * kStride];
+    __shared__ double2 abs_[kDegrees];
+    const int tid = threadIdx.x;
+    const AtTile tile = tiles[blockIdx.x];
+    const bool ok = tid < tile.count;
+    const size_t pt = (size_t)tile.begin + (ok ? tid : 0);
+    const size_t field_stride = (size_t)packed_count(Nq) * kNumbers;
+    double res[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) res[c] = 0.0;
+    for (int j0 = 0; j0 < W; j0 += E) {
+        const int live = min(E, W - j0);                             // fields of this chunk inside the window
+        const double* Qw = Q + (size_t)(tile.field + j0) * field_stride;
+        SolidColumn<kDirect> col;
+        col.start(xyz + pt * 3, R);
+        double acc[C][E];
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+#pragma unroll
+            for (int e = 0; e < E; ++e) acc[c][e] = 0.0;
+        for (int k = 0; k <= Nq; ++k) {
+            col.order(k);
+            const int off = order_offset(Nq, k);
+            for (int n0 = k; n0 <= Nq; n0 += kDegrees) {
+                const int cnt = min(kDegrees, Nq + 1 - n0);
+                __syncthreads();                                     // the previous chunk has been consumed
+                {
+                    // lane -> (field e fastest, number r): the stage is written in order, a field is read in runs of 256 / E doubles
+                    const double* src = Qw + (size_t)(off + n0 - k) * kNumbers;
+                    for (int i = tid; i < cnt * kStride; i += 256) {
+                        const int e = i % E, r = i / E;
+                        stage[(r / kNumbers) * kStride + (r % kNumbers) * E + e] = e < live ? src[(size_t)e * field_stride + r] : 0.0;
+                    }
+                    for (int i = tid; i < cnt; i += 256) abs_[i] = ab[off + n0 - k + i];
+                }
+                __syncthreads();
+                for (int j = 0; j < cnt; ++j) {
+                    double yc, ys;
+                    col.degree(n0 + j, k, abs_ + j, yc, ys);
+                    const double* q = stage + j * kStride;
+#pragma unroll
+                    for (int c = 0; c < C; ++c)
+#pragma unroll
+                        for (int e = 0; e < E; ++e) {
+                            acc[c][e] = fma(yc, q[(2 * c) * E + e], acc[c][e]);
+                            acc[c][e] = fma(ys, q[(2 * c + 1) * E + e], acc[c][e]);
+                        }
                 }
             }
         }
+        if (ok) {
+            const double* w = weights + pt * W + j0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const double we = e < live ? w[e] : 0.0;
+#pragma unroll
+                for (int c = 0; c < C; ++c) res[c] = fma(we, acc[c][e], res[c]);
+            }
+        }
+    }
+    if (ok) {
+        double v[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = res[c] * scale;
+        store_values<C>(out + pt * (C == 6 ? 9 : C), v);
     }
 }
 
@@ -397,3 +485,146 @@ extern "C" int shg_potential_points_om(int N, const double* xyz, int M, int layo
                                        void* stream) {
     return points_entry<Potential>("shg_potential_points_om", xyz, M, layout, CoefSource{nullptr, om, N, B, Bpad}, GM, R, V, stream);
 }
+
+// ---- every point at its own fields (shg_*_points_at): DESIGN.md section 4.22
+
+static std::atomic<long long> g_points_at_limit{0};                 // bytes of Q per launch group; 0: the default
+constexpr long long kPointsAtDefaultLimit = 256LL << 20;
+
+extern "C" int shg_points_at_set_workspace_limit(long long bytes) {
+    SHG_REQUIRE(bytes >= 0, "shg_points_at_set_workspace_limit: negative limit %lld", bytes);
+    g_points_at_limit.store(bytes);
+    return SHG_OK;
+}
+
+struct PointsAtArgs {
+    const double* xyz;
+    int M;
+    const int *run_first, *run_begin;
+    int runs;
+    const double* weights;
+    int W;
+    double GM, R;
+    double* out;
+};
+
+template <class F>
+static long long points_at_field_bytes(int N) {                      // Q of one field
+    return (long long)(N + F::kOffset + 1) * (N + F::kOffset + 2) / 2 * 2 * F::kComponents * 8;
+}
+
+// Arguments are checked before the first HIP call, the run tables in full: no table content reaches the kernel unchecked.
+template <class F>
+static int check_points_at(const char* fn, const CoefSource& src, const PointsAtArgs& a) {
+    const int N = src.N, B = src.B, M = a.M, W = a.W;
+    SHG_REQUIRE(N >= 0 && M >= 0 && B >= 0, "%s: negative size (N %d, M %d, B %d)", fn, N, M, B);
+    SHG_REQUIRE(W >= 1 && W <= 16, "%s: window of %d fields, expected 1 .. 16", fn, W);
+    SHG_REQUIRE(B >= W, "%s: %d fields, fewer than the window of %d", fn, B, W);
+    SHG_REQUIRE(a.runs >= 0, "%s: negative number of runs %d", fn, a.runs);
+    SHG_REQUIRE(src.Bpad >= B, "%s: Bpad %d below B %d", fn, src.Bpad, B);
+    SHG_REQUIRE(std::isfinite(a.GM) && std::isfinite(a.R) && a.R > 0.0, "%s: GM and R must be finite and R positive (GM %g, R %g)", fn, a.GM, a.R);
+    const long long values = (long long)F::kValues * M;
+    SHG_REQUIRE(values <= (1LL << 40), "%s: output of %lld values is too large", fn, values);
+    if constexpr (F::kCheckQ) {
+        const long long q_pass = points_at_field_bytes<F>(N) / 8 * F::kMaxEP;
+        SHG_REQUIRE(q_pass <= INT_MAX, "%s: degree %d is too large (a pass of Q holds %lld values)", fn, N, q_pass);
+    }
+    if (M == 0) return SHG_OK;
+    SHG_REQUIRE(a.xyz && (src.om ? src.om : src.anm) && a.run_first && a.run_begin && a.weights && a.out, "%s: NULL pointer", fn);
+    SHG_REQUIRE(a.run_begin[0] == 0, "%s: run_begin[0] is %d, not 0", fn, a.run_begin[0]);
+    for (int r = 0; r < a.runs; ++r) {
+        SHG_REQUIRE(a.run_begin[r + 1] > a.run_begin[r] && a.run_begin[r + 1] <= M, "%s: run_begin must increase strictly up to M %d (run %d: %d, %d)", fn,
+                    M, r, a.run_begin[r], a.run_begin[r + 1]);
+        SHG_REQUIRE(a.run_first[r] >= 0 && a.run_first[r] <= B - W, "%s: run %d starts at field %d, outside 0 .. B - W = %d", fn, r, a.run_first[r],
+                    B - W);
+    }
+    SHG_REQUIRE(a.run_begin[a.runs] == M, "%s: the runs end at point %d, not at M %d", fn, a.run_begin[a.runs], M);
+    return SHG_OK;
+}
+
+template <class F>
+static int solid_points_at(const char* fn, const CoefSource& src, const PointsAtArgs& a, long long limit, hipStream_t stream) {
+    constexpr int C = F::kComponents;
+    const int Nq = src.N + F::kOffset, B = src.B, W = a.W;
+    const long long per_field = points_at_field_bytes<F>(src.N) / 8;           // doubles of Q per field
+    // fields per launch group: Q of a group stays under the limit; groups overlap by W - 1 fields, a run goes to the group
+    // first / step, whose fields group * step .. group * step + G - 1 hold its window
+    const int G = (int)std::min<long long>(B, limit / 8 / per_field);
+    const int step = G - W + 1;
+    const int groups = (B - W) / step + 1;
+    std::vector<long long> tile0(groups + 1, 0);                               // first tile of every group
+    for (int r = 0; r < a.runs; ++r) tile0[a.run_first[r] / step + 1] += ceil_div(a.run_begin[r + 1] - a.run_begin[r], 256);
+    for (int g = 0; g < groups; ++g) tile0[g + 1] += tile0[g];
+    SHG_REQUIRE(tile0[groups] <= INT_MAX, "%s: %lld tiles are too many", fn, tile0[groups]);
+    std::vector<AtTile> tiles((size_t)tile0[groups]);
+    {
+        std::vector<long long> next(tile0.begin(), tile0.end() - 1);
+        for (int r = 0; r < a.runs; ++r) {
+            const int g = a.run_first[r] / step;
+            for (int p = a.run_begin[r]; p < a.run_begin[r + 1]; p += 256)
+                tiles[(size_t)next[g]++] = AtTile{a.run_first[r] - g * step, p, std::min(256, a.run_begin[r + 1] - p)};
+        }
+    }
+    // fields per sweep: a sweep of 16 (2 waves per SIMD) costs as much as four sweeps of 4, so it pays from 13 fields on
+    // (profiles/points_at_time.txt)
+    const int E = W <= 2 ? 2 : W <= 12 ? 4 : std::min(16, F::kMaxEP);
+    const double scale = F::scale(a.GM, a.R);
+    {
+        Workspace ws = Workspace::plain(stream);
+        double2* ab;
+        double* Q;
+        AtTile* table;
+        if (int rc = upload_solid_factors(fn, ws, Nq, stream, ab)) return rc;
+        if (!ws.alloc(Q, (size_t)G * per_field, table, tiles.size())) return fail(SHG_ERR_NOMEM, "%s: workspace allocation failed", fn);
+        SHG_HIP(hipMemcpyAsync(table, tiles.data(), tiles.size() * sizeof(AtTile), hipMemcpyHostToDevice, stream));
+        SHG_HIP(hipStreamSynchronize(stream));                       // as upload_solid_factors: the host table goes out of scope
+        for (int g = 0; g < groups; ++g) {
+            const int count = (int)(tile0[g + 1] - tile0[g]);
+            if (count == 0) continue;
+            const int fields = std::min(G, B - g * step);
+            const long long threads = (long long)packed_count(Nq) * fields;
+            hipLaunchKernelGGL(F::kCombine, dim3((unsigned)ceil_div64(threads, 256)), dim3(256), 0, stream, src, 1, g * step, fields, Q);
+            auto launch = [&](auto e) {
+                constexpr int kE = decltype(e)::value;
+                hipLaunchKernelGGL((solid_points_at_kernel<C, kE, stage_degrees(C, kE), F::kDirect>), dim3(count), dim3(256), 0, stream, Nq, W,
+                                   table + tile0[g], a.xyz, ab, Q, a.weights, a.R, scale, a.out);
+            };
+            if (E == 2)
+                launch(std::integral_constant<int, 2>());
+            else if (E == 4)
+                launch(std::integral_constant<int, 4>());
+            else if constexpr (F::kMaxEP == 16)
+                launch(std::integral_constant<int, 16>());
+            SHG_HIP(hipGetLastError());
+        }
+    }
+    SHG_HIP(hipGetLastError());
+    return SHG_OK;
+}
+
+template <class F>
+static int points_at_entry(const char* fn, CoefSource src, const PointsAtArgs& a, void* stream) {
+    if (int rc = check_points_at<F>(fn, src, a)) return rc;
+    if (a.M == 0) return SHG_OK;
+    long long limit = g_points_at_limit.load();
+    if (limit == 0) limit = kPointsAtDefaultLimit;
+    const long long window = points_at_field_bytes<F>(src.N) * a.W;
+    SHG_REQUIRE(limit >= window, "%s: the workspace limit of %lld bytes is below one window of %d fields (%lld bytes)", fn, limit, a.W, window);
+    return solid_points_at<F>(fn, src, a, limit, (hipStream_t)stream);
+}
+
+#define SHG_POINTS_AT(name, F, value)                                                                                                          \
+    extern "C" int name(int N, const double* xyz, int M, const double* anm, int B, const int* run_first, const int* run_begin, int runs,        \
+                        const double* weights, int W, double GM, double R, double* value, void* stream) {                                       \
+        return points_at_entry<F>(#name, CoefSource{anm, nullptr, N, B, B}, PointsAtArgs{xyz, M, run_first, run_begin, runs, weights, W, GM, R, value}, \
+                                  stream);                                                                                                     \
+    }                                                                                                                                          \
+    extern "C" int name##_om(int N, const double* xyz, int M, const double* om, int B, int Bpad, const int* run_first, const int* run_begin,    \
+                             int runs, const double* weights, int W, double GM, double R, double* value, void* stream) {                        \
+        return points_at_entry<F>(#name "_om", CoefSource{nullptr, om, N, B, Bpad}, PointsAtArgs{xyz, M, run_first, run_begin, runs, weights, W, GM, R, value}, \
+                                  stream);                                                                                                     \
+    }
+SHG_POINTS_AT(shg_acceleration_points_at, Acceleration, g)
+SHG_POINTS_AT(shg_potential_points_at, Potential, V)
+SHG_POINTS_AT(shg_gravitational_gradients_points_at, Gradients, T)
+#undef SHG_POINTS_AT

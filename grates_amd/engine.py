@@ -767,6 +767,119 @@ def potential_points(max_degree, xyz, coefficients, GM, R):
     return _functional_points('potential_points', (), max_degree, xyz, coefficients, GM, R)
 
 
+POINTS_AT_WINDOW = 16                                            # fields per point of one shg_*_points_at call
+
+
+def points_at_plan(first):
+    """(order, run_first, run_begin) of the window starts `first` [M] (host ints): the runs of consecutive points with one window start
+    as shg_*_points_at takes them (int32: run r covers the points run_begin[r] .. run_begin[r + 1] - 1 and starts at field
+    run_first[r]).  `order` is None where `first` is non-decreasing; else the stable sort of `first`, the runs are those of
+    first[order], and the result of point order[i] is row i of the call's output.  Host only."""
+    first = np.asarray(first)
+    M = int(first.shape[0])
+    order = None
+    if M > 1 and bool(np.any(first[1:] < first[:-1])):
+        order = np.argsort(first, kind='stable')
+        first = first[order]
+    if M == 0:
+        return order, np.zeros(0, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    starts = np.flatnonzero(np.concatenate(([True], first[1:] != first[:-1])))
+    return order, np.ascontiguousarray(first[starts], dtype=np.int32), np.concatenate((starts, [M])).astype(np.int32)
+
+
+def check_points_at(max_degree, xyz, coefficients, first, weights):
+    """(M, B, W, first) of a shg_*_points_at call: positions xyz [M, 3], the fields `coefficients` (a batch [B, N+1, N+1] or an
+    OrderMajorSeries of degree max_degree), window starts `first` [M] (host ints in 0 .. B - W, returned as an int64 array) and finite
+    weights [M, W], W >= 1; ValueError otherwise.  Host arrays are checked on the host, before anything reaches the device."""
+    M = check_positions(xyz)
+    if isinstance(coefficients, OrderMajorSeries):
+        if coefficients.max_degree != max_degree:
+            raise ValueError('the series holds degrees up to {0}, not {1}'.format(coefficients.max_degree, max_degree))
+        B = coefficients.epochs
+    else:
+        shape = tuple(coefficients.shape)
+        if len(shape) != 3 or shape[1] != shape[2] or shape[1] != max_degree + 1:
+            raise ValueError('coefficient batch must have shape (B, {0}, {0}), got {1}'.format(max_degree + 1, shape))
+        B = int(shape[0])
+    first = np.asarray(first)
+    if first.shape != (M,) or first.dtype.kind not in 'iu':
+        raise ValueError('first must be an integer array of shape ({0},), got {1} of {2}'.format(M, first.dtype, first.shape))
+    first = first.astype(np.int64)
+    if not hasattr(weights, 'shape'):
+        weights = np.asarray(weights, dtype=np.float64)
+    shape = tuple(weights.shape)
+    if len(shape) != 2 or shape[0] != M or shape[1] < 1:
+        raise ValueError('weights must have shape ({0}, W) with W >= 1, got {1}'.format(M, shape))
+    W = int(shape[1])
+    if W > B:
+        raise ValueError('a window of {0} fields, but only {1} fields'.format(W, B))
+    if M and (int(first.min()) < 0 or int(first.max()) > B - W):
+        bad = int(np.flatnonzero((first < 0) | (first > B - W))[0])
+        raise ValueError('first[{0}] is {1}, outside 0 .. {2} ({3} fields, windows of {4})'.format(bad, int(first[bad]), B - W, B, W))
+    finite = bool(np.all(np.isfinite(weights))) if isinstance(weights, np.ndarray) else bool(weights.isfinite().all())
+    if not finite:
+        raise ValueError('weights must be finite')
+    return M, B, W, first
+
+
+def _functional_points_at(stem, tail, max_degree, xyz, coefficients, first, weights, GM, R):
+    """out [M, *tail] of shg_<stem>_at (a batch) / shg_<stem>_at_om (an OrderMajorSeries): sum_j weights[i, j] of the functional of field
+    first[i] + j at point i."""
+    M, B, W, first = check_points_at(max_degree, xyz, coefficients, first, weights)
+    if not (np.isfinite(GM) and np.isfinite(R) and R > 0):
+        raise ValueError('GM and R must be finite and R positive, got {0} and {1}'.format(GM, R))
+    torch = require_gpu()
+    om = isinstance(coefficients, OrderMajorSeries)
+    coef = coefficients.data if om else to_device(coefficients)
+    x, w = to_device(xyz, coef.device), to_device(weights, coef.device)
+    if M == 0:
+        return torch.empty((0,) + tail, dtype=torch.float64, device=coef.device)
+    order, run_first, run_begin = points_at_plan(first)
+    if order is not None:
+        index = torch.from_numpy(order).to(coef.device)
+        x, w = x.index_select(0, index), w.index_select(0, index)
+    fields = (_ptr(coef), B, coefficients.padded_epochs) if om else (_ptr(coef), B)
+    out = None
+    for j0 in range(0, W, POINTS_AT_WINDOW):                      # windows above 16 fields: calls of at most 16, added in order
+        count = min(POINTS_AT_WINDOW, W - j0)
+        part = torch.empty((M,) + tail, dtype=torch.float64, device=coef.device)
+        w_part = w if count == W else w[:, j0:j0 + count].contiguous()
+        shifted = np.ascontiguousarray(run_first + j0, dtype=np.int32)
+        _lib.call('shg_' + stem + ('_at_om' if om else '_at'), int(max_degree), _ptr(x), M, *fields, _host_ptr(shifted), _host_ptr(run_begin),
+                  int(run_first.shape[0]), _ptr(w_part), count, float(GM), float(R), _ptr(part), _stream())
+        out = part if out is None else out.add_(part)
+    if order is not None:
+        out = torch.empty_like(out).index_copy_(0, index, out)
+    return out
+
+
+def acceleration_points_at(max_degree, xyz, coefficients, first, weights, GM, R):
+    """Gravitational acceleration g [M, 3] (device, m/s^2) of a time-variable field, every point at its own epoch:
+    g[i] = sum_{j < W} weights[i, j] g(field first[i] + j)(xyz[i]) of the fields `coefficients` -- a batch [B, N+1, N+1] or an
+    OrderMajorSeries, read in its own layout -- with constants GM and R (shg_acceleration_points_at / _om).  xyz [M, 3] and weights
+    [M, W] on the host or on the device; first [M] host ints, the window start per point.  Where first is not non-decreasing the points
+    are reordered by a stable sort and the results scattered back; W > 16 takes one call per 16 fields, added in order."""
+    return _functional_points_at('acceleration_points', (3,), max_degree, xyz, coefficients, first, weights, GM, R)
+
+
+def gravitational_gradients_points_at(max_degree, xyz, coefficients, first, weights, GM, R):
+    """Gravitational gradient tensor T [M, 3, 3] (device, s^-2) of a time-variable field, every point at its own epoch: as
+    acceleration_points_at (shg_gravitational_gradients_points_at / _om)."""
+    return _functional_points_at('gravitational_gradients_points', (3, 3), max_degree, xyz, coefficients, first, weights, GM, R)
+
+
+def potential_points_at(max_degree, xyz, coefficients, first, weights, GM, R):
+    """Gravitational potential V [M] (device, m^2/s^2) of a time-variable field, every point at its own epoch: as
+    acceleration_points_at (shg_potential_points_at / _om)."""
+    return _functional_points_at('potential_points', (), max_degree, xyz, coefficients, first, weights, GM, R)
+
+
+def points_at_set_workspace_limit(nbytes):
+    """The bytes of combined coefficients one launch group of the shg_*_points_at calls may hold, process-wide (0: the default of
+    256 MB).  Host only."""
+    _lib.call('shg_points_at_set_workspace_limit', int(nbytes))
+
+
 def check_observation_weights(weights, points, components=3):
     """The layout of the weights of `points` observed positions with `components` observed values each: None (returns 0), w [M] per
     point (1) or w [M, components] per component (2), finite and >= 0; ValueError otherwise.  Host arrays are checked on the host,

@@ -8,6 +8,10 @@ Legendre + longitude stage); containers keep ``anm`` as NumPy arrays exactly lik
 batched entry points also accept / return device tensors.
 """
 
+import bisect
+import collections
+import datetime
+
 import numpy as np
 
 from . import engine, kernel as _kernel, utilities
@@ -449,6 +453,118 @@ def _stack_pairs(xyz_a, xyz_b):
     return torch.cat((a, engine.to_device(xyz_b, a.device)), dim=-2)
 
 
+# One engine.*_points_at call of a time-variable field at M points, each at its own epoch: the fields `coefficients` (a host batch
+# [B, N+1, N+1] or an engine.OrderMajorSeries) of degree max_degree with constants GM and R, the window start per point first [M] and
+# the weights [M, W] of the fields first[i] .. first[i] + W - 1.  fixed: every point reads the whole batch (first is zero), so the call
+# can be merged with a neighbour of its kind.
+_AtCall = collections.namedtuple('_AtCall', 'coefficients max_degree GM R first weights fixed')
+
+
+def _check_epochs(epochs, points):
+    """One epoch per point: a sequence of `points` datetime.datetime (returned as a list) or a float64 array [points] of modified
+    Julian dates in the convention of utilities._mjd (returned as it is); ValueError otherwise."""
+    if isinstance(epochs, np.ndarray) and epochs.dtype != object:
+        if epochs.dtype != np.float64 or epochs.ndim != 1:
+            raise ValueError('epochs as modified Julian dates must be a float64 array of shape (M,), got {0} of {1}'.format(epochs.dtype, epochs.shape))
+        if not np.all(np.isfinite(epochs)):
+            raise ValueError('epoch {0} is not finite'.format(int(np.flatnonzero(~np.isfinite(epochs))[0])))
+    else:
+        epochs = list(epochs)
+        for k, epoch in enumerate(epochs):
+            if not isinstance(epoch, datetime.datetime):
+                raise ValueError('epoch {0} is {1!r}: datetime.datetime objects or a float64 array of modified Julian dates expected'.format(k, epoch))
+    if len(epochs) != points:
+        raise ValueError('{0} epochs for {1} points: one epoch per point expected'.format(len(epochs), points))
+    return epochs
+
+
+def _merge_fixed_calls(calls):
+    """Adjacent calls on fixed batches of one GM and R as one call on the stacked batch (lower degrees zero-padded) with the weights
+    side by side: W = sum W_i."""
+    merged = []
+    for call in calls:
+        last = merged[-1] if merged else None
+        if last is not None and last.fixed and call.fixed and (last.GM, last.R) == (call.GM, call.R):
+            N = max(last.max_degree, call.max_degree)
+            batch = np.zeros((last.coefficients.shape[0] + call.coefficients.shape[0], N + 1, N + 1))
+            batch[:last.coefficients.shape[0], :last.max_degree + 1, :last.max_degree + 1] = last.coefficients
+            batch[last.coefficients.shape[0]:, :call.max_degree + 1, :call.max_degree + 1] = call.coefficients
+            merged[-1] = _AtCall(batch, N, last.GM, last.R, last.first, np.concatenate((last.weights, call.weights), axis=1), True)
+        else:
+            merged.append(call)
+    return merged
+
+
+class _FunctionalsAtEpochs:
+    """The point functionals of a time-variable field with every point at its own epoch, for whatever says, as `_at_calls(epochs)`,
+    which weighted sums of fixed fields it is at the checked epochs (a list of _AtCall, all host work: ValueError and TypeError come
+    from there, before the device is touched).  The results of the calls are added in list order on the device."""
+
+    def _at_calls(self, epochs):
+        raise NotImplementedError
+
+    def _functional_at(self, engine_function, xyz, epochs, points, copies=1):
+        calls = self._at_calls(_check_epochs(epochs, points))
+        x = engine.to_device(xyz)
+        out = None
+        for call in calls:
+            first, weights = call.first, call.weights
+            if copies > 1:                                           # the stacked points of pairs: the epochs repeated
+                first, weights = np.concatenate((first,) * copies), np.concatenate((weights,) * copies)
+            part = engine_function(call.max_degree, x, call.coefficients, first, weights, call.GM, call.R)
+            out = part if out is None else out + part
+        return out
+
+    def gravitational_acceleration_at(self, xyz, epochs, as_tensor=False):
+        """
+        Gravitational acceleration [m/s^2] at the cartesian positions xyz (M, 3), point i at its own epoch epochs[i]: [M, 3], the
+        diagonal of the [T, M, 3] of evaluating every epoch at every point (an orbit reduced by a time-variable background).  epochs
+        is a sequence of M datetime.datetime or a float64 array [M] of modified Julian dates.  The functionals are linear in the
+        coefficients, so the blend of the reference's evaluate_at(epochs[i]) is applied to the values of the fixed fields, inside the
+        GPU kernel (shg_acceleration_points_at).  Returns an ndarray, or the float64 device tensor with as_tensor=True; xyz may be an
+        ndarray or a device tensor.
+        """
+        g = self._functional_at(engine.acceleration_points_at, xyz, epochs, engine.check_positions(xyz))
+        return g if as_tensor else engine.to_host(g)
+
+    def gravitational_gradients_at(self, xyz, epochs, as_tensor=False):
+        """Gravitational gradient tensor [s^-2] at the positions xyz (M, 3), point i at its own epoch epochs[i]: [M, 3, 3], as
+        gravitational_acceleration_at (shg_gravitational_gradients_points_at)."""
+        T = self._functional_at(engine.gravitational_gradients_points_at, xyz, epochs, engine.check_positions(xyz))
+        return T if as_tensor else engine.to_host(T)
+
+    def gravitational_potential_at(self, xyz, epochs, as_tensor=False):
+        """Gravitational potential [m^2/s^2] at the positions xyz (M, 3), point i at its own epoch epochs[i]: [M], as
+        gravitational_acceleration_at (shg_potential_points_at)."""
+        V = self._functional_at(engine.potential_points_at, xyz, epochs, engine.check_positions(xyz))
+        return V if as_tensor else engine.to_host(V)
+
+    def line_of_sight_acceleration_at(self, xyz_a, xyz_b, epochs, directions=None, as_tensor=False):
+        """
+        Line-of-sight gravity difference [m/s^2] of M satellite pairs at the positions xyz_a (M, 3) and xyz_b (M, 3), pair i at its own
+        epoch epochs[i]: [M], l_i = e_i . (g(b_i) - g(a_i)).  directions (M, 3) are the lines of sight e (unit vectors within 1e-12);
+        without them e = (b - a) / |b - a|, and no pair may coincide.  One gravitational_acceleration_at call on the stacked 2 M points
+        with the epochs repeated, then the difference and the projection in torch.
+        """
+        M = engine.check_pair_positions(xyz_a, xyz_b)
+        if directions is not None:
+            engine.check_directions(directions, M)
+        else:
+            engine.check_pairs_apart(xyz_a, xyz_b)
+        g = self._functional_at(engine.acceleration_points_at, _stack_pairs(xyz_a, xyz_b), epochs, M, copies=2)
+        l = _project_line_of_sight(g, xyz_a, xyz_b, directions)
+        return l if as_tensor else engine.to_host(l)
+
+    def potential_difference_at(self, xyz_a, xyz_b, epochs, as_tensor=False):
+        """Potential difference V(b_i) - V(a_i) [m^2/s^2] of M satellite pairs at the positions xyz_a (M, 3) and xyz_b (M, 3), pair i
+        at its own epoch epochs[i]: [M].  One gravitational_potential_at call on the stacked 2 M points with the epochs repeated, then
+        the difference in torch."""
+        M = engine.check_pair_positions(xyz_a, xyz_b)
+        V = self._functional_at(engine.potential_points_at, _stack_pairs(xyz_a, xyz_b), epochs, M, copies=2)
+        d = V[M:] - V[:M]
+        return d if as_tensor else engine.to_host(d)
+
+
 def synthesize(anm_batch, grid, kernel='ewh', GM=3.9860044150e+14, R=6.3781363000e+06):
     """
     Batched synthesis: anm_batch [B, N+1, N+1] (ndarray or device tensor) -> device tensor
@@ -478,7 +594,7 @@ def synthesize(anm_batch, grid, kernel='ewh', GM=3.9860044150e+14, R=6.378136300
     return plan.synthesis(anm_batch)
 
 
-class TimeSeries:
+class TimeSeries(_FunctionalsAtEpochs):
     """
     Time series of gravity fields of one type, sorted by epoch (grates/gravityfield.py:815-1052).
 
@@ -789,6 +905,50 @@ class TimeSeries:
         M = shape[-2]
         d = V[:, M:] - V[:, :M]
         return d if as_tensor else engine.to_host(d)
+
+    # ---- every point at its own epoch (the *_at methods of _FunctionalsAtEpochs)
+    def interpolation_windows(self, epochs):
+        """(first [M], weights [M, 2]) of the piecewise linear interpolation to the checked `epochs`: for t_k < t <= t_{k+1} first = k
+        and the weights (1 - w, w) of interpolate_to, the fields np.searchsorted(t, epoch) of the reference selects; t = t_0 gives
+        first = 0 and (1, 0).  No extrapolation: an epoch outside the series is a ValueError naming the first one.  Host only, float64."""
+        t = self.epochs()
+        if len(t) < 2:
+            raise ValueError("at least two data points are required for interpolation")
+        M = len(epochs)
+        first, w = np.zeros(M, dtype=np.int64), np.zeros(M)
+        if isinstance(epochs, np.ndarray):
+            nodes = np.array([utilities._mjd(e) for e in t])
+            outside = ~((epochs >= nodes[0]) & (epochs <= nodes[-1]))
+            if outside.any():
+                k = int(np.flatnonzero(outside)[0])
+                raise ValueError('epoch {0} (MJD {1!r}) lies outside the series ({2!r} .. {3!r}): no extrapolation'.format(k, float(epochs[k]), nodes[0],
+                                                                                                                       nodes[-1]))
+            right = np.searchsorted(nodes, epochs)                    # first node at or after the epoch (side='left', as interpolate_to)
+            inner = right > 0
+            first[inner] = right[inner] - 1
+            before, after = nodes[first[inner]], nodes[first[inner] + 1]
+            w[inner] = (epochs[inner] - before) / (after - before)
+        else:
+            for k, epoch in enumerate(epochs):
+                if not (t[0] <= epoch <= t[-1]):
+                    raise ValueError('epoch {0} ({1}) lies outside the series ({2} .. {3}): no extrapolation'.format(k, epoch, t[0], t[-1]))
+                right = bisect.bisect_left(t, epoch)
+                if right > 0:
+                    first[k] = right - 1
+                    w[k] = (epoch - t[right - 1]).total_seconds() / (t[right] - t[right - 1]).total_seconds()
+        return first, np.stack((1 - w, w), axis=1)
+
+    def _at_calls(self, epochs):
+        first, weights = self.interpolation_windows(epochs)
+        if self.__series is not None:                                # read in its own layout: the series stays on the device
+            GM, R = self._constants()
+            return [_AtCall(self.__series, self.__series.max_degree, GM, R, first, weights, False)]
+        fields = self.__data
+        GM, R = fields[0].GM, fields[0].R
+        if any(d.GM != GM or d.R != R for d in fields):
+            raise ValueError("the functionals at epochs need a common GM and R for all fields of the series")
+        batch = self.to_coefficient_batch()
+        return [_AtCall(batch, batch.shape[-1] - 1, GM, R, first, weights, False)]
 
     def detrend(self, basis_functions):
         """

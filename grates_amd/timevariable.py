@@ -5,13 +5,22 @@ work happens where the evaluated fields are used (`gravityfield.gridded_rms`, ba
 
 Every constituent here is a weighted sum of fixed fields, V(t) = sum_i w_i(tau) V_i with tau the time since the reference epoch
 in the constituent's own unit -- `Trend` has one term with w = tau, `Oscillation` two with w = (cos, sin)(2 pi tau).
+
+The point functionals are linear in the coefficients, so along an orbit, point i at its own epoch t_i, the same weights blend the
+values of the fixed fields: the `*_at(xyz, epochs)` methods (gravityfield._FunctionalsAtEpochs) compute the weights of all epochs on
+the host and hand them to one shg_*_points_at call per group of fields.
 """
 
 import functools
 import math
 
+import numpy as np
 
-class _WeightedFields:
+from . import utilities
+from .gravityfield import PotentialCoefficients, TimeSeries, _AtCall, _FunctionalsAtEpochs, _merge_fixed_calls
+
+
+class _WeightedFields(_FunctionalsAtEpochs):
     """V(t) = sum_i w_i(tau(t)) V_i; the fields are copied on construction (anything with `copy`, `*` by a float and `+`)."""
 
     def __init__(self, fields, reference_epoch, unit_days):
@@ -29,6 +38,30 @@ class _WeightedFields:
         out.epoch = epoch
         return out
 
+    def _weights_at(self, tau):
+        """_weights of every tau [M] at once: [M, W], float64"""
+        raise NotImplementedError
+
+    def weights_at(self, epochs):
+        """The weights [M, W] of the fields at the checked `epochs` (a list of datetimes or float64 modified Julian dates): tau as
+        evaluate_at computes it, total_seconds() of the difference over the unit.  Host only."""
+        if isinstance(epochs, np.ndarray):
+            tau = (epochs - utilities._mjd(self._t0)) * 86400.0 / self._unit
+        else:
+            tau = np.array([(epoch - self._t0).total_seconds() / self._unit for epoch in epochs], dtype=np.float64)
+        return self._weights_at(tau)
+
+    def _at_calls(self, epochs):
+        fields = self._fields
+        if not all(isinstance(f, PotentialCoefficients) for f in fields):
+            raise TypeError('the functionals at epochs need PotentialCoefficients, not {0}'.format(
+                next(type(f).__name__ for f in fields if not isinstance(f, PotentialCoefficients))))
+        GM, R = fields[0].GM, fields[0].R
+        if any(f.GM != GM or f.R != R for f in fields):
+            raise ValueError('the functionals at epochs need a common GM and R for all fields')
+        batch = TimeSeries._stack(fields)
+        return [_AtCall(batch, batch.shape[-1] - 1, GM, R, np.zeros(len(epochs), dtype=np.int64), self.weights_at(epochs), True)]
+
 
 class Trend(_WeightedFields):
     """Linear trend V(t) = V (t - t0) / time_scale, `time_scale` in days (default: a Julian year), grates/gravityfield.py:1054-1094."""
@@ -38,6 +71,9 @@ class Trend(_WeightedFields):
 
     def _weights(self, tau):
         return (tau,)
+
+    def _weights_at(self, tau):
+        return tau[:, np.newaxis]
 
 
 class Oscillation(_WeightedFields):
@@ -50,8 +86,12 @@ class Oscillation(_WeightedFields):
         phase = 2.0 * math.pi * tau
         return (math.cos(phase), math.sin(phase))
 
+    def _weights_at(self, tau):
+        phase = 2.0 * math.pi * tau
+        return np.stack((np.cos(phase), np.sin(phase)), axis=1)
 
-class TimeVariableGravityField:
+
+class TimeVariableGravityField(_FunctionalsAtEpochs):
     """Sum of constituents (trend, cycles, an interpolated `TimeSeries`, ...), each with `evaluate_at`; `constituents` stays a
     public list like upstream (grates/gravityfield.py:784-812)."""
 
@@ -61,3 +101,14 @@ class TimeVariableGravityField:
     def evaluate_at(self, epoch):
         parts = [c.evaluate_at(epoch) for c in self.constituents]
         return functools.reduce(lambda acc, part: acc + part, parts[1:], parts[0])
+
+    def _at_calls(self, epochs):
+        """the calls of the constituents in list order, adjacent trends and cycles of one GM and R merged into one"""
+        if not self.constituents:
+            raise ValueError('a time-variable field without constituents has no functionals')
+        calls = []
+        for constituent in self.constituents:
+            if not hasattr(constituent, '_at_calls'):
+                raise TypeError('constituent {0!r} has no functionals at epochs: a TimeSeries, Trend or Oscillation expected'.format(constituent))
+            calls.extend(constituent._at_calls(epochs))
+        return _merge_fixed_calls(calls)

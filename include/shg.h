@@ -573,6 +573,49 @@ int shg_potential_points_om(int N, const double* xyz, int M, int layout, const d
                             double* V, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Point functionals of time-variable fields, every point at its own epoch (no reference counterpart: the reference blends the
+ * coefficients per epoch, TimeSeries.interpolate_to / Trend / Oscillation.evaluate_at, and evaluates one point at a time)
+ *   A time-variable field is a weighted sum of fixed fields, V(t) = sum_j w_j(t) V_j, and the functionals are linear, so
+ *     out[i][c] = scale sum_{j < W} weights[i][j] S_c(field first_i + j, x_i)
+ *   with S the unscaled component sum of shg_acceleration_points / shg_potential_points / shg_gravitational_gradients_points and
+ *   scale their GM / (2 R^2), GM / R, GM / (4 R^3): g [M][3], V [M] or T [M][3][3] (each off-diagonal value stored twice) at the
+ *   Cartesian positions xyz [M][3], of the B fields anm [B][N+1][N+1] (one GM and R for all), 1 <= W <= 16 of them per point.
+ *   xyz, weights [M][W], the fields and the output are device pointers.  run_first [runs] and run_begin [runs + 1] are HOST arrays:
+ *   run r covers the consecutive points run_begin[r] .. run_begin[r + 1] - 1, all of which use the consecutive fields
+ *   run_first[r] .. run_first[r] + W - 1 (a time-ordered orbit against a series: one run per interval between two nodes).
+ *   Runs are cut into workgroups of at most 256 points; per workgroup the column recursion of the existing point kernel sweeps
+ *   the window in chunks of 2, 4 or 16 fields (gradients: 2 or 4), with the Q values of the existing combine kernels and the same fma
+ *   order over orders and degrees, so the sum of a field is bitwise the existing entry point's.  The weighted sum then runs over j
+ *   ascending from 0.0 with one fma per term, and the product with scale comes last, once.  No atomics and no read-modify-write: a
+ *   point's result depends only on its position, its W weights and its W fields -- not on how the points are cut into runs or
+ *   workgroups, on the other points, on B or on the source layout -- and repeated calls are bitwise equal.  With weights that are
+ *   one 1.0 and zeros the result equals the existing entry point's value of that field at that point.
+ *   The combined coefficients of a launch group of fields stay under a workspace limit (256 MB by default); with more fields the call
+ *   loops over field ranges that overlap by W - 1 and launches the runs whose window lies in the range.
+ *   shg_*_points_at_om  the same from an order-major series om [(N+1)^2][Bpad] (shg_order_major_pack), Bpad >= B.
+ *   shg_points_at_set_workspace_limit  that limit in bytes, process-wide (0 restores the default; negative values are refused); a
+ *   call whose window of W fields does not fit the limit fails with a message.
+ *   Arguments are checked before the first HIP call: negative sizes, W outside 1 .. 16, B < W, runs < 0, Bpad < B, GM or R not
+ *   finite, R <= 0, more than 2^40 output values, the gradients' degree rule of shg_gravitational_gradients_points; then, for
+ *   M > 0, NULL pointers, run_begin[0] != 0, run_begin not strictly increasing or not ending at M, and run_first[r] outside
+ *   0 .. B - W, so that no table content can make the kernel read outside its buffers.  M = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_acceleration_points_at(int N, const double* xyz, int M, const double* anm, int B, const int* run_first, const int* run_begin, int runs,
+                               const double* weights, int W, double GM, double R, double* g, void* stream);
+int shg_acceleration_points_at_om(int N, const double* xyz, int M, const double* om, int B, int Bpad, const int* run_first, const int* run_begin,
+                                  int runs, const double* weights, int W, double GM, double R, double* g, void* stream);
+int shg_potential_points_at(int N, const double* xyz, int M, const double* anm, int B, const int* run_first, const int* run_begin, int runs,
+                            const double* weights, int W, double GM, double R, double* V, void* stream);
+int shg_potential_points_at_om(int N, const double* xyz, int M, const double* om, int B, int Bpad, const int* run_first, const int* run_begin,
+                               int runs, const double* weights, int W, double GM, double R, double* V, void* stream);
+int shg_gravitational_gradients_points_at(int N, const double* xyz, int M, const double* anm, int B, const int* run_first, const int* run_begin,
+                                          int runs, const double* weights, int W, double GM, double R, double* T, void* stream);
+int shg_gravitational_gradients_points_at_om(int N, const double* xyz, int M, const double* om, int B, int Bpad, const int* run_first,
+                                             const int* run_begin, int runs, const double* weights, int W, double GM, double R, double* T,
+                                             void* stream);
+int shg_points_at_set_workspace_limit(long long bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * Design matrices of the energy-balance observations: the potential at points, and the potential difference V(b_i) - V(a_i) of
  * satellite pairs (the partial derivatives of shg_potential_points with respect to the coefficients; no reference counterpart)
  *   At [P][ldt], transposed like shg_acceleration_design: row p is coefficient p of utilities.ravel_coefficients(., min_degree, N),
