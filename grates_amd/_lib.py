@@ -154,6 +154,8 @@ PROTOTYPES = {
                              ctypes.c_int, ctypes.c_void_p, c_double_p, ctypes.c_void_p],
     'shg_segment_lag_products': [ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_double_p,
                                  ctypes.c_void_p],
+    'shg_window_expand': [ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p,
+                          ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p],
 }
 STRING_GETTERS = ('shg_last_error', 'shg_version')
 

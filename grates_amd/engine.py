@@ -1412,6 +1412,66 @@ def segment_lag_products(X, seg, lags, out=None):
     return out
 
 
+WINDOW_SLOTS = 16                                                # slots of one shg_window_expand call: W <= E <= 16
+
+
+def check_window_runs(run_slot, run_begin, n, W, E):
+    """(run_slot, run_begin) of a shg_window_expand call as contiguous int32 arrays: run r covers the columns run_begin[r] ..
+    run_begin[r + 1] - 1 of n and starts at slot run_slot[r].  ValueError unless 1 <= W <= E <= 16, run_begin ascends strictly from 0 to
+    n and every run_slot lies in 0 .. E - W.  Host only."""
+    n, W, E = int(n), int(W), int(E)
+    if not 1 <= W <= E <= WINDOW_SLOTS:
+        raise ValueError('a window of {0} fields in {1} slots: expected 1 <= W <= E <= {2}'.format(W, E, WINDOW_SLOTS))
+    slot, begin = np.asarray(run_slot), np.asarray(run_begin)
+    if slot.ndim != 1 or begin.shape != (slot.shape[0] + 1,) or slot.dtype.kind not in 'iu' or begin.dtype.kind not in 'iu':
+        raise ValueError('run_slot [runs] and run_begin [runs + 1] must be integer arrays, got {0} and {1}'.format(slot.shape, begin.shape))
+    if n < 0 or (n > 0 and slot.shape[0] < 1) or int(begin[0]) != 0 or int(begin[-1]) != n or np.any(np.diff(begin) <= 0):
+        raise ValueError('run_begin must ascend strictly from 0 to the {0} columns'.format(n))
+    if slot.size and (int(slot.min()) < 0 or int(slot.max()) > E - W):
+        raise ValueError('a run starts at slot {0}, outside 0 .. E - W = {1}'.format(int(slot[(slot < 0) | (slot > E - W)][0]), E - W))
+    return np.ascontiguousarray(slot, dtype=np.int32), np.ascontiguousarray(begin, dtype=np.int32)
+
+
+def window_expand(T, factors, run_slot, run_begin, E, out=None):
+    """The transposed design matrix of a block, expanded to the E slots of its time-variable parameters (shg_window_expand):
+    S[e, ..., t] = factors[t, e - slot(t)] * T[..., t] inside the window slot(t) <= e < slot(t) + W of column t and +0.0 outside, with
+    slot(t) = run_slot[r] along the columns run_begin[r] .. run_begin[r + 1] - 1 (host int tables, check_window_runs).  T [..., n] and
+    factors [n, W] are float64 device tensors; a two-dimensional T may be a column slice of a wider matrix (unit stride along the
+    rows), anything else that is not dense is copied.  Returns out, or a new dense tensor [E, ..., n]; every entry is written, the
+    zeros included.  out [E, rows, n], if given, may be a view with strides (slot, row, 1) of a larger buffer: nothing else of it is
+    touched."""
+    torch = require_gpu()
+    n, E = int(T.shape[-1]), int(E)
+    lead = tuple(int(s) for s in T.shape[:-1])
+    if T.dtype != torch.float64:
+        raise ValueError('T must be float64, got {0}'.format(T.dtype))
+    if factors.dim() != 2 or int(factors.shape[0]) != n or factors.dtype != torch.float64 or not factors.is_contiguous() or factors.device != T.device:
+        raise ValueError('factors must be a dense float64 tensor of shape ({0}, W) beside T, got {1}'.format(n, tuple(factors.shape)))
+    W = int(factors.shape[1])
+    run_slot, run_begin = check_window_runs(run_slot, run_begin, n, W, E)
+    if T.dim() == 2 and T.stride(1) == 1 and T.stride(0) >= n:
+        ldt = int(T.stride(0))
+    else:
+        T, ldt = T.contiguous(), n
+    rows = 1
+    for size in lead:
+        rows *= size
+    if out is None:
+        out = torch.empty((E,) + lead + (n,), dtype=torch.float64, device=T.device)
+        lds, slot_stride = n, rows * n
+    else:
+        if tuple(out.shape) != (E, rows, n) or out.dtype != torch.float64 or out.device != T.device or (n > 1 and out.stride(2) != 1):
+            raise ValueError('out must be a float64 tensor of shape ({0}, {1}, {2}) with unit stride along the columns'.format(E, rows, n))
+        lds = int(out.stride(1)) if rows > 1 else max(int(out.stride(1)), n)
+        slot_stride = int(out.stride(0)) if E > 1 else max(int(out.stride(0)), (rows - 1) * lds + n)
+        if lds < n or slot_stride < (rows - 1) * lds + n:
+            raise ValueError('the rows or the slots of out overlap (strides {0})'.format(tuple(out.stride())))
+        Plan._written(out)
+    _lib.call('shg_window_expand', rows, n, _ptr(T), ldt, _host_ptr(run_slot), _host_ptr(run_begin), int(run_slot.shape[0]), _ptr(factors), W, E,
+              _ptr(out), lds, slot_stride, _stream())
+    return out
+
+
 class OrderMajorSeries:
     """A time series of coefficient sets that stays on the device between operators (the batching of TimeSeries.to_array,
     grates/gravityfield.py:964-980, in the layout the order-wise operators work on): `data` [(N+1)^2, Bpad] with the epochs fastest

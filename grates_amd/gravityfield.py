@@ -431,6 +431,72 @@ def potential_difference_design_matrix(xyz_a, xyz_b, min_degree, max_degree, GM=
     return A if as_tensor else engine.to_host(A)
 
 
+def linear_interpolation_windows(nodes, epochs):
+    """(first [M], weights [M, 2]) of the piecewise linear interpolation between the ascending `nodes` at the checked `epochs`, the rule
+    of TimeSeries.interpolation_windows and of lstsq.TemporalParameters.linear: for t_k < t <= t_{k+1} first = k and the weights
+    (1 - w, w); t = t_0 gives first = 0 and (1, 0).  nodes and epochs are each a list of datetime.datetime or a float64 array of modified
+    Julian dates; where the two differ in kind, the datetimes go through utilities._mjd.  ValueError for fewer than two nodes and for
+    an epoch outside them (no extrapolation), naming the first one.  Host only, float64."""
+    t = nodes
+    if len(t) < 2:
+        raise ValueError("at least two data points are required for interpolation")
+    M = len(epochs)
+    first, w = np.zeros(M, dtype=np.int64), np.zeros(M)
+    if isinstance(t, np.ndarray) and not isinstance(epochs, np.ndarray):
+        epochs = np.array([utilities._mjd(e) for e in epochs], dtype=np.float64)
+    if isinstance(epochs, np.ndarray):
+        nodes = t if isinstance(t, np.ndarray) else np.array([utilities._mjd(e) for e in t])
+        outside = ~((epochs >= nodes[0]) & (epochs <= nodes[-1]))
+        if outside.any():
+            k = int(np.flatnonzero(outside)[0])
+            raise ValueError('epoch {0} (MJD {1!r}) lies outside the series ({2!r} .. {3!r}): no extrapolation'.format(k, float(epochs[k]), nodes[0],
+                                                                                                                   nodes[-1]))
+        right = np.searchsorted(nodes, epochs)                    # first node at or after the epoch (side='left', as interpolate_to)
+        inner = right > 0
+        first[inner] = right[inner] - 1
+        before, after = nodes[first[inner]], nodes[first[inner] + 1]
+        w[inner] = (epochs[inner] - before) / (after - before)
+    else:
+        for k, epoch in enumerate(epochs):
+            if not (t[0] <= epoch <= t[-1]):
+                raise ValueError('epoch {0} ({1}) lies outside the series ({2} .. {3}): no extrapolation'.format(k, epoch, t[0], t[-1]))
+            right = bisect.bisect_left(t, epoch)
+            if right > 0:
+                first[k] = right - 1
+                w[k] = (epoch - t[right - 1]).total_seconds() / (t[right] - t[right - 1]).total_seconds()
+    return first, np.stack((1 - w, w), axis=1)
+
+
+def temporal_design_matrix(design, first, factors, fields, as_tensor=False):
+    """
+    Design matrix [K M, B P] of parameters that vary in time, from a static design matrix `design` [K M, P] of M points (rows
+    point-major, K rows per point: what acceleration_design_matrix ... rbf_potential_difference_design_matrix return; ndarray or
+    device tensor): the statement of the model of lstsq.TemporalParameters.  Point i sees the W fields first[i] .. first[i] + W - 1 of
+    B = fields with the factors[i, :], so its rows are factors[i, j] times its static rows in the columns (first[i] + j) P ..
+    (first[i] + j + 1) P of field first[i] + j, and zero elsewhere; the parameter vector is field-major.  first [M] (host ints) and
+    factors [M, W] are checked as TemporalParameters checks them (ValueError, on the host).  The result holds B times the static
+    matrix and is built by plain indexing on the device: it is meant for small M, for tests and for looking at the model;
+    TemporalParameters.from_* never forms it.  Returns an ndarray, or the float64 device tensor with as_tensor=True.
+    """
+    from . import lstsq
+    first, factors, B = lstsq._check_windows(first, factors, fields)
+    M, W = factors.shape
+    rows = int(design.shape[0]) if len(design.shape) == 2 else -1
+    if rows < 0 or (M == 0 and rows != 0) or (M > 0 and (rows % M != 0 or rows == 0)):
+        raise ValueError('design must have shape (K M, P) with M = {0} points, got {1}'.format(M, tuple(design.shape)))
+    torch = engine.require_gpu()
+    A = engine.to_device(design)
+    K, P = (rows // M if M else 1), int(A.shape[1])
+    out = torch.zeros((M, K, B, P), dtype=torch.float64, device=A.device)
+    if M:
+        point = torch.arange(M, device=A.device)
+        start, f = torch.from_numpy(first).to(A.device), engine.to_device(factors, A.device)
+        for j in range(W):
+            out[point, :, start + j] = f[:, j, None, None] * A.reshape(M, K, P)
+    out = out.reshape(M * K, B * P)
+    return out if as_tensor else engine.to_host(out)
+
+
 def _project_line_of_sight(g, xyz_a, xyz_b, directions):
     """e . (g_b - g_a) [..., M] in torch from the accelerations g [..., 2 M, 3] of the stacked points (a first, then b): the
     difference per component first, then the projection, as shg_los_design orders them"""
@@ -910,33 +976,9 @@ class TimeSeries(_FunctionalsAtEpochs):
     def interpolation_windows(self, epochs):
         """(first [M], weights [M, 2]) of the piecewise linear interpolation to the checked `epochs`: for t_k < t <= t_{k+1} first = k
         and the weights (1 - w, w) of interpolate_to, the fields np.searchsorted(t, epoch) of the reference selects; t = t_0 gives
-        first = 0 and (1, 0).  No extrapolation: an epoch outside the series is a ValueError naming the first one.  Host only, float64."""
-        t = self.epochs()
-        if len(t) < 2:
-            raise ValueError("at least two data points are required for interpolation")
-        M = len(epochs)
-        first, w = np.zeros(M, dtype=np.int64), np.zeros(M)
-        if isinstance(epochs, np.ndarray):
-            nodes = np.array([utilities._mjd(e) for e in t])
-            outside = ~((epochs >= nodes[0]) & (epochs <= nodes[-1]))
-            if outside.any():
-                k = int(np.flatnonzero(outside)[0])
-                raise ValueError('epoch {0} (MJD {1!r}) lies outside the series ({2!r} .. {3!r}): no extrapolation'.format(k, float(epochs[k]), nodes[0],
-                                                                                                                       nodes[-1]))
-            right = np.searchsorted(nodes, epochs)                    # first node at or after the epoch (side='left', as interpolate_to)
-            inner = right > 0
-            first[inner] = right[inner] - 1
-            before, after = nodes[first[inner]], nodes[first[inner] + 1]
-            w[inner] = (epochs[inner] - before) / (after - before)
-        else:
-            for k, epoch in enumerate(epochs):
-                if not (t[0] <= epoch <= t[-1]):
-                    raise ValueError('epoch {0} ({1}) lies outside the series ({2} .. {3}): no extrapolation'.format(k, epoch, t[0], t[-1]))
-                right = bisect.bisect_left(t, epoch)
-                if right > 0:
-                    first[k] = right - 1
-                    w[k] = (epoch - t[right - 1]).total_seconds() / (t[right] - t[right - 1]).total_seconds()
-        return first, np.stack((1 - w, w), axis=1)
+        first = 0 and (1, 0).  No extrapolation: an epoch outside the series is a ValueError naming the first one.  Host only, float64
+        (linear_interpolation_windows on the epochs of the series)."""
+        return linear_interpolation_windows(self.epochs(), epochs)
 
     def _at_calls(self, epochs):
         first, weights = self.interpolation_windows(epochs)

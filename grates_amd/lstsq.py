@@ -17,6 +17,8 @@ Not built (outside the smoother path): UnscentedTransformSymmetric, teigh, trsvd
 AutoregressiveModel.from_transformed_coefficients (pseudo-inverse).
 """
 
+import collections
+
 import numpy as np
 
 from . import engine
@@ -588,17 +590,23 @@ class _StochasticModel:
         return engine.whiten_rows(X, taps=self.taps, stage=self.stage[start:start + int(X.shape[-1])], channels=int(self.taps.shape[0]), skip=skip)
 
 
-def _prepare(observations, model, block_points, fit=None):
+def _prepare(observations, model, block_points, fit=None, windows=None):
     """Every from_* and of_* call between the checks of its observations and its pass: block_points as a positive int (None: the default),
-    the model, the solution and the vectors of a PostFit, every ValueError before anything reaches the device; then the uploads."""
-    block_points = int(NormalEquations.default_block_points(observations.P, observations.K) if block_points is None else block_points)
+    the model, the solution and the vectors of a PostFit and, under TemporalParameters, the blocks of the call's _Windows, every
+    ValueError before anything reaches the device; then the uploads."""
+    default = NormalEquations.default_block_points if windows is None else windows.default_block_points
+    block_points = int(default(observations.P, observations.K) if block_points is None else block_points)
     if block_points < 1:
         raise ValueError('block_points must be positive, got {0}'.format(block_points))
     model.check(observations.M, observations.K)
     if fit is not None:
-        fit._check(observations.P)
+        fit._check(observations.P if windows is None else windows.B * observations.P)
+    if windows is not None:
+        windows.plan(model, block_points)
     observations.to_device()
     model.to_device(observations.l.device)
+    if windows is not None:
+        windows.to_device(observations.l.device)
     return block_points
 
 
@@ -621,6 +629,123 @@ def _design_blocks(observations, model, block_points):
             At = model.whiten(plain, start, first - start).reshape(P, K * (last - first))
             lb = model.whiten(l[start:last].t().contiguous(), start, first - start).reshape(-1, 1)
             yield first, last, At, lb, plain.reshape(P, K * (last - start)), first - start
+
+
+MAX_TEMPORAL_SLOTS = engine.WINDOW_SLOTS      # of shg_window_expand: the fields one block of points may span
+
+_TemporalBlock = collections.namedtuple('_TemporalBlock', 'start first last field slots run_slot run_begin supports')
+
+
+def temporal_blocks(first, W, block_points, stage=None):
+    """
+    The blocks of a from_* or of_* call under TemporalParameters (host, NumPy only): first [M] are the window
+    starts of the points in the order of the call, W the fields per window, stage [M] the history every point takes along under a
+    noise model (arc_stages), None without one.  A block is a _TemporalBlock: it owns the points first .. last - 1, reads start =
+    first - stage[first] .. last - 1 (n columns, the first `skip` = first - start of them history only), spans the fields `field` ..
+    field + slots - 1 with slots = E = (largest - smallest window start of its n points) + W <= 16, and carries run_slot / run_begin, the
+    runs of columns with one window start as shg_window_expand takes them (slots relative to `field`).  supports[e] is the range
+    (c0, c1) of owned columns, counted from `first`, outside of which slot e of the whitened expanded block is structurally zero --
+    column t is inside when one of the points t - stage[t] .. t holds the slot in its window -- or None where no owned column does.
+
+    Without a noise model `first` must not decrease (the caller sorts: the normals are permutation-invariant); blocks are cut at
+    every change of the window start and restart at the first point of a run, so E = W and no zero is multiplied.  With one the order
+    of the points is kept; a block ends early where one more point would need more than 16 slots, and where a change of the window
+    start meets the start of an arc (nothing crosses it, so the blocks behind it are those of a call on those points alone).
+    ValueError where a single point with its history spans more than 16 slots.
+    """
+    first, W, block_points = np.asarray(first, dtype=np.int64), int(W), int(block_points)
+    M = int(first.shape[0])
+    if stage is None and M > 1 and bool(np.any(first[1:] < first[:-1])):
+        raise ValueError('without a noise model the window starts must not decrease: sort the points (engine.points_at_plan)')
+    halo = np.zeros(M, dtype=np.int64) if stage is None else np.asarray(stage, dtype=np.int64)
+    blocks, t = [], 0
+    while t < M:
+        start = t - int(halo[t])
+        end = min(t + block_points, M)
+        window = first[start:end]
+        if stage is None:
+            change = np.flatnonzero(window[1:] != window[0])
+            if change.size:
+                end = t + 1 + int(change[0])
+        else:
+            span = np.maximum.accumulate(window) - np.minimum.accumulate(window) + W
+            if span[t - start] > MAX_TEMPORAL_SLOTS:
+                raise ValueError('point {0} and its history of {1} points span {2} fields: at most {3} fit one block'.format(
+                    t, t - start, int(span[t - start]), MAX_TEMPORAL_SLOTS))
+            over = np.flatnonzero(span[t - start:] > MAX_TEMPORAL_SLOTS)
+            if over.size:
+                end = t + int(over[0])
+            cut = np.flatnonzero((halo[t + 1:end] == 0) & (first[t + 1:end] != first[t:end - 1]))
+            if cut.size:
+                end = t + 1 + int(cut[0])
+        blocks.append(_temporal_block(first, halo, W, start, t, end))
+        t = end
+    return blocks
+
+
+def _temporal_block(first, halo, W, start, own, end):
+    """the _TemporalBlock of the points own .. end - 1 with the history start .. own - 1"""
+    window = first[start:end]
+    field = int(window.min())
+    local, slots = window - field, int(window.max()) - field + W
+    n, skip = end - start, own - start
+    runs = np.flatnonzero(np.concatenate(([True], local[1:] != local[:-1])))
+    columns, reach = np.arange(skip, n), halo[start + skip:end]
+    supports = []
+    for e in range(slots):
+        held = np.concatenate(([0], np.cumsum((local <= e) & (e < local + W))))
+        inside = np.flatnonzero(held[columns + 1] - held[columns - reach] > 0)
+        supports.append((int(inside[0]), int(inside[-1]) + 1) if inside.size else None)
+    return _TemporalBlock(start, own, end, field, slots, local[runs].astype(np.int32), np.concatenate((runs, [n])).astype(np.int32), supports)
+
+
+def temporal_pattern(blocks):
+    """the set of (f, f'), f <= f', of the blocks of the normal matrix that the blocks of temporal_blocks touch: the pairs of slots of one
+    block whose supports intersect.  Host only."""
+    pattern = set()
+    for block in blocks:
+        for a, b, _, _ in _slot_pairs(block):
+            pattern.add((block.field + a, block.field + b))
+    return pattern
+
+
+def _slot_pairs(block):
+    """(a, b, c0, c1) of the pairs of slots a <= b of a block whose supports intersect in the columns c0 .. c1 - 1"""
+    for a in range(block.slots):
+        for b in range(a, block.slots):
+            if block.supports[a] is not None and block.supports[b] is not None:
+                c0, c1 = max(block.supports[a][0], block.supports[b][0]), min(block.supports[a][1], block.supports[b][1])
+                if c0 < c1:
+                    yield a, b, c0, c1
+
+
+def _temporal_design_blocks(observations, model, windows):
+    """The blocks of a call under TemporalParameters, one after the other: (block, S~ [E, P, K Mb], lb [K Mb, 1], S [E, P, K n], skip).
+    The transposed design matrix T [P, K, n] of the points block.start .. block.last, as design_block gives it (scaled by sqrt(w)), is
+    expanded to the E slots of the block by shg_window_expand, S[e] = factor * T inside the window of a point and +0.0 outside; only
+    then shg_whiten_rows mixes neighbouring points, which have different factors, into S~ of the points block.first .. block.last (the
+    row index of S ends in the component, so row % K is the channel).  Without a noise model S~ is S and skip 0."""
+    P, K, l = observations.P, observations.K, observations.l
+    for block in windows.blocks:
+        start, first, last, E = block.start, block.first, block.last, block.slots
+        n = last - start
+        T = observations.design_block(start, last).reshape(P * K, n)
+        S = engine.window_expand(T, windows.device_factors[start:last], block.run_slot, block.run_begin, E).reshape(E, P, K * n)
+        if model.taps is None:
+            yield block, S, l[first:last].t().reshape(-1, 1), S, 0
+        else:
+            St = model.whiten(S.reshape(E * P * K, n), start, first - start).reshape(E, P, K * (last - first))
+            lb = model.whiten(l[start:last].t().contiguous(), start, first - start).reshape(-1, 1)
+            yield block, St, lb, S, first - start
+
+
+def _temporal_pass_blocks(observations, model, windows):
+    """_temporal_design_blocks as PostFit._pass reads _design_blocks, with the columns of the solution that a block sees behind: the
+    field-major order makes the window of a block one contiguous slice"""
+    P = observations.P
+    for block, St, lb, S, skip in _temporal_design_blocks(observations, model, windows):
+        E = block.slots
+        yield block.first, block.last, St.reshape(E * P, -1), lb, S.reshape(E * P, -1), skip, slice(block.field * P, (block.field + E) * P)
 
 
 class _ArcSetup:
@@ -1075,11 +1200,14 @@ class NormalEquations:
         return max(cls.DESIGN_BLOCK_BYTES // (8 * components * parameters) // 256 * 256, 256)
 
     @classmethod
-    def _normals(cls, observations, model, block_points):
+    def _normals(cls, observations, model, block_points, windows=None):
         """Every from_* behind the checks of its observations (an _Observations) under a _StochasticModel.  Per block of _design_blocks
         N += At At^T, n += At l and l^T P l += |l|^2 on the fp64 MFMA product; both triangles of N are computed and the upper one is
         mirrored.  Under ArcParameters the parameters of the arcs are eliminated block by block (_ArcSetup, _ArcSweep), with
-        l^T P l -= |R^T b|^2 and observation_count -= sum of the ranks."""
+        l^T P l -= |R^T b|^2 and observation_count -= sum of the ranks.  windows (the _Windows of a TemporalParameters call; default
+        None: nothing here changes) sends the call to _temporal_normals."""
+        if windows is not None:
+            return cls._temporal_normals(observations, model, block_points, windows)
         block_points = _prepare(observations, model, block_points)
         torch = engine.require_gpu()
         P = observations.P
@@ -1103,6 +1231,44 @@ class NormalEquations:
             system.observation_square_sum -= float(np.sum(sweep.setup.g * sweep.setup.g))
             system.observation_count -= system.arc_elimination.count
         return system
+
+    @classmethod
+    def _temporal_normals(cls, observations, model, block_points, windows):
+        """The from_* of TemporalParameters: the normal matrix is block-banded in the B fields.  Per block of
+        _temporal_design_blocks and pair of its slots a <= b whose supports intersect, block (f + a, f + b) += S~[a] S~[b]^T over the
+        columns of the intersection alone, n[f + a] += S~[a] l~ and l^T P l += |l~|^2, all on the fp64 MFMA product.  Where the
+        intersection is the whole block (always without a noise model) the product is the one call of _normals on At [P, K Mb];
+        elsewhere one call per component, on column slices.  Both triangles of a diagonal block are computed and the upper one is
+        mirrored, as _normals mirrors; a block (f, f') that no pair touches is not stored."""
+        _prepare(observations, model, block_points, windows=windows)
+        torch = engine.require_gpu()
+        P, K, B = observations.P, observations.K, windows.B
+        blocks, side, square_sum = {}, _zeros((B * P, 1)), _zeros((1, 1))
+        for block, St, lb, _, _ in _temporal_design_blocks(observations, model, windows):
+            points = block.last - block.first
+            for a, support in enumerate(block.supports):
+                if support is not None:
+                    field = block.field + a
+                    engine.gemm(St[a], lb, beta=1.0, out=side[field * P:(field + 1) * P])
+            for a, b, c0, c1 in _slot_pairs(block):
+                key = (block.field + a, block.field + b)
+                if key not in blocks:
+                    blocks[key] = _zeros((P, P))
+                if (c0, c1) == (0, points):
+                    engine.gemm(St[a], St[b], transb=True, beta=1.0, out=blocks[key])
+                else:
+                    left, right = St[a].reshape(P, K, points), St[b].reshape(P, K, points)
+                    for k in range(K):
+                        engine.gemm(left[:, k, c0:c1], right[:, k, c0:c1], transb=True, beta=1.0, out=blocks[key])
+            engine.gemm(lb, lb, transa=True, beta=1.0, out=square_sum)
+        block_index = np.arange(0, (B + 1) * P, P, dtype=int)
+        matrix = BlockMatrix(block_index, block_index)
+        for (row, column), block in sorted(blocks.items()):
+            if row == column:
+                block.triu_()
+                block.add_(torch.triu(block, 1).t())
+            matrix._set_device(row, column, block)
+        return cls(matrix, side, float(square_sum.item()), observations.K * observations.M)
 
     @classmethod
     def from_accelerations(cls, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
@@ -1463,6 +1629,280 @@ class RadialBasisParameters:
                                         lambda: self.__potential_differences(xyz_a, xyz_b, differences, weights), block_points)
 
 
+def _check_windows(first, factors, fields):
+    """(first [M] int64, factors [M, W] float64, B) of a window model, on the host: factors [M, W] finite, 1 <= W <= 16, first [M] integers
+    with 0 <= first <= B - W, B = fields an integer; ValueError otherwise"""
+    if _is_tensor(factors):
+        factors = engine.to_host(factors)
+    factors = np.asarray(factors, dtype=np.float64)
+    if factors.ndim != 2:
+        raise ValueError('factors must have shape (M, W), got {0}'.format(factors.shape))
+    M, W = factors.shape
+    if not 1 <= W <= MAX_TEMPORAL_SLOTS:
+        raise ValueError('a window of {0} fields: expected 1 .. {1}'.format(W, MAX_TEMPORAL_SLOTS))
+    first = np.asarray(first)
+    if first.shape != (M,) or first.dtype.kind not in 'iu':
+        raise ValueError('first must be an integer array of shape ({0},), got {1} of {2}'.format(M, first.dtype, first.shape))
+    first = first.astype(np.int64)
+    if isinstance(fields, bool) or int(fields) != fields:
+        raise ValueError('fields must be an integer, got {0!r}'.format(fields))
+    B = int(fields)
+    if B < W:
+        raise ValueError('a window of {0} fields, but only {1} fields'.format(W, B))
+    if M and (int(first.min()) < 0 or int(first.max()) > B - W):
+        bad = int(np.flatnonzero((first < 0) | (first > B - W))[0])
+        raise ValueError('first[{0}] is {1}, outside 0 .. {2} ({3} fields, windows of {4})'.format(bad, int(first[bad]), B - W, B, W))
+    if not np.all(np.isfinite(factors)):
+        raise ValueError('factors must be finite')
+    return first, np.ascontiguousarray(factors), B
+
+
+def _take(values, order):
+    """the entries `order` of a per-point argument (None, a host array or a device tensor) along its first axis"""
+    if values is None:
+        return None
+    if _is_tensor(values):
+        return values.index_select(0, engine._torch().from_numpy(order).to(values.device))
+    return np.asarray(values)[order]
+
+
+class _Windows:
+    """The window model of one from_* or of_* call under a TemporalParameters, for M points: first and factors in the order the call
+    works in, W, B and `order`, the stable sort by `first` that a call without a noise model applies where first decreases somewhere
+    (None otherwise; take() applies it to a per-point argument, restore() puts the last axis of a result back).  plan() fills blocks
+    (temporal_blocks) on the host, to_device() the factors on the device."""
+
+    def __init__(self, temporal, M):
+        if temporal.first.shape[0] != M:
+            raise ValueError('{0} points but the temporal parameters hold the windows of {1}'.format(M, temporal.first.shape[0]))
+        self.first, self.factors, self.B, self.W = temporal.first, temporal.factors, temporal.field_count, int(temporal.factors.shape[1])
+        self.order = None if temporal.model is not None else engine.points_at_plan(self.first)[0]
+        if self.order is not None:
+            self.first, self.factors = self.first[self.order], np.ascontiguousarray(self.factors[self.order])
+        self.blocks = self.device_factors = None
+
+    def take(self, values):
+        return _take(values, self.order)
+
+    def restore(self, sorted_values):
+        torch = engine._torch()
+        index = torch.from_numpy(self.order).to(sorted_values.device)
+        return torch.empty_like(sorted_values).index_copy_(sorted_values.dim() - 1, index, sorted_values)
+
+    def default_block_points(self, parameters, components):
+        return TemporalParameters.default_block_points(parameters, components, self.W)
+
+    def plan(self, model, block_points):
+        self.blocks = temporal_blocks(self.first, self.W, block_points, None if model.whitening is None else model.whitening[1])
+
+    def to_device(self, device):
+        self.device_factors = engine.to_device(self.factors, device)
+
+
+def _as_mjd(epochs):
+    from . import utilities
+    return epochs if isinstance(epochs, np.ndarray) else np.array([utilities._mjd(epoch) for epoch in epochs], dtype=np.float64)
+
+
+class TemporalParameters:
+    """
+    Parameters that vary in time, bound to the constructors of NormalEquations and of PostFit like ColouredNoise, ArcParameters and
+    RadialBasisParameters: B = `fields` sets of the P coefficients of degrees min_degree .. max_degree, of
+    which point i sees the W consecutive ones first[i] .. first[i] + W - 1 with the factors[i, :] -- the window model of the *_at
+    functionals (gravityfield._FunctionalsAtEpochs), read backwards.  The design row of an observation of point i with respect to field
+    f is factors[i, f - first[i]] times its static row (gravityfield.temporal_design_matrix states that for small M), so the normal
+    matrix is block-banded in the fields.  The parameter vector is field-major, x = [x_0 .. x_(B-1)], each x_f [P] in the order of
+    utilities.ravel_coefficients; fields(x) returns it as [B, P].
+
+    first [M] host ints, 0 <= first <= B - W; factors [M, W] finite and signed, 1 <= W <= 16; model None (white noise) or a
+    ColouredNoise.  An ArcParameters is a ValueError: arc elimination under temporal parameters is not built yet.  linear (nodes in
+    time with linear interpolation, W = 2), constant (independent fields per interval, W = 1) and harmonic (static part, trend and
+    cycles, one window of all fields) compute first and factors on the host, in float64.  Every check runs before anything reaches the
+    device.
+
+    from_accelerations, from_gradients, from_line_of_sight, from_potentials and from_potential_differences take the arguments of the
+    classmethods of NormalEquations of the same name and return NormalEquations of the B P parameters: a BlockMatrix with block_index
+    arange(0, (B + 1) P, P) that holds the upper blocks the observations touch (exactly symmetric diagonal blocks), the right-hand
+    side [B P, 1] on the device and observation_count = K M.  accumulate_normals adds a process-dynamics constraint,
+    AutoregressiveModelSequence.normal_equations(B) of dimension P; solve, compute_covariance, posterior_sigma, redundancy and
+    compute_variance_factors work as on any block-banded system.  of_accelerations ... of_potential_differences take the solution [B P]
+    or [B P, 1] first and vectors [B P, S] last and return the PostFit of that solution.
+
+    Per block of points the transposed design matrix T [P, K, n] is expanded to the E <= 16 fields the block spans, S [E, P, K, n]
+    (shg_window_expand), then whitened, then multiplied slot pair by slot pair.  Without a noise model points whose window starts
+    decrease somewhere are sorted by them first (the normals are permutation-invariant; PostFit returns the residuals in the order
+    given), blocks restart at every change of the window start and E = W.  With a noise model the order of the points is the order
+    in time and is kept, and a block spans the window starts of its points and of the up to q points of history in front.
+    block_points defaults to default_block_points(P, K, W).  Peak memory of a block of Mb points with history h in E slots:
+    (1 + E) P K (Mb + h) doubles for T and S, and E P K Mb more for the whitened copy under a noise model.
+    """
+
+    def __init__(self, first, factors, fields, model=None):
+        if isinstance(model, ArcParameters):
+            raise ValueError('arc elimination under temporal parameters is not built yet: model must be None or a ColouredNoise')
+        _StochasticModel.of(model)
+        self.first, self.factors, self.field_count = _check_windows(first, factors, fields)
+        self.model = model
+
+    @staticmethod
+    def default_block_points(parameters, components, window):
+        """The default block of the from_* and of_* calls: the largest multiple of 256 points that keeps the expanded block
+        S [W, parameters, components Mb] within NormalEquations.DESIGN_BLOCK_BYTES, at least 256."""
+        return max(NormalEquations.DESIGN_BLOCK_BYTES // (8 * components * parameters * window) // 256 * 256, 256)
+
+    @classmethod
+    def linear(cls, nodes, epochs, model=None):
+        """B = len(nodes) >= 2 fields at the ascending `nodes` in time, linear interpolation between them (W = 2): first and factors by
+        the rule of TimeSeries.interpolation_windows (gravityfield.linear_interpolation_windows), bit for bit.  nodes and epochs [M] are
+        each a sequence of datetime.datetime or a float64 array of modified Julian dates.  ValueError for nodes that do not ascend
+        strictly and for an epoch outside them (no extrapolation)."""
+        from .gravityfield import _check_epochs, linear_interpolation_windows
+        nodes, epochs = _check_epochs(nodes, len(nodes)), _check_epochs(epochs, len(epochs))
+        if any(not earlier < later for earlier, later in zip(nodes[:-1], nodes[1:])):
+            raise ValueError('nodes must ascend strictly')
+        first, factors = linear_interpolation_windows(nodes, epochs)
+        return cls(first, factors, len(nodes), model)
+
+    @classmethod
+    def constant(cls, edges, epochs, model=None):
+        """B = len(edges) - 1 independent fields, field k for the epochs of the half-open interval [e_k, e_(k+1)) (W = 1, factor 1.0):
+        many solutions in one pass, block-diagonal normals.  edges and epochs [M] as in linear.  ValueError for fewer than two edges,
+        edges that do not ascend strictly and an epoch outside them, naming the first one."""
+        import bisect
+        from .gravityfield import _check_epochs
+        edges, epochs = _check_epochs(edges, len(edges)), _check_epochs(epochs, len(epochs))
+        B = len(edges) - 1
+        if B < 1 or any(not earlier < later for earlier, later in zip(edges[:-1], edges[1:])):
+            raise ValueError('edges must be at least two and ascend strictly')
+        if isinstance(edges, np.ndarray) or isinstance(epochs, np.ndarray):
+            limits, values = _as_mjd(edges), _as_mjd(epochs)
+            index = np.searchsorted(limits, values, side='right').astype(np.int64) - 1
+        else:
+            index = np.array([bisect.bisect_right(edges, epoch) - 1 for epoch in epochs], dtype=np.int64)
+        outside = (index < 0) | (index >= B)
+        if outside.any():
+            k = int(np.flatnonzero(outside)[0])
+            if isinstance(edges, np.ndarray) or isinstance(epochs, np.ndarray):
+                raise ValueError('epoch {0} (MJD {1!r}) lies outside the edges ({2!r} .. {3!r}): the intervals are half-open'.format(
+                    k, float(values[k]), float(limits[0]), float(limits[-1])))
+            raise ValueError('epoch {0} ({1}) lies outside the edges ({2} .. {3}): the intervals are half-open'.format(k, epochs[k], edges[0], edges[-1]))
+        return cls(index, np.ones((len(epochs), 1)), B, model)
+
+    @classmethod
+    def harmonic(cls, epochs, reference_epoch, periods=(), trend=True, static=True, time_scale=365.25, model=None):
+        """One window of all B = W fields (first = 0): the static field (factor 1) if `static`, the trend per `time_scale` days (factor
+        tau) if `trend`, then a cosine and a sine field per period [days] (factors cos and sin of 2 pi tau_T), tau the time since
+        reference_epoch in units of time_scale and tau_T in units of the period -- the expressions, and the bits, of Trend.weights_at and
+        Oscillation.weights_at (timevariable.epoch_arguments).  epochs [M] as in linear.  ValueError for a period or time_scale that is
+        not finite and positive, and for no column at all or more than 16."""
+        import datetime
+        from .gravityfield import _check_epochs
+        from .timevariable import Oscillation, Trend, epoch_arguments
+        epochs = _check_epochs(epochs, len(epochs))
+        if not isinstance(reference_epoch, datetime.datetime):
+            raise ValueError('reference_epoch must be a datetime.datetime, got {0!r}'.format(reference_epoch))
+        periods = np.asarray(periods, dtype=np.float64).reshape(-1)
+        if not np.all(np.isfinite(periods) & (periods > 0)) or not (np.isfinite(time_scale) and time_scale > 0):
+            raise ValueError('periods and time_scale must be finite and positive')
+        columns = [np.ones((len(epochs), 1))] if static else []
+        if trend:
+            columns.append(Trend._weights_at(epoch_arguments(epochs, reference_epoch, 86400.0 * time_scale)))
+        for period in periods:
+            columns.append(Oscillation._weights_at(epoch_arguments(epochs, reference_epoch, 86400.0 * period)))
+        if not columns:
+            raise ValueError('no column at all: static, trend or a period is needed')
+        factors = np.concatenate(columns, axis=1)
+        return cls(np.zeros(len(epochs), dtype=np.int64), factors, factors.shape[1], model)
+
+    def fields(self, x):
+        """the solution x [B P] or [B P, 1] (host array or device tensor) as [B, P]"""
+        size = int(np.prod(tuple(x.shape)))
+        if len(x.shape) not in (1, 2) or (len(x.shape) == 2 and x.shape[1] != 1) or size % self.field_count:
+            raise ValueError('the solution must have shape (B P,) or (B P, 1) with B = {0}, got {1}'.format(self.field_count, tuple(x.shape)))
+        return x.reshape(self.field_count, size // self.field_count)
+
+    def __windows(self, build):
+        """(observations, windows) of a call: build(take) makes the record of the observations from the per-point arguments as take
+        returns them -- first as given, for the checks of the kind, then sorted where the call sorts"""
+        observations = build(lambda values: values)
+        windows = _Windows(self, observations.M)
+        return (observations if windows.order is None else build(windows.take)), windows
+
+    def __normals(self, build, block_points):
+        observations, windows = self.__windows(build)
+        return NormalEquations._normals(observations, _StochasticModel.of(self.model), block_points, windows)
+
+    def __post_fit(self, solution, vectors, template, build, block_points):
+        observations, windows = self.__windows(build)
+        return PostFit._of_observations(solution, vectors, self.model, template, lambda: observations, block_points, windows)
+
+    @staticmethod
+    def __accelerations(xyz, g, min_degree, max_degree, GM, R, weights):
+        return lambda take: _acceleration_observations(xyz=take(xyz), g=take(g), min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
+                                                       weights=take(weights))
+
+    @staticmethod
+    def __gradients(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights):
+        return lambda take: _gradient_observations(xyz=take(xyz), gradients=take(gradients), min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
+                                                   frames=take(frames), components=components, weights=take(weights))
+
+    @staticmethod
+    def __line_of_sight(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights):
+        return lambda take: _los_observations(xyz_a=take(xyz_a), xyz_b=take(xyz_b), differences=take(differences), min_degree=min_degree,
+                                              max_degree=max_degree, GM=GM, R=R, directions=take(directions), weights=take(weights))
+
+    @staticmethod
+    def __potentials(xyz, potentials, min_degree, max_degree, GM, R, weights):
+        return lambda take: _potential_observations(xyz=take(xyz), potentials=take(potentials), min_degree=min_degree, max_degree=max_degree, GM=GM,
+                                                    R=R, weights=take(weights))
+
+    @staticmethod
+    def __potential_differences(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights):
+        return lambda take: _potential_difference_observations(xyz_a=take(xyz_a), xyz_b=take(xyz_b), differences=take(differences),
+                                                               min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=take(weights))
+
+    def from_accelerations(self, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
+        return self.__normals(self.__accelerations(xyz, g, min_degree, max_degree, GM, R, weights), block_points)
+
+    def from_gradients(self, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
+                       weights=None, block_points=None):
+        return self.__normals(self.__gradients(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights), block_points)
+
+    def from_line_of_sight(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
+                           weights=None, block_points=None):
+        return self.__normals(self.__line_of_sight(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights), block_points)
+
+    def from_potentials(self, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
+        return self.__normals(self.__potentials(xyz, potentials, min_degree, max_degree, GM, R, weights), block_points)
+
+    def from_potential_differences(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None,
+                                   block_points=None):
+        return self.__normals(self.__potential_differences(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights), block_points)
+
+    def of_accelerations(self, solution, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
+                         vectors=None):
+        return self.__post_fit(solution, vectors, xyz, self.__accelerations(xyz, g, min_degree, max_degree, GM, R, weights), block_points)
+
+    def of_gradients(self, solution, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
+                     weights=None, block_points=None, vectors=None):
+        return self.__post_fit(solution, vectors, xyz, self.__gradients(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights),
+                               block_points)
+
+    def of_line_of_sight(self, solution, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
+                         weights=None, block_points=None, vectors=None):
+        return self.__post_fit(solution, vectors, xyz_a,
+                               self.__line_of_sight(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights), block_points)
+
+    def of_potentials(self, solution, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None,
+                      block_points=None, vectors=None):
+        return self.__post_fit(solution, vectors, xyz, self.__potentials(xyz, potentials, min_degree, max_degree, GM, R, weights), block_points)
+
+    def of_potential_differences(self, solution, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06,
+                                 weights=None, block_points=None, vectors=None):
+        return self.__post_fit(solution, vectors, xyz_a,
+                               self.__potential_differences(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights), block_points)
+
+
 class PostFit:
     """
     What a solution says about the stochastic model it was computed under: the residuals of the observations, the square sum, the
@@ -1536,10 +1976,11 @@ class PostFit:
         return fit._pass(observations, fit.__model, block_points)
 
     @classmethod
-    def _of_observations(cls, solution, vectors, model, template, build, block_points):
-        """an of_* call on the observations that build() returns (the record of another parameterisation: RadialBasisParameters)"""
+    def _of_observations(cls, solution, vectors, model, template, build, block_points, windows=None):
+        """an of_* call on the observations that build() returns (the record of another parameterisation: RadialBasisParameters, and
+        TemporalParameters with the _Windows of the call)"""
         fit = cls(solution, vectors, model, template)
-        return fit._pass(build(), fit.__model, block_points)
+        return fit._pass(build(), fit.__model, block_points, windows)
 
     def _check(self, parameters):
         """the solution and the vectors against the number of parameters: ValueError before anything reaches the device"""
@@ -1551,28 +1992,35 @@ class PostFit:
             if len(shape) != 2 or shape[0] != parameters or shape[1] < 1:
                 raise ValueError('vectors must have shape ({0}, S), got {1}'.format(parameters, shape))
 
-    def _pass(self, observations, model, block_points):
-        """the pass over the blocks of NormalEquations._normals, with its arguments; returns self"""
-        block_points = _prepare(observations, model, block_points, self)
+    def _pass(self, observations, model, block_points, windows=None):
+        """the pass over the blocks of NormalEquations._normals, with its arguments; returns self.  Under TemporalParameters (windows)
+        the solution holds B fields, a block multiplies the columns of its own fields with its expanded design matrix, and points that
+        the call sorted come back in the order they were given in"""
+        block_points = _prepare(observations, model, block_points, self, windows)
         torch = engine.require_gpu()
         l, M, K, P = observations.l, observations.M, observations.K, observations.P
-        x = engine.to_device(self.__solution, l.device).reshape(P, 1)
+        parameters = P if windows is None else windows.B * P
+        x = engine.to_device(self.__solution, l.device).reshape(parameters, 1)
         X = x if self.__vectors is None else torch.cat((x, engine.to_device(self.__vectors, l.device)), dim=1)
         rows = int(X.shape[1])
-        Xt = torch.empty((rows, P), dtype=torch.float64, device=l.device).copy_(X.t())                   # [1 + S, P], row stride P also for one row
+        Xt = torch.empty((rows, parameters), dtype=torch.float64, device=l.device).copy_(X.t())          # [1 + S, P], row stride P also for one row
         bounds = np.append(model.starts, M)
         arcs = len(bounds) - 1
         V = torch.empty((rows, K, M), dtype=torch.float64, device=l.device)                             # the whitened model values of x and the z_j
         lt, plain = torch.empty((K, M), dtype=torch.float64, device=l.device), torch.empty((K, M), dtype=torch.float64, device=l.device)
-        for first, last, At, lb, At_plain, skip in _design_blocks(observations, model, block_points):
-            V[:, :, first:last] = engine.gemm(Xt, At).reshape(rows, K, last - first)
+        blocks = _design_blocks(observations, model, block_points) if windows is None else _temporal_pass_blocks(observations, model, windows)
+        for first, last, At, lb, At_plain, skip, *columns in blocks:
+            Xb = Xt[:, columns[0]] if columns else Xt                                                    # the fields of the block
+            V[:, :, first:last] = engine.gemm(Xb, At).reshape(rows, K, last - first)
             lt[:, first:last] = lb.reshape(K, last - first)
             if model.taps is None:
                 plain[:, first:last] = V[0, :, first:last]                                               # white noise: the same values
             else:
-                plain[:, first:last] = engine.gemm(Xt[0:1], At_plain).reshape(K, skip + last - first)[:, skip:]
+                plain[:, first:last] = engine.gemm(Xb[0:1], At_plain).reshape(K, skip + last - first)[:, skip:]
         V[0] = lt - V[0]                                                                                 # l~ - A~ x
         plain = l.t().contiguous() - plain                                                               # sqrt(w) (l - A x), dense [K, M]
+        if windows is not None and windows.order is not None:
+            V, plain = windows.restore(V), windows.restore(plain)
         seg = torch.from_numpy(bounds.astype(np.int32)).to(l.device)
         self.arc_parameters, self.ranks = None, np.zeros((arcs, K), dtype=np.int64)
         if model.parameters is not None:

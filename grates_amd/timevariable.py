@@ -20,6 +20,15 @@ from . import utilities
 from .gravityfield import PotentialCoefficients, TimeSeries, _AtCall, _FunctionalsAtEpochs, _merge_fixed_calls
 
 
+def epoch_arguments(epochs, reference_epoch, unit_seconds):
+    """tau [M] of the checked `epochs` (a list of datetimes or float64 modified Julian dates): the time since reference_epoch in units
+    of unit_seconds, as _WeightedFields.evaluate_at computes it.  The one expression behind the weights of Trend and Oscillation and
+    the factors of lstsq.TemporalParameters.harmonic.  Host only."""
+    if isinstance(epochs, np.ndarray):
+        return (epochs - utilities._mjd(reference_epoch)) * 86400.0 / unit_seconds
+    return np.array([(epoch - reference_epoch).total_seconds() / unit_seconds for epoch in epochs], dtype=np.float64)
+
+
 class _WeightedFields(_FunctionalsAtEpochs):
     """V(t) = sum_i w_i(tau(t)) V_i; the fields are copied on construction (anything with `copy`, `*` by a float and `+`)."""
 
@@ -45,11 +54,7 @@ class _WeightedFields(_FunctionalsAtEpochs):
     def weights_at(self, epochs):
         """The weights [M, W] of the fields at the checked `epochs` (a list of datetimes or float64 modified Julian dates): tau as
         evaluate_at computes it, total_seconds() of the difference over the unit.  Host only."""
-        if isinstance(epochs, np.ndarray):
-            tau = (epochs - utilities._mjd(self._t0)) * 86400.0 / self._unit
-        else:
-            tau = np.array([(epoch - self._t0).total_seconds() / self._unit for epoch in epochs], dtype=np.float64)
-        return self._weights_at(tau)
+        return self._weights_at(epoch_arguments(epochs, self._t0, self._unit))
 
     def _at_calls(self, epochs):
         fields = self._fields
@@ -72,7 +77,8 @@ class Trend(_WeightedFields):
     def _weights(self, tau):
         return (tau,)
 
-    def _weights_at(self, tau):
+    @staticmethod
+    def _weights_at(tau):
         return tau[:, np.newaxis]
 
 
@@ -86,7 +92,8 @@ class Oscillation(_WeightedFields):
         phase = 2.0 * math.pi * tau
         return (math.cos(phase), math.sin(phase))
 
-    def _weights_at(self, tau):
+    @staticmethod
+    def _weights_at(tau):
         phase = 2.0 * math.pi * tau
         return np.stack((np.cos(phase), np.sin(phase)), axis=1)
 

@@ -799,6 +799,30 @@ int shg_segment_products(long long rows, int channels, int M, const double* X, l
 int shg_segment_lag_products(long long rows, int M, const double* X, long long ldx, int lags, int nseg, const int32_t* seg, double* S,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Window expansion of a transposed design matrix: the adjoint of the window model of the shg_*_points_at calls, for parameters
+ * that vary in time (no reference counterpart)
+ *   T [rows][ldt] with n columns in use (the transposed design matrix At [P][K][ldt] of a block is rows = P K).  factors (device)
+ *   [n][W], 1 <= W <= 16: the W factors of every column.  run_slot [runs] and run_begin [runs + 1] are HOST tables, as the
+ *   shg_*_points_at calls take theirs: run r covers the columns run_begin[r] .. run_begin[r + 1] - 1, whose window starts at slot
+ *   run_slot[r], 0 <= run_slot[r] <= E - W, W <= E <= 16.
+ *   S[e][r][t] = factors[t][e - slot(t)] * T[r][t] for slot(t) <= e < slot(t) + W and +0.0 for every other e < E, at
+ *   S + e slot_stride + r lds + t: all E slots of the n columns of every row are written, each exactly once, the zeros included (no
+ *   memset, no read of S, no atomics; one IEEE product per entry inside the window, whatever the launch geometry: repeated calls are
+ *   bitwise equal).  The entries of a row of S from n to lds and whatever lies between the slots are not touched.
+ *   Bandwidth-bound: one read of T and E writes.  Lanes run along t; a lane keeps the factors of its columns in registers and walks
+ *   down the rows.  With T and S on 16-byte boundaries and ldt, lds and slot_stride even, a lane holds two adjacent columns and
+ *   stores 16 bytes (a pair across a run boundary and the last column of an odd n: 8 bytes); otherwise one column, 8 bytes.  A flat
+ *   64-bit index, so rows x ld may exceed 2^31.
+ *   Arguments are checked before the first HIP call (negative sizes, W outside 1 .. 16, E outside W .. 16, ldt < n, lds < n,
+ *   slot_stride below the extent of one slot, more than 2^40 values of T or S, NULL pointers, address ranges of T and S that overlap),
+ *   the run tables in full (run_begin[0] = 0, strictly increasing, run_begin[runs] = n, every run_slot in 0 .. E - W): no table
+ *   content can make the kernel read or write outside its buffers.  The tables reach the device through a workspace of the call
+ *   (one copy and one wait on the stream).  rows = 0 or n = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_window_expand(long long rows, int n, const double* T, long long ldt, const int32_t* run_slot, const int32_t* run_begin, int runs,
+                      const double* factors, int W, int E, double* S, long long lds, long long slot_stride, void* stream);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
