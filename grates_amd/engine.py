@@ -5,6 +5,7 @@ contiguous); every routine hands raw device pointers and the current HIP stream 
 Nothing in here computes on the CPU: without the library or without a GPU the calls raise.
 """
 
+import collections
 import ctypes
 import hashlib
 
@@ -924,10 +925,7 @@ def acceleration_design(max_degree, xyz, GM, R, min_degree=0, weights=None):
     """Transposed design matrix At [P, 3, M] (device) of the gravitational acceleration at the positions xyz [M, 3]: At[p, c, i] is the
     derivative of component c of g at point i with respect to coefficient p of utilities.ravel_coefficients(., min_degree, max_degree),
     P = (max_degree + 1)^2 - min_degree^2 (shg_acceleration_design).  weights [M] or [M, 3] scale the entries by sqrt(w)."""
-    min_degree, max_degree = check_degrees(min_degree, max_degree)
-    layout = check_observation_weights(weights, check_positions(xyz))
-    x = to_device(xyz)
-    return acceleration_design_checked(max_degree, min_degree, x, to_device(weights, x.device) if layout else None, GM, R)
+    return _design('accelerations', dict(xyz=xyz, weights=weights), Band(*check_degrees(min_degree, max_degree), GM, R))
 
 
 def acceleration_design_checked(max_degree, min_degree, x, weights, GM, R):
@@ -977,28 +975,14 @@ def check_frames(frames, points):
         raise ValueError('frames must have orthonormal rows: |F F^T - I| is {0:.3g}, above {1:g}'.format(defect, FRAME_TOLERANCE))
 
 
-def _check_gradient_observations(xyz, frames, components, weights):
-    """(picked, layout): what gradient_design and rbf_gradient_design check alike, in this order: the positions, the components (their
-    ascending positions `picked`), the weights (their layout) and the frames; ValueError otherwise."""
-    M = check_positions(xyz)
-    picked = gradient_components(components)
-    layout = check_observation_weights(weights, M, len(picked))
-    if frames is not None:
-        check_frames(frames, M)
-    return picked, layout
-
-
 def gradient_design(max_degree, xyz, GM, R, min_degree=0, frames=None, components=None, weights=None):
     """Transposed design matrix At [P, K, M] (device) of the gravitational gradient tensor at the positions xyz [M, 3]: At[p, k, i] is
     the derivative of the k-th selected component of T' = F T F^T at point i with respect to coefficient p of
     utilities.ravel_coefficients(., min_degree, max_degree) (shg_gradient_design).  frames [M, 3, 3] hold the instrument axes as rows
     (None: the Earth-fixed tensor); components is a sequence of distinct names from GRADIENT_COMPONENTS in any order (None: all six),
     the output always in canonical order; weights [M] or [M, K] scale the entries by sqrt(w)."""
-    min_degree, max_degree = check_degrees(min_degree, max_degree)
-    picked, layout = _check_gradient_observations(xyz, frames, components, weights)
-    x = to_device(xyz)
-    return gradient_design_checked(max_degree, min_degree, x, None if frames is None else to_device(frames, x.device), picked,
-                                   to_device(weights, x.device) if layout else None, GM, R)
+    return _design('gradients', dict(xyz=xyz, frames=frames, components=components, weights=weights),
+                   Band(*check_degrees(min_degree, max_degree), GM, R))
 
 
 def gradient_design_checked(max_degree, min_degree, x, frames, picked, weights, GM, R):
@@ -1054,16 +1038,8 @@ def los_design(max_degree, xyz_a, xyz_b, GM, R, min_degree=0, directions=None, w
     utilities.ravel_coefficients(., min_degree, max_degree), P = (max_degree + 1)^2 - min_degree^2 (shg_los_design).  directions
     [M, 3] are the lines of sight e (unit vectors; None: (b - a) / |b - a|, and no pair may then coincide); weights [M] scale the
     entries by sqrt(w)."""
-    min_degree, max_degree = check_degrees(min_degree, max_degree)
-    M = check_pair_positions(xyz_a, xyz_b)
-    layout = check_point_weights(weights, M)
-    if directions is not None:
-        check_directions(directions, M)
-    else:
-        check_pairs_apart(xyz_a, xyz_b)
-    a = to_device(xyz_a)
-    return los_design_checked(max_degree, min_degree, a, to_device(xyz_b, a.device), None if directions is None else to_device(directions, a.device),
-                              to_device(weights, a.device) if layout else None, GM, R)
+    return _design('line_of_sight', dict(xyz_a=xyz_a, xyz_b=xyz_b, directions=directions, weights=weights),
+                   Band(*check_degrees(min_degree, max_degree), GM, R))
 
 
 def los_design_checked(max_degree, min_degree, a, b, directions, weights, GM, R):
@@ -1097,10 +1073,7 @@ def potential_design(max_degree, xyz, GM, R, min_degree=0, weights=None):
     """Transposed design matrix At [P, M] (device) of the gravitational potential at the positions xyz [M, 3]: At[p, i] is the
     derivative of V at point i with respect to coefficient p of utilities.ravel_coefficients(., min_degree, max_degree),
     P = (max_degree + 1)^2 - min_degree^2 (shg_potential_design).  weights [M] scale the entries by sqrt(w)."""
-    min_degree, max_degree = check_degrees(min_degree, max_degree)
-    layout = check_point_weights(weights, check_positions(xyz))
-    x = to_device(xyz)
-    return potential_design_checked(max_degree, min_degree, x, to_device(weights, x.device) if layout else None, GM, R)
+    return _design('potentials', dict(xyz=xyz, weights=weights), Band(*check_degrees(min_degree, max_degree), GM, R))
 
 
 def potential_design_checked(max_degree, min_degree, x, weights, GM, R):
@@ -1117,11 +1090,7 @@ def potential_difference_design(max_degree, xyz_a, xyz_b, GM, R, min_degree=0, w
     At[p, i] is the derivative of V(b_i) - V(a_i) with respect to coefficient p of utilities.ravel_coefficients(., min_degree,
     max_degree) (shg_potential_difference_design).  A pair with a == b is legal and gives a zero column; weights [M] scale the entries
     by sqrt(w)."""
-    min_degree, max_degree = check_degrees(min_degree, max_degree)
-    layout = check_point_weights(weights, check_pair_positions(xyz_a, xyz_b))
-    a = to_device(xyz_a)
-    return potential_difference_design_checked(max_degree, min_degree, a, to_device(xyz_b, a.device), to_device(weights, a.device) if layout else None,
-                                               GM, R)
+    return _design('potential_differences', dict(xyz_a=xyz_a, xyz_b=xyz_b, weights=weights), Band(*check_degrees(min_degree, max_degree), GM, R))
 
 
 def potential_difference_design_checked(max_degree, min_degree, a, b, weights, GM, R):
@@ -1182,28 +1151,15 @@ def rbf_design(kind, basis, xyz, xyz_b=None, directions=None, weights=None):
     columns equal those of the spherical harmonic design matrix of the basis's band times basis.to_potential_coefficients_matrix()."""
     if kind not in RBF_KINDS:
         raise ValueError('unknown kind {0!r}: expected one of {1}'.format(kind, RBF_KINDS))
-    pairs = kind in ('line_of_sight', 'potential_difference')
-    if pairs:
-        if xyz_b is None:
-            raise ValueError('{0} needs the positions of the second satellite'.format(kind))
-        M = check_pair_positions(xyz, xyz_b)
-    else:
-        M = check_positions(xyz)
-    layout = check_observation_weights(weights, M) if kind == 'acceleration' else check_point_weights(weights, M)
-    if kind == 'line_of_sight':
-        if directions is not None:
-            check_directions(directions, M)
-        else:
-            check_pairs_apart(xyz, xyz_b)
-    rbf_node_table(basis)                                            # an anisotropic K is refused before anything else reaches the device
-    a = to_device(xyz)
-    return rbf_design_checked(kind, basis, a, to_device(xyz_b, a.device) if pairs else None,
-                              to_device(directions, a.device) if kind == 'line_of_sight' and directions is not None else None,
-                              to_device(weights, a.device) if layout else None)
+    entry = OBSERVATION_KINDS[RBF_OBSERVATION_KINDS[kind]]
+    if 'xyz_b' in entry.points and xyz_b is None:
+        raise ValueError('{0} needs the positions of the second satellite'.format(kind))
+    given = dict(xyz=xyz, xyz_a=xyz, xyz_b=xyz_b, directions=directions, weights=weights)
+    return _design(RBF_OBSERVATION_KINDS[kind], {name: given[name] for name in entry.points + ('weights',) if name != entry.observed}, basis_band(basis))
 
 
 def rbf_design_checked(kind, basis, a, b, directions, weights):
-    """shg_rbf_design on device tensors that rbf_design (or a NormalEquations.from_*(basis=...), once for all its blocks) has checked:
+    """shg_rbf_design on device tensors that rbf_design (or a RadialBasisParameters.from_* or of_*, once for all its blocks) has checked:
     positions a [M, 3], b [M, 3] or None, directions [M, 3] or None, weights [M], [M, 3] or None."""
     shape, nodes, J, M, out = _rbf_design_output(basis, a, *((3,) if kind == 'acceleration' else ()))
     _lib.call('shg_rbf_design', RBF_KINDS.index(kind), int(basis.max_degree), int(basis.min_degree), _host_ptr(shape), _ptr(nodes), J, _ptr(a),
@@ -1220,11 +1176,7 @@ def rbf_gradient_design(basis, xyz, frames=None, components=None, weights=None):
     distinct names from GRADIENT_COMPONENTS (None: all six), the output always in canonical order, weights [M] or [M, K] scale the
     entries by sqrt(w).  The columns equal those of gradient_design of the basis's band times
     basis.to_potential_coefficients_matrix()."""
-    picked, layout = _check_gradient_observations(xyz, frames, components, weights)
-    rbf_node_table(basis)                                            # an anisotropic K is refused before anything else reaches the device
-    x = to_device(xyz)
-    return rbf_gradient_design_checked(basis, x, None if frames is None else to_device(frames, x.device), picked,
-                                       to_device(weights, x.device) if layout else None)
+    return _design('gradients', dict(xyz=xyz, frames=frames, components=components, weights=weights), basis_band(basis))
 
 
 def rbf_gradient_design_checked(basis, x, frames, picked, weights):
@@ -1236,6 +1188,146 @@ def rbf_gradient_design_checked(basis, x, frames, picked, weights):
               None if frames is None else _ptr(frames), sum(1 << j for j in picked), None if weights is None else _ptr(weights),
               0 if weights is None else weights.dim(), float(basis.GM), float(basis.R), _ptr(out), M, _stream())
     return out
+
+
+# ---- the kinds of observation: what the *_design functions above and every from_* and of_* of lstsq know of a kind, stated once ---------
+Band = collections.namedtuple('Band', 'min_degree max_degree GM R basis', defaults=(None,))
+Band.__doc__ = """The parameters of a design call: the coefficients of degrees min_degree .. max_degree with the constants GM and R, or the
+node values of the isotropic gravityfield.RadialBasisFunctions `basis` (None: the coefficients)."""
+
+ObservationKind = collections.namedtuple('ObservationKind', 'points observed options check values design rbf_design')
+ObservationKind.__doc__ = """One kind of observation.  points: its per-point arguments in call order (weights [M] or [M, K], which every
+kind takes, come after them); the first decides whether results are host arrays or device tensors, `observed` names the one that holds
+the observed values, which the *_design functions do not take.  options: its per-call arguments.  check(arguments) runs the host checks
+of the kind on the dict of a call, in a fixed order, and returns (M, K, the layout of the weights, extra), extra being what the design
+call needs beyond the tensors; the shape of the observed values is checked only where the dict holds them: before the weights, and
+for gradients behind the components, which give K.  values(l, extra): the observed values on the device as l [M, K].  design(band,
+tensors, extra) and rbf_design(band, tensors, extra): the transposed design matrix [P, K, Mb] or [P, Mb] with respect to the
+coefficients, and to the node values of band.basis, of a slice of the per-point tensors and the weights, on the device and checked."""
+
+
+def basis_band(basis):
+    """the Band of the node values of a gravityfield.RadialBasisFunctions"""
+    return Band(basis.min_degree, basis.max_degree, basis.GM, basis.R, basis)
+
+
+def _check_scalar_observations(arguments, name, M, unit):
+    """one observed value per point (pair), where the call holds them: `name` [M]"""
+    if name in arguments:
+        values = arguments[name]
+        if len(values.shape) != 1:
+            raise ValueError('{0} must have shape (M,), got {1}'.format(name, tuple(values.shape)))
+        if int(values.shape[0]) != M:
+            raise ValueError('{0} {1} but {2} {3}'.format(M, unit, int(values.shape[0]), name))
+
+
+def _check_accelerations(a):
+    M = check_positions(a['xyz'])
+    if 'g' in a and check_positions(a['g'], 'accelerations') != M:
+        raise ValueError('{0} positions but {1} accelerations'.format(M, int(a['g'].shape[0])))
+    return M, 3, check_observation_weights(a['weights'], M), None
+
+
+def _check_gradients(a):
+    M = check_positions(a['xyz'])
+    picked = gradient_components(a['components'])
+    K, full = len(picked), False
+    if 'gradients' in a:
+        shape = tuple(a['gradients'].shape)
+        full = len(shape) == 3 and shape[1:] == (3, 3)
+        if not full and (len(shape) != 2 or shape[1] != K):
+            raise ValueError('gradients must have shape (M, {0}) or (M, 3, 3), got {1}'.format(K, shape))
+        if shape[0] != M:
+            raise ValueError('{0} positions but {1} gradients'.format(M, shape[0]))
+    layout = check_observation_weights(a['weights'], M, K)
+    if a['frames'] is not None:
+        check_frames(a['frames'], M)
+    return M, K, layout, (picked, full)
+
+
+def _check_line_of_sight(a):
+    M = check_pair_positions(a['xyz_a'], a['xyz_b'])
+    _check_scalar_observations(a, 'differences', M, 'pairs')
+    layout = check_point_weights(a['weights'], M)
+    if a['directions'] is not None:
+        check_directions(a['directions'], M)
+    else:
+        check_pairs_apart(a['xyz_a'], a['xyz_b'])
+    return M, 1, layout, None
+
+
+def _check_potentials(a):
+    M = check_positions(a['xyz'])
+    _check_scalar_observations(a, 'potentials', M, 'positions')
+    return M, 1, check_point_weights(a['weights'], M), None
+
+
+def _check_potential_differences(a):
+    M = check_pair_positions(a['xyz_a'], a['xyz_b'])
+    _check_scalar_observations(a, 'differences', M, 'pairs')
+    return M, 1, check_point_weights(a['weights'], M), None
+
+
+def _picked_entries(l, extra):
+    """the selected upper-triangle entries of gradients given as [M, 3, 3]"""
+    picked, full = extra
+    return l.reshape(int(l.shape[0]), 9)[:, [(0, 1, 2, 4, 5, 8)[i] for i in picked]] if full else l
+
+
+def _one_column(l, extra):
+    return l.reshape(-1, 1)
+
+
+def _rbf_call(kind):
+    """the design call of a kind of RBF_KINDS on the tensors of a table entry"""
+    first = 'xyz_a' if kind in ('line_of_sight', 'potential_difference') else 'xyz'
+    return lambda band, t, extra: rbf_design_checked(kind, band.basis, t[first], t.get('xyz_b'), t.get('directions'), t['weights'])
+
+
+OBSERVATION_KINDS = {
+    'accelerations': ObservationKind(
+        ('xyz', 'g'), 'g', (), _check_accelerations, lambda l, extra: l,
+        lambda band, t, extra: acceleration_design_checked(band.max_degree, band.min_degree, t['xyz'], t['weights'], band.GM, band.R),
+        _rbf_call('acceleration')),
+    'gradients': ObservationKind(
+        ('xyz', 'gradients', 'frames'), 'gradients', ('components',), _check_gradients, _picked_entries,
+        lambda band, t, extra: gradient_design_checked(band.max_degree, band.min_degree, t['xyz'], t['frames'], extra[0], t['weights'], band.GM, band.R),
+        lambda band, t, extra: rbf_gradient_design_checked(band.basis, t['xyz'], t['frames'], extra[0], t['weights'])),
+    'line_of_sight': ObservationKind(
+        ('xyz_a', 'xyz_b', 'differences', 'directions'), 'differences', (), _check_line_of_sight, _one_column,
+        lambda band, t, extra: los_design_checked(band.max_degree, band.min_degree, t['xyz_a'], t['xyz_b'], t['directions'], t['weights'], band.GM, band.R),
+        _rbf_call('line_of_sight')),
+    'potentials': ObservationKind(
+        ('xyz', 'potentials'), 'potentials', (), _check_potentials, _one_column,
+        lambda band, t, extra: potential_design_checked(band.max_degree, band.min_degree, t['xyz'], t['weights'], band.GM, band.R),
+        _rbf_call('potential')),
+    'potential_differences': ObservationKind(
+        ('xyz_a', 'xyz_b', 'differences'), 'differences', (), _check_potential_differences, _one_column,
+        lambda band, t, extra: potential_difference_design_checked(band.max_degree, band.min_degree, t['xyz_a'], t['xyz_b'], t['weights'], band.GM, band.R),
+        _rbf_call('potential_difference')),
+}
+RBF_OBSERVATION_KINDS = dict(zip(RBF_KINDS, ('accelerations', 'line_of_sight', 'potentials', 'potential_differences')))      # the table's names
+
+
+def upload_observations(kind, arguments):
+    """The per-point arguments and the weights of a checked call as device tensors, {name: tensor or None}: the first on the current
+    device, the others where it is.  An argument the call does not hold (the observed values, for the *_design functions) is left out."""
+    first = to_device(arguments[kind.points[0]])
+    tensors = {kind.points[0]: first}
+    for name in kind.points[1:] + ('weights',):
+        if name in arguments:
+            tensors[name] = None if arguments[name] is None else to_device(arguments[name], first.device)
+    return tensors
+
+
+def _design(kind, arguments, band):
+    """The public *_design functions behind check_degrees: the checks of the kind on the host, an anisotropic basis refused before
+    anything else reaches the device, then the design call on the uploaded arguments."""
+    kind = OBSERVATION_KINDS[kind]
+    extra = kind.check(arguments)[3]
+    if band.basis is not None:
+        rbf_node_table(band.basis)
+    return (kind.design if band.basis is None else kind.rbf_design)(band, upload_observations(kind, arguments), extra)
 
 
 def rbf_surface_info():

@@ -1313,7 +1313,7 @@ class RadialBasisFunctions:
     def degree_factors(self):
         """k_n [N+1] of an isotropic basis: every C slot K[n, 0..n] and every S slot K[m-1, n] of degree n holds the same bits, and k_n
         is that value.  ValueError otherwise: the closed Legendre sums of the design matrices (rbf_acceleration_design_matrix,
-        NormalEquations.from_*(basis=...)) exist for isotropic shapes only."""
+        RadialBasisParameters.from_* and of_*) exist for isotropic shapes only."""
         K, N = np.ascontiguousarray(self.__K, dtype=np.float64), self.__max_degree
         if K.shape != (N + 1, N + 1):
             raise ValueError('shape factors of shape {0} do not hold degrees 0 .. {1}'.format(K.shape, N))
@@ -1476,8 +1476,8 @@ def rbf_acceleration_design_matrix(basis, xyz, weights=None, as_tensor=False):
     ``basis.gravitational_acceleration(xyz).ravel()``, and A equals acceleration_design_matrix of the basis's band times
     ``basis.to_potential_coefficients_matrix()``.  Always computed on the GPU (shg_rbf_design: a closed Legendre sum per point and
     node); weights (M,) per point or (M, 3) per component scale the rows by sqrt(w).  Returns an ndarray, or the float64 device tensor
-    with as_tensor=True.  The kernel builds the transposed matrix (engine.rbf_design, what NormalEquations.from_accelerations(...,
-    basis=basis) accumulates block by block); the transposition here is a copy meant for modest sizes.
+    with as_tensor=True.  The kernel builds the transposed matrix (engine.rbf_design, what
+    RadialBasisParameters(basis).from_accelerations accumulates block by block); the transposition here is a copy meant for modest sizes.
     """
     At = engine.rbf_design('acceleration', basis, xyz, weights=weights)
     A = At.permute(2, 1, 0).reshape(3 * At.shape[2], At.shape[0])

@@ -404,150 +404,63 @@ def _arc_reduction(G, b):
 
 
 class _Observations:
-    """The observations of one from_* or of_* call.  The constructors below, one per kind, run the checks of their kind on the host and
-    fill the degrees, P, M, K and the layout of the weights (engine.check_observation_weights).  to_device, after every other check of
-    the call, fills l [M, K], the observations times root, root = sqrt(w) [M, K] or [M, 1] (None without weights) and design_block(first,
-    last), the transposed design matrix [P, K, Mb] (or [P, Mb]) of the points first .. last, scaled alike; upload() is the kind's part of
-    it: from the weights on the device, or None, it returns (l [M, K], design_block)."""
+    """The observations of one from_* or of_* call, as _observations checked them on the host: the degrees, P, M, K and the weights with
+    their layout (engine.check_observation_weights).  The per-point arguments stay as the call gave them until to_device; take(order)
+    puts them in another order of the points before that.  to_device, after every other check of the call, fills l [M, K], the
+    observations times root, root = sqrt(w) [M, K] or [M, 1] (None without weights) and design_block(first, last), the transposed design
+    matrix [P, K, Mb] (or [P, Mb]) of the points first .. last, scaled alike: the design call of the kind (engine.OBSERVATION_KINDS) on
+    the slice of every per-point tensor and of the weights."""
 
-    def __init__(self, min_degree, max_degree, M, K, weights, layout, upload):
-        self.min_degree, self.max_degree, self.P = min_degree, max_degree, (max_degree + 1) ** 2 - min_degree ** 2
-        self.M, self.K, self.weights, self.layout = M, K, weights, layout
-        self.__upload = upload
+    def __init__(self, kind, arguments, band, M, K, layout, extra):
+        self.min_degree, self.max_degree, self.P = band.min_degree, band.max_degree, (band.max_degree + 1) ** 2 - band.min_degree ** 2
+        self.M, self.K, self.weights, self.layout = M, K, arguments['weights'], layout
+        self.__kind, self.__arguments, self.__band, self.__extra = kind, arguments, band, extra
         self.l = self.root = self.design_block = None
+
+    def take(self, order):
+        per_point = {name: _take(self.__arguments[name], order) for name in self.__kind.points + ('weights',)}
+        self.__arguments, self.weights = dict(self.__arguments, **per_point), per_point['weights']
 
     def to_device(self):
         torch = engine.require_gpu()
-        w = engine.to_device(self.weights) if self.layout else None
-        l, self.design_block = self.__upload(w)
+        kind, band, extra = self.__kind, self.__band, self.__extra
+        tensors = engine.upload_observations(kind, self.__arguments)
+        l, w = kind.values(tensors.pop(kind.observed), extra), tensors['weights']
+        design = kind.design if band.basis is None else kind.rbf_design
+        self.design_block = lambda first, last: design(band, {name: None if t is None else t[first:last] for name, t in tensors.items()}, extra)
         self.root = torch.sqrt(w if self.layout == 2 else w[:, None]) if self.layout else None
         self.l = l * self.root if self.layout else l
 
 
-def _node_parameters(observations, basis, GM, R):
-    """The observations of a call with basis=...: the parameters are the node values of the gravityfield.RadialBasisFunctions `basis`
-    instead of the coefficients, so P is its node count; the degrees and constants of the call must be the basis's (ValueError
-    otherwise, as for an anisotropic basis: all of it on the host).  Returns the observations."""
-    for name, given, own in (('min_degree', observations.min_degree, int(basis.min_degree)), ('max_degree', observations.max_degree, int(basis.max_degree)),
-                             ('GM', float(GM), float(basis.GM)), ('R', float(R), float(basis.R))):
-        if given != own:
-            raise ValueError('{0} of the call is {1!r} but the basis has {2!r}: pass the values of the basis'.format(name, given, own))
-    basis.degree_factors
-    observations.P = int(basis.point_distribution.longitude.size)
+def _observations(kind, arguments, band):
+    """The record of the observations of a from_* or of_* call: kind names an entry of engine.OBSERVATION_KINDS, arguments is the dict of
+    its per-point arguments, options and weights, band an engine.Band.  check_degrees, then the checks of the kind; with a basis the
+    parameters are the node values of that gravityfield.RadialBasisFunctions instead of the coefficients, so P is its node count, and
+    the degrees and constants of the call must be the basis's (ValueError otherwise, as for an anisotropic basis).  All of it on the
+    host."""
+    kind = engine.OBSERVATION_KINDS[kind]
+    min_degree, max_degree = engine.check_degrees(band.min_degree, band.max_degree)
+    observations = _Observations(kind, arguments, band._replace(min_degree=min_degree, max_degree=max_degree), *kind.check(arguments))
+    basis = band.basis
+    if basis is not None:
+        for name, given, own in (('min_degree', min_degree, int(basis.min_degree)), ('max_degree', max_degree, int(basis.max_degree)),
+                                 ('GM', float(band.GM), float(basis.GM)), ('R', float(band.R), float(basis.R))):
+            if given != own:
+                raise ValueError('{0} of the call is {1!r} but the basis has {2!r}: pass the values of the basis'.format(name, given, own))
+        basis.degree_factors
+        observations.P = int(basis.point_distribution.longitude.size)
     return observations
 
 
-def _acceleration_observations(xyz, g, min_degree, max_degree, GM, R, weights, basis=None):
-    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
-    M = engine.check_positions(xyz)
-    if engine.check_positions(g, 'accelerations') != M:
-        raise ValueError('{0} positions but {1} accelerations'.format(M, int(g.shape[0])))
-    layout = engine.check_observation_weights(weights, M)
-
-    def upload(w):
-        x, l = engine.to_device(xyz), engine.to_device(g)
-        if basis is not None:
-            return l, lambda first, last: engine.rbf_design_checked('acceleration', basis, x[first:last], None, None, None if w is None else w[first:last])
-        return l, lambda first, last: engine.acceleration_design_checked(
-            max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R)
-    observations = _Observations(min_degree, max_degree, M, 3, weights, layout, upload)
-    return observations if basis is None else _node_parameters(observations, basis, GM, R)
-
-
-def _gradient_observations(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights, basis=None):
-    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
-    M = engine.check_positions(xyz)
-    picked = engine.gradient_components(components)
-    K = len(picked)
-    shape = tuple(gradients.shape)
-    full = len(shape) == 3 and shape[1:] == (3, 3)
-    if not full and (len(shape) != 2 or shape[1] != K):
-        raise ValueError('gradients must have shape (M, {0}) or (M, 3, 3), got {1}'.format(K, shape))
-    if shape[0] != M:
-        raise ValueError('{0} positions but {1} gradients'.format(M, shape[0]))
-    layout = engine.check_observation_weights(weights, M, K)
-    if frames is not None:
-        engine.check_frames(frames, M)
-
-    def upload(w):
-        x, l = engine.to_device(xyz), engine.to_device(gradients)
-        f = engine.to_device(frames) if frames is not None else None
-        if full:
-            l = l.reshape(M, 9)[:, [(0, 1, 2, 4, 5, 8)[i] for i in picked]]                              # the selected upper-triangle entries
-        if basis is not None:
-            return l, lambda first, last: engine.rbf_gradient_design_checked(
-                basis, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last])
-        return l, lambda first, last: engine.gradient_design_checked(
-            max_degree, min_degree, x[first:last], None if f is None else f[first:last], picked, None if w is None else w[first:last], GM, R)
-    observations = _Observations(min_degree, max_degree, M, K, weights, layout, upload)
-    return observations if basis is None else _node_parameters(observations, basis, GM, R)
-
-
-def _los_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights, basis=None):
-    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
-    M = engine.check_pair_positions(xyz_a, xyz_b)
-    if len(differences.shape) != 1:
-        raise ValueError('differences must have shape (M,), got {0}'.format(tuple(differences.shape)))
-    if int(differences.shape[0]) != M:
-        raise ValueError('{0} pairs but {1} differences'.format(M, int(differences.shape[0])))
-    layout = engine.check_observation_weights(weights, M, 1)
-    if layout and len(weights.shape) != 1:
-        raise ValueError('weights must have shape ({0},), got {1}'.format(M, tuple(weights.shape)))
-    if directions is not None:
-        engine.check_directions(directions, M)
-    else:
-        engine.check_pairs_apart(xyz_a, xyz_b)
-
-    def upload(w):
-        a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
-        e = engine.to_device(directions) if directions is not None else None
-        if basis is not None:
-            return l, lambda first, last: engine.rbf_design_checked(
-                'line_of_sight', basis, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last])
-        return l, lambda first, last: engine.los_design_checked(
-            max_degree, min_degree, a[first:last], b[first:last], None if e is None else e[first:last], None if w is None else w[first:last], GM, R)
-    observations = _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
-    return observations if basis is None else _node_parameters(observations, basis, GM, R)
-
-
-def _check_scalar_observations(values, M, name, unit):
-    """one observed value per point (pair): `name` [M]"""
-    if len(values.shape) != 1:
-        raise ValueError('{0} must have shape (M,), got {1}'.format(name, tuple(values.shape)))
-    if int(values.shape[0]) != M:
-        raise ValueError('{0} {1} but {2} {3}'.format(M, unit, int(values.shape[0]), name))
-
-
-def _potential_observations(xyz, potentials, min_degree, max_degree, GM, R, weights, basis=None):
-    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
-    M = engine.check_positions(xyz)
-    _check_scalar_observations(potentials, M, 'potentials', 'positions')
-    layout = engine.check_point_weights(weights, M)
-
-    def upload(w):
-        x, l = engine.to_device(xyz), engine.to_device(potentials).reshape(-1, 1)
-        if basis is not None:
-            return l, lambda first, last: engine.rbf_design_checked('potential', basis, x[first:last], None, None, None if w is None else w[first:last])
-        return l, lambda first, last: engine.potential_design_checked(max_degree, min_degree, x[first:last], None if w is None else w[first:last], GM, R)
-    observations = _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
-    return observations if basis is None else _node_parameters(observations, basis, GM, R)
-
-
-def _potential_difference_observations(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights, basis=None):
-    min_degree, max_degree = engine.check_degrees(min_degree, max_degree)
-    M = engine.check_pair_positions(xyz_a, xyz_b)
-    _check_scalar_observations(differences, M, 'differences', 'pairs')
-    layout = engine.check_point_weights(weights, M)
-
-    def upload(w):
-        a, b, l = engine.to_device(xyz_a), engine.to_device(xyz_b), engine.to_device(differences).reshape(-1, 1)
-        if basis is not None:
-            return l, lambda first, last: engine.rbf_design_checked(
-                'potential_difference', basis, a[first:last], b[first:last], None, None if w is None else w[first:last])
-        return l, lambda first, last: engine.potential_difference_design_checked(
-            max_degree, min_degree, a[first:last], b[first:last], None if w is None else w[first:last], GM, R)
-    observations = _Observations(min_degree, max_degree, M, 1, weights, layout, upload)
-    return observations if basis is None else _node_parameters(observations, basis, GM, R)
+def _route(kind, arguments, band, model, block_points, temporal=None, fit=None):
+    """Every public from_* and of_*: the observations of the kind, under model (None, a ColouredNoise, an ArcParameters or a
+    _StochasticModel), in blocks of block_points; temporal is the TemporalParameters of the call, whose _Windows puts the points in
+    its order before the upload, fit the PostFit of an of_* call.  Returns the NormalEquations, or the PostFit after its pass."""
+    observations, model = _observations(kind, arguments, band), _StochasticModel.of(model)
+    windows = None if temporal is None else _Windows(temporal, observations)
+    if fit is None:
+        return NormalEquations._normals(observations, model, block_points, windows)
+    return fit._pass(observations, model, block_points, windows)
 
 
 class _StochasticModel:
@@ -562,6 +475,8 @@ class _StochasticModel:
 
     @classmethod
     def of(cls, model):
+        if isinstance(model, cls):
+            return model
         if isinstance(model, _BoundModel):
             return cls(model.noise_model, model.arcs, model if isinstance(model, ArcParameters) else None)
         if model is None:
@@ -629,6 +544,12 @@ def _design_blocks(observations, model, block_points):
             At = model.whiten(plain, start, first - start).reshape(P, K * (last - first))
             lb = model.whiten(l[start:last].t().contiguous(), start, first - start).reshape(-1, 1)
             yield first, last, At, lb, plain.reshape(P, K * (last - start)), first - start
+
+
+def _mirror_upper(N):
+    """the upper triangle of N [P, P], of which both were computed, onto the lower one: N is exactly symmetric afterwards"""
+    N.triu_()
+    N.add_(engine._torch().triu(N, 1).t())
 
 
 MAX_TEMPORAL_SLOTS = engine.WINDOW_SLOTS      # of shg_window_expand: the fields one block of points may span
@@ -1195,8 +1116,9 @@ class NormalEquations:
 
     @classmethod
     def default_block_points(cls, parameters, components):
-        """Default block of from_accelerations (3 components), from_gradients (K) and from_line_of_sight (1): the largest multiple
-        of 256 points that keeps At [parameters, components Mb] within DESIGN_BLOCK_BYTES, at least 256."""
+        """Default block of every from_* and of_* (3 components for accelerations, K for gradients, 1 for the line of sight, potentials
+        and potential differences): the largest multiple of 256 points that keeps At [parameters, components Mb] within
+        DESIGN_BLOCK_BYTES, at least 256."""
         return max(cls.DESIGN_BLOCK_BYTES // (8 * components * parameters) // 256 * 256, 256)
 
     @classmethod
@@ -1221,8 +1143,7 @@ class NormalEquations:
                 sweep.block(first, last, At)
         if sweep is not None:
             sweep.flush()
-        normals.triu_()
-        normals.add_(torch.triu(normals, 1).t())
+        _mirror_upper(normals)
         matrix = BlockMatrix([0, P], [0, P])
         matrix._set_device(0, 0, normals)
         system = cls(matrix, side, float(square_sum.item()), observations.K * observations.M)
@@ -1265,8 +1186,7 @@ class NormalEquations:
         matrix = BlockMatrix(block_index, block_index)
         for (row, column), block in sorted(blocks.items()):
             if row == column:
-                block.triu_()
-                block.add_(torch.triu(block, 1).t())
+                _mirror_upper(block)
             matrix._set_device(row, column, block)
         return cls(matrix, side, float(square_sum.item()), observations.K * observations.M)
 
@@ -1292,14 +1212,14 @@ class NormalEquations:
         meaning and scale the rows by sqrt(w) before the whitening, so the weight matrix in effect is D^1/2 W^T W D^1/2.  block_points
         keeps its default: a block takes up to q points in front of it along as history, the whitened copy doubles the peak memory of
         a block, and observation_count is unchanged.  noise_model=None changes nothing; arcs without it is a ValueError.
-        ColouredNoise(noise_model, arcs) offers the same for all three kinds of observation; ArcParameters(basis, arcs, noise_model)
+        ColouredNoise(noise_model, arcs) offers the same for all five kinds of observation; ArcParameters(basis, arcs, noise_model)
         also eliminates parameters that last one arc (biases, drifts, once-per-revolution terms).
 
         Returns NormalEquations with a one-block BlockMatrix [P, P] and the right-hand side [P, 1] on the device, and
         observation_count = 3 M: components of zero weight still count as observations.
         """
-        observations = _acceleration_observations(xyz=xyz, g=g, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
-        return cls._normals(observations, _StochasticModel(noise_model, arcs), block_points)
+        return _route('accelerations', dict(xyz=xyz, g=g, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), _StochasticModel(noise_model, arcs), block_points)
 
     @classmethod
     def from_gradients(cls, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
@@ -1321,9 +1241,8 @@ class NormalEquations:
         noise), every arc decorrelated on its own as in from_accelerations.  A data gap is a new arc, not a zero weight; block_points
         keeps its default, the peak memory of a block doubles and observation_count is unchanged.
         """
-        observations = _gradient_observations(xyz=xyz, gradients=gradients, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, frames=frames,
-                                              components=components, weights=weights)
-        return cls._normals(observations, _StochasticModel(), block_points)
+        return _route('gradients', dict(xyz=xyz, gradients=gradients, frames=frames, components=components, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), None, block_points)
 
     @classmethod
     def from_line_of_sight(cls, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
@@ -1345,9 +1264,8 @@ class NormalEquations:
         from_accelerations.  A data gap is a new arc, not a zero weight; block_points keeps its default, the peak memory of a block
         doubles and observation_count is unchanged.
         """
-        observations = _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
-                                         directions=directions, weights=weights)
-        return cls._normals(observations, _StochasticModel(), block_points)
+        return _route('line_of_sight', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), None, block_points)
 
     @classmethod
     def from_potentials(cls, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
@@ -1366,8 +1284,8 @@ class NormalEquations:
         256 points that keeps At within 256 MB, at least 256.  Returns NormalEquations with a one-block BlockMatrix [P, P] and the
         right-hand side [P, 1] on the device, and observation_count = M.  Normals of the same degrees add up through accumulate_normals.
         """
-        observations = _potential_observations(xyz=xyz, potentials=potentials, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
-        return cls._normals(observations, _StochasticModel(), block_points)
+        return _route('potentials', dict(xyz=xyz, potentials=potentials, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), None, block_points)
 
     @classmethod
     def from_potential_differences(cls, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None,
@@ -1384,9 +1302,8 @@ class NormalEquations:
         from_potentials.  Returns NormalEquations with a one-block BlockMatrix [P, P] and the right-hand side [P, 1] on the device, and
         observation_count = M.
         """
-        observations = _potential_difference_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree,
-                                                          max_degree=max_degree, GM=GM, R=R, weights=weights)
-        return cls._normals(observations, _StochasticModel(), block_points)
+        return _route('potential_differences', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), None, block_points)
 
     def __cholesky(self):
         """factor the matrix once; a matrix that already holds covariances cannot be factored again (ValueError, as upstream)"""
@@ -1473,42 +1390,39 @@ class TikhonovRegularization(NormalEquations):
 
 
 class _BoundModel:
-    """the from_* of ColouredNoise and ArcParameters: the arguments of the classmethods of NormalEquations, the normals under this model"""
+    """the from_* of ColouredNoise and ArcParameters, one per kind of observation: the arguments of the classmethods of NormalEquations,
+    the normals under this model"""
 
     def from_accelerations(self, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
-        observations = _acceleration_observations(xyz=xyz, g=g, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
-        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+        return _route('accelerations', dict(xyz=xyz, g=g, weights=weights), engine.Band(min_degree, max_degree, GM, R), self, block_points)
 
     def from_gradients(self, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
                        weights=None, block_points=None):
-        observations = _gradient_observations(xyz=xyz, gradients=gradients, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, frames=frames,
-                                              components=components, weights=weights)
-        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+        return _route('gradients', dict(xyz=xyz, gradients=gradients, frames=frames, components=components, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self, block_points)
 
     def from_line_of_sight(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
                            weights=None, block_points=None):
-        observations = _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
-                                         directions=directions, weights=weights)
-        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+        return _route('line_of_sight', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self, block_points)
 
     def from_potentials(self, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
-        observations = _potential_observations(xyz=xyz, potentials=potentials, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
-        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+        return _route('potentials', dict(xyz=xyz, potentials=potentials, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self, block_points)
 
     def from_potential_differences(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None,
                                    block_points=None):
-        observations = _potential_difference_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree,
-                                                          max_degree=max_degree, GM=GM, R=R, weights=weights)
-        return NormalEquations._normals(observations, _StochasticModel.of(self), block_points)
+        return _route('potential_differences', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self, block_points)
 
 
 class ColouredNoise(_BoundModel):
     """
     A noise model of the observations along the series of points, bound to the constructors of NormalEquations: noise_model is one
     scalar AutoregressiveModelSequence (shared by the components) or a sequence of them, one per component, arcs the start indices of
-    the arcs (default: one arc), as NormalEquations.from_accelerations describes them.  from_accelerations, from_gradients and
-    from_line_of_sight take the arguments of the classmethods of the same name and return the NormalEquations of the decorrelated
-    observations.  The model is checked here (whitening_taps), the arcs against the number of points in every call; all of it before
+    the arcs (default: one arc), as NormalEquations.from_accelerations describes them.  from_accelerations, from_gradients,
+    from_line_of_sight, from_potentials and from_potential_differences take the arguments of the classmethods of the same name and
+    return the NormalEquations of the decorrelated observations.  The model is checked here (whitening_taps), the arcs against the number of points in every call; all of it before
     anything reaches the device.
     """
 
@@ -1527,8 +1441,8 @@ class ArcParameters(_BoundModel):
     indices of the arcs (default: one arc); noise_model is that of ColouredNoise, with the same arcs.  The basis goes the way of
     the design matrix: times sqrt(w), then the arc's W.
 
-    from_accelerations, from_gradients and from_line_of_sight take the arguments of the classmethods of the same name and return the
-    NormalEquations of the coefficients alone, N = A^T A - sum_a C_a G_a^+ C_a^T with C_a = A_a^T B_a, G_a = B_a^T B_a (n and l^T P l
+    from_accelerations, from_gradients, from_line_of_sight, from_potentials and from_potential_differences take the arguments of the
+    classmethods of the same name and return the NormalEquations of the coefficients alone, N = A^T A - sum_a C_a G_a^+ C_a^T with C_a = A_a^T B_a, G_a = B_a^T B_a (n and l^T P l
     alike), with observation_count reduced by the sum of the ranks of the G_a: posterior_sigma, redundancy and
     compute_variance_factors see the redundancy of the eliminated system.  Directions of G_a with eigenvalues at or below 1e-12 of the
     largest are dropped (an arc shorter than u', an arc of zero weights).  ne.arc_elimination (ArcElimination) holds the ranks and,
@@ -1573,60 +1487,43 @@ class RadialBasisParameters:
         basis.degree_factors
         self.basis, self.model = basis, model
 
-    def __band(self):
-        basis = self.basis
-        return dict(min_degree=basis.min_degree, max_degree=basis.max_degree, GM=basis.GM, R=basis.R, basis=basis)
-
-    def __accelerations(self, xyz, g, weights):
-        return _acceleration_observations(xyz=xyz, g=g, weights=weights, **self.__band())
-
-    def __gradients(self, xyz, gradients, frames, components, weights):
-        return _gradient_observations(xyz=xyz, gradients=gradients, frames=frames, components=components, weights=weights, **self.__band())
-
-    def __line_of_sight(self, xyz_a, xyz_b, differences, directions, weights):
-        return _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights, **self.__band())
-
-    def __potentials(self, xyz, potentials, weights):
-        return _potential_observations(xyz=xyz, potentials=potentials, weights=weights, **self.__band())
-
-    def __potential_differences(self, xyz_a, xyz_b, differences, weights):
-        return _potential_difference_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, weights=weights, **self.__band())
-
-    def __normals(self, observations, block_points):
-        return NormalEquations._normals(observations, _StochasticModel.of(self.model), block_points)
-
     def from_accelerations(self, xyz, g, weights=None, block_points=None):
-        return self.__normals(self.__accelerations(xyz, g, weights), block_points)
+        return _route('accelerations', dict(xyz=xyz, g=g, weights=weights), engine.basis_band(self.basis), self.model, block_points)
 
     def from_gradients(self, xyz, gradients, frames=None, components=None, weights=None, block_points=None):
-        return self.__normals(self.__gradients(xyz, gradients, frames, components, weights), block_points)
+        return _route('gradients', dict(xyz=xyz, gradients=gradients, frames=frames, components=components, weights=weights),
+                      engine.basis_band(self.basis), self.model, block_points)
 
     def from_line_of_sight(self, xyz_a, xyz_b, differences, directions=None, weights=None, block_points=None):
-        return self.__normals(self.__line_of_sight(xyz_a, xyz_b, differences, directions, weights), block_points)
+        return _route('line_of_sight', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights),
+                      engine.basis_band(self.basis), self.model, block_points)
 
     def from_potentials(self, xyz, potentials, weights=None, block_points=None):
-        return self.__normals(self.__potentials(xyz, potentials, weights), block_points)
+        return _route('potentials', dict(xyz=xyz, potentials=potentials, weights=weights), engine.basis_band(self.basis), self.model, block_points)
 
     def from_potential_differences(self, xyz_a, xyz_b, differences, weights=None, block_points=None):
-        return self.__normals(self.__potential_differences(xyz_a, xyz_b, differences, weights), block_points)
+        return _route('potential_differences', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, weights=weights),
+                      engine.basis_band(self.basis), self.model, block_points)
 
     def of_accelerations(self, solution, xyz, g, weights=None, block_points=None, vectors=None):
-        return PostFit._of_observations(solution, vectors, self.model, xyz, lambda: self.__accelerations(xyz, g, weights), block_points)
+        return _route('accelerations', dict(xyz=xyz, g=g, weights=weights),
+                      engine.basis_band(self.basis), self.model, block_points, fit=PostFit(solution, vectors, self.model, xyz))
 
     def of_gradients(self, solution, xyz, gradients, frames=None, components=None, weights=None, block_points=None, vectors=None):
-        return PostFit._of_observations(solution, vectors, self.model, xyz,
-                                        lambda: self.__gradients(xyz, gradients, frames, components, weights), block_points)
+        return _route('gradients', dict(xyz=xyz, gradients=gradients, frames=frames, components=components, weights=weights),
+                      engine.basis_band(self.basis), self.model, block_points, fit=PostFit(solution, vectors, self.model, xyz))
 
     def of_line_of_sight(self, solution, xyz_a, xyz_b, differences, directions=None, weights=None, block_points=None, vectors=None):
-        return PostFit._of_observations(solution, vectors, self.model, xyz_a,
-                                        lambda: self.__line_of_sight(xyz_a, xyz_b, differences, directions, weights), block_points)
+        return _route('line_of_sight', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights),
+                      engine.basis_band(self.basis), self.model, block_points, fit=PostFit(solution, vectors, self.model, xyz_a))
 
     def of_potentials(self, solution, xyz, potentials, weights=None, block_points=None, vectors=None):
-        return PostFit._of_observations(solution, vectors, self.model, xyz, lambda: self.__potentials(xyz, potentials, weights), block_points)
+        return _route('potentials', dict(xyz=xyz, potentials=potentials, weights=weights),
+                      engine.basis_band(self.basis), self.model, block_points, fit=PostFit(solution, vectors, self.model, xyz))
 
     def of_potential_differences(self, solution, xyz_a, xyz_b, differences, weights=None, block_points=None, vectors=None):
-        return PostFit._of_observations(solution, vectors, self.model, xyz_a,
-                                        lambda: self.__potential_differences(xyz_a, xyz_b, differences, weights), block_points)
+        return _route('potential_differences', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, weights=weights),
+                      engine.basis_band(self.basis), self.model, block_points, fit=PostFit(solution, vectors, self.model, xyz_a))
 
 
 def _check_windows(first, factors, fields):
@@ -1669,20 +1566,18 @@ def _take(values, order):
 class _Windows:
     """The window model of one from_* or of_* call under a TemporalParameters, for M points: first and factors in the order the call
     works in, W, B and `order`, the stable sort by `first` that a call without a noise model applies where first decreases somewhere
-    (None otherwise; take() applies it to a per-point argument, restore() puts the last axis of a result back).  plan() fills blocks
-    (temporal_blocks) on the host, to_device() the factors on the device."""
+    (None otherwise; it is applied to the per-point arguments of the observations here, before their upload, and restore() puts the last
+    axis of a result back).  plan() fills blocks (temporal_blocks) on the host, to_device() the factors on the device."""
 
-    def __init__(self, temporal, M):
-        if temporal.first.shape[0] != M:
-            raise ValueError('{0} points but the temporal parameters hold the windows of {1}'.format(M, temporal.first.shape[0]))
+    def __init__(self, temporal, observations):
+        if temporal.first.shape[0] != observations.M:
+            raise ValueError('{0} points but the temporal parameters hold the windows of {1}'.format(observations.M, temporal.first.shape[0]))
         self.first, self.factors, self.B, self.W = temporal.first, temporal.factors, temporal.field_count, int(temporal.factors.shape[1])
         self.order = None if temporal.model is not None else engine.points_at_plan(self.first)[0]
         if self.order is not None:
             self.first, self.factors = self.first[self.order], np.ascontiguousarray(self.factors[self.order])
+            observations.take(self.order)
         self.blocks = self.device_factors = None
-
-    def take(self, values):
-        return _take(values, self.order)
 
     def restore(self, sorted_values):
         torch = engine._torch()
@@ -1821,95 +1716,62 @@ class TemporalParameters:
             raise ValueError('the solution must have shape (B P,) or (B P, 1) with B = {0}, got {1}'.format(self.field_count, tuple(x.shape)))
         return x.reshape(self.field_count, size // self.field_count)
 
-    def __windows(self, build):
-        """(observations, windows) of a call: build(take) makes the record of the observations from the per-point arguments as take
-        returns them -- first as given, for the checks of the kind, then sorted where the call sorts"""
-        observations = build(lambda values: values)
-        windows = _Windows(self, observations.M)
-        return (observations if windows.order is None else build(windows.take)), windows
-
-    def __normals(self, build, block_points):
-        observations, windows = self.__windows(build)
-        return NormalEquations._normals(observations, _StochasticModel.of(self.model), block_points, windows)
-
-    def __post_fit(self, solution, vectors, template, build, block_points):
-        observations, windows = self.__windows(build)
-        return PostFit._of_observations(solution, vectors, self.model, template, lambda: observations, block_points, windows)
-
-    @staticmethod
-    def __accelerations(xyz, g, min_degree, max_degree, GM, R, weights):
-        return lambda take: _acceleration_observations(xyz=take(xyz), g=take(g), min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
-                                                       weights=take(weights))
-
-    @staticmethod
-    def __gradients(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights):
-        return lambda take: _gradient_observations(xyz=take(xyz), gradients=take(gradients), min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
-                                                   frames=take(frames), components=components, weights=take(weights))
-
-    @staticmethod
-    def __line_of_sight(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights):
-        return lambda take: _los_observations(xyz_a=take(xyz_a), xyz_b=take(xyz_b), differences=take(differences), min_degree=min_degree,
-                                              max_degree=max_degree, GM=GM, R=R, directions=take(directions), weights=take(weights))
-
-    @staticmethod
-    def __potentials(xyz, potentials, min_degree, max_degree, GM, R, weights):
-        return lambda take: _potential_observations(xyz=take(xyz), potentials=take(potentials), min_degree=min_degree, max_degree=max_degree, GM=GM,
-                                                    R=R, weights=take(weights))
-
-    @staticmethod
-    def __potential_differences(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights):
-        return lambda take: _potential_difference_observations(xyz_a=take(xyz_a), xyz_b=take(xyz_b), differences=take(differences),
-                                                               min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=take(weights))
-
     def from_accelerations(self, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
-        return self.__normals(self.__accelerations(xyz, g, min_degree, max_degree, GM, R, weights), block_points)
+        return _route('accelerations', dict(xyz=xyz, g=g, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self)
 
     def from_gradients(self, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
                        weights=None, block_points=None):
-        return self.__normals(self.__gradients(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights), block_points)
+        return _route('gradients', dict(xyz=xyz, gradients=gradients, frames=frames, components=components, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self)
 
     def from_line_of_sight(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
                            weights=None, block_points=None):
-        return self.__normals(self.__line_of_sight(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights), block_points)
+        return _route('line_of_sight', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self)
 
     def from_potentials(self, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None):
-        return self.__normals(self.__potentials(xyz, potentials, min_degree, max_degree, GM, R, weights), block_points)
+        return _route('potentials', dict(xyz=xyz, potentials=potentials, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self)
 
     def from_potential_differences(self, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None,
                                    block_points=None):
-        return self.__normals(self.__potential_differences(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights), block_points)
+        return _route('potential_differences', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self)
 
     def of_accelerations(self, solution, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
                          vectors=None):
-        return self.__post_fit(solution, vectors, xyz, self.__accelerations(xyz, g, min_degree, max_degree, GM, R, weights), block_points)
+        return _route('accelerations', dict(xyz=xyz, g=g, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self, PostFit(solution, vectors, self.model, xyz))
 
     def of_gradients(self, solution, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
                      weights=None, block_points=None, vectors=None):
-        return self.__post_fit(solution, vectors, xyz, self.__gradients(xyz, gradients, min_degree, max_degree, GM, R, frames, components, weights),
-                               block_points)
+        return _route('gradients', dict(xyz=xyz, gradients=gradients, frames=frames, components=components, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self, PostFit(solution, vectors, self.model, xyz))
 
     def of_line_of_sight(self, solution, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
                          weights=None, block_points=None, vectors=None):
-        return self.__post_fit(solution, vectors, xyz_a,
-                               self.__line_of_sight(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, directions, weights), block_points)
+        return _route('line_of_sight', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self, PostFit(solution, vectors, self.model, xyz_a))
 
     def of_potentials(self, solution, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None,
                       block_points=None, vectors=None):
-        return self.__post_fit(solution, vectors, xyz, self.__potentials(xyz, potentials, min_degree, max_degree, GM, R, weights), block_points)
+        return _route('potentials', dict(xyz=xyz, potentials=potentials, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self, PostFit(solution, vectors, self.model, xyz))
 
     def of_potential_differences(self, solution, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06,
                                  weights=None, block_points=None, vectors=None):
-        return self.__post_fit(solution, vectors, xyz_a,
-                               self.__potential_differences(xyz_a, xyz_b, differences, min_degree, max_degree, GM, R, weights), block_points)
+        return _route('potential_differences', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), self.model, block_points, self, PostFit(solution, vectors, self.model, xyz_a))
 
 
 class PostFit:
     """
     What a solution says about the stochastic model it was computed under: the residuals of the observations, the square sum, the
     redundancy and the variance factor of every arc, and the empirical covariance function of the residuals, from one more pass over
-    the blocks of the design matrix.  of_accelerations, of_gradients and of_line_of_sight take the solution
-    [P] or [P, 1] (host or device), then the arguments of NormalEquations.from_accelerations / from_gradients / from_line_of_sight with
-    the same checks, then
+    the blocks of the design matrix.  of_accelerations, of_gradients, of_line_of_sight, of_potentials and
+    of_potential_differences take the solution [P] or [P, 1] (host or device), then the arguments of the from_* of NormalEquations for
+    the same kind with the same checks, then
 
     model   : None (white noise), the ColouredNoise or the ArcParameters the system was built with,
     vectors : [P, S], optional: the Monte-Carlo vectors of the solved (combined) system, ne.monte_carlo_vectors.
@@ -1935,52 +1797,38 @@ class PostFit:
     """
 
     def __init__(self, solution, vectors, model, template):
-        self.__model, self.__solution, self.__vectors, self.__template = _StochasticModel.of(model), solution, vectors, template
+        _StochasticModel.of(model)
+        self.__solution, self.__vectors, self.__template = solution, vectors, template
 
     @classmethod
     def of_accelerations(cls, solution, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
                          model=None, vectors=None):
-        fit = cls(solution, vectors, model, xyz)
-        observations = _acceleration_observations(xyz=xyz, g=g, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
-        return fit._pass(observations, fit.__model, block_points)
+        return _route('accelerations', dict(xyz=xyz, g=g, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), model, block_points, fit=cls(solution, vectors, model, xyz))
 
     @classmethod
     def of_gradients(cls, solution, xyz, gradients, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, frames=None, components=None,
                      weights=None, block_points=None, model=None, vectors=None):
-        fit = cls(solution, vectors, model, xyz)
-        observations = _gradient_observations(xyz=xyz, gradients=gradients, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, frames=frames,
-                                              components=components, weights=weights)
-        return fit._pass(observations, fit.__model, block_points)
+        return _route('gradients', dict(xyz=xyz, gradients=gradients, frames=frames, components=components, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), model, block_points, fit=cls(solution, vectors, model, xyz))
 
     @classmethod
     def of_line_of_sight(cls, solution, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, directions=None,
                          weights=None, block_points=None, model=None, vectors=None):
-        fit = cls(solution, vectors, model, xyz_a)
-        observations = _los_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R,
-                                         directions=directions, weights=weights)
-        return fit._pass(observations, fit.__model, block_points)
+        return _route('line_of_sight', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, directions=directions, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), model, block_points, fit=cls(solution, vectors, model, xyz_a))
 
     @classmethod
     def of_potentials(cls, solution, xyz, potentials, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
                       model=None, vectors=None):
-        fit = cls(solution, vectors, model, xyz)
-        observations = _potential_observations(xyz=xyz, potentials=potentials, min_degree=min_degree, max_degree=max_degree, GM=GM, R=R, weights=weights)
-        return fit._pass(observations, fit.__model, block_points)
+        return _route('potentials', dict(xyz=xyz, potentials=potentials, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), model, block_points, fit=cls(solution, vectors, model, xyz))
 
     @classmethod
     def of_potential_differences(cls, solution, xyz_a, xyz_b, differences, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06,
                                  weights=None, block_points=None, model=None, vectors=None):
-        fit = cls(solution, vectors, model, xyz_a)
-        observations = _potential_difference_observations(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, min_degree=min_degree,
-                                                          max_degree=max_degree, GM=GM, R=R, weights=weights)
-        return fit._pass(observations, fit.__model, block_points)
-
-    @classmethod
-    def _of_observations(cls, solution, vectors, model, template, build, block_points, windows=None):
-        """an of_* call on the observations that build() returns (the record of another parameterisation: RadialBasisParameters, and
-        TemporalParameters with the _Windows of the call)"""
-        fit = cls(solution, vectors, model, template)
-        return fit._pass(build(), fit.__model, block_points, windows)
+        return _route('potential_differences', dict(xyz_a=xyz_a, xyz_b=xyz_b, differences=differences, weights=weights),
+                      engine.Band(min_degree, max_degree, GM, R), model, block_points, fit=cls(solution, vectors, model, xyz_a))
 
     def _check(self, parameters):
         """the solution and the vectors against the number of parameters: ValueError before anything reaches the device"""
@@ -2049,7 +1897,7 @@ class PostFit:
         self.rows = V
         self.whitened = _like_input(V[0].t().contiguous(), self.__template)
         self.residuals = _like_input(plain.t().contiguous(), self.__template)
-        self.__solution = self.__vectors = self.__model = None
+        self.__solution = self.__vectors = None
         return self
 
     def arc_redundancies(self, variance_factor=1.0):

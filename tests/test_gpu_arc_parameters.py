@@ -220,7 +220,7 @@ def test_reduced_normals_of_accelerations(block_points, noise):
     assert _same(_build_accelerations(block_points, noise), ne)                                    # two runs are bitwise equal
     assert _same(_build_accelerations(block_points, noise, keep=False), ne)
     internal = ga.lstsq.NormalEquations._normals(
-        ga.lstsq._acceleration_observations(xyz=xyz, g=obs, min_degree=0, max_degree=NA, GM=di.GM, R=di.R, weights=w),
+        ga.lstsq._observations('accelerations', dict(xyz=xyz, g=obs, weights=w), ga.engine.Band(0, NA, di.GM, di.R)),
         ga.lstsq._StochasticModel(model if noise else None, ARCS, ga.lstsq.ArcParameters(basis)), block_points)
     assert _same(internal, ne)                                                                     # the bound form is the internal path
     plain = ga.lstsq.NormalEquations.from_accelerations(xyz, obs, 0, NA, di.GM, di.R, weights=w, block_points=block_points,

@@ -124,10 +124,13 @@ def test_basis_mismatch_is_refused_before_the_device():
     a, b = ri.pairs('b2_8')
     M = a.shape[0]
     lstsq = ga.lstsq
-    builders = (lambda **kw: lstsq._acceleration_observations(xyz=a, g=np.zeros((M, 3)), weights=None, basis=basis, **kw),
-                lambda **kw: lstsq._los_observations(xyz_a=a, xyz_b=b, differences=np.zeros(M), directions=ri.directions('b2_8'), weights=None, basis=basis, **kw),
-                lambda **kw: lstsq._potential_observations(xyz=a, potentials=np.zeros(M), weights=None, basis=basis, **kw),
-                lambda **kw: lstsq._potential_difference_observations(xyz_a=a, xyz_b=b, differences=np.zeros(M), weights=None, basis=basis, **kw))
+    Band = ga.engine.Band
+    builders = (lambda **kw: lstsq._observations('accelerations', dict(xyz=a, g=np.zeros((M, 3)), weights=None), Band(basis=basis, **kw)),
+                lambda **kw: lstsq._observations('line_of_sight', dict(xyz_a=a, xyz_b=b, differences=np.zeros(M), directions=ri.directions('b2_8'),
+                                                                       weights=None), Band(basis=basis, **kw)),
+                lambda **kw: lstsq._observations('potentials', dict(xyz=a, potentials=np.zeros(M), weights=None), Band(basis=basis, **kw)),
+                lambda **kw: lstsq._observations('potential_differences', dict(xyz_a=a, xyz_b=b, differences=np.zeros(M), weights=None),
+                                                 Band(basis=basis, **kw)))
     good = dict(min_degree=2, max_degree=8, GM=GM, R=R)
     for build in builders:
         observations = build(**good)
@@ -137,7 +140,7 @@ def test_basis_mismatch_is_refused_before_the_device():
                 build(**dict(good, **{name: value}))
             own = {'min_degree': '2', 'max_degree': '8', 'GM': repr(GM), 'R': repr(R)}[name]
             assert name in str(err.value) and shown in str(err.value) and own in str(err.value)      # both values are named
-    plain = lstsq._acceleration_observations(xyz=a, g=np.zeros((M, 3)), weights=None, **good)
+    plain = lstsq._observations('accelerations', dict(xyz=a, g=np.zeros((M, 3)), weights=None), Band(**good))
     assert plain.P == 81 - 4
 
 
@@ -202,9 +205,9 @@ def test_signatures():
     assert names(gf.rbf_line_of_sight_design_matrix) == ['basis', 'xyz_a', 'xyz_b', 'directions', 'weights', 'as_tensor']
     assert names(gf.rbf_potential_design_matrix) == ['basis', 'xyz', 'weights', 'as_tensor']
     assert names(gf.rbf_potential_difference_design_matrix) == ['basis', 'xyz_a', 'xyz_b', 'weights', 'as_tensor']
-    for name in ('_acceleration_observations', '_los_observations', '_potential_observations', '_potential_difference_observations'):
-        last = list(inspect.signature(getattr(lstsq, name)).parameters.values())[-1]
-        assert (last.name, last.default) == ('basis', None)
+    assert names(lstsq._observations) == ['kind', 'arguments', 'band']                 # one builder for every kind; the basis is the band's
+    last = list(inspect.signature(engine.Band).parameters.values())[-1]
+    assert (last.name, last.default) == ('basis', None)
     assert names(lstsq.RadialBasisParameters) == ['basis', 'model']
     tail = ['weights', 'block_points']
     bound, field = lstsq.RadialBasisParameters, gf.PotentialCoefficients

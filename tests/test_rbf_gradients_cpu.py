@@ -87,7 +87,7 @@ def test_signatures():
     assert names(engine.rbf_gradient_design_checked) == ['basis', 'x', 'frames', 'picked', 'weights'] and not defaults(engine.rbf_gradient_design_checked)
     assert names(gf.rbf_gradient_design_matrix) == ['basis', 'xyz', 'frames', 'components', 'weights', 'as_tensor']
     assert defaults(gf.rbf_gradient_design_matrix) == [None, None, None, False]
-    last = list(inspect.signature(lstsq._gradient_observations).parameters.values())[-1]
+    last = list(inspect.signature(engine.Band).parameters.values())[-1]
     assert (last.name, last.default) == ('basis', None)
     bound = lstsq.RadialBasisParameters
     assert names(bound.from_gradients) == ['self', 'xyz', 'gradients', 'frames', 'components', 'weights', 'block_points']
@@ -161,8 +161,8 @@ def test_basis_mismatch_is_refused_before_the_device():
     M = xyz.shape[0]
 
     def build(**kw):
-        return ga.lstsq._gradient_observations(xyz=xyz, gradients=np.zeros((M, 4)), frames=rg.frames(M), components=rg.LOOP_COMPONENTS, weights=None,
-                                               basis=basis, **kw)
+        return ga.lstsq._observations('gradients', dict(xyz=xyz, gradients=np.zeros((M, 4)), frames=rg.frames(M), components=rg.LOOP_COMPONENTS,
+                                                        weights=None), ga.engine.Band(basis=basis, **kw))
     good = dict(min_degree=2, max_degree=8, GM=GM, R=R)
     observations = build(**good)
     assert observations.P == 24 and observations.K == 4 and observations.design_block is None      # nothing uploaded yet
@@ -171,7 +171,8 @@ def test_basis_mismatch_is_refused_before_the_device():
             build(**dict(good, **{name: value}))
         own = {'min_degree': '2', 'max_degree': '8', 'GM': repr(GM), 'R': repr(R)}[name]
         assert name in str(err.value) and shown in str(err.value) and own in str(err.value)      # both values are named
-    plain = ga.lstsq._gradient_observations(xyz=xyz, gradients=np.zeros((M, 6)), frames=None, components=None, weights=None, **good)
+    plain = ga.lstsq._observations('gradients', dict(xyz=xyz, gradients=np.zeros((M, 6)), frames=None, components=None, weights=None),
+                                   ga.engine.Band(**good))
     assert plain.P == 81 - 4
 
 
