@@ -148,6 +148,7 @@ PROTOTYPES = {
                         ctypes.c_int, ctypes.c_void_p],
     'shg_rbf_surface_info': [ctypes.POINTER(ctypes.c_int)],
     'shg_column_dots': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
+    'shg_leverages': [ctypes.c_int, ctypes.c_longlong, c_double_p, ctypes.c_int, c_double_p, ctypes.c_longlong, c_double_p, ctypes.c_void_p],
     'shg_whiten_rows': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, c_double_p, ctypes.c_int,
                         ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p],
     'shg_segment_products': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, c_double_p, ctypes.c_longlong, ctypes.c_int,

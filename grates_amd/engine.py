@@ -1400,6 +1400,32 @@ def column_dots(X, Y):
     return out
 
 
+def leverages(Ui, X, out=None):
+    """out [cols] (device) with out[j] = |Ui^T x_j|^2 for the columns x_j of the float64 device tensor X [n, cols] and the upper
+    triangular Ui [n, n] = U^-1 of a Cholesky factor N = U^T U, as trtri returns it: x_j^T N^-1 x_j, the leverage of the
+    observation whose whitened, weighted row of the design matrix is x_j (shg_leverages).  Ui^T X is formed on the fp64 MFMA and
+    never stored; what Ui holds below its diagonal is not used.  Row strides are honoured.  An entry depends on n, Ui and its own
+    column only: a column gives the same bits alone, in any batch, at any position and in every call.  out: a contiguous float64
+    device vector [cols] to write to (default: a new one)."""
+    torch = require_gpu()
+    for t, name in ((Ui, 'Ui'), (X, 'X')):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2):
+            raise ValueError('leverages: {0} must be a two-dimensional float64 device tensor'.format(name))
+    ldu, ldx = _rows_of_doubles(Ui, 'Ui'), _rows_of_doubles(X, 'X')
+    n, cols = int(X.shape[0]), int(X.shape[1])
+    if tuple(Ui.shape) != (n, n) or Ui.device != X.device:
+        raise ValueError('leverages: Ui {0} must be ({1}, {1}) on the device of X'.format(tuple(Ui.shape), n))
+    if out is None:
+        out = torch.empty((cols,), dtype=torch.float64, device=X.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (cols,) and out.is_contiguous()
+              and out.device == X.device):
+        raise ValueError('leverages: out must be a contiguous float64 device vector of {0} entries'.format(cols))
+    else:
+        Plan._written(out)
+    _lib.call('shg_leverages', n, cols, _ptr(Ui), ldu, _ptr(X), ldx, _ptr(out), _stream())
+    return out
+
+
 def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
     """Decorrelation along the last axis of the device tensor X [..., M] (shg_whiten_rows): Y[..., t - skip] = sum_k h[n][k] X[..., t - k]
     for skip <= t < M with n = min(stage[t], q, t); the rows of X, all axes but the last flattened, belong to channel row % channels.

@@ -13,11 +13,12 @@ lives in HBM as its own fp64 tensor and every block operation is a libshg call:
 Vectors may be passed as NumPy arrays (results come back as NumPy arrays, like the reference) or as device tensors
 (results stay on the device).  There is no CPU fallback.
 
-Not built (outside the smoother path): UnscentedTransformSymmetric, teigh, trsvd, robust_least_squares,
+Not built (outside the smoother path): UnscentedTransformSymmetric, teigh, trsvd,
 AutoregressiveModel.from_transformed_coefficients (pseudo-inverse).
 """
 
 import collections
+import weakref
 
 import numpy as np
 
@@ -713,7 +714,7 @@ class ArcElimination:
     def __init__(self, ranks, R, g, shared, columns):
         self.ranks = ranks
         self.count = int(ranks.sum())
-        self.__R, self.__g, self.__shared, self.__columns = R, g, shared, columns
+        self.__R, self.__g, self.__shared, self.__columns, self.__merged = R, g, shared, columns, None
 
     def parameters(self, solution):
         if self.__columns is None:
@@ -723,6 +724,15 @@ class ArcElimination:
         y = self.__g - np.concatenate(products).reshape(self.__g.shape)
         y = np.einsum('akjr,akr->akj', self.__R, y)
         return y if self.__shared else y[:, 0]
+
+    def _columns(self):
+        """the kept D_a = C_a R_a of all arcs side by side, [P, arcs Kc u] on the device (arc-major, then the component of a shared
+        basis, then the direction), or None after ArcParameters(keep=False): what PostFit.leverages reduces the rows with"""
+        if self.__columns is None or not self.__columns:
+            return None
+        if self.__merged is None:                                     # (parameters() keeps its products per block of the sweep)
+            self.__merged = self.__columns[0] if len(self.__columns) == 1 else engine._torch().cat(self.__columns, dim=1)
+        return self.__merged
 
 
 class _ArcSweep:
@@ -884,6 +894,10 @@ class BlockMatrix:
         self.__check_bounds(key[0], key[1])
         block = self.__data.get((int(key[0]), int(key[1])))
         return None if block is None else engine.to_host(block)
+
+    def _extent(self):
+        """(rows, columns) of the whole matrix"""
+        return int(self.__row_index[-1]), int(self.__column_index[-1])
 
     def device_block(self, i, j):
         """device tensor of block (i, j), or None"""
@@ -1799,6 +1813,12 @@ class PostFit:
     def __init__(self, solution, vectors, model, template):
         _StochasticModel.of(model)
         self.__solution, self.__vectors, self.__template = solution, vectors, template
+        self.__bound = self.__hat = None
+
+    def _bind(self, observations, model, block_points, setup, temporal):
+        """what leverages() runs the design blocks once more with: the _Observations, the _StochasticModel and block_points of the pass,
+        under ArcParameters its _ArcSetup -- per-point tensors, small beside `rows`; temporal: the pass was one of TemporalParameters"""
+        self.__bound, self.__hat = (observations, model, block_points, setup, bool(temporal)), None
 
     @classmethod
     def of_accelerations(cls, solution, xyz, g, min_degree, max_degree, GM=3.9860044150e+14, R=6.3781363000e+06, weights=None, block_points=None,
@@ -1871,6 +1891,7 @@ class PostFit:
             V, plain = windows.restore(V), windows.restore(plain)
         seg = torch.from_numpy(bounds.astype(np.int32)).to(l.device)
         self.arc_parameters, self.ranks = None, np.zeros((arcs, K), dtype=np.int64)
+        setup = None
         if model.parameters is not None:
             setup = _ArcSetup(observations, model, plain=True)
             u, Kc, units = setup.u, setup.Kc, arcs * setup.Kc
@@ -1898,7 +1919,137 @@ class PostFit:
         self.whitened = _like_input(V[0].t().contiguous(), self.__template)
         self.residuals = _like_input(plain.t().contiguous(), self.__template)
         self.__solution = self.__vectors = None
+        self._bind(observations, model, block_points, setup, windows is not None)
         return self
+
+    def _leverage_operands(self, normals, elimination):
+        """every check of leverages(), on the host: returns (factor block, kept columns of the arcs or None)"""
+        if self.__bound is None:
+            raise ValueError('the leverages need the pass of an of_* call')
+        observations, model, _, setup, temporal = self.__bound
+        matrix = normals.matrix
+        if temporal or matrix.shape != (1, 1):
+            raise ValueError('leverages: a normal matrix of several blocks (TemporalParameters) is out of scope: a one-block matrix is '
+                             'expected, got {0} x {1} blocks'.format(*matrix.shape))
+        if normals.status != 'cholesky_factor' or matrix._holds_factor_inverses:
+            raise ValueError('leverages: the matrix holds {0}: solve the system first (status cholesky_factor)'.format(
+                'the inverses of the factor blocks' if normals.status == 'cholesky_factor' else normals.status))
+        if matrix._extent() != (observations.P, observations.P):
+            raise ValueError('leverages: the system has {0} x {1} parameters, the observations {2}'.format(*matrix._extent(), observations.P))
+        columns = None
+        if model.parameters is not None:
+            elimination = normals.arc_elimination if elimination is None else elimination
+            if elimination is None:
+                raise ValueError('leverages: the fit is one under ArcParameters: pass elimination=ne.arc_elimination of its own system')
+            columns = elimination._columns()
+            if columns is None:
+                raise ValueError('leverages: the hat matrix needs the eliminated columns: build with ArcParameters(keep=True)')
+            if setup is not None and tuple(columns.shape) != (observations.P, setup.arcs * setup.Kc * setup.u):
+                raise ValueError('leverages: the elimination holds columns {0}, this fit has {1} arcs of {2} x {3} parameters'.format(
+                    tuple(columns.shape), setup.arcs, setup.Kc, setup.u))
+        return matrix.device_block(0, 0), columns
+
+    def __hat_diagonal(self, normals, elimination):
+        """h [K, M] on the device; kept for the next call with the same system (redundancies, then standardised), which is held
+        weakly; callers get copies, never this tensor"""
+        factor, columns = self._leverage_operands(normals, elimination)
+        key = (weakref.ref(normals), None if elimination is None else weakref.ref(elimination), factor.data_ptr())
+        if self.__hat is not None and self.__hat[0][0]() is normals and self.__hat[0][2] == key[2] and \
+                (elimination is None if self.__hat[0][1] is None else self.__hat[0][1]() is elimination):
+            return self.__hat[1]
+        torch = engine.require_gpu()
+        observations, model, block_points, setup, _ = self.__bound
+        P, K, M = observations.P, observations.K, observations.M
+        Ui = engine.trtri(factor)
+        h = torch.empty((K, M), dtype=torch.float64, device=factor.device)
+        Q = q2 = None
+        if setup is not None:
+            # q_i = R_a^T b~_i for every observation: Q [u, K, M], by arc; |q_i|^2 is the part of the hat matrix the arc parameters take
+            Q = torch.empty_like(setup.Bt)
+            u, Kc = setup.u, setup.Kc
+            for a in range(setup.arcs):
+                a0, a1 = int(setup.bounds[a]), int(setup.bounds[a + 1])
+                if a1 > a0:
+                    Ra = setup.R_d[a * Kc:(a + 1) * Kc] if setup.shared else setup.R_d[a]
+                    engine.gemm_ex(Ra, setup.Bt[:, :, a0:a1].permute(1, 0, 2), Q[:, :, a0:a1].permute(1, 0, 2), transa=True)
+            flat = Q.reshape(u, K * M)
+            q2 = engine.column_dots(flat, flat).reshape(K, M)
+        for first, last, At, _, _, _ in _design_blocks(observations, model, block_points):
+            Mb = last - first
+            if setup is not None:
+                # At~ -= D_a Q_a^T for the arcs that meet the block: the rows of (I - Q Q^T) A~
+                At3 = At.reshape(P, K, Mb)
+                u, Kc = setup.u, setup.Kc
+                a_first = int(np.searchsorted(setup.bounds, first, side='right')) - 1
+                for a in range(a_first, setup.arcs):
+                    a0, a1 = max(int(setup.bounds[a]), first), min(int(setup.bounds[a + 1]), last)
+                    if a0 >= last:
+                        break
+                    if a1 <= a0:
+                        continue
+                    D = columns[:, a * Kc * u:(a + 1) * Kc * u]
+                    D = D.reshape(P, Kc, u).permute(1, 0, 2) if setup.shared else D
+                    engine.gemm_ex(D, Q[:, :, a0:a1].permute(1, 0, 2), At3[:, :, a0 - first:a1 - first].permute(1, 0, 2), alpha=-1.0, beta=1.0)
+            h[:, first:last] = engine.leverages(Ui, At).reshape(K, Mb)
+        if q2 is not None:
+            h += q2
+        self.__hat = (key, h)
+        return h
+
+    def leverages(self, normals, elimination=None):
+        """
+        h [M, K], the diagonal of the hat matrix: h_i = a~_i^T N^-1 a~_i for every whitened, weighted row a~_i of the design matrix, a
+        device tensor where the positions were one and a host array otherwise.  normals is a solved
+        NormalEquations (status 'cholesky_factor') with a one-block matrix over the parameters of this fit: the group's own system
+        or a combined one from accumulate_normals, regularisation included (the rows are taken as this fit whitened and weighted
+        them: a group that entered the combination with a variance factor s^2 has the leverages h / s^2).  U^-1 comes from
+        engine.trtri of its factor block, once per call, then one more pass over the design blocks of the fit with engine.leverages
+        per block; under a noise model the rows are the whitened ones, with the halo of every block as in the pass.
+
+        Under ArcParameters the hat matrix of the full model [A~ B~] is P_B + (I - P_B) A~ N^-1 A~^T (I - P_B) with P_B = Q Q^T,
+        Q_a = B~_a R_a as the elimination forms them: h_i = |q_i|^2 + |U^-T (a~_i - D_a q_i)|^2 with the D_a that
+        ArcParameters(keep=True) retains.  elimination defaults to normals.arc_elimination; a combined system has none, pass the
+        one of this group's own system.
+
+        The fit keeps the last h [K, M] on the device (K M doubles) for a following redundancies() or standardised() with the same
+        system, which it refers to weakly; every call returns a tensor or array of its own.
+
+        ValueError, before anything reaches the device: a matrix of several blocks (TemporalParameters is out of scope), a status
+        other than 'cholesky_factor', a parameter count that does not match, an ArcParameters fit without kept columns.
+        """
+        return _like_input(self.__hat_diagonal(normals, elimination).t().clone(memory_format=engine._torch().contiguous_format), self.__template)
+
+    def redundancies(self, normals, elimination=None):
+        """r = 1 - h [M, K] of leverages(); their sum is the redundancy of the adjustment when the normals are the group's own"""
+        return _like_input((1.0 - self.__hat_diagonal(normals, elimination)).t().contiguous(), self.__template)
+
+    def standardised(self, normals, sigma=None, factors=None, elimination=None):
+        """
+        t = |e~| / (sqrt(f) sigma sqrt(r)) [M, K], the standardised residual of every observation: e~ is `whitened`, r the
+        redundancies of the same arguments; sigma defaults to sqrt(sum e~^2 / (normals.observation_count - parameters)); factors
+        [M] or [M, K] (default 1) are the Huber factors the weights of this fit already hold, so that t measures the residual
+        against the standard deviation of the observation before its downweighting (the reference's loss_argument).  nan where
+        r <= 0.  Device tensor or host array as `whitened`.
+        """
+        h = self.__hat_diagonal(normals, elimination)
+        torch = engine.require_gpu()
+        e = self.rows[0]
+        if sigma is None:
+            freedom = normals.observation_count - self.__bound[0].P
+            if freedom <= 0:
+                raise ValueError('standardised: {0} observations do not determine sigma beside {1} parameters'.format(
+                    normals.observation_count, self.__bound[0].P))
+            sigma = float(torch.sqrt((e * e).sum() / freedom).item())
+        scale = float(sigma)
+        r = 1.0 - h
+        usable = r > 0
+        t = e.abs() / (scale * torch.sqrt(torch.where(usable, r, torch.ones_like(r))))
+        if factors is not None:
+            f = engine.to_device(factors, e.device) if not _is_tensor(factors) else factors.to(e.device)
+            f = f.reshape(f.shape[0], -1).to(torch.float64)
+            t = t / torch.sqrt(f.t().expand_as(t) if f.shape[1] == t.shape[0] else f.t().expand(t.shape[0], -1))
+        t = torch.where(usable, t, torch.full_like(t, float('nan')))
+        return _like_input(t.t().contiguous(), self.__template)
 
     def arc_redundancies(self, variance_factor=1.0):
         """r_a = n_a - (1 / S) sum_j |(I - Q_a Q_a^T) A~_a z_j|^2 / variance_factor [arcs]: the estimator of NormalEquations.redundancy,
@@ -1961,3 +2112,159 @@ def compute_variance_factors(normal_equations, combined_normals, solution, varia
     """Variance component estimates of the individual systems (grates/lstsq.py:1122-1149)."""
     return np.array([part.residual_square_sum(solution) / part.redundancy(combined_normals, factor)
                      for part, factor in zip(normal_equations, variance_factors)])
+
+
+def huber_factors(standardised, redundancies, factors=None, threshold=2.5, downweight_power=1.5, redundancy_threshold=1e-4):
+    """
+    One step of the Huber reweighting: (new_factors, outliers) from the standardised residuals t and the redundancies r of every
+    observation (PostFit.standardised, PostFit.redundancies; host arrays or device tensors of one shape, [M, K] or [k]).  An
+    observation is flagged where t is finite, t > threshold and r > redundancy_threshold, and a flagged observation gets the weight
+    factor f = (threshold / t)^(2 downweight_power): the reference's std_dev = (t / threshold)^downweight_power, applied as
+    1 / std_dev^2 (grates/lstsq.py:1362-1363).  An observation that is not flagged keeps its earlier factor (`factors`, default 1), as
+    in the reference.  The factors multiply the base weights of the observations.
+
+    factors has the shape of t, [M, K], where the kind of observation takes weights per component; for a kind that takes weights
+    per point only (line of sight, potentials, potential differences), or weights given per point, pass factors [M]: the new factor
+    of a point is then the smallest over its components, flagged components at (threshold / t)^(2 downweight_power) and the others
+    at the earlier factor of the point.  outliers always has the shape of t.
+    """
+    tensor = _is_tensor(standardised)
+    xp = engine._torch() if tensor else np
+    t = standardised if tensor else np.asarray(standardised, dtype=np.float64)
+    r = redundancies if tensor else np.asarray(redundancies, dtype=np.float64)
+    if tuple(t.shape) != tuple(r.shape):
+        raise ValueError('huber_factors: standardised {0} and redundancies {1} must have one shape'.format(tuple(t.shape), tuple(r.shape)))
+    if not (threshold > 0 and downweight_power > 0):
+        raise ValueError('huber_factors: threshold and downweight_power must be positive')
+    if factors is None:
+        f = xp.ones_like(t)
+    elif tensor:
+        f = (factors if _is_tensor(factors) else engine.to_device(np.asarray(factors, dtype=np.float64))).to(device=t.device, dtype=t.dtype)
+    else:
+        f = np.asarray(engine.to_host(factors) if _is_tensor(factors) else factors, dtype=np.float64)
+    per_point = f.ndim == t.ndim - 1
+    if tuple(f.shape) != (tuple(t.shape[:-1]) if per_point else tuple(t.shape)):
+        raise ValueError('huber_factors: factors {0} fit neither {1} nor {2}'.format(tuple(f.shape), tuple(t.shape), tuple(t.shape[:-1])))
+    outliers = xp.isfinite(t) & (t > threshold) & (r > redundancy_threshold)
+    safe = xp.where(outliers, t, xp.ones_like(t))                      # (no nan, inf or zero reaches the power)
+    earlier = f[..., None] if per_point else f
+    new = xp.where(outliers, (threshold / safe) ** (2.0 * downweight_power), earlier + xp.zeros_like(t))
+    if per_point:
+        new = new.min(dim=-1).values if tensor else new.min(axis=-1)
+    return new, outliers
+
+
+# The factors "no longer change" within this, relative.  With stable flags the loop contracts by about 0.02 per iteration (the factors
+# depend on each other through sigma0 alone), so bitwise repetition takes longer than the reference's ten iterations; sigma0 itself is
+# known to 1 / sqrt(2 (k - p)), a few percent, and a factor that moves by 1e-6 of itself changes nothing a weight means.
+HUBER_TOLERANCE = 1e-6
+
+
+def _huber_settled(factors, flags, new_factors, new_flags):
+    if flags is None or factors is None:
+        return False
+    xp = engine._torch() if _is_tensor(new_factors) else np
+    return bool((flags == new_flags).all()) and bool((xp.abs(new_factors - factors) <= HUBER_TOLERANCE * xp.abs(factors)).all())
+
+
+def huber_iterate(system, post_fit, weights, threshold=2.5, downweight_power=1.5, redundancy_threshold=1e-4, max_iter=10):
+    """
+    The solve, reweight loop per observation: system(w) returns the NormalEquations under the weights w,
+    post_fit(x, w, ne) the PostFit of the solution x [P, 1] under the same weights and model, e.g.
+
+        system = lambda w: model.from_accelerations(xyz, g, 2, 96, weights=w)
+        post_fit = lambda x, w, ne: PostFit.of_accelerations(x, xyz, g, 2, 96, weights=w, model=model)
+
+    weights [M] or [M, K] (host array; None: 1) are the base weights.  Every iteration solves the system under weights * factors,
+    takes t = post_fit.standardised(ne, factors=factors) and r = post_fit.redundancies(ne) and the new factors and flags from
+    huber_factors.  It stops when the flags are the same and the factors agree within 1e-6 of themselves (HUBER_TOLERANCE) with those of the
+    iteration before, or after max_iter solutions.  Returns (x, ne, factors, outliers) of the last solution: x and ne belong to
+    the factors of the iteration before, which are the returned ones where the loop stopped by itself; factors has the shape of
+    weights (without weights: [M, K], or [M] for K = 1), outliers [M, K]; both are host arrays.
+
+    Under a noise model the residual and the leverage are those of the decorrelated rows, and the factor goes to the weight of the
+    sample with the same index: a spike in one sample spreads over the q samples behind it in the decorrelated series, so the
+    neighbours of an outlier may be flagged with it.  That is the usual approximation.
+    """
+    base = None if weights is None else np.asarray(engine.to_host(weights) if _is_tensor(weights) else weights, dtype=np.float64)
+    if int(max_iter) < 1:
+        raise ValueError('huber_iterate: max_iter must be at least 1')
+    factors = flags = x = ne = None
+    for _ in range(int(max_iter)):
+        w = base if factors is None else (factors if base is None else base * factors)
+        ne = system(w)
+        x = ne.solve()
+        fit = post_fit(x, w, ne)
+        t = fit.standardised(ne, factors=factors)
+        r = fit.redundancies(ne)
+        t, r = (engine.to_host(v) if _is_tensor(v) else v for v in (t, r))
+        if factors is None:
+            shape = base.shape if base is not None else (t.shape if t.shape[1] > 1 else t.shape[:1])
+            earlier = np.ones(shape)
+        else:
+            earlier = factors
+        new_factors, new_flags = huber_factors(t, r, earlier, threshold, downweight_power, redundancy_threshold)
+        settled = _huber_settled(factors if factors is not None else earlier, flags if flags is not None else np.zeros_like(new_flags),
+                                 new_factors, new_flags)
+        factors, flags = new_factors, new_flags
+        if settled:
+            break
+    return x, ne, factors, flags
+
+
+def robust_least_squares(l, A, threshold=2.5, downweight_power=1.5, redundancy_threshold=1e-4, max_iter=10):
+    """
+    Iterative robust least squares adjustment with the Huber estimator (grates/lstsq.py:1320-1365: the same arguments and the same
+    return triple) for explicit observations l [k] and a design matrix A [k, p], host arrays or device tensors.
+
+    Returns x_hat [p], C [p, p] = sigma0^2 N^-1 and outlier_flag [k] (bool) of the last iteration, host arrays or device tensors as A.
+    As in the reference x_hat and C are those of the weights the last iteration started with, and an observation that is not
+    flagged keeps the factor it has.
+
+    Every iteration runs on the device: the rows are scaled by sqrt(f), N = A~^T A~ and n = A~^T l~ on engine.gemm, the factor by
+    engine.potrf, U^-1 by engine.trtri, x_hat = U^-1 U^-T n, the leverages a~_i^T N^-1 a~_i by engine.leverages on A~^T, then
+    huber_factors.  Unlike the reference, which always runs max_iter iterations, the loop ends as soon as the flags are those of the
+    iteration before and every factor agrees with its predecessor within HUBER_TOLERANCE = 1e-6 of itself -- not bitwise: what comes
+    back may be the solution of an earlier iteration than the reference's last, and differs from it by what a relative change of 1e-6 in
+    the weights of the flagged observations moves (below 1e-9 of x_hat in the tests' problems, by the argument at HUBER_TOLERANCE,
+    not by a derived bound).  max_iter iterations are never exceeded.
+
+    This is the textbook estimator: weights 1 / std_dev^2, redundancy r_i = 1 - a~_i^T N^-1 a~_i, standardised residual
+    |e~_i| std_dev_i / (sigma0 sqrt(r_i)).  The body of the reference does something else: it inverts A_bar^T A (one factor of
+    1 / std_dev, not two) and takes 1 - sum(A_bar^2, axis=1) as the redundancy, which is the diagonal of the hat matrix only for
+    orthonormal columns and unit weights.  The two agree in that setting at max_iter=1 (tests/golden/g32_robust.npz) and nowhere
+    else; the reference's formulas are not mirrored.
+    """
+    torch = engine.require_gpu()
+    host = not _is_tensor(A)
+    At = _dev(A).t().contiguous()                                                                  # [p, k]
+    p, k = int(At.shape[0]), int(At.shape[1])
+    lt = _dev(l).reshape(-1)
+    if int(lt.shape[0]) != k:
+        raise ValueError('robust_least_squares: l has {0} entries, A {1} rows'.format(int(lt.shape[0]), k))
+    if k <= p:
+        raise ValueError('robust_least_squares: {0} observations do not determine sigma0 beside {1} parameters'.format(k, p))
+    if int(max_iter) < 1:
+        raise ValueError('robust_least_squares: max_iter must be at least 1')
+    factors, flags = torch.ones(k, dtype=torch.float64, device=At.device), torch.zeros(k, dtype=torch.bool, device=At.device)
+    for _ in range(int(max_iter)):
+        root = torch.sqrt(factors)
+        Aw, lw = At * root, (lt * root).reshape(k, 1)
+        N = engine.gemm(Aw, Aw, transb=True)
+        n = engine.gemm(Aw, lw)
+        Ui = engine.trtri(engine.potrf(N))
+        x = engine.gemm(Ui, engine.gemm(Ui, n, transa=True))
+        e = (lw - engine.gemm(Aw, x, transa=True)).reshape(k)
+        r = 1.0 - engine.leverages(Ui, Aw)
+        variance = (e * e).sum() / (k - p)
+        usable = r > 0
+        t = e.abs() / (root * torch.sqrt(variance) * torch.sqrt(torch.where(usable, r, torch.ones_like(r))))
+        t = torch.where(usable, t, torch.full_like(t, float('nan')))
+        C = engine.gemm(Ui, Ui, transb=True) * variance
+        new_factors, new_flags = huber_factors(t, r, factors, threshold, downweight_power, redundancy_threshold)
+        settled = _huber_settled(factors, flags, new_factors, new_flags)
+        factors, flags = new_factors, new_flags
+        if settled:
+            break
+    x = x.reshape(p)
+    return (engine.to_host(x), engine.to_host(C), flags.cpu().numpy()) if host else (x, C, flags)

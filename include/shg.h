@@ -730,6 +730,29 @@ int shg_rbf_surface_info(int which[4]);
 int shg_column_dots(int rows, int cols, const double* X, int ldx, const double* Y, int ldy, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Leverages of observations: out[j] = sum_{p < n} z_pj^2, z_pj = sum_{q <= p} Ui[q][p] X[q][j]  (no reference
+ * counterpart)
+ *   Ui [n][ldu] (device): the upper triangular inverse U^-1 of the Cholesky factor N = U^T U, as shg_trtri writes it; what lies below
+ *   its diagonal is not used and may hold anything, NaN included (the entries are replaced by zeros while a tile of the diagonal block
+ *   is staged, as under the SHG_GEMM_A_* flags).  X [n][ldx] (device) with `cols` columns in use: a block At~ [P][K Mb] of the whitened,
+ *   weighted transposed design matrix as it stands.  out [cols]: out[j] = |U^-T x_j|^2 = x_j^T N^-1 x_j, the diagonal of the hat matrix.
+ *   Z = Ui^T X is never written: a workgroup forms a 128 x 128 tile of it on the fp64 MFMA (v_mfma_f64_16x16x4_f64), squares the
+ *   accumulators and sums them over the rows of the tile.  The K range of row tile t ends with its diagonal block (q < 128 t + 128):
+ *   half the MFMAs of the full product.  Workgroups tile (row tile, column tile), longest row tiles first; every tile writes its sums
+ *   to [row tiles][cols] doubles of the stream's scratch (shg_scratch_release) and a second kernel adds the row tiles in ascending
+ *   order.
+ *   Order: q ascending from 0 in steps of 4 (one MFMA each), whatever cols, the alignment or the launch; per tile and column the
+ *   squares are added by fma in ascending row order per lane, the four lanes of a column by the butterfly over lanes ^ 16, ^ 32, then
+ *   the two wave rows.  No atomics: out[j] depends on n, Ui and column j only -- a column computed alone, in any batch or at any column
+ *   offset gives the same bits, and repeated calls are bitwise equal.
+ *   A flat 64-bit index, so n x ldx may exceed 2^31.  The entries of out beyond cols and the padding of X from cols to ldx are neither
+ *   read nor written.
+ *   Arguments are checked before the first HIP call (negative sizes, ldu < n, ldx < cols, more than 2^40 values of Ui or X, and with
+ *   cols > 0: NULL out, NULL Ui or X when n > 0); cols = 0 returns 0 at once, n = 0 writes zeros.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_leverages(int n, long long cols, const double* Ui, int ldu, const double* X, long long ldx, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decorrelation of coloured observation noise along the point axis (the banded lower-triangular W with W^T W = Sigma^-1 of a sequence
  * of scalar AR models of orders 0 .. q; no reference counterpart)
  *   X [rows][ldx] with M columns in use, row r of channel r % channels: the transposed design matrix At [P][K][ldt] of the three calls
