@@ -151,6 +151,8 @@ PROTOTYPES = {
     'shg_leverages': [ctypes.c_int, ctypes.c_longlong, c_double_p, ctypes.c_int, c_double_p, ctypes.c_longlong, c_double_p, ctypes.c_void_p],
     'shg_whiten_rows': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, c_double_p, ctypes.c_int,
                         ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p],
+    'shg_whiten_rows_long': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, c_double_p, ctypes.c_int,
+                             ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p],
     'shg_segment_products': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, c_double_p, ctypes.c_longlong, ctypes.c_int,
                              ctypes.c_int, ctypes.c_void_p, c_double_p, ctypes.c_void_p],
     'shg_segment_lag_products': [ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_double_p,

@@ -1426,12 +1426,17 @@ def leverages(Ui, X, out=None):
     return out
 
 
+WHITEN_ROWS_ORDER = 128        # the longest filter of shg_whiten_rows; above it whiten_rows calls shg_whiten_rows_long
+
+
 def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
     """Decorrelation along the last axis of the device tensor X [..., M] (shg_whiten_rows): Y[..., t - skip] = sum_k h[n][k] X[..., t - k]
     for skip <= t < M with n = min(stage[t], q, t); the rows of X, all axes but the last flattened, belong to channel row % channels.
     taps [channels, q + 1, q + 1] (float64) and stage [M] (int32) are device tensors, as lstsq.whitening_taps and lstsq.arc_stages
     build them.  A two-dimensional X or out may be a column slice of a wider matrix (unit stride along the rows); anything else that
-    is not dense is copied.  Returns out, or a new tensor [..., M - skip]."""
+    is not dense is copied.  Returns out, or a new tensor [..., M - skip].
+    Up to q = 128 the filter runs as a chain of FMAs per value (shg_whiten_rows); a longer one, q <= 4095, as a banded product on the
+    fp64 MFMA (shg_whiten_rows_long), which needs the columns of X finite and repeats bitwise per call, not per tiling."""
     torch = require_gpu()
     M, skip, channels = int(X.shape[-1]), int(skip), int(channels)
     lead = tuple(int(s) for s in X.shape[:-1])
@@ -1455,8 +1460,9 @@ def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
         out = torch.empty(lead + (max(M - skip, 0),), dtype=torch.float64, device=X.device)
     elif tuple(out.shape) != lead + (M - skip,) or out.dtype != torch.float64 or rows_of(out, M - skip)[0] is not out:
         raise ValueError('out must be a float64 tensor of shape {0}, dense or a column slice of a matrix'.format(lead + (M - skip,)))
-    _lib.call('shg_whiten_rows', rows, channels, M, _ptr(X), ldx, _ptr(stage), _ptr(taps), int(taps.shape[-1]) - 1, skip, _ptr(out),
-              rows_of(out, M - skip)[1], _stream())
+    q = int(taps.shape[-1]) - 1
+    _lib.call('shg_whiten_rows' if q <= WHITEN_ROWS_ORDER else 'shg_whiten_rows_long', rows, channels, M, _ptr(X), ldx, _ptr(stage), _ptr(taps), q,
+              skip, _ptr(out), rows_of(out, M - skip)[1], _stream())
     return out
 
 

@@ -225,6 +225,98 @@ class AutoregressiveModelSequence:
 
 
 MAX_WHITENING_ORDER = 128      # of shg_whiten_rows: the halo of a tile of its kernel
+MAX_COVARIANCE_ORDER = 4095    # of shg_whiten_rows_long: the longest filter of a CovarianceFunction
+
+
+class CovarianceFunction:
+    """
+    Stationary scalar noise given by its covariance function c_0 .. c_q, as a noise model of the observations along the series of
+    points (host, NumPy only; no reference counterpart).  Accepted wherever an AutoregressiveModelSequence is: ColouredNoise,
+    ArcParameters(noise_model=), the noise_model keyword of NormalEquations.from_accelerations, decorrelate, and through them
+    RadialBasisParameters, TemporalParameters and every PostFit.of_*.
+
+    covariance_function holds the lags 0 .. q, 0 <= q <= MAX_COVARIANCE_ORDER: a one-dimensional array, or a sequence of [1, 1]
+    arrays as AutoregressiveModelSequence.from_covariance_function takes and PostFit.covariance_function returns.  An arc of up to
+    q + 1 points is decorrelated with its full covariance matrix, W = inv(cholesky(Toeplitz(c_0 .. c_(n-1)))); a longer arc with
+    that of its first q + 1 points and the AR(q) continuation beyond, the banded W with W^T W the inverse covariance matrix of the
+    AR(q) process that matches c_0 .. c_q.  taps() is the table of whitening_taps, built by a Levinson-Durbin recursion in O(q^2):
+    the same numbers as whitening_taps(AutoregressiveModelSequence.from_covariance_function(...)) up to rounding, without the
+    q + 1 AR models.  Up to q = 128 the filter runs on shg_whiten_rows, bitwise as an AR sequence with these taps; above, on
+    shg_whiten_rows_long.
+
+    ValueError for lags that are not finite, c_0 <= 0, q above the limit, [d, d] lags with d != 1, and a function that is not
+    positive definite: the order at which the prediction-error variance stops being finite and positive is named.
+    """
+
+    def __init__(self, covariance_function):
+        try:
+            lags = [np.asarray(lag, dtype=np.float64) for lag in covariance_function]
+        except (TypeError, ValueError):
+            lags = []
+        if not lags or not all(lag.shape in ((), (1,)) or (lag.ndim == 2 and lag.shape[0] == lag.shape[1]) for lag in lags):
+            raise ValueError('covariance_function must hold the lags 0 .. q: a one-dimensional array or a sequence of [1, 1] arrays')
+        for lag in lags:
+            if lag.ndim == 2 and lag.shape != (1, 1):
+                raise ValueError('covariance function of dimension {0}: only scalar noise (dimension 1) decorrelates an arc'.format(lag.shape[0]))
+        c = np.array([float(lag.reshape(())) for lag in lags])
+        q = c.size - 1
+        if q > MAX_COVARIANCE_ORDER:
+            raise ValueError('maximum order {0} of the covariance function above {1}'.format(q, MAX_COVARIANCE_ORDER))
+        if not np.all(np.isfinite(c)):
+            raise ValueError('the covariance function is not finite at lag {0}'.format(int(np.flatnonzero(~np.isfinite(c))[0])))
+        if not c[0] > 0.0:
+            raise ValueError('variance c_0 = {0} of the covariance function is not positive'.format(c[0]))
+        self.__lags = c
+        self.__taps = self.__levinson(c)
+
+    @staticmethod
+    def __levinson(c):
+        """h [q + 1, q + 1]: row s holds 1 / sigma_s and -phi_k / sigma_s of the best linear predictor of order s"""
+        q = c.size - 1
+        taps = np.zeros((q + 1, q + 1))
+        phi, variance = np.zeros(0), c[0]
+        taps[0, 0] = 1.0 / np.sqrt(variance)
+        for s in range(1, q + 1):
+            reflection = (c[s] - np.dot(phi, c[s - 1:0:-1])) / variance
+            phi = np.concatenate((phi - reflection * phi[::-1], (reflection,)))
+            variance = variance * (1.0 - reflection * reflection)
+            if not (np.isfinite(variance) and variance > 0.0):
+                raise ValueError('prediction-error variance {0} at order {1} is not finite and positive: the covariance function is not '
+                                 'positive definite there'.format(variance, s))
+            sigma = np.sqrt(variance)
+            taps[s, 0] = 1.0 / sigma
+            taps[s, 1:s + 1] = -phi / sigma
+        return taps
+
+    @property
+    def maximum_order(self):
+        return self.__lags.size - 1
+
+    @property
+    def dimension(self):
+        return 1
+
+    @property
+    def covariance_function(self):
+        """the lags 0 .. q as given, ndarray [q + 1]"""
+        return self.__lags.copy()
+
+    def taps(self):
+        """ndarray [q + 1, q + 1] in the layout of whitening_taps: h[s][0] = 1 / sigma_s, h[s][k] = -phi_k / sigma_s, zero beyond"""
+        return self.__taps.copy()
+
+
+def _covariance_taps(noise_model):
+    """whitening_taps of one CovarianceFunction or a list of them; None for anything else"""
+    if isinstance(noise_model, CovarianceFunction):
+        return noise_model.taps()[None]
+    functions = noise_model
+    if not isinstance(functions, list) or not functions or not all(isinstance(function, CovarianceFunction) for function in functions):
+        return None
+    orders = sorted(set(function.maximum_order for function in functions))
+    if len(orders) != 1:
+        raise ValueError('the noise models of the components differ in their maximum order: {0}'.format(orders))
+    return np.stack([function.taps() for function in functions])
 
 
 def whitening_taps(noise_model):
@@ -238,7 +330,18 @@ def whitening_taps(noise_model):
     noise_model is one AutoregressiveModelSequence (shared by all components, C = 1) or a sequence of them, one per component in
     the component order of the observations.  ValueError for a model of dimension other than 1, sequences of differing maximum
     order, an order above 128, models that are not of orders 0, 1, ..., q, and a variance that is not finite and positive.
+
+    One CovarianceFunction, or a sequence of them of equal order, one per component, gives their stacked taps() instead, of orders
+    up to MAX_COVARIANCE_ORDER.  A sequence that mixes the two types is refused.
     """
+    if not isinstance(noise_model, (AutoregressiveModelSequence, CovarianceFunction, list)):
+        try:
+            noise_model = list(noise_model)                # once: it may be an iterator
+        except TypeError:
+            pass
+    taps = _covariance_taps(noise_model)
+    if taps is not None:
+        return taps
     try:
         sequences = [noise_model] if isinstance(noise_model, AutoregressiveModelSequence) else list(noise_model)
     except TypeError:
@@ -1226,6 +1329,8 @@ class NormalEquations:
         meaning and scale the rows by sqrt(w) before the whitening, so the weight matrix in effect is D^1/2 W^T W D^1/2.  block_points
         keeps its default: a block takes up to q points in front of it along as history, the whitened copy doubles the peak memory of
         a block, and observation_count is unchanged.  noise_model=None changes nothing; arcs without it is a ValueError.
+        A CovarianceFunction (or one per component) in place of the sequences gives every arc of up to q + 1 points its full
+        covariance matrix, q <= 4095, and the AR(q) continuation beyond (shg_whiten_rows_long above q = 128).
         ColouredNoise(noise_model, arcs) offers the same for all five kinds of observation; ArcParameters(basis, arcs, noise_model)
         also eliminates parameters that last one arc (biases, drifts, once-per-revolution terms).
 
@@ -1433,8 +1538,8 @@ class _BoundModel:
 class ColouredNoise(_BoundModel):
     """
     A noise model of the observations along the series of points, bound to the constructors of NormalEquations: noise_model is one
-    scalar AutoregressiveModelSequence (shared by the components) or a sequence of them, one per component, arcs the start indices of
-    the arcs (default: one arc), as NormalEquations.from_accelerations describes them.  from_accelerations, from_gradients,
+    scalar AutoregressiveModelSequence or CovarianceFunction (shared by the components) or a sequence of them, one per component, arcs
+    the start indices of the arcs (default: one arc), as NormalEquations.from_accelerations describes them.  from_accelerations, from_gradients,
     from_line_of_sight, from_potentials and from_potential_differences take the arguments of the classmethods of the same name and
     return the NormalEquations of the decorrelated observations.  The model is checked here (whitening_taps), the arcs against the number of points in every call; all of it before
     anything reaches the device.

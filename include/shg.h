@@ -775,6 +775,34 @@ int shg_whiten_rows(long long rows, int channels, int M, const double* X, long l
                     int skip, double* Y, long long ldy, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Decorrelation with long filters, 0 <= q <= 4095: the arcs of a series under their full covariance matrices, W = inv(cholesky(
+ * Toeplitz(c_0 .. c_q))) for every arc of up to q + 1 points and the AR(q) continuation beyond (no reference
+ * counterpart)
+ *   The arguments and the definition of shg_whiten_rows: X [rows][ldx] with M columns in use, row r of channel r % channels, taps
+ *   (device) [channels][q+1][q+1], stage (device) [M], and
+ *   Y[r][t - skip] = sum_{k = 0 .. n} h_c[n][k] X[r][t - k] for skip <= t < M, n = min(max(stage[t], 0), q, t), c = r % channels.
+ *   Per channel this is the product Y_c = X_c B_c with the banded upper triangular B_c[t'][t] = h_c[n_t][t - t'] (0 <= t - t' <= n_t,
+ *   +0.0 elsewhere) on the fp64 MFMA (v_mfma_f64_16x16x4_f64).  B is never stored: a workgroup owns 128 rows of one channel by 128
+ *   output columns and generates the 16 x 128 tiles of its band of B from the tap table while it stages them; its K range runs from
+ *   the smallest t - n_t of its columns to its last column, 2 rows (M - skip) (q~ + 128) flops in all, fewer in the start-up tiles of
+ *   an arc.  Grid (column tiles, row tiles x channels), the latter in launches of 32768; a flat 64-bit index, so rows x ld may
+ *   exceed 2^31.
+ *   Order: one workgroup per output tile, K ascending from the first column of the band in steps of 4 (one MFMA each).  No atomics;
+ *   repeated calls are bitwise equal.
+ *   The one difference from shg_whiten_rows: the zeros of B multiply values of X outside x[t - n .. t], so the columns 0 .. M - 1 of
+ *   X must be finite, and Y[r][t - skip] depends on the position of t in its tile: a block whitened with its halo equals the same
+ *   columns of the whole within the rounding bound (n + 2) 2^-53 sum_k |h[n][k]| |x[t-k]| of either, not bitwise.
+ *   The padding of X from M to ldx is never read, the padding of Y from M - skip to ldy never written.  stage is clamped as in
+ *   shg_whiten_rows: a wrong table gives wrong numbers, never an access outside a row or the tap table.  Rows past `rows` and columns
+ *   past M are clamped on load and not stored.
+ *   Arguments are checked before the first HIP call as in shg_whiten_rows (negative sizes, channels < 1, rows not a multiple of
+ *   channels, q outside 0 .. 4095, skip outside 0 .. M, ldx < M, ldy < M - skip, more than 2^40 values of X or Y, NULL pointers,
+ *   address ranges of X and Y that overlap); rows = 0 or M = skip returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_whiten_rows_long(long long rows, int channels, int M, const double* X, long long ldx, const int32_t* stage, const double* taps, int q,
+                         int skip, double* Y, long long ldy, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Products of the rows of a matrix with a basis, cut at arc boundaries: what the elimination of arc-wise parameters needs of the
  * transposed design matrix (C_a = A_a^T B_a; no reference counterpart)
  *   X [rows][ldx] with M columns in use, row r of channel r % channels (the row convention of shg_whiten_rows: At [P][K][ldt] is
