@@ -157,6 +157,9 @@ PROTOTYPES = {
                              ctypes.c_int, ctypes.c_void_p, c_double_p, ctypes.c_void_p],
     'shg_segment_lag_products': [ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_double_p,
                                  ctypes.c_void_p],
+    'shg_segment_lag_products_long': [ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                      c_double_p, ctypes.c_void_p],
+    'shg_segment_lag_long_info': [ctypes.POINTER(ctypes.c_int)] * 3,
     'shg_window_expand': [ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p,
                           ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p],
 }

@@ -16,19 +16,10 @@
 // the reads of x[t + k] by consecutive lanes are consecutive doubles of LDS: no bank conflicts, and the chain order costs nothing.
 #include "common.h"
 
+#include "lags_device.h"          // segment_range, shared with lags_long.hip
 #include "lags_host.h"
 
 namespace shg {
-
-// the table clamped to 0 .. M and made non-decreasing: start = max of the clamped entries 0 .. s, end = max(start, entry s + 1); all
-// lanes of the wave call it and get the same values
-__device__ inline void segment_range(const int32_t* __restrict__ seg, int s, int M, int lane, int& start, int& end) {
-    start = 0;
-    for (int i = lane; i <= s; i += 64) start = max(start, min(max(seg[i], 0), M));
-#pragma unroll
-    for (int mask = 32; mask >= 1; mask >>= 1) start = max(start, __shfl_xor(start, mask));
-    end = max(start, min(max(seg[s + 1], 0), M));
-}
 
 __global__ __launch_bounds__(kLagWaves * 64) void segment_squares_kernel(long long items, long long rows, int M, const double* __restrict__ X,
                                                                          long long ldx, int nseg, const int32_t* __restrict__ seg,

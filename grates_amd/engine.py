@@ -1505,13 +1505,8 @@ def segment_products(X, Bt, seg, channels=1, out=None):
     return out
 
 
-def segment_lag_products(X, seg, lags, out=None):
-    """Lagged products of the rows of the device tensor X [..., M] with themselves, cut at arc boundaries (shg_segment_lag_products):
-    S[..., s, k] = sum of X[..., t] X[..., t + k] over seg[s] <= t, t + k < seg[s + 1], for k = 0 .. lags (0 <= lags <= 128): lag 0 is
-    the square sum of a segment, lags 0 .. q its empirical autocovariance times the number of pairs.  seg [nseg + 1] (int32) holds the
-    column indices of the boundaries, a device tensor; the kernel clamps it to 0 .. M and makes it non-decreasing.  A two-dimensional
-    X may be a column slice of a wider matrix (unit stride along the rows); anything else that is not dense is copied.  Returns out,
-    or a new dense tensor [..., nseg, lags + 1]; every entry is written."""
+def _segment_lag_products(entry, X, seg, lags, out):
+    """the views, checks and call that segment_lag_products and segment_lag_products_long share; entry: the name in libshg"""
     torch = require_gpu()
     M, lags = int(X.shape[-1]), int(lags)
     lead = tuple(int(s) for s in X.shape[:-1])
@@ -1532,8 +1527,35 @@ def segment_lag_products(X, seg, lags, out=None):
         out = torch.empty(shape, dtype=torch.float64, device=X.device)
     elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous():
         raise ValueError('out must be a dense float64 tensor of shape {0}'.format(shape))
-    _lib.call('shg_segment_lag_products', rows, M, _ptr(X), ldx, lags, nseg, _ptr(seg), _ptr(out), _stream())
+    _lib.call(entry, rows, M, _ptr(X), ldx, lags, nseg, _ptr(seg), _ptr(out), _stream())
     return out
+
+
+def segment_lag_products(X, seg, lags, out=None):
+    """Lagged products of the rows of the device tensor X [..., M] with themselves, cut at arc boundaries (shg_segment_lag_products):
+    S[..., s, k] = sum of X[..., t] X[..., t + k] over seg[s] <= t, t + k < seg[s + 1], for k = 0 .. lags (0 <= lags <= 128): lag 0 is
+    the square sum of a segment, lags 0 .. q its empirical autocovariance times the number of pairs.  seg [nseg + 1] (int32) holds the
+    column indices of the boundaries, a device tensor; the kernel clamps it to 0 .. M and makes it non-decreasing.  A two-dimensional
+    X may be a column slice of a wider matrix (unit stride along the rows); anything else that is not dense is copied.  Returns out,
+    or a new dense tensor [..., nseg, lags + 1]; every entry is written."""
+    return _segment_lag_products('shg_segment_lag_products', X, seg, lags, out)
+
+
+def segment_lag_products_long(X, seg, lags, out=None):
+    """segment_lag_products for 0 <= lags <= 4095 on the fp64 MFMA (shg_segment_lag_products_long): the same arguments, views, checks
+    and result, S[..., s, k] = sum of X[..., t] X[..., t + k] over seg[s] <= t, t + k < seg[s + 1].  Always the long kernel, whatever
+    lags is; segment_lag_products never calls it.  An entry depends on the values of its segment and on k alone and repeats bitwise,
+    but is not bitwise that of segment_lag_products (another summation order); the values inside a segment must be finite, columns
+    outside every segment are not read.  segment_lag_long_info() gives the chunk length and the lags of an accumulator tile."""
+    return _segment_lag_products('shg_segment_lag_products_long', X, seg, lags, out)
+
+
+def segment_lag_long_info():
+    """{'chunk', 'tile_lags', 'max_lags'} of shg_segment_lag_products_long: the columns of a work item, counted from the start of a
+    segment, the lags of one accumulator tile and the largest lag.  Host only."""
+    values = [ctypes.c_int(0) for _ in range(3)]
+    _lib.call('shg_segment_lag_long_info', *(ctypes.byref(value) for value in values))
+    return dict(zip(('chunk', 'tile_lags', 'max_lags'), (int(value.value) for value in values)))
 
 
 WINDOW_SLOTS = 16                                                # slots of one shg_window_expand call: W <= E <= 16

@@ -2176,21 +2176,84 @@ class PostFit:
         semi-definite by construction; biased=False: d_k = sum_a max(len_a - k, 0).  The components are pooled into one function
         (K d_k in the divisor), or per_component=True gives one function each.  Returns what
         AutoregressiveModelSequence.from_covariance_function takes, a list of [1, 1] arrays, or a list of K such lists.  ValueError
-        for a maximum_lag outside 0 .. 128 and, with biased=False, for a lag no arc is long enough for.
+        for a maximum_lag outside 0 .. 128 and, with biased=False, for a lag no arc is long enough for.  covariance_lags gives the
+        same numbers as arrays, up to lag 4095.
         """
         if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_WHITENING_ORDER:
             raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_WHITENING_ORDER, maximum_lag))
-        q = int(maximum_lag)
+        c = self.__covariance(int(maximum_lag), per_component, biased)
+        if per_component:
+            return [[np.array([[value]]) for value in row] for row in c]
+        return [np.array([[value]]) for value in c]
+
+    def __covariance(self, q, per_component, biased):
+        """c [q + 1] or [K, q + 1] of covariance_function and covariance_lags; up to lag 128 shg_segment_lag_products, beyond it
+        shg_segment_lag_products_long"""
         lengths = np.diff(np.append(self.arcs, int(self.__rows.shape[1])))
         pairs = np.array([np.maximum(lengths - k, 0).sum() for k in range(q + 1)], dtype=np.float64)
         if biased:
             pairs[:] = pairs[0]
         elif not np.all(pairs > 0):
             raise ValueError('no arc is longer than {0} points: no pair at lag {1}'.format(int(lengths.max()), int(np.argmin(pairs > 0))))
-        sums = engine.to_host(engine.segment_lag_products(self.__rows, self.__seg, q)).sum(axis=1)       # [K, q + 1]
+        products = engine.segment_lag_products if q <= MAX_WHITENING_ORDER else engine.segment_lag_products_long
+        sums = engine.to_host(products(self.__rows, self.__seg, q)).sum(axis=1)                           # [K, q + 1]
         if per_component:
-            return [[np.array([[value]]) for value in row / pairs] for row in sums]
-        return [np.array([[value]]) for value in sums.sum(axis=0) / (sums.shape[0] * pairs)]
+            return sums / pairs
+        return sums.sum(axis=0) / (sums.shape[0] * pairs)
+
+    def covariance_lags(self, maximum_lag, per_component=False, biased=True):
+        """
+        The numbers of covariance_function as plain arrays, ndarray [q + 1] or, with per_component, [K, q + 1], for
+        0 <= maximum_lag <= MAX_COVARIANCE_ORDER = 4095: the same divisors, pooling and meaning of `biased`.  Up to lag 128 it is
+        bitwise covariance_function (shg_segment_lag_products); beyond, the sums run on the fp64 MFMA
+        (shg_segment_lag_products_long), which needs finite residuals.  ValueError, before anything reaches
+        the device, for a maximum_lag that is no integer in 0 .. 4095 and, with biased=False, for a lag no arc is long enough for.
+        """
+        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_COVARIANCE_ORDER:
+            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_COVARIANCE_ORDER, maximum_lag))
+        return self.__covariance(int(maximum_lag), per_component, biased)
+
+    def covariance_model(self, maximum_lag, per_component=False, window=None):
+        """
+        The noise model of the residuals: a CovarianceFunction of the biased covariance_lags(maximum_lag), or a list of K of them
+        with per_component, for ColouredNoise, ArcParameters(noise_model=), TemporalParameters(model=) and RadialBasisParameters.
+        The biased estimate is a sum of positive semi-definite sequences, so the Levinson-Durbin recursion accepts it unless the
+        residuals are degenerate; a CovarianceFunction that is not positive definite raises its own ValueError.  window tapers the
+        lags on the host first, c_k w_k with lag_window(window, maximum_lag): None, 'bartlett', 'parzen' (both positive
+        semi-definite, so the product stays so) or an array [q + 1] with w_0 = 1.  ValueError for any other window and for the
+        maximum_lag, before anything reaches the device.
+        """
+        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_COVARIANCE_ORDER:
+            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_COVARIANCE_ORDER, maximum_lag))
+        taper = lag_window(window, int(maximum_lag))
+        c = self.__covariance(int(maximum_lag), per_component, True) * taper
+        return [CovarianceFunction(row) for row in c] if per_component else CovarianceFunction(c)
+
+
+def lag_window(window, maximum_lag):
+    """
+    w [q + 1], the taper of the lags 0 .. q = maximum_lag of an estimated covariance function (host, NumPy only), w_0 = 1:
+    None: all ones.  'bartlett': w_k = 1 - k / (q + 1).  'parzen': with m = q + 1, w_k = 1 - 6 (k/m)^2 + 6 (k/m)^3 for k <= m / 2 and
+    2 (1 - k/m)^3 above.  Both are positive semi-definite sequences, so they keep an estimate positive semi-definite.  An array
+    [q + 1] with w_0 = 1 is taken as given.  ValueError for anything else.
+    """
+    q = int(maximum_lag)
+    if window is None:
+        return np.ones(q + 1)
+    if isinstance(window, str):
+        x = np.arange(q + 1) / (q + 1.0)
+        if window == 'bartlett':
+            return 1.0 - x
+        if window == 'parzen':
+            return np.where(x <= 0.5, 1.0 - 6.0 * x * x + 6.0 * x * x * x, 2.0 * (1.0 - x) ** 3)
+        raise ValueError("window must be None, 'bartlett', 'parzen' or an array of {0} weights, got {1!r}".format(q + 1, window))
+    try:
+        w = np.array(window, dtype=np.float64)
+    except (TypeError, ValueError):
+        w = None
+    if w is None or w.shape != (q + 1,) or not np.all(np.isfinite(w)) or w[0] != 1.0:
+        raise ValueError("window must be None, 'bartlett', 'parzen' or an array of {0} finite weights with w_0 = 1".format(q + 1))
+    return w
 
 
 def accumulate_normals(normal_equations, variance_factors):

@@ -851,6 +851,38 @@ int shg_segment_lag_products(long long rows, int M, const double* X, long long l
                              void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same lagged products for up to 4095 lags, on the fp64 MFMA: the covariance function of post-fit residuals as far as
+ * shg_whiten_rows_long can use it (no reference counterpart)
+ *   The definition, the arguments and the layout of S are those of shg_segment_lag_products, with 0 <= lags <= 4095:
+ *   S[r][s][k] = sum over t with seg[s] <= t and t + k < seg[s+1] of X[r][t] X[r][t + k], k = 0 .. lags;  S [rows][nseg][lags + 1] is
+ *   dense and every entry is written; an entry without a pair (a segment of k columns or fewer, an empty segment) is exactly 0.0.
+ *   Formulation: relative to the start of the segment, A[i][c] = x[c - 16 i], B[c][j] = x[c + j + k0] and D = A B on
+ *   v_mfma_f64_16x16x4_f64: D[i][j] is the lag k0 + 16 i + j, so one 16 x 16 accumulator holds `tile_lags` = 256 consecutive lags and
+ *   nothing is discarded.  A segment is cut into chunks of `chunk` = 2048 columns counted from its start, the last one taking what is
+ *   left, up to 2560; a chunk is one workgroup, which stages its values of x in LDS once; wave w of 4 takes the first factors x[t]
+ *   of quarter w of the chunk (512 columns; a fourth, rounded up to a multiple of 4, of a chunk above 2048).
+ *   Summation order of an entry: per quarter the chain of MFMA steps over t ascending, 4 columns a step, from the start of the
+ *   quarter; the quarters of a chunk are added as ((q0 + q1) + q2) + q3 (a quarter past the end of the segment is +0.0) and written
+ *   to a workspace of the call; a second kernel adds the chunks of a segment in ascending order.  No atomics.
+ *   Locality: S[r][s][k] depends only on X[r][seg[s] .. seg[s+1]) and on k, not on the row index, rows, nseg, M, lags, the other
+ *   segments, the position of the segment in the row (odd offsets included) or the launch; repeated calls are bitwise equal.
+ *   Positions outside the segment become +0.0 by a select while the values are staged, never by a product: columns outside every
+ *   segment and the padding from M to ldx may hold anything (NaN, 1e300) and are not read.  Zeros do multiply values of the segment
+ *   itself (a partner past its end, a first factor of another quarter), so the values inside a segment must be finite, unlike under
+ *   shg_segment_lag_products and as under shg_whiten_rows_long.
+ *   Clamping: entry i of seg is read as c_i = max over k <= i of min(max(seg[k], 0), M), by the function shg_segment_lag_products
+ *   uses; a wrong table gives wrong numbers, never an access outside a row, the table or the workspace.
+ *   Workspace (stream-ordered, freed with the call): rows x (M / 2048 + nseg) x 256 (lags / 256 + 1) doubles of partial sums and
+ *   two small tables.
+ *   Arguments are checked before the first HIP call (negative sizes, lags outside 0 .. 4095, nseg < 0, ldx < M, more than 2^40 values
+ *   of X, of S or of the workspace, NULL pointers); rows = 0 or nseg = 0 returns 0 after these checks, before any pointer is looked at.
+ *   shg_segment_lag_long_info: chunk (2048), tile_lags (256) and max_lags (4095); host only, NULL pointers are skipped.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_segment_lag_products_long(long long rows, int M, const double* X, long long ldx, int lags, int nseg, const int32_t* seg, double* S,
+                                  void* stream);
+int shg_segment_lag_long_info(int* chunk, int* tile_lags, int* max_lags);
+
+/* ------------------------------------------------------------------------------------------------
  * Window expansion of a transposed design matrix: the adjoint of the window model of the shg_*_points_at calls, for parameters
  * that vary in time (no reference counterpart)
  *   T [rows][ldt] with n columns in use (the transposed design matrix At [P][K][ldt] of a block is rows = P K).  factors (device)
