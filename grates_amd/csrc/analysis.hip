@@ -92,7 +92,6 @@ __global__ __launch_bounds__(256) void weight_fold_kernel(int nb, int nlat, int 
 // chunks of 8 columns through two LDS stages; per chunk every thread loads two columns of one row in their four images (and
 // the weights), folds them, and one row of the trig chunk.  Operand fragments: A = T[order][c] (LDS [c][order]), B = F[c][row]
 // (LDS [group][c][row]), D row = order fk + 4 reg, column = row fr.
-typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef double double2_t __attribute__((ext_vector_type(2)));
 #ifndef SHG_ANA_PARITY
 #define SHG_ANA_PARITY 1     // 0: A/B builds without the north-south parity split of the operator product

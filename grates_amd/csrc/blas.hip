@@ -10,7 +10,7 @@
 // U12 = U11^-T A12 and trailing update A22 -= U12^T U12 as MFMA GEMMs (upper tiles only).
 #include <memory>
 
-#include "common.h"
+#include "mfma_tile.h"
 
 #ifndef SHG_GEMM_TAIL
 #define SHG_GEMM_TAIL 1             // tall products in 64-tiles: the rows of the last, mostly empty round as a product of their own (split over K)
@@ -23,8 +23,6 @@
 #endif
 
 namespace shg {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int XK = 16;
 constexpr int XLR = 17;      // [row][k] staging: 17-double rows (operand contiguous along k in memory)
@@ -116,19 +114,7 @@ __global__ __launch_bounds__(256, T == 128 ? 2 : 3) void gemm_ex_kernel(GemmExPa
     double areg[8], breg[8];
     // Addressing of the steady state: fp64 MFMAs and the VALU instructions of all waves of a SIMD share one issue pipe
     // (tools/mfma64_issue.hip), so every load is "uniform 64-bit base, advanced per K tile by scalar instructions, + 32-bit
-    // lane offset fixed for the whole kernel" (see gemm.hip for the idiom: the base is pinned in scalar registers, the lane
-    // offset is pinned next to its use so that the scalar-base form of the load is selected).
-    typedef const double __attribute__((address_space(1))) gdouble_t;
-    typedef const char __attribute__((address_space(1))) gbyte_t;
-    auto pin = [](unsigned v) {
-        asm volatile("" : "+v"(v));
-        return v;
-    };
-    auto at = [](const double* base, unsigned byte_off) {
-        unsigned long long b = reinterpret_cast<unsigned long long>(base);
-        asm volatile("" : "+s"(b));
-        return *reinterpret_cast<gdouble_t*>(reinterpret_cast<gbyte_t*>(b) + byte_off);
-    };
+    // lane offset fixed for the whole kernel" (load_uniform_base and pin_vector of mfma_tile.h).
     // R-type operand ([row][k]): offsets of the F row pieces (two elements each) relative to the block's first row;
     // K-type operand ([k][row]): offsets of the column pair (T = 128) or the single column (T = 64) relative to the block's first column
     unsigned ar_off[F], br_off[F];
@@ -148,21 +134,21 @@ __global__ __launch_bounds__(256, T == 128 ? 2 : 3) void gemm_ex_kernel(GemmExPa
         const double* bk = base + k0;
 #pragma unroll
         for (int h = 0; h < F; ++h) {
-            const unsigned o = pin(off[h]);
-            reg[2 * h] = at(bk, o);
-            reg[2 * h + 1] = at(bk + 1, o);
+            const unsigned o = pin_vector(off[h]);
+            reg[2 * h] = load_uniform_base(bk, o);
+            reg[2 * h + 1] = load_uniform_base(bk + 1, o);
         }
     };
     auto fetch_k = [&](double* reg, const double* base, int ld, unsigned off0, unsigned off1, int k0) {
-        const unsigned o0 = pin(off0), o1 = pin(off1);
+        const unsigned o0 = pin_vector(off0), o1 = pin_vector(off1);
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
             const double* bk = base + (size_t)(k0 + k_k + 4 * h) * ld;
             if (T == 128) {
-                reg[2 * h] = at(bk, o0);
-                reg[2 * h + 1] = at(bk, o1);
+                reg[2 * h] = load_uniform_base(bk, o0);
+                reg[2 * h + 1] = load_uniform_base(bk, o1);
             } else {
-                reg[h] = at(bk, o0);
+                reg[h] = load_uniform_base(bk, o0);
             }
         }
     };
@@ -253,41 +239,25 @@ __global__ __launch_bounds__(256, T == 128 ? 2 : 3) void gemm_ex_kernel(GemmExPa
             bf[b] = TB ? Bs[(wc * HALF + b * 16 + fr) * XLR + (ks) * 4 + fk] : Bs[((ks) * 4 + fk) * XLK + wc * HALF + b * 16 + fr]; \
         __builtin_amdgcn_sched_barrier(0);                                                                                     \
     } while (0)
-#define SHG_MFMAS(af, bf)                                                                                                      \
-    do {                                                                                                                       \
-        _Pragma("unroll") for (int a = 0; a < F; ++a)                                                                         \
-            _Pragma("unroll") for (int b = 0; b < F; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0); \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-    } while (0)
-#define SHG_MFMAS_LOADS(af, bf, nloads)                                                                                        \
-    do {                                                                                                                       \
-        _Pragma("unroll") for (int a = 0; a < F; ++a)                                                                         \
-            _Pragma("unroll") for (int b = 0; b < F; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0); \
-        _Pragma("unroll") for (int i = 0; i < (nloads); ++i) {                                                                \
-            __builtin_amdgcn_sched_group_barrier(0x008, (F * F) / (nloads) > 0 ? (F * F) / (nloads) : 1, 0);                   \
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                                                 \
-        }                                                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-    } while (0)
     // k-steps 0 .. 2 of the tile in `buf` (set 0 holds the fragments of k-step 0); leaves k-step 3 in set 1
 #define SHG_TILE_HEAD(buf, knext, prefetch)             \
     do {                                                \
         SHG_FRAGS(af1, bf1, buf, 1);                    \
         if (prefetch) {                                 \
             fetch_a(knext);                             \
-            SHG_MFMAS_LOADS(af0, bf0, NLOAD_A);         \
+            tile_mfmas<F, NLOAD_A>(af0, bf0, acc);      \
         } else {                                        \
-            SHG_MFMAS(af0, bf0);                        \
+            tile_mfmas<F, 0>(af0, bf0, acc);            \
         }                                               \
         SHG_FRAGS(af0, bf0, buf, 2);                    \
         if (prefetch) {                                 \
             fetch_b(knext);                             \
-            SHG_MFMAS_LOADS(af1, bf1, NLOAD_B);         \
+            tile_mfmas<F, NLOAD_B>(af1, bf1, acc);      \
         } else {                                        \
-            SHG_MFMAS(af1, bf1);                        \
+            tile_mfmas<F, 0>(af1, bf1, acc);            \
         }                                               \
         SHG_FRAGS(af1, bf1, buf, 3);                    \
-        SHG_MFMAS(af0, bf0);                            \
+        tile_mfmas<F, 0>(af0, bf0, acc);                \
     } while (0)
 
     if (Kz > 0) {
@@ -307,7 +277,7 @@ __global__ __launch_bounds__(256, T == 128 ? 2 : 3) void gemm_ex_kernel(GemmExPa
         stage((buf) ^ 1);                               \
         __syncthreads();                                \
         SHG_FRAGS(af0, bf0, (buf) ^ 1, 0);              \
-        SHG_MFMAS(af1, bf1);                            \
+        tile_mfmas<F, 0>(af1, bf1, acc);                \
     } while (0)
     int t = 0;
     for (; t + 2 < nfull; t += 2) {
@@ -331,7 +301,7 @@ __global__ __launch_bounds__(256, T == 128 ? 2 : 3) void gemm_ex_kernel(GemmExPa
                 SHG_FRAGS(af0, bf0, 0, 0);
             }
         }
-        SHG_MFMAS(af1, bf1);
+        tile_mfmas<F, 0>(af1, bf1, acc);
     }
     if (has_tail) {
         if (nfull & 1) {
@@ -339,13 +309,11 @@ __global__ __launch_bounds__(256, T == 128 ? 2 : 3) void gemm_ex_kernel(GemmExPa
         } else {
             SHG_TILE_HEAD(0, 0, false);
         }
-        SHG_MFMAS(af1, bf1);
+        tile_mfmas<F, 0>(af1, bf1, acc);
     }
     }   // Kz > 0
 #undef SHG_STEP
 #undef SHG_TILE_HEAD
-#undef SHG_MFMAS_LOADS
-#undef SHG_MFMAS
 #undef SHG_FRAGS
 
     // epilogue.  C/D layout: column = lane & 15, row = (lane >> 4) + 4 * reg

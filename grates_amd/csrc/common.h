@@ -16,6 +16,8 @@
 
 namespace shg {
 
+typedef double double4_t __attribute__((ext_vector_type(4)));        // the accumulator of one v_mfma_f64_16x16x4_f64
+
 int fail(int code, const char* fmt, ...);
 // Zero fills as kernels of this library (plan.hip), for the paths that several host threads feed at once (the chains of the
 // block-banded smoother, one thread and one stream each): on ROCm 7.2 a 4-byte hipMemsetAsync issued from four threads on

@@ -8,11 +8,10 @@
 // MFMA fragment read is conflict free.  Tile 128 x 128, BK = 16, 4 waves x (64 x 64), 2 workgroups per CU,
 // register prefetch of the next K tile, one barrier per K tile.  Epilogue: row-dot with the regenerated A tile, reduced over
 // the 128 columns; per-column-block partial sums are summed in a fixed order by covprop_reduce_kernel (gemm.hip).
-#include "common.h"
+// The tile is that of mfma_tile.h; the K loop is this kernel's own (a fetch that advances (degree, rank) per call, a peeled tail).
+#include "mfma_tile.h"
 
 namespace shg {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int CT = 128;          // tile edge
 constexpr int CK = 16;           // K slots per stage
@@ -103,18 +102,7 @@ __global__ __launch_bounds__(256, 2) void covprop_rows_kernel(CovParams P) {
     auto compute = [&](int buf) {
         const double* Ab = As[buf] + fk * CLD + wr * 64 + fr;
         const double* Bb = Bs[buf] + fk * CLD + wc * 64 + fr;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            double af[4], bf[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) af[a] = Ab[ks * 4 * CLD + a * 16];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) bf[b] = Bb[ks * 4 * CLD + b * 16];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
-        }
+        tile_multiply<4, 4 * CLD, 16, 4 * CLD, 16>(Ab, Bb, acc);
     };
     const int nfull = P.P / CK;
     const bool has_tail = (P.P % CK) != 0;

@@ -14,7 +14,6 @@ namespace shg {
 #define SHG_FILT_GROUP 0  // orders per workgroup: 0 = the largest of 8, 4, 2 whose LDS stage fits
 #endif
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef double double2_t __attribute__((ext_vector_type(2)));
 typedef unsigned int uint4_t __attribute__((ext_vector_type(4)));
 

@@ -8,11 +8,10 @@
 //
 // Block tile 128 x 128, BK = 16, 4 waves as 2 x 2, wave tile 64 x 64 (16 accumulators).  Global -> register
 // prefetch of the next K tile overlaps the 64 MFMAs of the current one; one barrier per K tile.
-#include "common.h"
+#include "mfma_tile.h"
 
 namespace shg {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 128, BK = 16;
@@ -117,7 +116,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
     // B: 16 k-rows x 64 pieces of 2 doubles; piece h: k = (tid >> 6) + 4 h, col = (tid & 63) * 2
     // Addressing: fp64 MFMAs and the VALU instructions of all waves of a SIMD share one issue pipe (tools/mfma64_issue.hip),
     // so the K loop keeps address arithmetic on the scalar unit: every load is "uniform 64-bit base (advanced per K tile by
-    // scalar instructions) + per-lane 32-bit byte offset (fixed for the whole kernel)".
+    // scalar instructions) + per-lane 32-bit byte offset (fixed for the whole kernel)": load_uniform_base, load2_uniform_base
+    // and pin_vector of mfma_tile.h.
     double areg[8];
     double creg[8];             // COVPROP: cos/sin factors; the product with areg is formed when the tile is staged, i.e.
                                 // after the MFMAs of the current tile, so that the loads stay in flight across them
@@ -125,30 +125,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
     const int a_kk = (tid & 7) * 2;
     const int b_k = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform first k row of the B pieces
     const int b_col = (tid & 63) * 2;
-    // (the empty asm pins the uniform base in scalar registers -- without it the compiler folds base + lane offset into one
-    //  loop-invariant 64-bit vector address and adds the scalar part with a VALU instruction per load; the address goes
-    //  through an integer, so the pointer is rebuilt in the global address space explicitly.  The 32 -> 64 bit extension of
-    //  the lane offset has to stay in the basic block of the load for the scalar-base form to be selected: `pin` below.)
-    auto pin = [](unsigned v) {
-        asm volatile("" : "+v"(v));
-        return v;
-    };
-    typedef const double __attribute__((address_space(1))) gdouble_t;
-    typedef const char __attribute__((address_space(1))) gbyte_t;
     typedef int __attribute__((address_space(4))) crank_t;
-    typedef double gdouble2_v __attribute__((ext_vector_type(2)));
-    typedef const gdouble2_v __attribute__((address_space(1))) gdouble2_t;
-    auto at = [](const double* base, unsigned byte_off) {
-        unsigned long long b = reinterpret_cast<unsigned long long>(base);
-        asm volatile("" : "+s"(b));
-        return *reinterpret_cast<gdouble_t*>(reinterpret_cast<gbyte_t*>(b) + byte_off);
-    };
-    auto at2 = [](const double* base, unsigned byte_off) {
-        unsigned long long b = reinterpret_cast<unsigned long long>(base);
-        asm volatile("" : "+s"(b));
-        const gdouble2_v v = *reinterpret_cast<gdouble2_t*>(reinterpret_cast<gbyte_t*>(b) + byte_off);
-        return make_double2(v.x, v.y);
-    };
     // PLAIN A: per-lane offsets of the four row pieces relative to row m0 (clamped rows stay inside the matrix)
     unsigned a_voff[4] = {0, 0, 0, 0};
     const double* a_base = nullptr;                                  // uniform: &A[m0][0]
@@ -256,14 +233,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
     constexpr int NLOAD2 = (MODE == MODE_PLAIN || BUF) ? 0 : (VEC ? 4 : 8);
     constexpr int NLOADB = VEC ? 4 : 8;
     auto fetch_old_B = [&](int k0) {
-        const unsigned boff0 = pin(b_voff0), boff1 = pin(b_voff1);
+        const unsigned boff0 = pin_vector(b_voff0), boff1 = pin_vector(b_voff1);
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
             const double* brow = P.B + (size_t)(k0 + b_k + 4 * h) * P.ldb;      // uniform
             if (VEC)
-                breg[h] = at2(brow, boff0);
+                breg[h] = load2_uniform_base(brow, boff0);
             else
-                breg[h] = make_double2(at(brow, boff0), at(brow, boff1));
+                breg[h] = make_double2(load_uniform_base(brow, boff0), load_uniform_base(brow, boff1));
         }
     };
     auto fetch_part = [&](int k0, int part) {
@@ -272,14 +249,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
                 const double* ak = a_base + k0;                       // uniform
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
-                    const unsigned off = pin(a_voff[h]);
+                    const unsigned off = pin_vector(a_voff[h]);
                     if (VEC) {
-                        const double2 t = at2(ak, off);
+                        const double2 t = load2_uniform_base(ak, off);
                         areg[2 * h] = t.x;
                         areg[2 * h + 1] = t.y;
                     } else {
-                        areg[2 * h] = at(ak, off);
-                        areg[2 * h + 1] = at(ak + 1, off);
+                        areg[2 * h] = load_uniform_base(ak, off);
+                        areg[2 * h + 1] = load_uniform_base(ak + 1, off);
                     }
                 }
             } else if (part == 1 && !PDMA) {
@@ -290,11 +267,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
         } else if (part < 2) {
             // degree-wise index p = n^2 + r: the rank r inside the degree selects the cos/sin row (table lookup on the scalar unit)
             const double* pk = pk_base + k0 + khalf;                  // uniform
-            const unsigned poff = pin(pk_voff), coff = pin(cs_voff);
+            const unsigned poff = pin_vector(pk_voff), coff = pin_vector(cs_voff);
 #pragma unroll
             for (int h = 4 * part; h < 4 * part + 4; ++h) {
-                areg[h] = PKT ? at(pk_base + (size_t)(k0 + khalf + 2 * h) * P.ldp, poff) : at(pk + 2 * h, poff);
-                creg[h] = at(P.csr + (size_t)rank[h] * P.ldcs, coff);
+                areg[h] = PKT ? load_uniform_base(pk_base + (size_t)(k0 + khalf + 2 * h) * P.ldp, poff) : load_uniform_base(pk + 2 * h, poff);
+                creg[h] = load_uniform_base(P.csr + (size_t)rank[h] * P.ldcs, coff);
             }
         } else {
             fetch_old_B(k0);
@@ -327,8 +304,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
             for (int h = 0; h < 8; ++h) {
                 const int gk = k0 + 2 * h + khalf;
                 const int kc = min(gk, P.K - 1);
-                areg[h] = gk < P.K ? (PKT ? at(pk_base + (size_t)kc * P.ldp, pk_voff) : at(pk_base + kc, pk_voff)) : 0.0;
-                creg[h] = at(P.csr + (size_t)reinterpret_cast<const crank_t*>(reinterpret_cast<unsigned long long>(P.rslot))[kc + P.p_off] * P.ldcs, cs_voff);
+                areg[h] = gk < P.K ? (PKT ? load_uniform_base(pk_base + (size_t)kc * P.ldp, pk_voff) : load_uniform_base(pk_base + kc, pk_voff)) : 0.0;
+                creg[h] = load_uniform_base(P.csr + (size_t)reinterpret_cast<const crank_t*>(reinterpret_cast<unsigned long long>(P.rslot))[kc + P.p_off] * P.ldcs, cs_voff);
             }
         }
         if (DMA) return;                          // the Sigma rows of the partial tile are in LDS already (rows beyond K read as zero)
@@ -336,8 +313,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
         for (int h = 0; h < 4; ++h) {
             const int gk = k0 + b_k + 4 * h;
             const double* brow = P.B + (size_t)min(gk, P.K - 1) * P.ldb;
-            const double x = at(brow, b_voff0);
-            const double y = VEC ? at(brow + 1, b_voff0) : at(brow, b_voff1);
+            const double x = load_uniform_base(brow, b_voff0);
+            const double y = VEC ? load_uniform_base(brow + 1, b_voff0) : load_uniform_base(brow, b_voff1);
             breg[h] = gk < P.K ? make_double2(x, y) : make_double2(0.0, 0.0);
         }
     };
@@ -386,11 +363,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
     // the last k-step of a tile is issued after the barrier that publishes the next tile, behind the request for that tile's
     // first fragments, so the LDS latency after the barrier is covered as well.
     double af0[4], bf0[4], af1[4], bf1[4];
-    // Every fragment is one ds_read_b64 "lane base + 16-bit immediate": the bases are opaque to the compiler (it would split the
-    // 72 KB of offsets differently and add to the base with a VALU instruction per k-step) and the B reads are volatile, which
-    // keeps them from being paired into ds_read2_b64, whose 8-bit offsets need such an add as well.  An integer VALU instruction
-    // costs the MFMA pipe more than a tenth of an MFMA (profiles/r01_mfma64_issue.txt).
-    typedef double __attribute__((address_space(3))) lds_double_t;       // 32-bit LDS addresses: the bases stay ds_read / ds_write operands
+    // Every fragment is one ds_read_b64 "lane base + 16-bit immediate" (lds_double_t in mfma_tile.h): opaque bases, and the B reads,
+    // 16 doubles apart, are volatile so that they are not paired into ds_read2_b64.
     const lds_double_t* a_frag_base = (const lds_double_t*)(As[0] + (wr * 64 + fr) * LDA + fk);
     const lds_double_t* b_frag_base = (const lds_double_t*)(Bs[0] + fk * LDB + wc * 64 + fr);
     asm volatile("" : "+v"(a_frag_base));
@@ -403,50 +377,33 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
         _Pragma("unroll") for (int b = 0; b < 4; ++b) bf[b] = Bb_[b * 16];                                           \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
     } while (0)
-#define SHG_MFMA16(af, bf)                                                                                           \
-    do {                                                                                                             \
-        _Pragma("unroll") for (int a = 0; a < 4; ++a)                                                                \
-            _Pragma("unroll") for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0); \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-    } while (0)
-    // 16 MFMAs with `nloads` operand loads (issued in front of them in the source) dealt between them, two MFMAs per load: a
-    // wave issues in order, and 24 loads in a row keep it away from the MFMA pipe for ~1800 cycles (the address unit takes one
-    // load per ~16 cycles and serves eight waves)
-#define SHG_MFMA16_LOADS(af, bf, nloads)                                                                             \
-    do {                                                                                                             \
-        _Pragma("unroll") for (int a = 0; a < 4; ++a)                                                                \
-            _Pragma("unroll") for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0); \
-        _Pragma("unroll") for (int i = 0; i < (SHG_GEMM_INTERLEAVE ? (nloads) : 0); ++i) {                           \
-            __builtin_amdgcn_sched_group_barrier(0x008, (nloads) > 8 ? 1 : ((nloads) > 4 ? 2 : 4), 0);                \
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                                       \
-        }                                                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-    } while (0)
+    // 16 MFMAs with `nloads` operand loads (issued in front of them in the source) dealt between them (tile_mfmas)
+#define SHG_DEALT(nloads) (SHG_GEMM_INTERLEAVE ? (nloads) : 0)
     // k-steps 0 .. 2 of the tile in `buf` (set 0 holds the fragments of k-step 0); leaves k-step 3 in set 1.  BUF: the A operand
     // of the next tile (at knext) is requested under k-steps 0 and 1
-#define SHG_TILE_HEAD(buf, knext, prefetch) \
-    do {                                    \
-        SHG_FRAGS(af1, bf1, buf, 1);        \
-        if (prefetch) {                     \
-            fetch_part(knext, 0);           \
-            SHG_MFMA16_LOADS(af0, bf0, NLOAD0); \
-        } else {                            \
-            SHG_MFMA16(af0, bf0);           \
-        }                                   \
-        SHG_FRAGS(af0, bf0, buf, 2);        \
-        if ((prefetch) && NLOAD1 > 0) {     \
-            fetch_part(knext, 1);           \
-            SHG_MFMA16_LOADS(af1, bf1, NLOAD1); \
-        } else {                            \
-            SHG_MFMA16(af1, bf1);           \
-        }                                   \
-        SHG_FRAGS(af1, bf1, buf, 3);        \
-        if ((prefetch) && NLOAD2 > 0) {     \
-            fetch_part(knext, 2);           \
-            SHG_MFMA16_LOADS(af0, bf0, NLOAD2); \
-        } else {                            \
-            SHG_MFMA16(af0, bf0);           \
-        }                                   \
+#define SHG_TILE_HEAD(buf, knext, prefetch)                  \
+    do {                                                     \
+        SHG_FRAGS(af1, bf1, buf, 1);                         \
+        if (prefetch) {                                      \
+            fetch_part(knext, 0);                            \
+            tile_mfmas<4, SHG_DEALT(NLOAD0)>(af0, bf0, acc); \
+        } else {                                             \
+            tile_mfmas<4, 0>(af0, bf0, acc);                 \
+        }                                                    \
+        SHG_FRAGS(af0, bf0, buf, 2);                         \
+        if ((prefetch) && NLOAD1 > 0) {                      \
+            fetch_part(knext, 1);                            \
+            tile_mfmas<4, SHG_DEALT(NLOAD1)>(af1, bf1, acc); \
+        } else {                                             \
+            tile_mfmas<4, 0>(af1, bf1, acc);                 \
+        }                                                    \
+        SHG_FRAGS(af1, bf1, buf, 3);                         \
+        if ((prefetch) && NLOAD2 > 0) {                      \
+            fetch_part(knext, 2);                            \
+            tile_mfmas<4, SHG_DEALT(NLOAD2)>(af0, bf0, acc); \
+        } else {                                             \
+            tile_mfmas<4, 0>(af0, bf0, acc);                 \
+        }                                                    \
     } while (0)
 
     const int nfull = Keff / BK;
@@ -512,12 +469,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
         if (BUF && !(SHG_GEMM_X & 4)) {                                       \
             fetch_B(((t) + 2) * BK, buf);                                     \
             fetch_A(((t) + 2) * BK, 0, 4);                                    \
-            SHG_MFMA16_LOADS(af1, bf1, NLOADB + NLOADA);                      \
+            tile_mfmas<4, SHG_DEALT(NLOADB + NLOADA)>(af1, bf1, acc);         \
         } else if (PDMA && !(SHG_GEMM_X & 4)) {                               \
             fetch_B(((t) + 2) * BK, buf);                                     \
-            SHG_MFMA16_LOADS(af1, bf1, NLOADB);                               \
+            tile_mfmas<4, SHG_DEALT(NLOADB)>(af1, bf1, acc);                  \
         } else {                                                              \
-            SHG_MFMA16(af1, bf1);                                             \
+            tile_mfmas<4, 0>(af1, bf1, acc);                                  \
         }                                                                     \
         if (SHG_GEMM_PRIO == 3) __builtin_amdgcn_s_setprio(0);                \
         SHG_TL_MARK(3);                                                       \
@@ -546,7 +503,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
                 SHG_FRAGS(af0, bf0, 0, 0);
             }
         }
-        SHG_MFMA16(af1, bf1);
+        tile_mfmas<4, 0>(af1, bf1, acc);
     }
     if (has_tail) {
         if (SYM && nfull == tdiag && tdiag > 0) double_accumulators();
@@ -555,13 +512,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
         } else {
             SHG_TILE_HEAD(0, 0, false);
         }
-        SHG_MFMA16(af1, bf1);
+        tile_mfmas<4, 0>(af1, bf1, acc);
     }
 #undef SHG_STEP
-#undef SHG_MFMA16_LOADS
 #undef SHG_TILE_HEAD
 #undef SHG_FRAGS
-#undef SHG_MFMA16
+#undef SHG_DEALT
     __syncthreads();
 
 #ifdef SHG_TIMELINE

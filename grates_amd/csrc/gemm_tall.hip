@@ -23,7 +23,6 @@
 namespace shg {
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kTallWaves = 8;                              // one workgroup of eight waves per CU
 constexpr int kTallRows = 16 * kTallWaves;                 // rows of an output tile

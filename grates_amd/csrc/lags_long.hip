@@ -33,8 +33,6 @@
 namespace shg {
 namespace {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
 struct LagLongSlot {            // what a workgroup needs of its chunk
     int start, end;             // the segment in the clamped table; start > end: no chunk has this slot
     int first;                  // first column of the chunk, relative to start

@@ -12,13 +12,11 @@
 // Every tile writes the sums of its 128 rows to partial[t][j]; leverage_sum_kernel adds the row tiles in ascending order.  No
 // atomics; the K order is ascending from q = 0 in steps of 4 whatever the column, the epilogue order is fixed by the row alone, so
 // out[j] depends on n, Ui and column j only.
-// Address arithmetic stays on the scalar unit (see gemm.hip): a load is "uniform 64-bit row base + per-lane 32-bit byte offset".
-#include "common.h"
+// The tile, its K loop and the loads "uniform 64-bit row base + per-lane 32-bit byte offset" are those of mfma_tile.h.
+#include "mfma_tile.h"
 
 namespace shg {
 namespace {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int LT = 128;        // rows of Z and columns per workgroup
 constexpr int LK = 16;         // K tile
@@ -47,25 +45,20 @@ __global__ __launch_bounds__(256, 2) void leverage_kernel(int n, long long cols,
     const unsigned x_off = (unsigned)(min(j0 + c, cols - 1) - j0) * 8u;
     const double* u_base = Ui + p0;
     const double* x_base = X + j0;
-    typedef const double __attribute__((address_space(1))) gdouble_t;
-    typedef const char __attribute__((address_space(1))) gbyte_t;
-    auto at = [](const double* base, unsigned byte_off) {
-        unsigned long long b = reinterpret_cast<unsigned long long>(base);
-        asm volatile("" : "+s"(b));
-        return *reinterpret_cast<gdouble_t*>(reinterpret_cast<gbyte_t*>(b) + byte_off);
-    };
 
     double ureg[8], xreg[8];
-    auto fetch = [&](int k0) {
+    auto fetch = [&](int i) {
+        const int k0 = i * LK;
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
             const int q = min(k0 + kh + 2 * h, n - 1);                // uniform; only the last K tile can reach n
-            ureg[h] = at(u_base + (size_t)q * ldu, u_off);
-            xreg[h] = at(x_base + (size_t)q * ldx, x_off);
+            ureg[h] = load_uniform_base(u_base + (size_t)q * ldu, u_off);
+            xreg[h] = load_uniform_base(x_base + (size_t)q * ldx, x_off);
         }
     };
     double* stage_base = lds + kh * LLD + c;
-    auto stage = [&](int buf, int k0) {
+    auto stage = [&](int buf, int i) {
+        const int k0 = i * LK;
         double* As = stage_base + buf * (2 * LK * LLD);
         double* Bs = As + LK * LLD;
         const bool masked = (k0 + LK - 1 > p0) || (k0 + LK > n);      // uniform: tiles of the diagonal block, and the last one
@@ -88,9 +81,7 @@ __global__ __launch_bounds__(256, 2) void leverage_kernel(int n, long long cols,
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
 
-    // every fragment is one ds_read_b64 "lane base + immediate": volatile keeps the reads from being paired into ds_read2_b64, which
-    // moves half the bytes per LDS cycle
-    typedef double __attribute__((address_space(3))) lds_double_t;
+    // every fragment is one ds_read_b64 "lane base + immediate" (lds_double_t of mfma_tile.h)
     const lds_double_t* a_frag = (const lds_double_t*)(lds + fk * LLD + wr * 64 + fr);
     const lds_double_t* b_frag = (const lds_double_t*)(lds + LK * LLD + fk * LLD + wc * 64 + fr);
     asm volatile("" : "+v"(a_frag));
@@ -98,36 +89,9 @@ __global__ __launch_bounds__(256, 2) void leverage_kernel(int n, long long cols,
     auto multiply = [&](int buf) {
         const volatile lds_double_t* Ab = a_frag + buf * (2 * LK * LLD);
         const volatile lds_double_t* Bb = b_frag + buf * (2 * LK * LLD);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            double af[4], bf[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) af[a] = Ab[ks * 4 * LLD + a * 16];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) bf[b] = Bb[ks * 4 * LLD + b * 16];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
-        }
+        tile_multiply<4, 4 * LLD, 16, 4 * LLD, 16>(Ab, Bb, acc);
     };
-    // tile i in buffer `buf`; the operands of tile i + 1 are requested in front of its MFMAs and staged behind them
-    auto step = [&](int buf, int i) {
-        const bool more = i + 1 < nt;                                 // uniform
-        if (more) fetch((i + 1) * LK);
-        multiply(buf);
-        if (more) stage(buf ^ 1, (i + 1) * LK);
-        __syncthreads();
-    };
-    fetch(0);
-    stage(0, 0);
-    __syncthreads();
-    int i = 0;
-    for (; i + 1 < nt; i += 2) {
-        step(0, i);
-        step(1, i + 1);
-    }
-    if (i < nt) step(0, i);
+    SHG_TILE_PIPELINE(nt, fetch, stage, multiply);
 
     // ---- epilogue.  C/D layout: column = lane & 15, row = (lane >> 4) + 4 * reg.  A lane sums the squares of its 16 rows of a
     //      column in ascending (a, reg) order, the four lanes of a column close as (s + s^16) + (s + s^16)^32, then wr 0 + wr 1.

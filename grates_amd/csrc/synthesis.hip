@@ -13,8 +13,6 @@
 
 namespace shg {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
 // ------------------------------------------------------------------------------------------------
 // pack_coefficients
 // ------------------------------------------------------------------------------------------------

@@ -17,7 +17,6 @@
 
 namespace shg {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
 constexpr int kPanelStride32 = 48;   // 32 rows + 16 pad: k-rows of a fragment read fall on disjoint LDS bank halves

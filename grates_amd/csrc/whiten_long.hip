@@ -7,8 +7,9 @@
 // elsewhere, formed tile by tile on the fp64 MFMA (v_mfma_f64_16x16x4_f64).  B is never stored: its tiles are generated from the tap
 // table while they are staged.
 // Workgroup = (128 rows of one channel: rows c, c + channels, ..., 128 output columns), 4 waves as 2 x 2, wave tile 64 x 64
-// (16 accumulators), BK = 16 as in leverage.hip.  The K range of a column tile is its band alone: from the smallest t - n_t of its
-// columns to its last column, so the start-up tiles of an arc take fewer steps and a stationary tile q + 128 columns of X.
+// (16 accumulators), BK = 16: the tile and the K loop of mfma_tile.h.  The K range of a column tile is its band alone: from the
+// smallest t - n_t of its columns to its last column, so the start-up tiles of an arc take fewer steps and a stationary tile
+// q + 128 columns of X.
 // The tile of X is read along its rows (16 consecutive doubles of 4 rows per wave load) and staged row-major [128][18]: a fragment
 // read is "row (lane & 15), k (lane >> 4)", and the row stride of 18 doubles puts the 32 lanes of a ds_read_b64 group on distinct
 // banks.  The tile of B is staged k-major [16][144] as in leverage.hip; thread c of a k-row gathers h[n_t][t - t'] of its own column
@@ -17,14 +18,12 @@
 // No atomics, one workgroup per output tile, K ascending from the first column of the band in steps of 4: repeated calls are bitwise
 // equal.  Zeros of B multiply values of X outside x[t - n .. t], so the columns 0 .. M - 1 of X must be finite; loads are clamped
 // to the rows and to the columns 0 .. M - 1 of X and to the tap row of the column, whatever stage holds.
-#include "common.h"
+#include "mfma_tile.h"
 
 #include <climits>
 
 namespace shg {
 namespace {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int WT = 128;        // rows and output columns per workgroup
 constexpr int WK = 16;         // K tile
@@ -75,7 +74,8 @@ __global__ __launch_bounds__(256, 2) void whiten_long_kernel(long long rpc, int 
     const int klast = M - 1 - t0;                                     // last column of X, relative to t0
 
     double xreg[8], breg[8];
-    auto fetch = [&](int k0) {                                        // k0: first column of the K tile, relative to t0
+    auto fetch = [&](int i) {
+        const int k0 = kbeg + i * WK;                                 // first column of the K tile, relative to t0
         const int kx = min(k0 + ka, klast);                           // what lies past M - 1 meets zeros of B only
 #pragma unroll
         for (int h = 0; h < 8; ++h) xreg[h] = xrow[h][kx];
@@ -87,7 +87,8 @@ __global__ __launch_bounds__(256, 2) void whiten_long_kernel(long long rpc, int 
     };
     double* a_stage = lds + ra * WLDA + ka;
     double* b_stage = lds + WT * WLDA + kh * WLDB + c;
-    auto stage_tiles = [&](int buf, int k0) {
+    auto stage_tiles = [&](int buf, int i) {
+        const int k0 = kbeg + i * WK;
         double* As = a_stage + buf * WIMG;
         double* Bs = b_stage + buf * WIMG;
 #pragma unroll
@@ -104,8 +105,7 @@ __global__ __launch_bounds__(256, 2) void whiten_long_kernel(long long rpc, int 
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
 
-    // every fragment is one ds_read_b64 "lane base + immediate" (see leverage.hip)
-    typedef double __attribute__((address_space(3))) lds_double_t;
+    // every fragment is one ds_read_b64 "lane base + immediate" (lds_double_t of mfma_tile.h)
     const lds_double_t* a_frag = (const lds_double_t*)(lds + (wr * 64 + fr) * WLDA + fk);
     const lds_double_t* b_frag = (const lds_double_t*)(lds + WT * WLDA + fk * WLDB + wc * 64 + fr);
     asm volatile("" : "+v"(a_frag));
@@ -113,36 +113,9 @@ __global__ __launch_bounds__(256, 2) void whiten_long_kernel(long long rpc, int 
     auto multiply = [&](int buf) {
         const volatile lds_double_t* Ab = a_frag + buf * WIMG;
         const volatile lds_double_t* Bb = b_frag + buf * WIMG;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            double af[4], bf[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) af[a] = Ab[a * 16 * WLDA + ks * 4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) bf[b] = Bb[ks * 4 * WLDB + b * 16];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
-        }
+        tile_multiply<4, 4, 16 * WLDA, 4 * WLDB, 16>(Ab, Bb, acc);
     };
-    // tile i in buffer `buf`; the operands of tile i + 1 are requested in front of its MFMAs and staged behind them
-    auto step = [&](int buf, int i) {
-        const bool more = i + 1 < nt;                                 // uniform
-        if (more) fetch(kbeg + (i + 1) * WK);
-        multiply(buf);
-        if (more) stage_tiles(buf ^ 1, kbeg + (i + 1) * WK);
-        __syncthreads();
-    };
-    fetch(kbeg);
-    stage_tiles(0, kbeg);
-    __syncthreads();
-    int i = 0;
-    for (; i + 1 < nt; i += 2) {
-        step(0, i);
-        step(1, i + 1);
-    }
-    if (i < nt) step(0, i);
+    SHG_TILE_PIPELINE(nt, fetch, stage_tiles, multiply);
 
     // ---- epilogue.  C/D layout: column = lane & 15, row = (lane >> 4) + 4 * reg: a store writes 16 consecutive doubles of 4 rows
 #pragma unroll
