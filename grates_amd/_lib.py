@@ -162,6 +162,8 @@ PROTOTYPES = {
     'shg_segment_lag_long_info': [ctypes.POINTER(ctypes.c_int)] * 3,
     'shg_window_expand': [ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p,
                           ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p],
+    'shg_jacobi_svd': [c_double_p, ctypes.c_int, ctypes.c_long, c_double_p, ctypes.c_int, ctypes.c_long, c_double_p, ctypes.c_int, ctypes.c_int,
+                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p],
 }
 STRING_GETTERS = ('shg_last_error', 'shg_version')
 

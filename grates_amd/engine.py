@@ -1928,3 +1928,109 @@ def axpby(alpha, X, beta, Y):
     Plan._written(Y)
     _lib.call('shg_axpby', X.shape[0], X.shape[1], float(alpha), _ptr(X), max(X.stride(0), 1), float(beta), _ptr(Y), max(Y.stride(0), 1), _stream())
     return Y
+
+
+JACOBI_MAX = 128       # the largest r and c of shg_jacobi_svd: one matrix must fit the LDS of a CU
+_UNIT_ROUNDOFF = 2.0 ** -53
+
+
+def _jacobi(G, max_sweeps, name):
+    """shg_jacobi_svd in place on a contiguous fp64 device tensor [batch, r, c] -> (V [batch, c, c], sigma [batch, c], sweeps [batch]
+    int32), raising numpy.linalg.LinAlgError when a matrix needed more than max_sweeps sweeps"""
+    torch = require_gpu()
+    batch, r, c = (int(s) for s in G.shape)
+    V = torch.empty((batch, c, c), dtype=torch.float64, device=G.device)
+    sigma = torch.empty((batch, c), dtype=torch.float64, device=G.device)
+    sweeps = torch.empty((batch,), dtype=torch.int32, device=G.device)
+    _lib.call('shg_jacobi_svd', _ptr(G), c, r * c, _ptr(V), c, c * c, _ptr(sigma), r, c, batch, int(max_sweeps), _ptr(sweeps), _stream())
+    if int(sweeps.min().item()) < 0:
+        raise np.linalg.LinAlgError('{0}: the Jacobi rotations did not converge within {1} sweeps'.format(name, int(max_sweeps)))
+    return V, sigma, sweeps
+
+
+def _small_matrices(X, name, square):
+    """(copy [batch, r, c] of the fp64 device tensor X [r, c] or [batch, r, c], whether X was a batch) for the LDS kernels"""
+    torch = require_gpu()
+    if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float64 and X.dim() in (2, 3)):
+        raise ValueError('{0}: a float64 device tensor [r, c] or [batch, r, c] is expected'.format(name))
+    r, c = int(X.shape[-2]), int(X.shape[-1])
+    if square and r != c:
+        raise ValueError('{0}: square matrices expected, got {1} x {2}'.format(name, r, c))
+    if not (1 <= c <= r <= JACOBI_MAX) or (X.dim() == 3 and X.shape[0] < 1):
+        raise ValueError('{0}: {1} x {2} is outside 1 <= columns <= rows <= {3}'.format(name, r, c, JACOBI_MAX))
+    return X.reshape(-1, r, c).clone(memory_format=torch.contiguous_format), X.dim() == 3
+
+
+def jacobi_svd(G, max_sweeps=30):
+    """(U, s, Vt, sweeps) with G = U diag(s) Vt for a float64 device tensor G [r, c] or [batch, r, c], c <= r <= 128, by one-sided Jacobi
+    rotations in LDS (shg_jacobi_svd, one workgroup per matrix; G is not changed).  s descends; U [.., r, c] is the rotated G over s,
+    with zero columns where s == 0; Vt [.., c, c] is orthogonal.  sweeps: the sweeps the kernel used (an int, or an int32 tensor
+    [batch]).  The order of the rotations is fixed: repeated calls are bitwise equal.  Raises numpy.linalg.LinAlgError when a matrix
+    has not converged after max_sweeps sweeps."""
+    torch = require_gpu()
+    work, batched = _small_matrices(G, 'jacobi_svd', False)
+    V, sigma, sweeps = _jacobi(work, max_sweeps, 'jacobi_svd')
+    s, order = torch.sort(sigma, dim=1, descending=True, stable=True)
+    pick = order.unsqueeze(1)
+    GV = torch.gather(work, 2, pick.expand(-1, work.shape[1], -1))
+    scale = torch.where(s > 0.0, s, torch.ones_like(s)).unsqueeze(1)
+    U = torch.where((s > 0.0).unsqueeze(1), GV / scale, torch.zeros_like(GV))
+    Vt = torch.gather(V, 2, pick.expand(-1, V.shape[1], -1)).transpose(1, 2).contiguous()
+    if batched:
+        return U, s, Vt, sweeps
+    return U[0], s[0], Vt[0], int(sweeps.item())
+
+
+def syev(A, max_sweeps=30):
+    """(w, v, sweeps): eigenvalues w ascending and eigenvectors v (columns) of the symmetric float64 device tensor A [n, n] or
+    [batch, n, n], n <= 128, of which only the upper triangle is read, by shg_jacobi_svd.  One-sided Jacobi diagonalises A^T A = A^2,
+    which cannot tell lambda from -lambda, so the kernel works on A + sigma0 I with the Gershgorin shift
+    sigma0 = max(0, max_i(sum_{j != i} |a_ij| - a_ii)), which is positive semi-definite: its right singular vectors are the
+    eigenvectors of A, and w_i = v_i . (A + sigma0 I) v_i - sigma0 (the Rayleigh quotients; the second factor is the kernel's rotated
+    matrix).  sweeps as in jacobi_svd; numpy.linalg.LinAlgError when max_sweeps did not suffice."""
+    torch = require_gpu()
+    work, batched = _small_matrices(A, 'syev', True)
+    work = torch.triu(work)
+    work = work + torch.triu(work, 1).transpose(1, 2)
+    diagonal = torch.diagonal(work, dim1=1, dim2=2)
+    shift = (work.abs().sum(dim=2) - diagonal.abs() - diagonal).amax(dim=1).clamp_min(0.0)
+    diagonal += shift.unsqueeze(1)              # a view: the diagonal of work
+    V, _, sweeps = _jacobi(work, max_sweeps, 'syev')
+    w = (V * work).sum(dim=1) - shift.unsqueeze(1)
+    w, order = torch.sort(w, dim=1, stable=True)
+    v = torch.gather(V, 2, order.unsqueeze(1).expand(-1, V.shape[1], -1))
+    if batched:
+        return w, v, sweeps
+    return w[0], v[0], int(sweeps.item())
+
+
+def orthonormalise(B):
+    """Q [m, k] with orthonormal columns that span those of the tall float64 device tensor B [m, k], k <= 128, m >= k, by shifted
+    CholeskyQR3 (Fukaya, Kannan, Nakatsukasa, Yamamoto, Yanagisawa, SIAM J. Sci. Comput. 42, 2020) on the fp64 MFMA: the Gram matrix
+    B^T B + s I with s = 11 (m k + k (k + 1)) u |B|_F^2, its Cholesky factor R (potrf), Q = B R^-1 (trtri, gemm), then two plain
+    CholeskyQR passes.  The shift bounds cond(Q) of the first pass by about u^-1/2 for cond(B) up to about 1 / (u sqrt(11 m k)).
+    Raises numpy.linalg.LinAlgError when B is numerically rank deficient: a pivot of the second or third pass that is not positive,
+    or a pivot of the second pass at or below u -- a column whose part outside the span of the earlier ones is smaller than the
+    shift, which the second pass would otherwise scale up from rounding noise to a unit vector."""
+    torch = require_gpu()
+    if not (isinstance(B, torch.Tensor) and B.is_cuda and B.dtype == torch.float64 and B.dim() == 2):
+        raise ValueError('orthonormalise: a two-dimensional float64 device tensor is expected')
+    m, k = int(B.shape[0]), int(B.shape[1])
+    if not (1 <= k <= JACOBI_MAX and m >= k):
+        raise ValueError('orthonormalise: {0} x {1} is outside 1 <= columns <= {2}, rows >= columns'.format(m, k, JACOBI_MAX))
+    Q = B
+    for step in range(3):
+        gram = gemm(Q, Q, transa=True)
+        if step == 0:
+            shift = 11.0 * (m * k + k * (k + 1)) * _UNIT_ROUNDOFF * float(torch.diagonal(gram).sum().item())
+            torch.diagonal(gram).add_(shift)
+        try:
+            potrf(gram)
+        except np.linalg.LinAlgError as err:
+            if step == 0:
+                raise np.linalg.LinAlgError('orthonormalise: the shifted Gram matrix is not positive definite (non-finite input?)') from err
+            raise np.linalg.LinAlgError('orthonormalise: the columns are numerically rank deficient (pass {0}: {1})'.format(step + 1, err)) from err
+        if step == 1 and not float(torch.diagonal(gram).min().item()) ** 2 > _UNIT_ROUNDOFF:
+            raise np.linalg.LinAlgError('orthonormalise: the columns are numerically rank deficient (a pivot of pass 2 is at rounding level)')
+        Q = gemm(Q, trtri(gram))
+    return Q

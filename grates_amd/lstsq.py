@@ -13,8 +13,10 @@ lives in HBM as its own fp64 tensor and every block operation is a libshg call:
 Vectors may be passed as NumPy arrays (results come back as NumPy arrays, like the reference) or as device tensors
 (results stay on the device).  There is no CPU fallback.
 
-Not built (outside the smoother path): UnscentedTransformSymmetric, teigh, trsvd,
-AutoregressiveModel.from_transformed_coefficients (pseudo-inverse).
+Dense eigen and singular value decompositions (teigh, trsvd, and UnscentedTransformSymmetric on their results) run on
+shg_jacobi_svd, one-sided Jacobi rotations in LDS, with the products around it on shg_gemm.
+
+Not built: AutoregressiveModel.from_transformed_coefficients (pseudo-inverse).
 """
 
 import collections
@@ -2436,3 +2438,173 @@ def robust_least_squares(l, A, threshold=2.5, downweight_power=1.5, redundancy_t
             break
     x = x.reshape(p)
     return (engine.to_host(x), engine.to_host(C), flags.cpu().numpy()) if host else (x, C, flags)
+
+
+class UnscentedTransformSymmetric:
+    """
+    Unscented transform on the symmetric sigma point set of Julier and Uhlmann (Proc. IEEE 92, 2004), grates/lstsq.py:1152-1250: the
+    same constructor, set_size, weights(), sigma_points, average and sigma_point_covariance.  dim: dimension of the random variable
+    (the number of eigenpairs used), w0 < 1: the weight of the central point.  Arrays may be NumPy arrays (NumPy results) or device
+    tensors (device results); the products run on engine.gemm.
+
+    One deviation: the reference adds +sqrt(dim / (1 - w0)) sqrt(lambda_i) v_i for BOTH halves of the set (its scale vector has no
+    negative entries), so its points are not symmetric and their weighted mean is not x0.  Here the second half has the minus sign
+    of the paper: average(sigma_points(x0, ...)) is x0, and sigma_point_covariance of the deviations from it is V diag(lambda) V^T.
+    """
+
+    def __init__(self, dim, w0):
+        self.w0 = w0
+        self.dim = dim
+        self.__w = np.full(self.set_size, 0.5 * (1 - self.w0) / self.dim)
+        self.__w[0] = self.w0
+        self.__s = np.full(self.set_size, np.sqrt(self.dim / (1 - self.w0)))
+        self.__s[0] = 0
+        self.__s[self.dim + 1:] *= -1.0
+
+    @property
+    def set_size(self):
+        """the number of sigma points, 2 dim + 1"""
+        return 2 * self.dim + 1
+
+    def weights(self):
+        """the weights of the mean and of the covariance (the same NumPy vector [2 dim + 1] twice, as in the reference)"""
+        return self.__w, self.__w
+
+    def sigma_points(self, x0, eigen_values, eigen_vectors):
+        """S [n, 2 dim + 1] = x0, x0 + s sqrt(lambda_i) v_i, x0 - s sqrt(lambda_i) v_i (i < dim, s = sqrt(dim / (1 - w0))) for the mean
+        x0 [n], eigenvalues [p] and eigenvectors [n, p] with p >= dim, as teigh returns them: one broadcast on the device"""
+        n, p = tuple(eigen_vectors.shape)
+        if int(x0.shape[0]) != n or int(eigen_values.shape[0]) != p or p < self.dim:
+            raise ValueError('sigma_points: x0 {0}, eigenvalues {1} and eigenvectors {2} do not fit dimension {3}'.format(
+                tuple(x0.shape), tuple(eigen_values.shape), (n, p), self.dim))
+        torch = engine.require_gpu()
+        pick = torch.arange(self.set_size, device=engine.device())
+        pick = (torch.where(pick > self.dim, pick - self.dim, pick) - 1).clamp_min(0)  # the eigenpair of every point (the centre: any)
+        s = engine.to_device(self.__s)
+        scale = torch.where(s == 0.0, s, s * torch.sqrt(_dev(eigen_values))[pick])     # the centre has s = 0
+        return _like_input(_dev(x0).reshape(n, 1) + _dev(eigen_vectors)[:, pick] * scale, x0)
+
+    def average(self, sigma_points):
+        """x [n] = sum_j w_j S[:, j]"""
+        w, _ = self.weights()
+        return _like_input(engine.gemm(_dev(sigma_points), engine.to_device(w).reshape(-1, 1)).reshape(-1), sigma_points)
+
+    def sigma_point_covariance(self, sigma_points):
+        """C [n, n] = (S * w) S^T (not centred, as in the reference: pass deviations from the mean for a covariance about it)"""
+        _, w = self.weights()
+        S = _dev(sigma_points)
+        return _like_input(engine.gemm(S * engine.to_device(w), S, transb=True), sigma_points)
+
+
+TEIGH_BLOCK = engine.JACOBI_MAX        # width of the iterated subspace of teigh (the Rayleigh-Ritz problem must fit engine.syev)
+TEIGH_OVERSAMPLING = 16                # columns of that subspace beyond the wanted pairs, at least
+_DEFAULT_SEED = 20040301
+
+
+def _device_generator(generator, device):
+    """a torch generator on `device`: `generator` itself when it is one, else seeded from it (an int, a numpy Generator or
+    RandomState, a torch generator of another device) or, for None, from a fixed default so that calls repeat"""
+    torch = engine._torch()
+    if isinstance(generator, torch.Generator) and generator.device == device:
+        return generator
+    if generator is None:
+        seed = _DEFAULT_SEED
+    elif isinstance(generator, torch.Generator):
+        seed = generator.initial_seed()
+    elif isinstance(generator, np.random.Generator):
+        seed = int(generator.integers(2 ** 62))
+    elif isinstance(generator, np.random.RandomState):
+        seed = int(generator.randint(2 ** 31 - 1))
+    else:
+        seed = int(generator)
+    return torch.Generator(device=device).manual_seed(seed)
+
+
+def _check_count(name, what, count, most):
+    if int(count) != count or not 1 <= int(count) <= most:
+        raise ValueError('{0}: {1} {2} is outside 1 .. {3}'.format(name, what, count, most))
+    return int(count)
+
+
+def teigh(M, eigenvalue_count, tolerance=1e-12, max_iter=100, generator=None):
+    """
+    Truncated eigenvalue decomposition of a symmetric matrix (grates/lstsq.py:1253-1274): the eigenvalue_count largest eigenvalues
+    w [k], descending, and their eigenvectors v [n, k], NumPy arrays or device tensors as M.  Like the reference (lower=False) the
+    strict lower triangle of M is never read.
+
+    n <= 128: all eigenpairs by engine.syev (Jacobi rotations in LDS), of which the top k are returned; tolerance, max_iter and
+    generator play no part.  n > 128: block subspace iteration with Rayleigh-Ritz extraction on a block of 128 columns, k <= 112
+    (ValueError above: at least 16 columns oversample).  Q = orthonormalise(randn(n, 128)); then Y = M Q on the fp64 MFMA (M
+    mirrored once into a work copy), H = Q^T Y, its eigenpairs by engine.syev, the k largest Ritz pairs (theta_i, v_i = Q s_i); it
+    ends when max_i |M v_i - theta_i v_i|_2 <= tolerance |M|_F and continues with Q = orthonormalise(Y) otherwise.
+    numpy.linalg.LinAlgError after max_iter iterations without convergence, and from orthonormalise when M Q is numerically rank
+    deficient (rank of M below 128: no eigenvalue decay left to iterate on).  The iteration finds the eigenvalues of largest
+    magnitude; they are the largest ones for the positive semi-definite matrices (covariances, normals) this is meant for.
+    generator: an int seed, a numpy or torch generator, or None for a fixed seed; the same seed gives the same result.
+    """
+    shape = tuple(int(s) for s in M.shape)
+    if len(shape) != 2 or shape[0] != shape[1]:
+        raise ValueError('teigh: a square matrix is expected, got shape {0}'.format(shape))
+    n = shape[0]
+    k = _check_count('teigh', 'eigenvalue_count', eigenvalue_count, n)
+    if n > engine.JACOBI_MAX and k > TEIGH_BLOCK - TEIGH_OVERSAMPLING:
+        raise ValueError('teigh: eigenvalue_count {0} above {1} for a matrix wider than {2}'.format(k, TEIGH_BLOCK - TEIGH_OVERSAMPLING,
+                                                                                                 engine.JACOBI_MAX))
+    if int(max_iter) < 1:
+        raise ValueError('teigh: max_iter must be at least 1')
+    torch = engine.require_gpu()
+    A = _dev(M)
+    if n <= engine.JACOBI_MAX:
+        w, v, _ = engine.syev(A)
+        return _like_input(w[n - k:].flip(0), M), _like_input(v[:, n - k:].flip(1), M)
+    _mirror_upper(A)
+    norm = float(torch.linalg.norm(A).item())
+    b = TEIGH_BLOCK
+    Q = engine.orthonormalise(torch.randn((n, b), generator=_device_generator(generator, A.device), dtype=torch.float64, device=A.device))
+    for _ in range(int(max_iter)):
+        Y = engine.gemm(A, Q)
+        H = engine.gemm(Q, Y, transa=True)
+        theta, S, _ = engine.syev(0.5 * (H + H.t()))
+        theta, S = theta[b - k:].flip(0), S[:, b - k:].flip(1)
+        v = engine.gemm(Q, S)
+        residual = float((engine.gemm(Y, S) - v * theta).norm(dim=0).max().item())
+        if residual <= tolerance * norm:
+            return _like_input(theta, M), _like_input(v, M)
+        Q = engine.orthonormalise(Y)
+    raise np.linalg.LinAlgError('teigh: residual {0:.3e} above {1:.3e} = tolerance |M|_F after {2} iterations'.format(
+        residual, tolerance * norm, int(max_iter)))
+
+
+def trsvd(A, singular_value_count, iteration_count=5, generator=None):
+    """
+    Randomized truncated singular value decomposition after Halko, Martinsson and Tropp (SIAM Review 53, 2011), the loop of
+    grates/lstsq.py:1277-1314: Q = orth(A Omega) with a Gaussian Omega [n, k], then iteration_count rounds of Q = orth(A orth(A^T Q)),
+    and the decomposition of B = Q^T A [k, n].  Returns U [m, k], s [k] descending and Vt [k, n], NumPy arrays or device tensors as A,
+    with A ~ U diag(s) Vt.  k = singular_value_count <= min(m, n, 128), ValueError otherwise.
+
+    Every product runs on the fp64 MFMA, every orth is engine.orthonormalise (shifted CholeskyQR3).  The small decomposition does not
+    go through B B^T, which would square the condition number: B^T = Q2 R2 (orthonormalise, R2 = Q2^T B^T [k, k]), R2^T = Us S Vs^T by
+    engine.jacobi_svd, U = Q Us, Vt = (Q2 Vs)^T.  The reference's numpy.linalg.svd(B) returns a full [n, n] Vt whose rows from k on
+    are an arbitrary basis of the null space of B; those rows are not produced here.  numpy.linalg.LinAlgError (from
+    orthonormalise) when the rank of A is numerically below k.
+    generator: an int seed, a numpy or torch generator, or None for a fixed seed; the same seed gives the same result.
+    """
+    shape = tuple(int(s) for s in A.shape)
+    if len(shape) != 2:
+        raise ValueError('trsvd: a matrix is expected, got shape {0}'.format(shape))
+    m, n = shape
+    k = _check_count('trsvd', 'singular_value_count', singular_value_count, min(m, n, engine.JACOBI_MAX))
+    if int(iteration_count) < 0:
+        raise ValueError('trsvd: iteration_count must not be negative')
+    torch = engine.require_gpu()
+    Ad = _dev(A)
+    omega = torch.randn((n, k), generator=_device_generator(generator, Ad.device), dtype=torch.float64, device=Ad.device)
+    Q = engine.orthonormalise(engine.gemm(Ad, omega))
+    for _ in range(int(iteration_count)):
+        Q = engine.orthonormalise(engine.gemm(Ad, Q, transa=True))
+        Q = engine.orthonormalise(engine.gemm(Ad, Q))
+    Bt = engine.gemm(Ad, Q, transa=True)
+    Q2 = engine.orthonormalise(Bt)
+    R2 = engine.gemm(Q2, Bt, transa=True)
+    Us, s, Vst, _ = engine.jacobi_svd(R2.t().contiguous())
+    return _like_input(engine.gemm(Q, Us), A), _like_input(s, A), _like_input(engine.gemm(Vst, Q2, transb=True), A)

@@ -906,6 +906,24 @@ int shg_segment_lag_long_info(int* chunk, int* tile_lags, int* max_lags);
 int shg_window_expand(long long rows, int n, const double* T, long long ldt, const int32_t* run_slot, const int32_t* run_begin, int runs,
                       const double* factors, int W, int E, double* S, long long lds, long long slot_stride, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * One-sided Jacobi singular value decomposition of small matrices, one workgroup per matrix, G in LDS for the whole call
+ * (jacobi.hip; no reference counterpart)
+ *   G [batch][r][ldg] row-major with c columns in use (device), in: the matrices, out: G V = U diag(sigma): its columns are
+ *   orthogonal.  V [batch][c][ldv]: the right singular vectors as columns (the product of the rotations); may not be NULL.
+ *   sigma [batch][c]: the column norms of the final G in the order of its columns (unsorted).  sweeps [batch] (device int): sweeps
+ *   used, the last of them without a rotation, or -1 when max_sweeps (>= 1) did not suffice.
+ *   Limits: 1 <= r <= 128, 1 <= c <= 128 (128 x 129 doubles of the CU's 160 KiB of LDS), batch >= 1, ldg >= c, ldv >= c, and for
+ *   batch > 1 strides that cover one matrix; anything else returns SHG_ERR_INVALID before any HIP call.  r < c is allowed (the
+ *   surplus columns end as zeros up to rounding).
+ *   Round-robin order of the pairs, rotation when |g_p.g_q| > sqrt(r) 2^-53 |g_p| |g_q| (LAPACK dgesvj); the order of every sum is
+ *   fixed, so repeated calls are bitwise equal.  A zero column stays zero.  Non-finite input fires no rotation: the call reports one
+ *   sweep and its outputs are unspecified, but in bounds.  Entries of G and V beyond column c and sigma, G, V of other matrices are
+ *   not touched.  Where G and V do not fit the LDS together, V is kept in a stream-ordered workspace of batch c^2 doubles.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_jacobi_svd(double* G, int ldg, long strideG, double* V, int ldv, long strideV, double* sigma, int r, int c, int batch, int max_sweeps,
+                   int* sweeps, void* stream);
+
 /* Some operations keep their scratch buffers per stream between calls (the split-K workspace of the block products, the
  * buffers of shg_analysis: freeing stream-ordered memory costs more than these calls take).  This gives them back; it waits
  * for the device first. */
