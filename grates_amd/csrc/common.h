@@ -19,6 +19,7 @@ namespace shg {
 typedef double double4_t __attribute__((ext_vector_type(4)));        // the accumulator of one v_mfma_f64_16x16x4_f64
 
 int fail(int code, const char* fmt, ...);
+unsigned hip_failures();      // how many HIP errors fail() has reported so far: device state that a launch leaves behind is suspect when this has moved
 // Zero fills as kernels of this library (plan.hip), for the paths that several host threads feed at once (the chains of the
 // block-banded smoother, one thread and one stream each): on ROCm 7.2 a 4-byte hipMemsetAsync issued from four threads on
 // four streams left 0x80808080 in its target about four runs in five (the pivot flag of blockchol.hip's factorisation; with a
@@ -347,8 +348,10 @@ struct shg_plan {
     int itemtab_rot = -1;       // panel slot convention of the work items: 0 = 4-fold kernel, R = rotation-folded kernel
     const double* om_src = nullptr;   // set for the duration of shg_synthesis_om: the coefficient repack reads this order-major series
     int om_N = 0, om_Bpad = 0;
-    shg::DeviceArray<int> sem_d; // token counter of the rotation-folded kernel's Legendre stage (synthesis_rot.hip), allocated by rot_set_stage_limit
-    int stage_limit = 0;        // workgroups that may run their Legendre stage at once (0 = no limit, the default)
+    shg::DeviceArray<int> tickets_d; // ticket queues of the rotation-folded kernel's Legendre stage, one 128-byte line per XCD (synthesis_rot.hip), allocated and zeroed by rot_set_stage_limit
+    unsigned tickets_failures = 0;   // hip_failures() when the queues were last zeroed: zeroed again before the first launch after a HIP error
+    int stage_limit = 0;        // workgroups that may run their Legendre stage at once (0 = no limit)
+    bool stage_limit_set = false;    // by rot_set_stage_limit; until then the first launch of that kernel sets the default (synthesis_rot.hip)
     shg::DeviceArray<int> blockmap_d; // XCD-aware (epoch tile, parallel tile) order of the fused kernel's workgroups
     int blockmap_nbt = 0, blockmap_nit = 0;
     std::vector<char> ns_badrow;    // per northern parallel: mirror image deviates too much to share the northern table

@@ -1,6 +1,7 @@
 // Plan creation: host-side generation of the small per-plan tables (recursion factors, sectorial
 // seeds, cos/sin tables) and their upload.  Table arithmetic keeps the reference's expression order
 // (grates/utilities.py:41-54) so that the Legendre values are bit-identical to the NumPy ones.
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -16,6 +17,7 @@
 namespace shg {
 
 static thread_local std::string g_last_error;
+static std::atomic<unsigned> g_hip_failures{0};       // HIP errors returned so far by any entry point (hip_failures())
 
 int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -24,8 +26,11 @@ int fail(int code, const char* fmt, ...) {
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     g_last_error = buf;
+    if (code == SHG_ERR_HIP) g_hip_failures.fetch_add(1, std::memory_order_relaxed);
     return code;
 }
+
+unsigned hip_failures() { return g_hip_failures.load(std::memory_order_relaxed); }
 
 // Stream-ordered scratch memory.  The default memory pool of a device gives freed memory back to the driver at the next
 // synchronisation unless its release threshold is raised; with the threshold at its maximum hipMallocAsync / hipFreeAsync

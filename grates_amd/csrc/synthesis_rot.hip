@@ -86,8 +86,8 @@ struct RotParams {
     const double* pkf;
     const int4* itemtab;
     int nrec, ntrip;
-    int* sem;                 // tokens of the Legendre stage in use (device-wide counter, 0 between launches)
-    int sem_limit;            // at most this many workgroups run their Legendre stage at the same time (0 = no limit)
+    int* tickets;             // ticket queues of the Legendre stage, one 128-byte line per XCD: {tickets handed out, stages finished}, 0 between launches
+    int xcd_limit;            // at most this many workgroups of one XCD run their Legendre stage at the same time (0 = no limit)
 #ifdef SHG_TIMELINE
     unsigned long long* tl;
 #endif
@@ -523,11 +523,55 @@ __device__ __forceinline__ void rot_phase2(const RotParams& P, const double* As,
 
 __device__ __forceinline__ void panel_put(double2_t* panel, int index, double2_t v) { panel[index] = v; }
 
+// Tickets of the Legendre stage.  A workgroup does not store while it runs its Legendre stage, and workgroups that share the HBM fall
+// into step (tools/timeline.py: the whole chip in the Legendre stage at once, the HBM idle, then the whole chip storing at twice the
+// rate the HBM takes).  In step the stage runs at the rate the L2s deliver its operands (690 KB per tile, every byte used once per
+// workgroup: 15 - 17 TB/s chip-wide), not at its MFMA time, and the L2 is a resource of the XCD: so the limit is kept per
+// XCD.  Workgroups b, b + 8, ... share an XCD and a queue of two words in a 128-byte line of their own: `head`, the tickets handed
+// out, and `served`, the stages finished.  A workgroup draws ticket t = head++ and enters the stage when t - served < limit; behind the
+// stage it adds one to served.  First come, first served; nobody takes anything back, waiters add to neither word, and a release
+// writes a word that only releases write.  Nothing but speed depends on the workgroups of a queue really sharing an XCD.
+//   * A waiter LOOKS at served with a read-modify-write that changes nothing: atomics execute at the memory side, a plain agent-scope
+//     load was served by the XCD's L2 and saw a release ~100 us late.
+//   * A waiter knows its distance d = t - served - limit + 1, the stages that must end before its turn, and the limit stages that run
+//     meanwhile end about one per (stage time / limit): it naps half of d such intervals in units of 0.27 us (s_sleep 10 at 2.4 GHz)
+//     and looks again, so that it looks once or twice per stage from far away and every 0.27 us plus the look's own round trip (~1 us
+//     beside the stores of the others) when it is next.  The stage time is taken as one unit per item of a wave (5 - 6 us for the 22
+//     items of a full block at d/o 96 when few workgroups share the L2).
+//   * The wait is bounded to a few milliseconds of naps and looks (words left unequal by an aborted launch must not hang the next
+//     one); a workgroup that gave up runs its stage and releases like every other, so the counts stay paired.
+//   * The last release of a queue's share of the grid takes both words back to 0 (each has been added to exactly `share` times).
+constexpr int kTicketQueues = 8, kTicketLineInts = 32;      // one queue per XCD, 128 bytes apart
+constexpr int kTicketNapBudget = 12000;                    // nap units (0.27 us), a look counts as four
+
+__device__ __forceinline__ void legendre_ticket_acquire(int* queue, int limit, int stage_units) {
+    const int t = __hip_atomic_fetch_add(queue, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int budget = kTicketNapBudget; budget > 0;) {
+        // (the look: a compare-and-swap of a value the word never holds against itself.  hipcc folds an add of 0 into the plain load.)
+        int served = -1;
+        (void)__hip_atomic_compare_exchange_strong(queue + 1, &served, -1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int d = t - served - limit + 1;
+        if (d <= 0) return;
+        const int naps = min(max(d * stage_units / (2 * limit), 1), 64);
+        for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(10);
+        budget -= naps + 4;
+    }
+}
+__device__ __forceinline__ void legendre_ticket_release(int* queue, int share) {
+    if (__hip_atomic_fetch_add(queue + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == share) {      // the last of this queue: every ticket is drawn, nobody waits
+        (void)__hip_atomic_fetch_add(queue, -share, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_add(queue + 1, -share, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // Phase 1: Legendre stage of tile (bt, it) (see synthesis_fused.hip).  The orders of the tile are dealt to the waves that call this
 // (work-item records `recs`, one list per wave); the result of order m is one 16-byte pair (A_m, B'_m) per panel row, written to
 // `panel` -- the LDS panel of the tile, or (persistent kernel) the image of the NEXT tile's panel in global memory.
+// `queue`: the ticket queue of the workgroup when the plan limits the stage (P.xcd_limit > 0).  The wait for the turn sits behind the
+// operand loads of the first three items: they are issued unconditionally either way, and a workgroup that gets its turn starts with
+// its pipeline full instead of one L2 round trip behind.
 template <bool NS, typename PanelPtr>
-__device__ __forceinline__ void rot_phase1(const RotParams& P, PanelPtr panel, const int4* recs_wave, int bt, int it, int lane) {
+__device__ __forceinline__ void rot_phase1(const RotParams& P, PanelPtr panel, const int4* recs_wave, int bt, int it, int lane, int* queue) {
     const int fr = lane & 15, fk = lane >> 4;
     // Everything that is the same for all lanes stays on the scalar unit: the work-item records come through scalar loads
     // (constant address space), every operand load is "scalar base + lane offset fixed for the kernel", the flags of a record
@@ -623,6 +667,11 @@ do {                                                                            
         __builtin_amdgcn_sched_barrier(0);
         ROT_P1_ISSUE(c2, zal, zah, zbl, zbh);
         __builtin_amdgcn_sched_barrier(0);
+        if (pass == 0 && P.xcd_limit > 0) {                       // (uniform) the turn of this workgroup; the other waves wait at the barrier
+            if (threadIdx.x == 0) legendre_ticket_acquire(queue, P.xcd_limit, P.nrec);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+        }
         for (int trip = 0; trip < P.ntrip; ++trip) {
             const int4_v a3 = n0, a4 = n1, a5 = n2, a6 = n3;
             crec_t* nr = recs + 4 * trip + 7;
@@ -646,29 +695,6 @@ do {                                                                            
 #undef ROT_P1_ISSUE
 #undef ROT_P1_CONSUME
 }
-
-// Tokens of the Legendre stage.  A workgroup does not store while it runs its Legendre stage, and workgroups that share the HBM fall
-// into step (tools/timeline.py: the whole chip in the Legendre stage at once, the HBM idle, then the whole chip storing at twice the
-// rate the HBM takes).  A quarter of the CUs saturate the HBM's write path (tools/store_bench.hip), so it is enough that never more
-// than `limit` workgroups are in the stage at once: one lane takes a token before the stage and returns it behind it.  The wait is
-// bounded to a few milliseconds (a counter left non-zero by an aborted launch must not hang the next one); the counter is 0 again
-// when the grid has drained.
-__device__ __forceinline__ void legendre_token_acquire(int* sem, int limit) {
-    // Take with an atomic add (any number of workgroups get their token in the same round trip; a compare-and-swap lets one through
-    // per round trip: measured 250 us for the first 128), give back when the add shows that the limit was passed.  A waiter only LOOKS
-    // (an add of 0: atomics execute at the memory side, a plain agent-scope load is served by this XCD's L2 and saw a returned token
-    // ~100 us late) and adds again when it has seen a free token, so that the counter is not inflated by the waiters.
-    for (int spin = 0; spin < 600; ++spin) {
-        if (__hip_atomic_fetch_add(sem, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < limit) return;
-        (void)__hip_atomic_fetch_add(sem, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        do {                               // (long naps: a few hundred waiters polling one word every microsecond keep the releases from it)
-            __builtin_amdgcn_s_sleep(127);
-            ++spin;
-        } while (spin < 600 && __hip_atomic_fetch_add(sem, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= limit);
-    }
-    (void)__hip_atomic_fetch_add(sem, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // (gave up waiting: the release still pairs)
-}
-__device__ __forceinline__ void legendre_token_release(int* sem) { (void)__hip_atomic_fetch_add(sem, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 template <bool NS, int R>
 __global__ __launch_bounds__(128 * EP) void synthesis_rot_kernel(RotParams P) {
@@ -734,14 +760,11 @@ __global__ __launch_bounds__(128 * EP) void synthesis_rot_kernel(RotParams P) {
     for (int d = 0; d < kRingDepth; ++d) rot_issue_piece(S, P, (unsigned)lane * 16u);
 
     // ---- phase 1: Legendre stage.  Orders are distributed over the waves of the workgroup.
-    if (P.sem_limit > 0) {
-        if (tid == 0) legendre_token_acquire(P.sem, P.sem_limit);
-        __syncthreads();
-    }
-    if (!SHG_DBG(P, 2)) rot_phase1<NS>(P, panel, P.itemtab + (size_t)wave * P.nrec, bt, it, lane);
+    int* const queue = P.tickets + (blockIdx.x % kTicketQueues) * kTicketLineInts;
+    if (!SHG_DBG(P, 2)) rot_phase1<NS>(P, panel, P.itemtab + (size_t)wave * P.nrec, bt, it, lane, queue);
     ROT_STAMP(1);
     __syncthreads();          // panel complete; from here on it is read-only and the waves run independently
-    if (P.sem_limit > 0 && tid == 0) legendre_token_release(P.sem);
+    if (P.xcd_limit > 0 && !SHG_DBG(P, 2) && tid == 0) legendre_ticket_release(queue, ((int)gridDim.x - (int)(blockIdx.x % kTicketQueues) + kTicketQueues - 1) / kTicketQueues);
     ROT_STAMP(2);
 #ifdef SHG_EXPERIMENT
     if (P.stagger2 > 0 && wave >= EP) {
@@ -1015,6 +1038,42 @@ static int launch_rot(bool ns, const RotParams& P, size_t lds, dim3 grid_dim, hi
     return SHG_OK;
 }
 
+// the ticket queues back to zero, synchronously: no launch is in flight when they are written and none can see them half written
+static int zero_tickets(shg_plan* p) {
+    const unsigned seen = hip_failures();
+    if (!p->tickets_d && p->tickets_d.assign(kTicketQueues * kTicketLineInts) != hipSuccess) return fail(SHG_ERR_NOMEM, "ticket queue allocation failed");
+    SHG_HIP(hipDeviceSynchronize());
+    SHG_HIP(hipMemset(p->tickets_d.get(), 0, p->tickets_d.size() * sizeof(int)));
+    SHG_HIP(hipDeviceSynchronize());
+    p->tickets_failures = seen;
+    return SHG_OK;
+}
+
+static int device_cus(int* cus) {
+    int dev = 0;
+    SHG_HIP(hipGetDevice(&dev));
+    SHG_HIP(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return SHG_OK;
+}
+
+// The limit of a plan on which rot_set_stage_limit was never called.  Measured on the headline (240 x d/o 96 -> 0.25 degree, 2700
+// workgroups; tools/stage_limit_sweep.py, profiles/tickets_ab.txt): 4/16 of the CUs in the stage at once is the best setting (-4.1 % of
+// the step), 5/16 and 6/16 take 2 % off, 3/16 no longer admits the share of the CUs that the stage needs and costs 12 %.  That share
+// is the stage's part of a tile's time: the stage's time goes with its operand octets (Qtot, 345 on the headline), the rest of the
+// tile's with the nlon (1440) columns it computes and stores -- so the default scales 4/16 by (Qtot / nlon) / (345 / 1440) and is no
+// limit where that reaches the whole device.  A grid of at most one workgroup per CU has nothing to keep out of step: no limit either.
+static int default_stage_limit(const shg_plan* p, int workgroups, int* limit) {
+    int cus = 0;
+    const int rc = device_cus(&cus);
+    if (rc) return rc;
+    *limit = 0;
+    if (workgroups <= cus) return SHG_OK;
+    const double share = 4.0 / 16.0 * ((double)p->Qtot / p->nlon) / (345.0 / 1440.0);
+    const int n = (int)std::ceil(cus * share);
+    if (n < cus) *limit = std::max(n, kTicketQueues);
+    return SHG_OK;
+}
+
 int synthesis_rot(shg_plan* p, const double* anm, int B, double* grid, hipStream_t stream) {
     if (!rot_applicable(p)) return fail(SHG_ERR_UNSUPPORTED, "rotation-folded synthesis kernel not applicable to this plan");
     const int R = p->rotR;
@@ -1047,10 +1106,22 @@ int synthesis_rot(shg_plan* p, const double* anm, int B, double* grid, hipStream
     P.itemtab = reinterpret_cast<const int4*>(p->itemtab_d.get());
     P.nrec = p->itemtab_nrec;
     P.ntrip = p->itemtab_ntrip;
-    P.sem = p->sem_d.get();                         // allocated and zeroed by rot_set_stage_limit; 0 again whenever a grid has drained
-    P.sem_limit = p->sem_d ? p->stage_limit : 0;
+    int limit = p->stage_limit;
+    if (!p->stage_limit_set) {                      // nobody has called rot_set_stage_limit: the default
+        rc = default_stage_limit(p, nbt * nit, &limit);
+        if (rc) return rc;
+    }
+    // The queues are allocated and zeroed synchronously before the first launch that uses them and are 0 again whenever a grid has
+    // drained.  A launch that did not drain may have left them unequal, and such a launch shows as a HIP error of some later call: zero
+    // them again behind any.
+    if (limit > 0 && (!p->tickets_d || p->tickets_failures != hip_failures())) {
+        rc = zero_tickets(p);
+        if (rc) return rc;
+    }
+    P.tickets = p->tickets_d.get();
+    P.xcd_limit = limit > 0 ? ceil_div(limit, kTicketQueues) : 0;
 #ifdef SHG_EXPERIMENT
-    if (getenv("SHG_SEM") && p->sem_d) P.sem_limit = atoi(getenv("SHG_SEM"));
+    if (getenv("SHG_SEM") && limit > 0) P.xcd_limit = ceil_div(atoi(getenv("SHG_SEM")), kTicketQueues);
 #endif
     P.badmap = p->badmap_d.get();
     P.blockmap = nullptr;
@@ -1082,23 +1153,23 @@ int synthesis_rot(shg_plan* p, const double* anm, int B, double* grid, hipStream
     return SHG_OK;
 }
 
-// Limit on the workgroups that run their Legendre stage at once (see legendre_token_acquire).  OFF by default: over six boxes of the
-// pool a limit of 7/16 of the CUs took 1.5 - 2 % off the kernel on the slower three and cost 2 - 4 % on the faster three (DESIGN.md
-// Appendix A) -- a tuning knob, not a default.  limit > 0: that many workgroups; < 0: that many sixteenths of the device's CUs;
-// 0: no limit.  The counter is allocated and zeroed here, synchronously, so that no launch can see it uninitialised.
+// Limit on the workgroups that run their Legendre stage at once (see legendre_ticket_acquire), kept per XCD: an eighth of it, rounded
+// up, per ticket queue.  limit > 0: that many workgroups; < 0: that many sixteenths of the device's CUs; 0: no limit.  A plan on which
+// this was never called runs with default_stage_limit; any call, 0 included, replaces the default for good.  The queues are allocated
+// and zeroed here, synchronously, so that no launch can see them uninitialised or left unequal by an aborted launch.
 int rot_set_stage_limit(shg_plan* p, int limit) {
     if (limit < 0) {
-        int dev = 0, cus = 0;
-        SHG_HIP(hipGetDevice(&dev));
-        SHG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        int cus = 0;
+        const int rc = device_cus(&cus);
+        if (rc) return rc;
         limit = std::max(1, cus * -limit / 16);
     }
-    if (limit > 0 && !p->sem_d) {
-        if (p->sem_d.assign(64) != hipSuccess) return fail(SHG_ERR_NOMEM, "token counter allocation failed");
-        SHG_HIP(hipMemset(p->sem_d.get(), 0, 256));
-        SHG_HIP(hipDeviceSynchronize());
+    if (limit > 0) {
+        const int rc = zero_tickets(p);
+        if (rc) return rc;
     }
     p->stage_limit = limit;
+    p->stage_limit_set = true;
     return SHG_OK;
 }
 

@@ -105,8 +105,9 @@ class Plan:
         _lib.call('shg_plan_set_path', self._handle, {'auto': 0, 'staged': 1, 'fused': 2, 'fused32': 5, 'rot': 6}[path])
 
     def set_stage_limit(self, limit):
-        """Rotation-folded kernel only: at most `limit` workgroups in their Legendre stage at once (< 0: sixteenths of the CUs, 0 = off,
-        the default).  A tuning knob whose sign differs between boxes (include/shg.h)."""
+        """Rotation-folded kernel only: at most `limit` workgroups in their Legendre stage at once (< 0: sixteenths of the CUs, 0 = off),
+        kept per XCD by ticket queues.  A plan on which this was never called limits grids of more than one workgroup per CU to a
+        share of the CUs that follows its shape (4/16 on the d/o 96 -> 0.25 degree headline)."""
         _lib.call('shg_plan_set_stage_limit', self._handle, int(limit))
 
     def set_order_pruning(self, enable):
