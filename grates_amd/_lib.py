@@ -160,6 +160,11 @@ PROTOTYPES = {
     'shg_segment_lag_products_long': [ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                       c_double_p, ctypes.c_void_p],
     'shg_segment_lag_long_info': [ctypes.POINTER(ctypes.c_int)] * 3,
+    'shg_whiten_rows_vector': [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, c_double_p, ctypes.c_int,
+                               ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p],
+    'shg_whiten_vector_info': [ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
+    'shg_segment_cross_lag_products': [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_double_p,
+                                       ctypes.c_void_p],
     'shg_window_expand': [ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p,
                           ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p],
     'shg_jacobi_svd': [c_double_p, ctypes.c_int, ctypes.c_long, c_double_p, ctypes.c_int, ctypes.c_long, c_double_p, ctypes.c_int, ctypes.c_int,

@@ -1467,6 +1467,79 @@ def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
     return out
 
 
+def whiten_vector_info(dimension):
+    """{'tile_columns'} of shg_whiten_rows_vector for models of that dimension: the output columns one workgroup takes.  Host only."""
+    tile = ctypes.c_int(0)
+    _lib.call('shg_whiten_vector_info', int(dimension), ctypes.byref(tile))
+    return {'tile_columns': int(tile.value)}
+
+
+def whiten_rows_vector(X, taps, stage, skip=0, out=None):
+    """Decorrelation of vector noise along the last axis of the device tensor X [..., M] (shg_whiten_rows_vector): the rows of X, all
+    axes but the last flattened, are groups of K consecutive rows, the K components of one series, and
+    Y[g K + c, t - skip] = sum_k sum_c' H[n][k][c][c'] X[g K + c', t - k] for skip <= t < M with n = min(stage[t], q, t).  taps
+    [q + 1, q + 1, K, K] (float64, 2 <= K <= 6, q <= 128) and stage [M] (int32) are device tensors, as lstsq.VectorNoise.taps and
+    lstsq.arc_stages build them.  A two-dimensional X or out may be a column slice of a wider matrix (unit stride along the rows);
+    anything else that is not dense is copied.  Returns out, or a new tensor [..., M - skip].  An output depends on the values of
+    its group, stage[t] and the taps only, and repeats bitwise in every call and tiling."""
+    torch = require_gpu()
+    M, skip = int(X.shape[-1]), int(skip)
+    lead = tuple(int(s) for s in X.shape[:-1])
+    if taps.dim() != 4 or taps.shape[0] != taps.shape[1] or taps.shape[2] != taps.shape[3] or taps.dtype != torch.float64 or not taps.is_contiguous():
+        raise ValueError('taps must be a dense float64 tensor of shape (q + 1, q + 1, K, K), got {0}'.format(tuple(taps.shape)))
+    q, K = int(taps.shape[0]) - 1, int(taps.shape[2])
+    if tuple(stage.shape) != (M,) or stage.dtype != torch.int32 or not stage.is_contiguous():
+        raise ValueError('stage must be a dense int32 tensor of shape ({0},), got {1} {2}'.format(M, stage.dtype, tuple(stage.shape)))
+    if X.dtype != torch.float64:
+        raise ValueError('X must be float64, got {0}'.format(X.dtype))
+    rows = 1
+    for size in lead:
+        rows *= size
+    if K < 1 or rows % K:
+        raise ValueError('the {0} rows of X are not groups of the {1} components of the model'.format(rows, K))
+
+    def rows_of(t, width):
+        """(tensor, leading dimension) of t as rows of `width` columns"""
+        if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= width:
+            return t, int(t.stride(0))
+        return t.contiguous(), width
+    X, ldx = rows_of(X, M)
+    if out is None:
+        out = torch.empty(lead + (max(M - skip, 0),), dtype=torch.float64, device=X.device)
+    elif tuple(out.shape) != lead + (M - skip,) or out.dtype != torch.float64 or rows_of(out, M - skip)[0] is not out:
+        raise ValueError('out must be a float64 tensor of shape {0}, dense or a column slice of a matrix'.format(lead + (M - skip,)))
+    _lib.call('shg_whiten_rows_vector', rows // K, K, M, _ptr(X), ldx, _ptr(stage), _ptr(taps), q, skip, _ptr(out), rows_of(out, M - skip)[1],
+              _stream())
+    return out
+
+
+def segment_cross_lag_products(X, seg, lags, out=None):
+    """Lagged products between the rows of the device tensor X [K, M], cut at arc boundaries (shg_segment_cross_lag_products):
+    S[s, k, c, c'] = sum of X[c, t] X[c', t + k] over seg[s] <= t, t + k < seg[s + 1], for k = 0 .. lags (0 <= lags <= 128, 1 <= K <= 6):
+    the empirical cross-covariance function of the components times the number of pairs.  seg [nseg + 1] (int32) holds the column
+    indices of the boundaries, a device tensor; the kernel clamps it to 0 .. M and makes it non-decreasing.  X may be a column slice
+    of a wider matrix (unit stride along the rows); anything else that is not dense is copied.  Returns out, or a new dense tensor
+    [nseg, lags + 1, K, K]; every entry is written, and S[s, k, c, c] is bitwise segment_lag_products of row c."""
+    torch = require_gpu()
+    if X.dim() != 2 or X.dtype != torch.float64:
+        raise ValueError('X must be a float64 tensor of shape (K, M), got {0} {1}'.format(X.dtype, tuple(X.shape)))
+    K, M, lags = int(X.shape[0]), int(X.shape[1]), int(lags)
+    if tuple(seg.shape) != (seg.numel(),) or seg.numel() < 1 or seg.dtype != torch.int32 or not seg.is_contiguous():
+        raise ValueError('seg must be a dense int32 tensor of shape (nseg + 1,), got {0} {1}'.format(seg.dtype, tuple(seg.shape)))
+    nseg = int(seg.numel()) - 1
+    if X.stride(1) == 1 and X.stride(0) >= M:
+        ldx = int(X.stride(0))
+    else:
+        X, ldx = X.contiguous(), M
+    shape = (nseg, max(lags, 0) + 1, K, K)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=X.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError('out must be a dense float64 tensor of shape {0}'.format(shape))
+    _lib.call('shg_segment_cross_lag_products', K, M, _ptr(X), ldx, lags, nseg, _ptr(seg), _ptr(out), _stream())
+    return out
+
+
 def segment_products(X, Bt, seg, channels=1, out=None):
     """Products of the rows of the device tensor X [..., M] with a basis, cut at arc boundaries (shg_segment_products):
     S[..., s, j] = sum of X[..., t] Bt[j, row % channels, t] over seg[s] <= t < seg[s + 1]; the rows of X, all axes but the last

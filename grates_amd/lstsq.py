@@ -341,6 +341,8 @@ def whitening_taps(noise_model):
             noise_model = list(noise_model)                # once: it may be an iterator
         except TypeError:
             pass
+    if isinstance(noise_model, list) and any(isinstance(model, VectorNoise) for model in noise_model):
+        raise ValueError('a VectorNoise couples all components of a point: pass it alone, not in a sequence of models, one per component')
     taps = _covariance_taps(noise_model)
     if taps is not None:
         return taps
@@ -375,6 +377,87 @@ def whitening_taps(noise_model):
     return taps
 
 
+MIN_VECTOR_DIMENSION, MAX_VECTOR_DIMENSION = 2, 6      # of shg_whiten_rows_vector: the components a lane of its kernel holds
+
+
+class VectorNoise:
+    """
+    Noise that couples the K components of a point, given by an AutoregressiveModelSequence of dimension K (VAR models of orders
+    0, 1, ..., q, as AutoregressiveModelSequence.from_covariance_function builds them from [K, K] lags), as a noise model of the
+    observations along the series of points (host, NumPy only; no reference counterpart).  Accepted
+    wherever a scalar AutoregressiveModelSequence is: ColouredNoise, ArcParameters(noise_model=), the noise_model keyword of
+    NormalEquations.from_accelerations, decorrelate, and through them RadialBasisParameters, TemporalParameters and every
+    PostFit.of_*.  A bare sequence of dimension K > 1 stays refused: the joint filter is opted into with this type.
+
+    taps() is the table H [q + 1, q + 1, K, K] of shg_whiten_rows_vector: H[s][0] = R_s^-T and H[s][k] = -R_s^-T B_k^(s) for
+    1 <= k <= s, zero beyond, from the coefficients B_k^(s) and the white-noise covariance Q_s = R_s^T R_s (R_s upper triangular) of
+    the model of order s.  With the start-up of an arc, stage[t] = min(t - arc start, q),
+    y[t] = sum_{k = 0 .. stage[t]} H[stage[t]][k] x[t - k] is the block lower-triangular banded W with
+    W^T W = sequence.normal_equations(L); for a sequence from a covariance function Sigma_k = E[x_t x_(t+k)^T], W Sigma_L W^T = I.
+
+    ValueError unless 2 <= K <= 6, the models have the orders 0, 1, ..., q with q <= 128, every coefficient is a finite [K, K]
+    matrix and every Q_s is finite, symmetric and positive definite (the order is named).
+    """
+
+    def __init__(self, sequence):
+        if not isinstance(sequence, AutoregressiveModelSequence):
+            raise ValueError('VectorNoise takes one AutoregressiveModelSequence, got {0!r}'.format(type(sequence).__name__))
+        models = sequence.models
+        q = len(models) - 1
+        if q < 0:
+            raise ValueError('a noise model without AR models')
+        if q > MAX_WHITENING_ORDER:
+            raise ValueError('maximum order {0} of the noise model above {1}'.format(q, MAX_WHITENING_ORDER))
+        K = int(np.shape(models[0].white_noise_covariance)[0]) if np.ndim(models[0].white_noise_covariance) == 2 else 1
+        if not MIN_VECTOR_DIMENSION <= K <= MAX_VECTOR_DIMENSION:
+            raise ValueError('vector noise of dimension {0}: expected {1} .. {2} (a scalar model is passed as the sequence itself)'.format(
+                K, MIN_VECTOR_DIMENSION, MAX_VECTOR_DIMENSION))
+        taps = np.zeros((q + 1, q + 1, K, K))
+        for s, model in enumerate(models):
+            if model.order != s:
+                raise ValueError('model {0} of the sequence has order {1}: expected the orders 0, 1, ..., {2}'.format(s, model.order, q))
+            Q = np.asarray(model.white_noise_covariance, dtype=np.float64)
+            # symmetric up to the rounding of the Yule-Walker solve that formed it (from_covariance_function: Q = Sigma_0 - X^T b as a product)
+            if Q.shape != (K, K) or not np.all(np.isfinite(Q)) or not np.all(np.abs(Q - Q.T) <= 1e-8 * np.max(np.abs(Q))):
+                raise ValueError('white-noise covariance of the model of order {0} is not a finite symmetric [{1}, {1}] matrix'.format(s, K))
+            try:
+                L = np.linalg.cholesky(np.triu(Q) + np.triu(Q, 1).T)          # the upper triangle, as engine.potrf reads it; Q = L L^T: R = L^T, R^-T = L^-1
+            except np.linalg.LinAlgError:
+                raise ValueError('white-noise covariance of the model of order {0} is not positive definite'.format(s)) from None
+            taps[s, 0] = np.linalg.inv(L)
+            for k in range(1, s + 1):
+                B = np.asarray(model.coefficients[k - 1], dtype=np.float64)
+                if B.shape != (K, K) or not np.all(np.isfinite(B)):
+                    raise ValueError('coefficient {0} of the model of order {1} is not a finite [{2}, {2}] matrix'.format(k, s, K))
+                taps[s, k] = -taps[s, 0] @ B
+        if not np.all(np.isfinite(taps)):
+            raise ValueError('the whitening taps of the noise model are not finite')
+        self.__sequence, self.__taps = sequence, taps
+
+    @property
+    def sequence(self):
+        return self.__sequence
+
+    @property
+    def dimension(self):
+        return int(self.__taps.shape[2])
+
+    @property
+    def maximum_order(self):
+        return int(self.__taps.shape[0]) - 1
+
+    def taps(self):
+        """ndarray [q + 1, q + 1, K, K]: H[s][0] = R_s^-T, H[s][k] = -R_s^-T B_k^(s) (1 <= k <= s), zero beyond"""
+        return self.__taps.copy()
+
+
+def _check_noise_model(noise_model):
+    """what the constructors check of a noise model: the ValueErrors of VectorNoise were raised when it was built, a scalar model goes
+    through whitening_taps"""
+    if not isinstance(noise_model, VectorNoise):
+        whitening_taps(noise_model)
+
+
 def _arc_starts(arcs, count):
     """start indices of the arcs of a series of `count` points, int64 ndarray (None: the single arc [0], no arc without points);
     ValueError unless they are integers, strictly increasing, start at 0 and stay below count"""
@@ -406,7 +489,13 @@ def arc_stages(arcs, count, order):
 
 def _whitening_tables(noise_model, arcs, count, components):
     """(taps [C, q + 1, q + 1], stage [count]) of a from_* call or of decorrelate, on the host; ValueError before anything reaches the
-    device"""
+    device.  A VectorNoise gives its taps [q + 1, q + 1, K, K] instead: the two kinds of table are told apart by the type of the
+    model, never by their shape"""
+    if isinstance(noise_model, VectorNoise):
+        if noise_model.dimension != components:
+            raise ValueError('a VectorNoise of dimension {0} for observations of {1} component{2}: the two must be equal'.format(
+                noise_model.dimension, components, '' if components == 1 else 's'))
+        return noise_model.taps(), arc_stages(arcs, count, noise_model.maximum_order)
     taps = whitening_taps(noise_model)
     if taps.shape[0] not in (1, components):
         raise ValueError('{0} noise models for {1} components: expected one, or one per component'.format(taps.shape[0], components))
@@ -417,7 +506,8 @@ def decorrelate(values, noise_model, arcs=None):
     """
     W values along the point axis, on the device (shg_whiten_rows): values [M] or [M, K] (host array or device tensor; the result
     has the same kind and shape), noise_model and arcs as in NormalEquations.from_accelerations.  What the normals of a whitened
-    adjustment see of the observations; residuals A x^ - l go through it the same way.
+    adjustment see of the observations; residuals A x^ - l go through it the same way.  A VectorNoise of dimension K whitens the K
+    components of values [M, K] jointly (shg_whiten_rows_vector).
     """
     shape = tuple(int(size) for size in values.shape)
     if len(shape) not in (1, 2):
@@ -426,7 +516,10 @@ def decorrelate(values, noise_model, arcs=None):
     taps, stage = _whitening_tables(noise_model, arcs, M, K)
     torch = engine.require_gpu()
     x = engine.to_device(values).reshape(M, K).t().contiguous()
-    y = engine.whiten_rows(x, engine.to_device(taps), torch.from_numpy(stage).to(x.device), channels=taps.shape[0])
+    if isinstance(noise_model, VectorNoise):
+        y = engine.whiten_rows_vector(x, engine.to_device(taps), torch.from_numpy(stage).to(x.device))
+    else:
+        y = engine.whiten_rows(x, engine.to_device(taps), torch.from_numpy(stage).to(x.device), channels=taps.shape[0])
     return _like_input(y.t().reshape(shape).contiguous(), values)
 
 
@@ -491,6 +584,28 @@ def frame_basis(basis, frames):
     if 3 * basis.shape[1] > MAX_ARC_PARAMETERS:
         raise ValueError('{0} columns of the frame basis: expected at most {1}'.format(3 * basis.shape[1], MAX_ARC_PARAMETERS))
     return np.einsum('ti,tak->tkia', basis, frames).reshape(basis.shape[0], 3, 3 * basis.shape[1])
+
+
+def component_basis(basis, components):
+    """
+    The shared basis [M, u'] of ArcParameters written in its general form, ndarray [M, K, K u'] (host, NumPy only), block-diagonal in
+    the K = components components: column c u' + j of component c is basis[:, j], every other column of that component is zero, so
+    every component has u' parameters of its own as under the shared form, and parameters(x) of the result is [arcs, K u'] with the
+    parameter index c u' + j.  What a VectorNoise needs in place of the shared form, whose components its joint filter couples.
+    ValueError for other shapes, K < 1 and K u' > 16.
+    """
+    basis, K = np.asarray(basis, dtype=np.float64), int(components)
+    if basis.ndim != 2 or basis.shape[1] < 1:
+        raise ValueError('basis must have shape (M, u), got {0}'.format(basis.shape))
+    if K < 1:
+        raise ValueError('components must be positive, got {0}'.format(components))
+    u = basis.shape[1]
+    if K * u > MAX_ARC_PARAMETERS:
+        raise ValueError('{0} columns of the component basis: expected at most {1}'.format(K * u, MAX_ARC_PARAMETERS))
+    general = np.zeros((basis.shape[0], K, K * u))
+    for c in range(K):
+        general[:, c, c * u:(c + 1) * u] = basis
+    return general
 
 
 def _arc_reduction(G, b):
@@ -578,6 +693,7 @@ class _StochasticModel:
     def __init__(self, noise_model=None, arcs=None, parameters=None):
         self.noise_model, self.arcs, self.parameters = noise_model, arcs, parameters
         self.whitening = self.starts = self.taps = self.stage = self.halo = None
+        self.vector = isinstance(noise_model, VectorNoise)               # the kind of the tables: taps [q + 1, q + 1, K, K] of shg_whiten_rows_vector
 
     @classmethod
     def of(cls, model):
@@ -600,6 +716,9 @@ class _StochasticModel:
             shape = self.parameters.basis.shape
             if shape[0] != M or (len(shape) == 3 and shape[1] != K):
                 raise ValueError('the arc basis must have shape ({0}, u) or ({0}, {1}, u), got {2}'.format(M, K, shape))
+            if self.vector and len(shape) == 2:
+                raise ValueError('a shared arc basis ({0}, u) gives every component parameters of its own, which a VectorNoise couples: pass the '
+                                 'general basis lstsq.component_basis(basis, {1}) of shape ({0}, {1}, {1} u)'.format(M, K))
 
     def to_device(self, device):
         if self.whitening is not None:
@@ -607,7 +726,10 @@ class _StochasticModel:
             self.taps, self.stage, self.halo = engine.to_device(self.whitening[0], device), torch.from_numpy(self.whitening[1]).to(device), self.whitening[1]
 
     def whiten(self, X, start=0, skip=0):
-        """W along the last axis of X [..., n], which holds the points start .. start + n; the first skip of them are history only"""
+        """W along the last axis of X [..., n], which holds the points start .. start + n; the first skip of them are history only.  Under a
+        VectorNoise the rows of X, all axes but the last flattened, are groups of its K components"""
+        if self.vector:
+            return engine.whiten_rows_vector(X, taps=self.taps, stage=self.stage[start:start + int(X.shape[-1])], skip=skip)
         return engine.whiten_rows(X, taps=self.taps, stage=self.stage[start:start + int(X.shape[-1])], channels=int(self.taps.shape[0]), skip=skip)
 
 
@@ -1544,11 +1666,12 @@ class ColouredNoise(_BoundModel):
     the start indices of the arcs (default: one arc), as NormalEquations.from_accelerations describes them.  from_accelerations, from_gradients,
     from_line_of_sight, from_potentials and from_potential_differences take the arguments of the classmethods of the same name and
     return the NormalEquations of the decorrelated observations.  The model is checked here (whitening_taps), the arcs against the number of points in every call; all of it before
-    anything reaches the device.
+    anything reaches the device.  A VectorNoise in place of the scalar models whitens the K components of a point jointly; its
+    dimension must be the K of the observations of every call.
     """
 
     def __init__(self, noise_model, arcs=None):
-        whitening_taps(noise_model)
+        _check_noise_model(noise_model)
         self.noise_model, self.arcs = noise_model, arcs
 
 
@@ -1581,7 +1704,10 @@ class ArcParameters(_BoundModel):
         if not np.all(np.isfinite(basis)):
             raise ValueError('the arc basis must be finite')
         if noise_model is not None:
-            whitening_taps(noise_model)
+            _check_noise_model(noise_model)
+        if isinstance(noise_model, VectorNoise) and basis.ndim == 2:
+            raise ValueError('a shared arc basis (M, u) gives every component parameters of its own, which a VectorNoise couples: pass the '
+                             'general basis lstsq.component_basis(basis, {0}) of shape (M, {0}, {0} u)'.format(noise_model.dimension))
         self.basis, self.arcs, self.noise_model, self.keep = basis, arcs, noise_model, bool(keep)
 
 
@@ -2230,6 +2356,53 @@ class PostFit:
         taper = lag_window(window, int(maximum_lag))
         c = self.__covariance(int(maximum_lag), per_component, True) * taper
         return [CovarianceFunction(row) for row in c] if per_component else CovarianceFunction(c)
+
+    def __cross_covariance(self, maximum_lag, biased):
+        """Sigma [q + 1, K, K] of cross_covariance_function; its checks on the host first"""
+        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_WHITENING_ORDER:
+            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_WHITENING_ORDER, maximum_lag))
+        q, K = int(maximum_lag), int(self.__rows.shape[0])
+        if K > MAX_VECTOR_DIMENSION:
+            raise ValueError('cross-covariances of {0} components: at most {1}'.format(K, MAX_VECTOR_DIMENSION))
+        lengths = np.diff(np.append(self.arcs, int(self.__rows.shape[1])))
+        pairs = np.array([np.maximum(lengths - k, 0).sum() for k in range(q + 1)], dtype=np.float64)
+        if biased:
+            pairs[:] = pairs[0]
+        elif not np.all(pairs > 0):
+            raise ValueError('no arc is longer than {0} points: no pair at lag {1}'.format(int(lengths.max()), int(np.argmin(pairs > 0))))
+        sums = engine.to_host(engine.segment_cross_lag_products(self.__rows, self.__seg, q)).sum(axis=0)      # [q + 1, K, K]
+        return sums / pairs[:, None, None]
+
+    def cross_covariance_function(self, maximum_lag, biased=True):
+        """
+        Empirical cross-covariance function of the K components of the unwhitened residuals,
+        Sigma_k[c, c'] = sum_a sum_t e^[t, c] e^[t + k, c'] / d_k over the pairs inside an arc (one call of
+        shg_segment_cross_lag_products), k = 0 .. maximum_lag <= 128, with the divisors of covariance_function: biased=True
+        d_k = d_0 = sum_a len_a, positive semi-definite as a block sequence by construction; biased=False d_k = sum_a max(len_a - k, 0).
+        Returns a list of q + 1 [K, K] arrays, Sigma_k = E[x_t x_(t+k)^T]: what AutoregressiveModelSequence.from_covariance_function
+        takes.  The diagonal entries are covariance_function(per_component=True).  ValueError, before anything reaches the device,
+        for a maximum_lag outside 0 .. 128, more than 6 components and, with biased=False, a lag no arc is long enough for.
+        """
+        return list(self.__cross_covariance(maximum_lag, biased))
+
+    def vector_noise(self, maximum_lag, window=None):
+        """
+        The vector noise model of the residuals, the counterpart of covariance_model for components that are correlated: the
+        VectorNoise of AutoregressiveModelSequence.from_covariance_function (block Yule-Walker systems on the device) of the biased
+        cross_covariance_function(maximum_lag), every lag tapered by lag_window(window, maximum_lag) first; for ColouredNoise,
+        ArcParameters(noise_model=), TemporalParameters(model=), RadialBasisParameters and decorrelate.  ValueError for the window, the
+        maximum_lag and fewer than 2 components before anything reaches the device; VectorNoise raises its own for an estimate that
+        is not positive definite.
+        """
+        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_WHITENING_ORDER:
+            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_WHITENING_ORDER, maximum_lag))
+        K = int(self.__rows.shape[0])
+        if not MIN_VECTOR_DIMENSION <= K <= MAX_VECTOR_DIMENSION:
+            raise ValueError('vector noise of {0} component{1}: expected {2} .. {3} (covariance_model gives the scalar model)'.format(
+                K, '' if K == 1 else 's', MIN_VECTOR_DIMENSION, MAX_VECTOR_DIMENSION))
+        taper = lag_window(window, int(maximum_lag))
+        lags = self.__cross_covariance(maximum_lag, True) * taper[:, None, None]
+        return VectorNoise(AutoregressiveModelSequence.from_covariance_function([np.ascontiguousarray(lag) for lag in lags]))
 
 
 def lag_window(window, maximum_lag):

@@ -883,6 +883,54 @@ int shg_segment_lag_products_long(long long rows, int M, const double* X, long l
 int shg_segment_lag_long_info(int* chunk, int* tile_lags, int* max_lags);
 
 /* ------------------------------------------------------------------------------------------------
+ * Decorrelation of vector noise along the point axis: the block lower-triangular banded W with W^T W = Sigma^-1 of a sequence of
+ * VAR models of dimension K and orders 0 .. q, which couple the components of a point (no reference
+ * counterpart)
+ *   X [groups K][ldx] with M columns in use, row g K + c is component c of group g: the transposed design matrix At [P][K][ldt] is
+ *   groups = P; observations laid out [K][M] are groups = 1.  2 <= K <= 6.
+ *   taps (device) [q+1][q+1][K][K]: H[s][0] = R_s^-T, H[s][k] = -R_s^-T B_k^(s) (1 <= k <= s) of the model of order s with coefficients
+ *   B_k^(s) and white-noise covariance R_s^T R_s (R_s upper triangular), zero beyond.  stage (device) [M]: the order in use at column t,
+ *   min(t - start of its arc, q).
+ *   Y[g K + c][t - skip] = sum_{k = 0 .. n} sum_{c' = 0 .. K-1} H[n][k][c][c'] X[g K + c'][t - k] for skip <= t < M, with
+ *   n = min(max(stage[t], 0), q, t): the first skip columns are read as history and not written (the halo of a block of a longer
+ *   series); the entries of a row of Y from M - skip to ldy are not touched, the padding of X from M to ldx is not read.  The kernel
+ *   never reads before column 0 of a row and never a tap outside its table, whatever stage holds.
+ *   The sum runs over k ascending and, inside, over c' ascending; the first term is a product, every later one acc = fma(H, x, acc):
+ *   an output depends on x[t-n .. t] of its group, stage[t] and the taps only, not on skip, M, the tiling or the other groups.  No
+ *   atomics; repeated calls are bitwise equal, and a block whitened with a halo of q columns is bitwise the same columns of the whole.
+ *   One workgroup per tile of columns of the K rows of a group, staged through LDS with the q columns in front; a lane owns 4 (K <= 3)
+ *   or 2 consecutive columns of all K rows, takes the taps of the stationary model through scalar loads and keeps the values of x it
+ *   meets again at the next lag in registers.  shg_whiten_vector_info gives the tile: 1024 columns for K <= 3, 512 above.  A flat
+ *   64-bit index, so groups x K x ld may exceed 2^31.
+ *   Arguments are checked before the first HIP call (negative sizes, K outside 2 .. 6, q outside 0 .. 128, skip outside 0 .. M,
+ *   ldx < M, ldy < M - skip, more than 2^40 values of X or Y, NULL pointers, address ranges of X and Y that overlap: the call is out
+ *   of place); groups = 0 or M = skip returns 0 at once.
+ *   shg_whiten_vector_info: host only; -1 for K outside 2 .. 6, a NULL pointer is skipped.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_whiten_rows_vector(long long groups, int K, int M, const double* X, long long ldx, const int32_t* stage, const double* taps, int q,
+                           int skip, double* Y, long long ldy, void* stream);
+int shg_whiten_vector_info(int K, int* tile_columns);
+
+/* ------------------------------------------------------------------------------------------------
+ * Lagged products between the rows of a matrix, cut at arc boundaries: the empirical cross-covariance function of the K components
+ * of post-fit residuals (no reference counterpart)
+ *   X [K][ldx] with M columns in use, 1 <= K <= 6.  seg (device) [nseg + 1]: column indices, segment s is seg[s] .. seg[s+1] - 1.
+ *   0 <= lags <= 128.
+ *   S[s][k][c][c'] = sum over t with seg[s] <= t and t + k < seg[s+1] of X[c][t] X[c'][t + k], k = 0 .. lags;  S [nseg][lags + 1][K][K]
+ *   is dense and every entry is written; an entry without a pair is exactly 0.0.
+ *   The summation order, the locality and the clamping of seg are those of shg_segment_lag_products: chain i of 64 is acc = 0,
+ *   acc = fma(x_c[t], x_c'[t + k], acc) over t = start + i, start + i + 64, ... ascending while t + k < end, the chains are added by
+ *   the butterfly v_i += v_(i ^ m) for m = 32, 16, 8, 4, 2, 1; entry i of seg is read as max over k <= i of min(max(seg[k], 0), M).
+ *   So S[s][k][c][c] is bitwise shg_segment_lag_products of row c; an entry depends on the two rows inside the segment and on k
+ *   only.  Columns outside every segment and the padding from M to ldx are not read.  No atomics; repeated calls are bitwise equal.
+ *   One workgroup of 4 waves per segment of a pair (c, c'), in tiles of 1024 columns staged in LDS.
+ *   Arguments are checked before the first HIP call (negative sizes, K outside 1 .. 6, lags outside 0 .. 128, nseg < 0 or above
+ *   2^24, ldx < M, more than 2^40 values of X, NULL pointers); nseg = 0 returns 0 at once.
+ * ------------------------------------------------------------------------------------------------ */
+int shg_segment_cross_lag_products(int K, int M, const double* X, long long ldx, int lags, int nseg, const int32_t* seg, double* S,
+                                   void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Window expansion of a transposed design matrix: the adjoint of the window model of the shg_*_points_at calls, for parameters
  * that vary in time (no reference counterpart)
  *   T [rows][ldt] with n columns in use (the transposed design matrix At [P][K][ldt] of a block is rows = P K).  factors (device)
