@@ -27,7 +27,8 @@ __global__ __launch_bounds__(kSegWaves * 64) void segment_products_kernel(long l
         const int s = (int)(item - group * nseg);
         const int c = (int)(group % channels);
         const long long p0 = group / channels * kRows;                           // rows (p0 + i) channels + c, p0 + i < outer
-        // the table clamped to 0 .. M and made non-decreasing: start = max of the clamped entries 0 .. s, end = max(start, entry s + 1)
+        // the table clamped to 0 .. M and made non-decreasing: start = max of the clamped entries 0 .. s, end = max(start, entry s + 1).
+        // segment_range of lags_device.h written out: with the call every kernel of this file compiles to other instructions
         int start = 0;
         for (int i = lane; i <= s; i += 64) start = max(start, min(max(seg[i], 0), M));
 #pragma unroll

@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "host_require.h"
+
 namespace shg {
 
 constexpr int kSegMaxParameters = 16;       // u of shg_segment_products, lstsq.MAX_ARC_PARAMETERS
@@ -25,27 +27,19 @@ struct SegmentGeometry {
 inline int segment_products_check(long long rows, int channels, int M, const void* X, long long ldx, const void* Bt, long long ldb, int u, int nseg,
                                   const void* seg, const void* S, char* message, size_t size) {
     const char* fn = "shg_segment_products";
-#define SHG_SEG_REQUIRE(cond, ...)                \
-    do {                                          \
-        if (!(cond)) {                            \
-            snprintf(message, size, __VA_ARGS__); \
-            return -1;                            \
-        }                                         \
-    } while (0)
-    SHG_SEG_REQUIRE(rows >= 0 && M >= 0 && ldx >= 0 && ldb >= 0, "%s: negative size (rows %lld, M %d, ldx %lld, ldb %lld)", fn, rows, M, ldx, ldb);
-    SHG_SEG_REQUIRE(channels >= 1, "%s: channels %d below 1", fn, channels);
-    SHG_SEG_REQUIRE(rows % channels == 0, "%s: rows %lld are not a multiple of channels %d", fn, rows, channels);
-    SHG_SEG_REQUIRE(u >= 1 && u <= kSegMaxParameters, "%s: u %d outside 1 .. %d", fn, u, kSegMaxParameters);
-    SHG_SEG_REQUIRE(nseg >= 0, "%s: nseg %d is negative", fn, nseg);
-    SHG_SEG_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
-    SHG_SEG_REQUIRE(ldb >= M, "%s: ldb %lld below M %d", fn, ldb, M);
+    SHG_HOST_REQUIRE(rows >= 0 && M >= 0 && ldx >= 0 && ldb >= 0, "%s: negative size (rows %lld, M %d, ldx %lld, ldb %lld)", fn, rows, M, ldx, ldb);
+    SHG_HOST_REQUIRE(channels >= 1, "%s: channels %d below 1", fn, channels);
+    SHG_HOST_REQUIRE(rows % channels == 0, "%s: rows %lld are not a multiple of channels %d", fn, rows, channels);
+    SHG_HOST_REQUIRE(u >= 1 && u <= kSegMaxParameters, "%s: u %d outside 1 .. %d", fn, u, kSegMaxParameters);
+    SHG_HOST_REQUIRE(nseg >= 0, "%s: nseg %d is negative", fn, nseg);
+    SHG_HOST_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
+    SHG_HOST_REQUIRE(ldb >= M, "%s: ldb %lld below M %d", fn, ldb, M);
     const long long limit = 1LL << 40;
-    SHG_SEG_REQUIRE(ldx == 0 || rows <= limit / ldx, "%s: %lld rows of %lld values of X are too large", fn, rows, ldx);
-    SHG_SEG_REQUIRE(nseg == 0 || rows <= limit / ((long long)nseg * u), "%s: %lld rows of %d segments and %d values of S are too large", fn, rows, nseg,
-                    u);
+    SHG_HOST_REQUIRE(ldx == 0 || rows <= limit / ldx, "%s: %lld rows of %lld values of X are too large", fn, rows, ldx);
+    SHG_HOST_REQUIRE(nseg == 0 || rows <= limit / ((long long)nseg * u), "%s: %lld rows of %d segments and %d values of S are too large", fn, rows, nseg,
+                     u);
     if (rows == 0 || nseg == 0) return 1;
-    SHG_SEG_REQUIRE(X && Bt && seg && S, "%s: NULL pointer", fn);
-#undef SHG_SEG_REQUIRE
+    SHG_HOST_REQUIRE(X && Bt && seg && S, "%s: NULL pointer", fn);
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// Device code that lags.hip and lags_long.hip share: the reading of a segment table.
+// Device code that the kernels of lags.hip (auto and cross lags) and lags_long.hip share: the reading of a segment table.
 #pragma once
 
 #include "common.h"

@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "host_require.h"
+
 namespace shg {
 
 constexpr int kLagMax = 128;                // lags of shg_segment_lag_products, lstsq.MAX_WHITENING_ORDER
@@ -33,24 +35,16 @@ struct LagGeometry {
 inline int segment_lag_products_check(long long rows, int M, const void* X, long long ldx, int lags, int nseg, const void* seg, const void* S,
                                       char* message, size_t size) {
     const char* fn = "shg_segment_lag_products";
-#define SHG_LAG_REQUIRE(cond, ...)                \
-    do {                                          \
-        if (!(cond)) {                            \
-            snprintf(message, size, __VA_ARGS__); \
-            return -1;                            \
-        }                                         \
-    } while (0)
-    SHG_LAG_REQUIRE(rows >= 0 && M >= 0 && ldx >= 0, "%s: negative size (rows %lld, M %d, ldx %lld)", fn, rows, M, ldx);
-    SHG_LAG_REQUIRE(lags >= 0 && lags <= kLagMax, "%s: lags %d outside 0 .. %d", fn, lags, kLagMax);
-    SHG_LAG_REQUIRE(nseg >= 0, "%s: nseg %d is negative", fn, nseg);
-    SHG_LAG_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
+    SHG_HOST_REQUIRE(rows >= 0 && M >= 0 && ldx >= 0, "%s: negative size (rows %lld, M %d, ldx %lld)", fn, rows, M, ldx);
+    SHG_HOST_REQUIRE(lags >= 0 && lags <= kLagMax, "%s: lags %d outside 0 .. %d", fn, lags, kLagMax);
+    SHG_HOST_REQUIRE(nseg >= 0, "%s: nseg %d is negative", fn, nseg);
+    SHG_HOST_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
     const long long limit = 1LL << 40;
-    SHG_LAG_REQUIRE(ldx == 0 || rows <= limit / ldx, "%s: %lld rows of %lld values of X are too large", fn, rows, ldx);
-    SHG_LAG_REQUIRE(nseg == 0 || rows <= limit / ((long long)nseg * (lags + 1)), "%s: %lld rows of %d segments and %d values of S are too large", fn,
-                    rows, nseg, lags + 1);
+    SHG_HOST_REQUIRE(ldx == 0 || rows <= limit / ldx, "%s: %lld rows of %lld values of X are too large", fn, rows, ldx);
+    SHG_HOST_REQUIRE(nseg == 0 || rows <= limit / ((long long)nseg * (lags + 1)), "%s: %lld rows of %d segments and %d values of S are too large", fn,
+                     rows, nseg, lags + 1);
     if (rows == 0 || nseg == 0) return 1;
-    SHG_LAG_REQUIRE(X && seg && S, "%s: NULL pointer", fn);
-#undef SHG_LAG_REQUIRE
+    SHG_HOST_REQUIRE(X && seg && S, "%s: NULL pointer", fn);
     return 0;
 }
 

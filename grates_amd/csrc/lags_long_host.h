@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "host_require.h"
+
 namespace shg {
 
 constexpr int kLagLongMax = 4095;           // lags of shg_segment_lag_products_long, lstsq.MAX_COVARIANCE_ORDER
@@ -68,27 +70,19 @@ inline LagLongGeometry segment_lag_products_long_geometry(long long rows, int M,
 inline int segment_lag_products_long_check(long long rows, int M, const void* X, long long ldx, int lags, int nseg, const void* seg, const void* S,
                                            char* message, size_t size) {
     const char* fn = "shg_segment_lag_products_long";
-#define SHG_LAG_LONG_REQUIRE(cond, ...)           \
-    do {                                          \
-        if (!(cond)) {                            \
-            snprintf(message, size, __VA_ARGS__); \
-            return -1;                            \
-        }                                         \
-    } while (0)
-    SHG_LAG_LONG_REQUIRE(rows >= 0 && M >= 0 && ldx >= 0, "%s: negative size (rows %lld, M %d, ldx %lld)", fn, rows, M, ldx);
-    SHG_LAG_LONG_REQUIRE(lags >= 0 && lags <= kLagLongMax, "%s: lags %d outside 0 .. %d", fn, lags, kLagLongMax);
-    SHG_LAG_LONG_REQUIRE(nseg >= 0, "%s: nseg %d is negative", fn, nseg);
-    SHG_LAG_LONG_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
+    SHG_HOST_REQUIRE(rows >= 0 && M >= 0 && ldx >= 0, "%s: negative size (rows %lld, M %d, ldx %lld)", fn, rows, M, ldx);
+    SHG_HOST_REQUIRE(lags >= 0 && lags <= kLagLongMax, "%s: lags %d outside 0 .. %d", fn, lags, kLagLongMax);
+    SHG_HOST_REQUIRE(nseg >= 0, "%s: nseg %d is negative", fn, nseg);
+    SHG_HOST_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
     const long long limit = 1LL << 40;
-    SHG_LAG_LONG_REQUIRE(ldx == 0 || rows <= limit / ldx, "%s: %lld rows of %lld values of X are too large", fn, rows, ldx);
-    SHG_LAG_LONG_REQUIRE(nseg == 0 || rows <= limit / ((long long)nseg * (lags + 1)), "%s: %lld rows of %d segments and %d values of S are too large", fn,
-                         rows, nseg, lags + 1);
+    SHG_HOST_REQUIRE(ldx == 0 || rows <= limit / ldx, "%s: %lld rows of %lld values of X are too large", fn, rows, ldx);
+    SHG_HOST_REQUIRE(nseg == 0 || rows <= limit / ((long long)nseg * (lags + 1)), "%s: %lld rows of %d segments and %d values of S are too large", fn,
+                     rows, nseg, lags + 1);
     const long long slots = (long long)(M / kLagLongChunk) + nseg, each = (long long)lag_long_tiles(lags) * kLagLongTile;
-    SHG_LAG_LONG_REQUIRE(nseg == 0 || (slots <= INT32_MAX && rows <= limit / (slots * each)),
-                         "%s: %lld rows of %lld chunks and %lld partial sums of the workspace are too large", fn, rows, slots, each);
+    SHG_HOST_REQUIRE(nseg == 0 || (slots <= INT32_MAX && rows <= limit / (slots * each)),
+                     "%s: %lld rows of %lld chunks and %lld partial sums of the workspace are too large", fn, rows, slots, each);
     if (rows == 0 || nseg == 0) return 1;
-    SHG_LAG_LONG_REQUIRE(X && seg && S, "%s: NULL pointer", fn);
-#undef SHG_LAG_LONG_REQUIRE
+    SHG_HOST_REQUIRE(X && seg && S, "%s: NULL pointer", fn);
     return 0;
 }
 

@@ -10,12 +10,13 @@
 // call it is computed in.
 #include "common.h"
 
+#include "whiten_host.h"          // the contract of the call and kWhitenMaxOrder
+
 namespace shg {
 
 constexpr int kWhitenThreads = 256;
 constexpr int kWhitenPerThread = 4;
 constexpr int kWhitenTile = kWhitenThreads * kWhitenPerThread;      // output columns of a work item
-constexpr int kWhitenMaxOrder = 128;
 constexpr int kWhitenBlocks = 256 * 8;                               // 8 workgroups of 4 waves fill a CU: the rest is a grid stride
 
 __global__ __launch_bounds__(kWhitenThreads) void whiten_rows_kernel(long long items, int tiles, int channels, int M, const double* __restrict__ X,
@@ -67,21 +68,10 @@ using namespace shg;
 
 extern "C" int shg_whiten_rows(long long rows, int channels, int M, const double* X, long long ldx, const int32_t* stage, const double* taps, int q,
                                int skip, double* Y, long long ldy, void* stream_) {
-    const char* fn = "shg_whiten_rows";
-    SHG_REQUIRE(rows >= 0 && M >= 0 && ldx >= 0 && ldy >= 0, "%s: negative size (rows %lld, M %d, ldx %lld, ldy %lld)", fn, rows, M, ldx, ldy);
-    SHG_REQUIRE(channels >= 1, "%s: channels %d below 1", fn, channels);
-    SHG_REQUIRE(rows % channels == 0, "%s: rows %lld are not a multiple of channels %d", fn, rows, channels);
-    SHG_REQUIRE(q >= 0 && q <= kWhitenMaxOrder, "%s: order q %d outside 0 .. %d", fn, q, kWhitenMaxOrder);
-    SHG_REQUIRE(skip >= 0 && skip <= M, "%s: skip %d outside 0 .. M %d", fn, skip, M);
-    SHG_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
-    SHG_REQUIRE(ldy >= M - skip, "%s: ldy %lld below M - skip %d", fn, ldy, M - skip);
-    const long long limit = 1LL << 40;
-    SHG_REQUIRE((ldx == 0 || rows <= limit / ldx) && (ldy == 0 || rows <= limit / ldy), "%s: %lld rows of %lld (X) and %lld (Y) values are too large", fn,
-                rows, ldx, ldy);
-    if (rows == 0 || M == skip) return SHG_OK;
-    SHG_REQUIRE(X && stage && taps && Y, "%s: NULL pointer", fn);
-    const uintptr_t x0 = (uintptr_t)X, x1 = (uintptr_t)(X + (rows - 1) * ldx + M), y0 = (uintptr_t)Y, y1 = (uintptr_t)(Y + (rows - 1) * ldy + (M - skip));
-    SHG_REQUIRE(x1 <= y0 || y1 <= x0, "%s: X and Y overlap (the call is out of place)", fn);
+    char message[256];
+    const int status = whiten_check(kWhitenRows, rows, 1, channels, M, X, ldx, stage, taps, q, skip, Y, ldy, message, sizeof(message));
+    if (status < 0) return shg::fail(SHG_ERR_INVALID, "%s", message);
+    if (status > 0) return SHG_OK;
     const int tiles = (int)ceil_div64((long long)M - skip, kWhitenTile);
     const long long items = rows * tiles;
     const unsigned blocks = (unsigned)std::min<long long>(items, kWhitenBlocks);

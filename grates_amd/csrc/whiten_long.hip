@@ -22,6 +22,8 @@
 
 #include <climits>
 
+#include "whiten_host.h"          // the contract of the call and kWhitenLongMaxOrder
+
 namespace shg {
 namespace {
 
@@ -30,7 +32,6 @@ constexpr int WK = 16;         // K tile
 constexpr int WLDA = 18;       // row of the staged tile of X: 16 + 2 doubles of padding (16 rows x 2 k of a fragment read fall on distinct banks)
 constexpr int WLDB = 144;      // k-row of the staged tile of B: 128 + 16 doubles of padding
 constexpr int WIMG = WT * WLDA + WK * WLDB;      // doubles of one buffer: X tile | B tile
-constexpr int kWhitenLongMaxOrder = 4095;
 
 __global__ __launch_bounds__(256, 2) void whiten_long_kernel(long long rpc, int channels, int M, const double* __restrict__ X, long long ldx,
                                                               const int32_t* __restrict__ stage, const double* __restrict__ taps, int q, int skip,
@@ -140,21 +141,10 @@ using namespace shg;
 
 extern "C" int shg_whiten_rows_long(long long rows, int channels, int M, const double* X, long long ldx, const int32_t* stage, const double* taps,
                                     int q, int skip, double* Y, long long ldy, void* stream_) {
-    const char* fn = "shg_whiten_rows_long";
-    SHG_REQUIRE(rows >= 0 && M >= 0 && ldx >= 0 && ldy >= 0, "%s: negative size (rows %lld, M %d, ldx %lld, ldy %lld)", fn, rows, M, ldx, ldy);
-    SHG_REQUIRE(channels >= 1, "%s: channels %d below 1", fn, channels);
-    SHG_REQUIRE(rows % channels == 0, "%s: rows %lld are not a multiple of channels %d", fn, rows, channels);
-    SHG_REQUIRE(q >= 0 && q <= kWhitenLongMaxOrder, "%s: order q %d outside 0 .. %d", fn, q, kWhitenLongMaxOrder);
-    SHG_REQUIRE(skip >= 0 && skip <= M, "%s: skip %d outside 0 .. M %d", fn, skip, M);
-    SHG_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
-    SHG_REQUIRE(ldy >= M - skip, "%s: ldy %lld below M - skip %d", fn, ldy, M - skip);
-    const long long limit = 1LL << 40;
-    SHG_REQUIRE((ldx == 0 || rows <= limit / ldx) && (ldy == 0 || rows <= limit / ldy), "%s: %lld rows of %lld (X) and %lld (Y) values are too large", fn,
-                rows, ldx, ldy);
-    if (rows == 0 || M == skip) return SHG_OK;
-    SHG_REQUIRE(X && stage && taps && Y, "%s: NULL pointer", fn);
-    const uintptr_t x0 = (uintptr_t)X, x1 = (uintptr_t)(X + (rows - 1) * ldx + M), y0 = (uintptr_t)Y, y1 = (uintptr_t)(Y + (rows - 1) * ldy + (M - skip));
-    SHG_REQUIRE(x1 <= y0 || y1 <= x0, "%s: X and Y overlap (the call is out of place)", fn);
+    char message[256];
+    const int status = whiten_check(kWhitenRowsLong, rows, 1, channels, M, X, ldx, stage, taps, q, skip, Y, ldy, message, sizeof(message));
+    if (status < 0) return shg::fail(SHG_ERR_INVALID, "%s", message);
+    if (status > 0) return SHG_OK;
     const size_t lds_bytes = (size_t)2 * WIMG * sizeof(double);
     SHG_SET_LDS_ONCE(whiten_long_kernel, lds_bytes);
     const long long rpc = rows / channels;

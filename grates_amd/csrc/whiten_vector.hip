@@ -14,11 +14,11 @@
 // product and every later one an fma.
 #include "common.h"
 
+#include "whiten_host.h"          // the contract of the call, kVectorMaxOrder and the dimensions
+
 namespace shg {
 
 constexpr int kVectorThreads = 256;
-constexpr int kVectorMaxOrder = 128;
-constexpr int kVectorMinDim = 2, kVectorMaxDim = 6;
 constexpr int kVectorBlocks = 256 * 8;                               // workgroups of a launch at most: the rest is a grid stride
 
 // columns of a lane: K J accumulators and K J window values stay in registers, and K times the tile with its halo leaves room for two
@@ -157,22 +157,10 @@ extern "C" int shg_whiten_vector_info(int K, int* tile_columns) {
 
 extern "C" int shg_whiten_rows_vector(long long groups, int K, int M, const double* X, long long ldx, const int32_t* stage, const double* taps, int q,
                                       int skip, double* Y, long long ldy, void* stream_) {
-    const char* fn = "shg_whiten_rows_vector";
-    SHG_REQUIRE(groups >= 0 && M >= 0 && ldx >= 0 && ldy >= 0, "%s: negative size (groups %lld, M %d, ldx %lld, ldy %lld)", fn, groups, M, ldx, ldy);
-    SHG_REQUIRE(K >= kVectorMinDim && K <= kVectorMaxDim, "%s: dimension K %d outside %d .. %d", fn, K, kVectorMinDim, kVectorMaxDim);
-    SHG_REQUIRE(q >= 0 && q <= kVectorMaxOrder, "%s: order q %d outside 0 .. %d", fn, q, kVectorMaxOrder);
-    SHG_REQUIRE(skip >= 0 && skip <= M, "%s: skip %d outside 0 .. M %d", fn, skip, M);
-    SHG_REQUIRE(ldx >= M, "%s: ldx %lld below M %d", fn, ldx, M);
-    SHG_REQUIRE(ldy >= M - skip, "%s: ldy %lld below M - skip %d", fn, ldy, M - skip);
-    const long long limit = 1LL << 40;
-    SHG_REQUIRE(groups <= limit / K, "%s: %lld groups of %d rows are too large", fn, groups, K);
-    const long long rows = groups * K;
-    SHG_REQUIRE((ldx == 0 || rows <= limit / ldx) && (ldy == 0 || rows <= limit / ldy),
-                "%s: %lld groups of %d rows of %lld (X) and %lld (Y) values are too large", fn, groups, K, ldx, ldy);
-    if (groups == 0 || M == skip) return SHG_OK;
-    SHG_REQUIRE(X && stage && taps && Y, "%s: NULL pointer", fn);
-    const uintptr_t x0 = (uintptr_t)X, x1 = (uintptr_t)(X + (rows - 1) * ldx + M), y0 = (uintptr_t)Y, y1 = (uintptr_t)(Y + (rows - 1) * ldy + (M - skip));
-    SHG_REQUIRE(x1 <= y0 || y1 <= x0, "%s: X and Y overlap (the call is out of place)", fn);
+    char message[256];
+    const int status = whiten_check(kWhitenRowsVector, groups, K, 1, M, X, ldx, stage, taps, q, skip, Y, ldy, message, sizeof(message));
+    if (status < 0) return shg::fail(SHG_ERR_INVALID, "%s", message);
+    if (status > 0) return SHG_OK;
     hipStream_t stream = (hipStream_t)stream_;
     switch (K) {
         case 2: launch_whiten_vector<2>(groups, M, X, ldx, stage, taps, q, skip, Y, ldy, stream); break;

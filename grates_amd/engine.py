@@ -1430,6 +1430,55 @@ def leverages(Ui, X, out=None):
 WHITEN_ROWS_ORDER = 128        # the longest filter of shg_whiten_rows; above it whiten_rows calls shg_whiten_rows_long
 
 
+def _rows_view(t, width):
+    """(tensor, leading dimension) of t as rows of `width` columns: t itself where it is two-dimensional with unit stride along its rows
+    (dense, or a column slice of a wider matrix), else a dense copy"""
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= width:
+        return t, int(t.stride(0))
+    return t.contiguous(), width
+
+
+def _row_count(lead):
+    """the rows of a tensor whose leading axes `lead` are flattened"""
+    rows = 1
+    for size in lead:
+        rows *= size
+    return rows
+
+
+def _check_stage(stage, M):
+    torch = _torch()
+    if tuple(stage.shape) != (M,) or stage.dtype != torch.int32 or not stage.is_contiguous():
+        raise ValueError('stage must be a dense int32 tensor of shape ({0},), got {1} {2}'.format(M, stage.dtype, tuple(stage.shape)))
+
+
+def _check_seg(seg):
+    """nseg of the boundary table seg [nseg + 1]"""
+    torch = _torch()
+    if tuple(seg.shape) != (seg.numel(),) or seg.numel() < 1 or seg.dtype != torch.int32 or not seg.is_contiguous():
+        raise ValueError('seg must be a dense int32 tensor of shape (nseg + 1,), got {0} {1}'.format(seg.dtype, tuple(seg.shape)))
+    return int(seg.numel()) - 1
+
+
+def _whiten(entry, X, taps, stage, q, skip, out, counts):
+    """the checks of stage and X, the views, the check of out and the call that whiten_rows and whiten_rows_vector share; entry: the
+    name in libshg, counts(rows): its two arguments in front of M"""
+    torch = _torch()
+    M, skip = int(X.shape[-1]), int(skip)
+    lead = tuple(int(s) for s in X.shape[:-1])
+    _check_stage(stage, M)
+    if X.dtype != torch.float64:
+        raise ValueError('X must be float64, got {0}'.format(X.dtype))
+    front = counts(_row_count(lead))
+    X, ldx = _rows_view(X, M)
+    if out is None:
+        out = torch.empty(lead + (max(M - skip, 0),), dtype=torch.float64, device=X.device)
+    elif tuple(out.shape) != lead + (M - skip,) or out.dtype != torch.float64 or _rows_view(out, M - skip)[0] is not out:
+        raise ValueError('out must be a float64 tensor of shape {0}, dense or a column slice of a matrix'.format(lead + (M - skip,)))
+    _lib.call(entry, *front, M, _ptr(X), ldx, _ptr(stage), _ptr(taps), q, skip, _ptr(out), _rows_view(out, M - skip)[1], _stream())
+    return out
+
+
 def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
     """Decorrelation along the last axis of the device tensor X [..., M] (shg_whiten_rows): Y[..., t - skip] = sum_k h[n][k] X[..., t - k]
     for skip <= t < M with n = min(stage[t], q, t); the rows of X, all axes but the last flattened, belong to channel row % channels.
@@ -1439,32 +1488,12 @@ def whiten_rows(X, taps, stage, channels=1, skip=0, out=None):
     Up to q = 128 the filter runs as a chain of FMAs per value (shg_whiten_rows); a longer one, q <= 4095, as a banded product on the
     fp64 MFMA (shg_whiten_rows_long), which needs the columns of X finite and repeats bitwise per call, not per tiling."""
     torch = require_gpu()
-    M, skip, channels = int(X.shape[-1]), int(skip), int(channels)
-    lead = tuple(int(s) for s in X.shape[:-1])
+    channels = int(channels)
     if tuple(taps.shape) != (channels, taps.shape[-1], taps.shape[-1]) or taps.dtype != torch.float64 or not taps.is_contiguous():
         raise ValueError('taps must be a dense float64 tensor of shape ({0}, q + 1, q + 1), got {1}'.format(channels, tuple(taps.shape)))
-    if tuple(stage.shape) != (M,) or stage.dtype != torch.int32 or not stage.is_contiguous():
-        raise ValueError('stage must be a dense int32 tensor of shape ({0},), got {1} {2}'.format(M, stage.dtype, tuple(stage.shape)))
-    if X.dtype != torch.float64:
-        raise ValueError('X must be float64, got {0}'.format(X.dtype))
-
-    def rows_of(t, width):
-        """(tensor, leading dimension) of t as rows of `width` columns"""
-        if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= width:
-            return t, int(t.stride(0))
-        return t.contiguous(), width
-    X, ldx = rows_of(X, M)
-    rows = 1
-    for size in lead:
-        rows *= size
-    if out is None:
-        out = torch.empty(lead + (max(M - skip, 0),), dtype=torch.float64, device=X.device)
-    elif tuple(out.shape) != lead + (M - skip,) or out.dtype != torch.float64 or rows_of(out, M - skip)[0] is not out:
-        raise ValueError('out must be a float64 tensor of shape {0}, dense or a column slice of a matrix'.format(lead + (M - skip,)))
     q = int(taps.shape[-1]) - 1
-    _lib.call('shg_whiten_rows' if q <= WHITEN_ROWS_ORDER else 'shg_whiten_rows_long', rows, channels, M, _ptr(X), ldx, _ptr(stage), _ptr(taps), q,
-              skip, _ptr(out), rows_of(out, M - skip)[1], _stream())
-    return out
+    return _whiten('shg_whiten_rows' if q <= WHITEN_ROWS_ORDER else 'shg_whiten_rows_long', X, taps, stage, q, skip, out,
+                   lambda rows: (rows, channels))
 
 
 def whiten_vector_info(dimension):
@@ -1483,34 +1512,15 @@ def whiten_rows_vector(X, taps, stage, skip=0, out=None):
     anything else that is not dense is copied.  Returns out, or a new tensor [..., M - skip].  An output depends on the values of
     its group, stage[t] and the taps only, and repeats bitwise in every call and tiling."""
     torch = require_gpu()
-    M, skip = int(X.shape[-1]), int(skip)
-    lead = tuple(int(s) for s in X.shape[:-1])
     if taps.dim() != 4 or taps.shape[0] != taps.shape[1] or taps.shape[2] != taps.shape[3] or taps.dtype != torch.float64 or not taps.is_contiguous():
         raise ValueError('taps must be a dense float64 tensor of shape (q + 1, q + 1, K, K), got {0}'.format(tuple(taps.shape)))
     q, K = int(taps.shape[0]) - 1, int(taps.shape[2])
-    if tuple(stage.shape) != (M,) or stage.dtype != torch.int32 or not stage.is_contiguous():
-        raise ValueError('stage must be a dense int32 tensor of shape ({0},), got {1} {2}'.format(M, stage.dtype, tuple(stage.shape)))
-    if X.dtype != torch.float64:
-        raise ValueError('X must be float64, got {0}'.format(X.dtype))
-    rows = 1
-    for size in lead:
-        rows *= size
-    if K < 1 or rows % K:
-        raise ValueError('the {0} rows of X are not groups of the {1} components of the model'.format(rows, K))
 
-    def rows_of(t, width):
-        """(tensor, leading dimension) of t as rows of `width` columns"""
-        if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= width:
-            return t, int(t.stride(0))
-        return t.contiguous(), width
-    X, ldx = rows_of(X, M)
-    if out is None:
-        out = torch.empty(lead + (max(M - skip, 0),), dtype=torch.float64, device=X.device)
-    elif tuple(out.shape) != lead + (M - skip,) or out.dtype != torch.float64 or rows_of(out, M - skip)[0] is not out:
-        raise ValueError('out must be a float64 tensor of shape {0}, dense or a column slice of a matrix'.format(lead + (M - skip,)))
-    _lib.call('shg_whiten_rows_vector', rows // K, K, M, _ptr(X), ldx, _ptr(stage), _ptr(taps), q, skip, _ptr(out), rows_of(out, M - skip)[1],
-              _stream())
-    return out
+    def groups(rows):
+        if K < 1 or rows % K:
+            raise ValueError('the {0} rows of X are not groups of the {1} components of the model'.format(rows, K))
+        return rows // K, K
+    return _whiten('shg_whiten_rows_vector', X, taps, stage, q, skip, out, groups)
 
 
 def segment_cross_lag_products(X, seg, lags, out=None):
@@ -1524,13 +1534,8 @@ def segment_cross_lag_products(X, seg, lags, out=None):
     if X.dim() != 2 or X.dtype != torch.float64:
         raise ValueError('X must be a float64 tensor of shape (K, M), got {0} {1}'.format(X.dtype, tuple(X.shape)))
     K, M, lags = int(X.shape[0]), int(X.shape[1]), int(lags)
-    if tuple(seg.shape) != (seg.numel(),) or seg.numel() < 1 or seg.dtype != torch.int32 or not seg.is_contiguous():
-        raise ValueError('seg must be a dense int32 tensor of shape (nseg + 1,), got {0} {1}'.format(seg.dtype, tuple(seg.shape)))
-    nseg = int(seg.numel()) - 1
-    if X.stride(1) == 1 and X.stride(0) >= M:
-        ldx = int(X.stride(0))
-    else:
-        X, ldx = X.contiguous(), M
+    nseg = _check_seg(seg)
+    X, ldx = _rows_view(X, M)
     shape = (nseg, max(lags, 0) + 1, K, K)
     if out is None:
         out = torch.empty(shape, dtype=torch.float64, device=X.device)
@@ -1558,24 +1563,16 @@ def segment_products(X, Bt, seg, channels=1, out=None):
     if Bt.dim() != 3 or tuple(Bt.shape[1:]) != (channels, M) or Bt.dtype != torch.float64:
         raise ValueError('Bt must be a float64 tensor of shape (u, {0}, {1}), got {2}'.format(channels, M, tuple(Bt.shape)))
     u = int(Bt.shape[0])
-    if tuple(seg.shape) != (seg.numel(),) or seg.numel() < 1 or seg.dtype != torch.int32 or not seg.is_contiguous():
-        raise ValueError('seg must be a dense int32 tensor of shape (nseg + 1,), got {0} {1}'.format(seg.dtype, tuple(seg.shape)))
-    nseg = int(seg.numel()) - 1
-    if X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= M:
-        ldx = int(X.stride(0))
-    else:
-        X, ldx = X.contiguous(), M
+    nseg = _check_seg(seg)
+    X, ldx = _rows_view(X, M)
     ldb = int(Bt.stride(0) if channels == 1 else Bt.stride(1))              # rows j channels + c of Bt, one leading dimension
     if Bt.stride(2) != 1 or ldb < M or (channels > 1 and Bt.stride(0) != channels * ldb):
         Bt, ldb = Bt.contiguous(), M
-    rows = 1
-    for size in lead:
-        rows *= size
     if out is None:
         out = torch.empty(lead + (nseg, u), dtype=torch.float64, device=X.device)
     elif tuple(out.shape) != lead + (nseg, u) or out.dtype != torch.float64 or not out.is_contiguous():
         raise ValueError('out must be a dense float64 tensor of shape {0}'.format(lead + (nseg, u)))
-    _lib.call('shg_segment_products', rows, channels, M, _ptr(X), ldx, _ptr(Bt), ldb, u, nseg, _ptr(seg), _ptr(out), _stream())
+    _lib.call('shg_segment_products', _row_count(lead), channels, M, _ptr(X), ldx, _ptr(Bt), ldb, u, nseg, _ptr(seg), _ptr(out), _stream())
     return out
 
 
@@ -1586,22 +1583,14 @@ def _segment_lag_products(entry, X, seg, lags, out):
     lead = tuple(int(s) for s in X.shape[:-1])
     if X.dtype != torch.float64:
         raise ValueError('X must be float64, got {0}'.format(X.dtype))
-    if tuple(seg.shape) != (seg.numel(),) or seg.numel() < 1 or seg.dtype != torch.int32 or not seg.is_contiguous():
-        raise ValueError('seg must be a dense int32 tensor of shape (nseg + 1,), got {0} {1}'.format(seg.dtype, tuple(seg.shape)))
-    nseg = int(seg.numel()) - 1
-    if X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= M:
-        ldx = int(X.stride(0))
-    else:
-        X, ldx = X.contiguous(), M
-    rows = 1
-    for size in lead:
-        rows *= size
+    nseg = _check_seg(seg)
+    X, ldx = _rows_view(X, M)
     shape = lead + (nseg, max(lags, 0) + 1)
     if out is None:
         out = torch.empty(shape, dtype=torch.float64, device=X.device)
     elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous():
         raise ValueError('out must be a dense float64 tensor of shape {0}'.format(shape))
-    _lib.call(entry, rows, M, _ptr(X), ldx, lags, nseg, _ptr(seg), _ptr(out), _stream())
+    _lib.call(entry, _row_count(lead), M, _ptr(X), ldx, lags, nseg, _ptr(seg), _ptr(out), _stream())
     return out
 
 

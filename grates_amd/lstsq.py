@@ -321,6 +321,19 @@ def _covariance_taps(noise_model):
     return np.stack([function.taps() for function in functions])
 
 
+def _check_model_orders(sequence):
+    """q of an AutoregressiveModelSequence whose models have the orders 0, 1, ..., q <= MAX_WHITENING_ORDER; ValueError else"""
+    q = len(sequence.models) - 1
+    if q < 0:
+        raise ValueError('a noise model without AR models')
+    if q > MAX_WHITENING_ORDER:
+        raise ValueError('maximum order {0} of the noise model above {1}'.format(q, MAX_WHITENING_ORDER))
+    for s, model in enumerate(sequence.models):
+        if model.order != s:
+            raise ValueError('model {0} of the sequence has order {1}: expected the orders 0, 1, ..., {2}'.format(s, model.order, q))
+    return q
+
+
 def whitening_taps(noise_model):
     """
     Tap rows of the decorrelation filter of scalar AR model sequences, ndarray [C, q + 1, q + 1] (host, NumPy only): row s of a
@@ -355,18 +368,13 @@ def whitening_taps(noise_model):
     orders = sorted(set(len(sequence.models) - 1 for sequence in sequences))
     if len(orders) != 1:
         raise ValueError('the noise models of the components differ in their maximum order: {0}'.format(orders))
-    q = orders[0]
-    if q < 0:
-        raise ValueError('a noise model without AR models')
-    if q > MAX_WHITENING_ORDER:
-        raise ValueError('maximum order {0} of the noise model above {1}'.format(q, MAX_WHITENING_ORDER))
+    for sequence in sequences:
+        q = _check_model_orders(sequence)
     taps = np.zeros((len(sequences), q + 1, q + 1))
     for c, sequence in enumerate(sequences):
         for s, model in enumerate(sequence.models):
             if model.dimension != 1:
                 raise ValueError('noise model of dimension {0}: only scalar AR models (dimension 1) decorrelate an arc'.format(model.dimension))
-            if model.order != s:
-                raise ValueError('model {0} of the sequence has order {1}: expected the orders 0, 1, ..., {2}'.format(s, model.order, q))
             variance = float(np.asarray(model.white_noise_covariance, dtype=np.float64).reshape(()))
             if not (np.isfinite(variance) and variance > 0.0):
                 raise ValueError('white-noise variance {0} of the model of order {1} is not finite and positive'.format(variance, s))
@@ -403,19 +411,13 @@ class VectorNoise:
         if not isinstance(sequence, AutoregressiveModelSequence):
             raise ValueError('VectorNoise takes one AutoregressiveModelSequence, got {0!r}'.format(type(sequence).__name__))
         models = sequence.models
-        q = len(models) - 1
-        if q < 0:
-            raise ValueError('a noise model without AR models')
-        if q > MAX_WHITENING_ORDER:
-            raise ValueError('maximum order {0} of the noise model above {1}'.format(q, MAX_WHITENING_ORDER))
+        q = _check_model_orders(sequence)
         K = int(np.shape(models[0].white_noise_covariance)[0]) if np.ndim(models[0].white_noise_covariance) == 2 else 1
         if not MIN_VECTOR_DIMENSION <= K <= MAX_VECTOR_DIMENSION:
             raise ValueError('vector noise of dimension {0}: expected {1} .. {2} (a scalar model is passed as the sequence itself)'.format(
                 K, MIN_VECTOR_DIMENSION, MAX_VECTOR_DIMENSION))
         taps = np.zeros((q + 1, q + 1, K, K))
         for s, model in enumerate(models):
-            if model.order != s:
-                raise ValueError('model {0} of the sequence has order {1}: expected the orders 0, 1, ..., {2}'.format(s, model.order, q))
             Q = np.asarray(model.white_noise_covariance, dtype=np.float64)
             # symmetric up to the rounding of the Yule-Walker solve that formed it (from_covariance_function: Q = Sigma_0 - X^T b as a product)
             if Q.shape != (K, K) or not np.all(np.isfinite(Q)) or not np.all(np.abs(Q - Q.T) <= 1e-8 * np.max(np.abs(Q))):
@@ -451,13 +453,6 @@ class VectorNoise:
         return self.__taps.copy()
 
 
-def _check_noise_model(noise_model):
-    """what the constructors check of a noise model: the ValueErrors of VectorNoise were raised when it was built, a scalar model goes
-    through whitening_taps"""
-    if not isinstance(noise_model, VectorNoise):
-        whitening_taps(noise_model)
-
-
 def _arc_starts(arcs, count):
     """start indices of the arcs of a series of `count` points, int64 ndarray (None: the single arc [0], no arc without points);
     ValueError unless they are integers, strictly increasing, start at 0 and stay below count"""
@@ -487,19 +482,46 @@ def arc_stages(arcs, count, order):
     return np.minimum(since, order).astype(np.int32)
 
 
+class _WhiteningTables:
+    """The tables of a noise model for one series of points: taps and stage on the host and, after to_device, on the device; joint:
+    the taps are the [q + 1, q + 1, K, K] of a VectorNoise (shg_whiten_rows_vector), else the [C, q + 1, q + 1] of whitening_taps
+    (shg_whiten_rows).  The one place that tells the two filters apart: by the type of the model, never by the shape of a table."""
+
+    def __init__(self, noise_model):
+        """every ValueError of the model itself: those of a VectorNoise were raised when it was built, a scalar model goes through
+        whitening_taps.  stage is filled for a series by _whitening_tables"""
+        self.joint = isinstance(noise_model, VectorNoise)
+        self.taps = noise_model.taps() if self.joint else whitening_taps(noise_model)
+        self.stage = self.device_taps = self.device_stage = None
+
+    def __iter__(self):
+        return iter((self.taps, self.stage))                  # taps, stage = _whitening_tables(...): the pair that it returned before
+
+    def to_device(self, device):
+        torch = engine.require_gpu()
+        self.device_taps, self.device_stage = engine.to_device(self.taps, device), torch.from_numpy(self.stage).to(device)
+        return self
+
+    def apply(self, X, start=0, skip=0):
+        """W along the last axis of X [..., n], which holds the points start .. start + n; the first skip of them are history only.  Under a
+        VectorNoise the rows of X, all axes but the last flattened, are groups of its K components"""
+        stage = self.device_stage[start:start + int(X.shape[-1])]
+        if self.joint:
+            return engine.whiten_rows_vector(X, taps=self.device_taps, stage=stage, skip=skip)
+        return engine.whiten_rows(X, taps=self.device_taps, stage=stage, channels=int(self.taps.shape[0]), skip=skip)
+
+
 def _whitening_tables(noise_model, arcs, count, components):
-    """(taps [C, q + 1, q + 1], stage [count]) of a from_* call or of decorrelate, on the host; ValueError before anything reaches the
-    device.  A VectorNoise gives its taps [q + 1, q + 1, K, K] instead: the two kinds of table are told apart by the type of the
-    model, never by their shape"""
-    if isinstance(noise_model, VectorNoise):
-        if noise_model.dimension != components:
-            raise ValueError('a VectorNoise of dimension {0} for observations of {1} component{2}: the two must be equal'.format(
-                noise_model.dimension, components, '' if components == 1 else 's'))
-        return noise_model.taps(), arc_stages(arcs, count, noise_model.maximum_order)
-    taps = whitening_taps(noise_model)
-    if taps.shape[0] not in (1, components):
+    """the _WhiteningTables of a from_* call or of decorrelate, on the host; ValueError before anything reaches the device"""
+    tables = _WhiteningTables(noise_model)
+    taps, joint = tables.taps, tables.joint
+    if joint and taps.shape[2] != components:
+        raise ValueError('a VectorNoise of dimension {0} for observations of {1} component{2}: the two must be equal'.format(
+            taps.shape[2], components, '' if components == 1 else 's'))
+    if not joint and taps.shape[0] not in (1, components):
         raise ValueError('{0} noise models for {1} components: expected one, or one per component'.format(taps.shape[0], components))
-    return taps, arc_stages(arcs, count, taps.shape[1] - 1)
+    tables.stage = arc_stages(arcs, count, taps.shape[0 if joint else 1] - 1)
+    return tables
 
 
 def decorrelate(values, noise_model, arcs=None):
@@ -513,13 +535,9 @@ def decorrelate(values, noise_model, arcs=None):
     if len(shape) not in (1, 2):
         raise ValueError('values must have shape (M,) or (M, K), got {0}'.format(shape))
     M, K = shape[0], (shape[1] if len(shape) == 2 else 1)
-    taps, stage = _whitening_tables(noise_model, arcs, M, K)
-    torch = engine.require_gpu()
+    tables = _whitening_tables(noise_model, arcs, M, K)
     x = engine.to_device(values).reshape(M, K).t().contiguous()
-    if isinstance(noise_model, VectorNoise):
-        y = engine.whiten_rows_vector(x, engine.to_device(taps), torch.from_numpy(stage).to(x.device))
-    else:
-        y = engine.whiten_rows(x, engine.to_device(taps), torch.from_numpy(stage).to(x.device), channels=taps.shape[0])
+    y = tables.to_device(x.device).apply(x)
     return _like_input(y.t().reshape(shape).contiguous(), values)
 
 
@@ -687,13 +705,12 @@ def _route(kind, arguments, band, model, block_points, temporal=None, fit=None):
 class _StochasticModel:
     """The stochastic model of one from_* or of_* call beyond the weights: noise_model and arcs as NormalEquations.from_accelerations
     takes them, parameters an ArcParameters or None; of(model) reads them from None, a ColouredNoise or an ArcParameters.  check(M, K)
-    fills whitening = (taps, stage) of _whitening_tables on the host (None without a noise model) and starts, the start indices of the
-    arcs; to_device the device's taps and stage (None without one) and halo, the host's stage table: what a block takes along in front."""
+    fills whitening, the _WhiteningTables of the call on the host (None without a noise model), and starts, the start indices of the
+    arcs; to_device uploads them and fills halo, the host's stage table: what a block takes along in front."""
 
     def __init__(self, noise_model=None, arcs=None, parameters=None):
         self.noise_model, self.arcs, self.parameters = noise_model, arcs, parameters
-        self.whitening = self.starts = self.taps = self.stage = self.halo = None
-        self.vector = isinstance(noise_model, VectorNoise)               # the kind of the tables: taps [q + 1, q + 1, K, K] of shg_whiten_rows_vector
+        self.whitening = self.starts = self.halo = None
 
     @classmethod
     def of(cls, model):
@@ -716,21 +733,13 @@ class _StochasticModel:
             shape = self.parameters.basis.shape
             if shape[0] != M or (len(shape) == 3 and shape[1] != K):
                 raise ValueError('the arc basis must have shape ({0}, u) or ({0}, {1}, u), got {2}'.format(M, K, shape))
-            if self.vector and len(shape) == 2:
+            if self.whitening is not None and self.whitening.joint and len(shape) == 2:
                 raise ValueError('a shared arc basis ({0}, u) gives every component parameters of its own, which a VectorNoise couples: pass the '
                                  'general basis lstsq.component_basis(basis, {1}) of shape ({0}, {1}, {1} u)'.format(M, K))
 
     def to_device(self, device):
         if self.whitening is not None:
-            torch = engine.require_gpu()
-            self.taps, self.stage, self.halo = engine.to_device(self.whitening[0], device), torch.from_numpy(self.whitening[1]).to(device), self.whitening[1]
-
-    def whiten(self, X, start=0, skip=0):
-        """W along the last axis of X [..., n], which holds the points start .. start + n; the first skip of them are history only.  Under a
-        VectorNoise the rows of X, all axes but the last flattened, are groups of its K components"""
-        if self.vector:
-            return engine.whiten_rows_vector(X, taps=self.taps, stage=self.stage[start:start + int(X.shape[-1])], skip=skip)
-        return engine.whiten_rows(X, taps=self.taps, stage=self.stage[start:start + int(X.shape[-1])], channels=int(self.taps.shape[0]), skip=skip)
+            self.halo = self.whitening.to_device(device).stage
 
 
 def _prepare(observations, model, block_points, fit=None, windows=None):
@@ -763,14 +772,14 @@ def _design_blocks(observations, model, block_points):
     P, M, K, l = observations.P, observations.M, observations.K, observations.l
     for first in range(0, M, block_points):
         last = min(first + block_points, M)
-        if model.taps is None:
+        if model.whitening is None:
             At = observations.design_block(first, last).reshape(P, K * (last - first))
             yield first, last, At, l[first:last].t().reshape(-1, 1), At, 0      # component-major, as the columns of At
         else:
             start = first - int(model.halo[first])
             plain = observations.design_block(start, last).reshape(P * K, last - start)
-            At = model.whiten(plain, start, first - start).reshape(P, K * (last - first))
-            lb = model.whiten(l[start:last].t().contiguous(), start, first - start).reshape(-1, 1)
+            At = model.whitening.apply(plain, start, first - start).reshape(P, K * (last - first))
+            lb = model.whitening.apply(l[start:last].t().contiguous(), start, first - start).reshape(-1, 1)
             yield first, last, At, lb, plain.reshape(P, K * (last - start)), first - start
 
 
@@ -880,11 +889,11 @@ def _temporal_design_blocks(observations, model, windows):
         n = last - start
         T = observations.design_block(start, last).reshape(P * K, n)
         S = engine.window_expand(T, windows.device_factors[start:last], block.run_slot, block.run_begin, E).reshape(E, P, K * n)
-        if model.taps is None:
+        if model.whitening is None:
             yield block, S, l[first:last].t().reshape(-1, 1), S, 0
         else:
-            St = model.whiten(S.reshape(E * P * K, n), start, first - start).reshape(E, P, K * (last - first))
-            lb = model.whiten(l[start:last].t().contiguous(), start, first - start).reshape(-1, 1)
+            St = model.whitening.apply(S.reshape(E * P * K, n), start, first - start).reshape(E, P, K * (last - first))
+            lb = model.whitening.apply(l[start:last].t().contiguous(), start, first - start).reshape(-1, 1)
             yield block, St, lb, S, first - start
 
 
@@ -913,8 +922,8 @@ class _ArcSetup:
         Bt = (Bt if root is None else Bt * root.expand(M, K).t()[None]).contiguous()                    # [u, K, M]
         lt = l.t().contiguous()
         self.plain_Bt = Bt if plain else None
-        if model.taps is not None:
-            Bt, lt = model.whiten(Bt), model.whiten(lt)
+        if model.whitening is not None:
+            Bt, lt = model.whitening.apply(Bt), model.whitening.apply(lt)
         self.Bt, self.u, self.Kc = Bt, int(Bt.shape[0]), (K if self.shared else 1)
         self.bounds = np.append(model.starts, M)
         self.arcs = len(self.bounds) - 1
@@ -1671,7 +1680,7 @@ class ColouredNoise(_BoundModel):
     """
 
     def __init__(self, noise_model, arcs=None):
-        _check_noise_model(noise_model)
+        _WhiteningTables(noise_model)
         self.noise_model, self.arcs = noise_model, arcs
 
 
@@ -1704,7 +1713,7 @@ class ArcParameters(_BoundModel):
         if not np.all(np.isfinite(basis)):
             raise ValueError('the arc basis must be finite')
         if noise_model is not None:
-            _check_noise_model(noise_model)
+            _WhiteningTables(noise_model)
         if isinstance(noise_model, VectorNoise) and basis.ndim == 2:
             raise ValueError('a shared arc basis (M, u) gives every component parameters of its own, which a VectorNoise couples: pass the '
                              'general basis lstsq.component_basis(basis, {0}) of shape (M, {0}, {0} u)'.format(noise_model.dimension))
@@ -1835,7 +1844,7 @@ class _Windows:
         return TemporalParameters.default_block_points(parameters, components, self.W)
 
     def plan(self, model, block_points):
-        self.blocks = temporal_blocks(self.first, self.W, block_points, None if model.whitening is None else model.whitening[1])
+        self.blocks = temporal_blocks(self.first, self.W, block_points, None if model.whitening is None else model.whitening.stage)
 
     def to_device(self, device):
         self.device_factors = engine.to_device(self.factors, device)
@@ -2114,7 +2123,7 @@ class PostFit:
             Xb = Xt[:, columns[0]] if columns else Xt                                                    # the fields of the block
             V[:, :, first:last] = engine.gemm(Xb, At).reshape(rows, K, last - first)
             lt[:, first:last] = lb.reshape(K, last - first)
-            if model.taps is None:
+            if model.whitening is None:
                 plain[:, first:last] = V[0, :, first:last]                                               # white noise: the same values
             else:
                 plain[:, first:last] = engine.gemm(Xb[0:1], At_plain).reshape(K, skip + last - first)[:, skip:]
@@ -2307,22 +2316,26 @@ class PostFit:
         for a maximum_lag outside 0 .. 128 and, with biased=False, for a lag no arc is long enough for.  covariance_lags gives the
         same numbers as arrays, up to lag 4095.
         """
-        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_WHITENING_ORDER:
-            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_WHITENING_ORDER, maximum_lag))
+        _check_maximum_lag(maximum_lag, MAX_WHITENING_ORDER)
         c = self.__covariance(int(maximum_lag), per_component, biased)
         if per_component:
             return [[np.array([[value]]) for value in row] for row in c]
         return [np.array([[value]]) for value in c]
 
-    def __covariance(self, q, per_component, biased):
-        """c [q + 1] or [K, q + 1] of covariance_function and covariance_lags; up to lag 128 shg_segment_lag_products, beyond it
-        shg_segment_lag_products_long"""
+    def __pairs(self, q, biased):
+        """d_k [q + 1] of covariance_function and cross_covariance_function, on the host"""
         lengths = np.diff(np.append(self.arcs, int(self.__rows.shape[1])))
         pairs = np.array([np.maximum(lengths - k, 0).sum() for k in range(q + 1)], dtype=np.float64)
         if biased:
             pairs[:] = pairs[0]
         elif not np.all(pairs > 0):
             raise ValueError('no arc is longer than {0} points: no pair at lag {1}'.format(int(lengths.max()), int(np.argmin(pairs > 0))))
+        return pairs
+
+    def __covariance(self, q, per_component, biased):
+        """c [q + 1] or [K, q + 1] of covariance_function and covariance_lags; up to lag 128 shg_segment_lag_products, beyond it
+        shg_segment_lag_products_long"""
+        pairs = self.__pairs(q, biased)
         products = engine.segment_lag_products if q <= MAX_WHITENING_ORDER else engine.segment_lag_products_long
         sums = engine.to_host(products(self.__rows, self.__seg, q)).sum(axis=1)                           # [K, q + 1]
         if per_component:
@@ -2337,8 +2350,7 @@ class PostFit:
         (shg_segment_lag_products_long), which needs finite residuals.  ValueError, before anything reaches
         the device, for a maximum_lag that is no integer in 0 .. 4095 and, with biased=False, for a lag no arc is long enough for.
         """
-        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_COVARIANCE_ORDER:
-            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_COVARIANCE_ORDER, maximum_lag))
+        _check_maximum_lag(maximum_lag, MAX_COVARIANCE_ORDER)
         return self.__covariance(int(maximum_lag), per_component, biased)
 
     def covariance_model(self, maximum_lag, per_component=False, window=None):
@@ -2351,25 +2363,18 @@ class PostFit:
         semi-definite, so the product stays so) or an array [q + 1] with w_0 = 1.  ValueError for any other window and for the
         maximum_lag, before anything reaches the device.
         """
-        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_COVARIANCE_ORDER:
-            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_COVARIANCE_ORDER, maximum_lag))
+        _check_maximum_lag(maximum_lag, MAX_COVARIANCE_ORDER)
         taper = lag_window(window, int(maximum_lag))
         c = self.__covariance(int(maximum_lag), per_component, True) * taper
         return [CovarianceFunction(row) for row in c] if per_component else CovarianceFunction(c)
 
     def __cross_covariance(self, maximum_lag, biased):
         """Sigma [q + 1, K, K] of cross_covariance_function; its checks on the host first"""
-        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_WHITENING_ORDER:
-            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_WHITENING_ORDER, maximum_lag))
+        _check_maximum_lag(maximum_lag, MAX_WHITENING_ORDER)
         q, K = int(maximum_lag), int(self.__rows.shape[0])
         if K > MAX_VECTOR_DIMENSION:
             raise ValueError('cross-covariances of {0} components: at most {1}'.format(K, MAX_VECTOR_DIMENSION))
-        lengths = np.diff(np.append(self.arcs, int(self.__rows.shape[1])))
-        pairs = np.array([np.maximum(lengths - k, 0).sum() for k in range(q + 1)], dtype=np.float64)
-        if biased:
-            pairs[:] = pairs[0]
-        elif not np.all(pairs > 0):
-            raise ValueError('no arc is longer than {0} points: no pair at lag {1}'.format(int(lengths.max()), int(np.argmin(pairs > 0))))
+        pairs = self.__pairs(q, biased)
         sums = engine.to_host(engine.segment_cross_lag_products(self.__rows, self.__seg, q)).sum(axis=0)      # [q + 1, K, K]
         return sums / pairs[:, None, None]
 
@@ -2394,8 +2399,7 @@ class PostFit:
         maximum_lag and fewer than 2 components before anything reaches the device; VectorNoise raises its own for an estimate that
         is not positive definite.
         """
-        if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= MAX_WHITENING_ORDER:
-            raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(MAX_WHITENING_ORDER, maximum_lag))
+        _check_maximum_lag(maximum_lag, MAX_WHITENING_ORDER)
         K = int(self.__rows.shape[0])
         if not MIN_VECTOR_DIMENSION <= K <= MAX_VECTOR_DIMENSION:
             raise ValueError('vector noise of {0} component{1}: expected {2} .. {3} (covariance_model gives the scalar model)'.format(
@@ -2403,6 +2407,11 @@ class PostFit:
         taper = lag_window(window, int(maximum_lag))
         lags = self.__cross_covariance(maximum_lag, True) * taper[:, None, None]
         return VectorNoise(AutoregressiveModelSequence.from_covariance_function([np.ascontiguousarray(lag) for lag in lags]))
+
+
+def _check_maximum_lag(maximum_lag, most):
+    if int(maximum_lag) != maximum_lag or not 0 <= maximum_lag <= most:
+        raise ValueError('maximum_lag must be an integer in 0 .. {0}, got {1!r}'.format(most, maximum_lag))
 
 
 def lag_window(window, maximum_lag):

@@ -172,30 +172,6 @@ SEGMENTS = [0, 1, 4, 300, 300, 700]   # the arcs of the whitening tests, with an
 INNER = [2, 5, 5, 650]                # columns 0, 1 and 650 .. 699 belong to no segment
 
 
-def _exact_cross(X, seg, lags):
-    """(S [nseg, lags + 1, K, K], magnitude, pairs [nseg, lags + 1]) in numpy.longdouble, rounded once: its own error is 2^-11 of u"""
-    K = X.shape[0]
-    Xl = X.astype(np.longdouble)
-    nseg = len(seg) - 1
-    S, magnitude = np.zeros((nseg, lags + 1, K, K)), np.zeros((nseg, lags + 1, K, K))
-    pairs = np.zeros((nseg, lags + 1), dtype=np.int64)
-    for s in range(nseg):
-        a, b = seg[s], seg[s + 1]
-        for k in range(lags + 1):
-            if b - a > k:
-                left, right = Xl[:, a:b - k], Xl[:, a + k:b]
-                S[s, k] = (left @ right.T).astype(np.float64)
-                magnitude[s, k] = (np.abs(left) @ np.abs(right).T).astype(np.float64)
-                pairs[s, k] = b - a - k
-    return S, magnitude, pairs
-
-
-def _cross_bound(magnitude, pairs):
-    """(ceil(pairs / 64) + 6 + 1) u sum |x y|: the FMAs of the longest of the 64 chains, the six additions of the butterfly and one unit
-    for the reference"""
-    return ((pairs + 63) // 64 + 7)[:, :, None, None] * U * magnitude
-
-
 @pytest.mark.parametrize('lags', [0, 5, 128])
 def test_cross_lag_products(lags):
     K = 3
@@ -208,8 +184,8 @@ def test_cross_lag_products(lags):
     scalar = _host(ga.engine.segment_lag_products(view, _int32(SEGMENTS), lags))                           # [K, nseg, lags + 1]
     for c in range(K):
         assert np.array_equal(S[:, :, c, c], scalar[c]), c                                                 # the diagonal, bitwise
-    reference, magnitude, pairs = _exact_cross(X, SEGMENTS, lags)
-    bound = _cross_bound(magnitude, pairs)
+    reference, magnitude, pairs = vr.exact_cross(X, SEGMENTS, lags)
+    bound = vr.cross_bound(magnitude, pairs)
     ratio = np.abs(S - reference) / np.where(bound > 0, bound, 1.0)
     print('lags {0}: {1:.3f} of the chain bound'.format(lags, ratio.max()))
     assert np.all(np.abs(S - reference) <= bound)

@@ -2,7 +2,8 @@
 NumPy helpers of the vector-noise tests (tests/test_vector_noise_cpu.py, tests/test_gpu_vector_noise.py): known stable VAR processes
 with non-symmetric coefficients, their covariance functions Sigma_k = E[x_t x_(t+k)^T] from the Lyapunov equation of the companion
 form, the block Yule-Walker systems solved in NumPy (AutoregressiveModelSequence.from_covariance_function needs the device), dense
-filters and an extended-precision evaluation of the filter.  No GPU, no file.
+filters, an extended-precision evaluation of the filter, and the exact cross-lag sums with their chain bound
+(tests/test_gpu_lag_body.py too).  No GPU, no file.
 """
 import numpy as np
 
@@ -141,3 +142,27 @@ def simulate(B, Q, arcs, count, seed, burn=200):
             x[t] = w[t] + sum(B[k] @ x[t - k - 1] for k in range(p) if t - k - 1 >= 0)
         out[bounds[a]:bounds[a + 1]] = x[burn:]
     return out
+
+
+def exact_cross(X, seg, lags):
+    """(S [nseg, lags + 1, K, K], magnitude, pairs [nseg, lags + 1]) in numpy.longdouble, rounded once: its own error is 2^-11 of u"""
+    K = X.shape[0]
+    Xl = X.astype(np.longdouble)
+    nseg = len(seg) - 1
+    S, magnitude = np.zeros((nseg, lags + 1, K, K)), np.zeros((nseg, lags + 1, K, K))
+    pairs = np.zeros((nseg, lags + 1), dtype=np.int64)
+    for s in range(nseg):
+        a, b = seg[s], seg[s + 1]
+        for k in range(lags + 1):
+            if b - a > k:
+                left, right = Xl[:, a:b - k], Xl[:, a + k:b]
+                S[s, k] = (left @ right.T).astype(np.float64)
+                magnitude[s, k] = (np.abs(left) @ np.abs(right).T).astype(np.float64)
+                pairs[s, k] = b - a - k
+    return S, magnitude, pairs
+
+
+def cross_bound(magnitude, pairs):
+    """(ceil(pairs / 64) + 6 + 1) u sum |x y|: the FMAs of the longest of the 64 chains, the six additions of the butterfly and one unit
+    for the reference"""
+    return ((pairs + 63) // 64 + 7)[:, :, None, None] * U * magnitude
