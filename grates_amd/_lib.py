@@ -35,6 +35,7 @@ PROTOTYPES = {
     'shg_plan_set_rotations': [c_plan_p, ctypes.c_int],
     'shg_plan_set_stage_limit': [c_plan_p, ctypes.c_int],
     'shg_plan_set_order_pruning': [c_plan_p, ctypes.c_int],
+    'shg_plan_set_half_tile_fold': [c_plan_p, ctypes.c_int],
     'shg_plan_order_cutoffs': [c_plan_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     'shg_rot_order_cutoffs': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
     'shg_rot_level_tables': [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_int32), c_double_p,

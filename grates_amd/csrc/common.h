@@ -294,6 +294,7 @@ struct shg_plan {
     shg::DeviceArray<double> rot_trig; // [column tiles][k-steps][64 lanes][2] cos / signed sin stream of that kernel, one per level of rot_level_set
     // order pruning of that kernel: a latitude block near a pole keeps the orders 0 .. level only (synthesis_rot.hip)
     bool order_pruning = true;        // shg_plan_set_order_pruning
+    bool half_tile_fold = true;       // shg_plan_set_half_tile_fold
     std::vector<int> rot_levels;      // per latitude block of that kernel: largest order kept (N = everything)
     std::vector<int> rot_level_set;   // the distinct levels, N first, then descending: one layout, trig stream and item table each
     std::vector<int> rot_trig_piece;  // per level: first piece of its trig stream in rot_trig
@@ -405,7 +406,7 @@ int rot_applicable(const shg_plan* p);
 int build_rot_trig(shg_plan* p, const double* lon_h);
 void rot_order_cutoffs(int N, int nlat, const double* colat, const double* kn, bool ns, std::vector<int>& levels);
 std::vector<int> rot_level_list(int N, const std::vector<int>& levels);
-void rot_trig_stream(int R, int N, int level, int nlon, const double* lon_h, std::vector<double>& tab);
+void rot_trig_stream(int R, int N, int level, int nlon, const double* lon_h, std::vector<double>& tab, bool fill_half);
 void item_table_host(const shg_plan* p, int N, int level, int od, const std::vector<int>& qoff, int rotR, std::vector<int>& table, int& nrec, int& ntrip);
 int synthesis_rot(shg_plan* p, const double* anm, int B, double* grid, hipStream_t stream);
 int rot_kernel_waves();           // waves per workgroup of the rotation-folded kernel

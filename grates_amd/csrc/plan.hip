@@ -576,6 +576,14 @@ extern "C" int shg_plan_set_order_pruning(shg_plan* p, int enable) {
     return SHG_OK;
 }
 
+extern "C" int shg_plan_set_half_tile_fold(shg_plan* p, int enable) {
+    SHG_REQUIRE(p != nullptr, "shg_plan_set_half_tile_fold: NULL plan");
+    SHG_REQUIRE(enable == 0 || enable == 1, "shg_plan_set_half_tile_fold: %d not in {0, 1}", enable);
+    std::unique_lock<std::mutex> lock(p->mtx);
+    p->half_tile_fold = enable != 0;
+    return SHG_OK;
+}
+
 extern "C" int shg_plan_order_cutoffs(const shg_plan* p, int* levels, int capacity, int* nblocks, int* enabled) {
     SHG_REQUIRE(p != nullptr && nblocks != nullptr, "shg_plan_order_cutoffs: NULL argument");
     SHG_REQUIRE(capacity >= 0 && (levels != nullptr || capacity == 0), "shg_plan_order_cutoffs: NULL table of %d entries", capacity);
@@ -615,7 +623,7 @@ extern "C" int shg_rot_level_tables(int R, int N, int level, int ns, int nlon, c
         header[8 + kRotMaxClasses + c] = cnt[c];
     }
     std::vector<double> tab;
-    rot_trig_stream(R, N, level, nlon, lon_h, tab);
+    rot_trig_stream(R, N, level, nlon, lon_h, tab, false);
     const int od = ns ? 16 : 8;
     std::vector<int> qoff(N + 2), table;
     int q = 0;
@@ -661,7 +669,8 @@ extern "C" int shg_plan_info(const shg_plan* p, int64_t which[8]) {
     which[0] = p->N;
     which[1] = p->nlat;
     which[2] = p->nlon;
-    which[3] = (p->sym4 ? 1 : 0) | (p->sym_ns ? 2 : 0) | (rot_applicable(p) ? 4 : 0);
+    which[3] = (p->sym4 ? 1 : 0) | (p->sym_ns ? 2 : 0) | (rot_applicable(p) ? 4 : 0) |
+               (rot_applicable(p) && p->half_tile_fold && (p->nlon / (2 * p->rotR)) % 16 == 8 ? 8 : 0);
     which[4] = p->chunk;
     which[5] = p->K;
     which[6] = (p->path >= 2 || (p->path == 0 && (rot_applicable(p) || fused_chunk_for(p) != 0 || fused32_applicable(p)))) ? 1 : 0;

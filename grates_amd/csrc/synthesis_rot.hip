@@ -66,12 +66,20 @@ struct RotTraits {
     static constexpr int kClasses = R / 2 + 1, kTwo = R % 2 == 0 ? 2 : 1, kAcc = 2 * R;
     // accumulators of class r: (CA, SB) at a(r) for the two-sum classes, (CA, SA, CB, SB) at a(r) for the others
     static constexpr int acc_of(int r) { return r == 0 ? 0 : (R % 2 == 0 && 2 * r == R) ? 2 : 2 * kTwo + 4 * (r - 1); }
+    static constexpr bool two_sums(int r) { return r == 0 || 2 * r == R; }
+    // behind rot_split: X_r(s) and Y_r(s) (-1: the class has none), s = 0 for the sign +1 and 1 for the sign -1, in the accumulators of
+    // their class -- X(+) for CA, X(-) for SB, Y(+) for CB, Y(-) for SA --, and the accumulator that rot_half leaves image k of sign s in:
+    // the k-th of the sign's own R accumulators (X_0, X_(R/2) for even R, then X_1, Y_1, X_2, Y_2, ...)
+    static constexpr int x_of(int r, int s) { return acc_of(r) + (two_sums(r) ? s : 3 * s); }
+    static constexpr int y_of(int r, int s) { return two_sums(r) ? -1 : acc_of(r) + 2 - s; }
+    static constexpr int img_of(int k, int s) { return k < kTwo ? x_of(k == 0 ? 0 : R / 2, s) : (k - kTwo) % 2 == 0 ? x_of(1 + (k - kTwo) / 2, s) : y_of(1 + (k - kTwo) / 2, s); }
 };
 
 struct RotParams {
     int N, nlat, nlon, B, nit, nh;
     int nd;                   // columns of the fundamental domain = nlon / (2 R)
     int nct;                  // column tiles of 16
+    int half_fold;            // 1: nd % 16 == 8 and the last column tile runs on the 16 real columns nd - 8 .. nd + 7, ascending images only (rot_phase2)
     int npieces;              // trig pieces (k-steps) per column tile = sum of cls_nk
     int cls_nk[kMaxClasses];  // k-steps (4 orders each) of the classes in K order; their panel slots follow each other: class c starts at 4 * (nk[0] + .. + nk[c-1])
     int cls_cnt[kMaxClasses]; // orders in each class (the slots up to 4 * cls_nk are zero padding)
@@ -149,151 +157,139 @@ __device__ __forceinline__ void wait_vmcnt() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// The 2 R images of one (row, column) from its sums, in place: acc[t] <- image t, t = k (s = +1, ascending columns) or R + k
-// (s = -1, descending columns).  X_r(s) = CA_r + s SB_r, Y_r(s) = CB_r - s SA_r.
+// The 2 R images of one (row, column) from its sums, in place and in two steps.  rot_split turns the sums of every class into
+// X_r(s) = CA_r + s SB_r and Y_r(s) = CB_r - s SA_r for both signs (RotTraits::x_of, y_of): from then on the sign s = +1 (ascending
+// columns) and the sign s = -1 (descending columns) own R accumulators each.  rot_half<R, S> forms the R images of one sign from that
+// sign's R accumulators and leaves image k in accumulator RotTraits::img_of(k, S): the folded last column tile (rot_phase2) never
+// runs the half of s = -1.  Every image is the same expression of the same sums whichever halves run, hence the same bits.
 template <int R>
-__device__ __forceinline__ void rot_images(double4_t* acc, int r);
+__device__ __forceinline__ void rot_split(double4_t* acc, int r) {
+    using T = RotTraits<R>;
+#pragma unroll
+    for (int c = 0; c <= R / 2; ++c) {
+        const int a = T::acc_of(c);
+        if (T::two_sums(c)) {
+            const double ca = acc[a][r], sb = acc[a + 1][r];
+            acc[T::x_of(c, 0)][r] = ca + sb;
+            acc[T::x_of(c, 1)][r] = ca - sb;
+        } else {
+            const double ca = acc[a][r], sa = acc[a + 1][r], cb = acc[a + 2][r], sb = acc[a + 3][r];
+            acc[T::x_of(c, 0)][r] = ca + sb;
+            acc[T::y_of(c, 0)][r] = cb - sa;
+            acc[T::x_of(c, 1)][r] = ca - sb;
+            acc[T::y_of(c, 1)][r] = cb + sa;
+        }
+    }
+}
 
-// R = 6, accumulators 0 CA_0, 1 SB_0, 2 CA_3, 3 SB_3, 4-7 (CA, SA, CB, SB)_1, 8-11 (CA, SA, CB, SB)_2.  With g = sqrt(3) / 2:
+// R = 6, classes 0, 3 (two sums) and 1, 2.  With g = sqrt(3) / 2:
 //   E_0 = X_0 + X_2,  E_1 = X_0 - X_2 / 2 + g Y_2,  E_2 = X_0 - X_2 / 2 - g Y_2        (classes 0, 2: period 3 in k)
 //   O_0 = X_1 + X_3,  O_1 = X_1 / 2 + g Y_1 - X_3,  O_2 = -X_1 / 2 + g Y_1 + X_3       (classes 1, 3: O_(k+3) = -O_k)
 //   f_k = E_k + O_k,  f_(k+3) = E_k - O_k,  k = 0, 1, 2.
-template <>
-__device__ __forceinline__ void rot_images<6>(double4_t* acc, int r) {
+template <int S>
+__device__ __forceinline__ void rot_half6(double4_t* acc, int r) {
+    using T = RotTraits<6>;
     constexpr double g = 0.86602540378443864676;
-    const double ca0 = acc[0][r], sb0 = acc[1][r], ca3 = acc[2][r], sb3 = acc[3][r];
-    const double ca1 = acc[4][r], sa1 = acc[5][r], cb1 = acc[6][r], sb1 = acc[7][r];
-    const double ca2 = acc[8][r], sa2 = acc[9][r], cb2 = acc[10][r], sb2 = acc[11][r];
-#pragma unroll
-    for (int sgn = 0; sgn < 2; ++sgn) {
-        const double x0 = sgn ? ca0 - sb0 : ca0 + sb0, x3 = sgn ? ca3 - sb3 : ca3 + sb3;
-        const double x1 = sgn ? ca1 - sb1 : ca1 + sb1, y1 = sgn ? cb1 + sa1 : cb1 - sa1;
-        const double x2 = sgn ? ca2 - sb2 : ca2 + sb2, y2 = sgn ? cb2 + sa2 : cb2 - sa2;
-        const double t = fma(-0.5, x2, x0);
-        const double e0 = x0 + x2, e1 = fma(g, y2, t), e2 = fma(-g, y2, t);
-        const double u = fma(0.5, x1, -x3);
-        const double o0 = x1 + x3, o1 = fma(g, y1, u), o2 = fma(g, y1, -u);
-        acc[6 * sgn + 0][r] = e0 + o0;
-        acc[6 * sgn + 3][r] = e0 - o0;
-        acc[6 * sgn + 1][r] = e1 + o1;
-        acc[6 * sgn + 4][r] = e1 - o1;
-        acc[6 * sgn + 2][r] = e2 + o2;
-        acc[6 * sgn + 5][r] = e2 - o2;
-    }
+    const double x0 = acc[T::x_of(0, S)][r], x3 = acc[T::x_of(3, S)][r];
+    const double x1 = acc[T::x_of(1, S)][r], y1 = acc[T::y_of(1, S)][r];
+    const double x2 = acc[T::x_of(2, S)][r], y2 = acc[T::y_of(2, S)][r];
+    const double t = fma(-0.5, x2, x0);
+    const double e0 = x0 + x2, e1 = fma(g, y2, t), e2 = fma(-g, y2, t);
+    const double u = fma(0.5, x1, -x3);
+    const double o0 = x1 + x3, o1 = fma(g, y1, u), o2 = fma(g, y1, -u);
+    acc[T::img_of(0, S)][r] = e0 + o0;
+    acc[T::img_of(3, S)][r] = e0 - o0;
+    acc[T::img_of(1, S)][r] = e1 + o1;
+    acc[T::img_of(4, S)][r] = e1 - o1;
+    acc[T::img_of(2, S)][r] = e2 + o2;
+    acc[T::img_of(5, S)][r] = e2 - o2;
 }
 
-// R = 3, accumulators 0 CA_0, 1 SB_0, 2-5 (CA, SA, CB, SB)_1:  f_0 = X_0 + X_1,  f_1,2 = X_0 - X_1 / 2 +- g Y_1.
-template <>
-__device__ __forceinline__ void rot_images<3>(double4_t* acc, int r) {
+// R = 3, classes 0 (two sums) and 1:  f_0 = X_0 + X_1,  f_1,2 = X_0 - X_1 / 2 +- g Y_1.
+template <int S>
+__device__ __forceinline__ void rot_half3(double4_t* acc, int r) {
+    using T = RotTraits<3>;
     constexpr double g = 0.86602540378443864676;
-    const double ca0 = acc[0][r], sb0 = acc[1][r];
-    const double ca1 = acc[2][r], sa1 = acc[3][r], cb1 = acc[4][r], sb1 = acc[5][r];
-#pragma unroll
-    for (int sgn = 0; sgn < 2; ++sgn) {
-        const double x0 = sgn ? ca0 - sb0 : ca0 + sb0;
-        const double x1 = sgn ? ca1 - sb1 : ca1 + sb1, y1 = sgn ? cb1 + sa1 : cb1 - sa1;
-        const double t = fma(-0.5, x1, x0);
-        acc[3 * sgn + 0][r] = x0 + x1;
-        acc[3 * sgn + 1][r] = fma(g, y1, t);
-        acc[3 * sgn + 2][r] = fma(-g, y1, t);
-    }
+    const double x0 = acc[T::x_of(0, S)][r];
+    const double x1 = acc[T::x_of(1, S)][r], y1 = acc[T::y_of(1, S)][r];
+    const double t = fma(-0.5, x1, x0);
+    acc[T::img_of(0, S)][r] = x0 + x1;
+    acc[T::img_of(1, S)][r] = fma(g, y1, t);
+    acc[T::img_of(2, S)][r] = fma(-g, y1, t);
 }
 
-// R = 9, accumulators 0 CA_0, 1 SB_0, 2 + 4 (r - 1) .. (CA, SA, CB, SB)_r, r = 1 .. 4.  With c_j = cos(40 j deg), s_j = sin(40 j deg)
+// R = 9, classes 0 (two sums) and 1 .. 4.  With c_j = cos(40 j deg), s_j = sin(40 j deg)
 // (c_3 = -1/2, s_3 = sqrt(3) / 2) and C_k = X_0 + sum_r c_(rk mod 9) X_r, S_k = sum_r s_(rk mod 9) Y_r:
 //   f_0 = X_0 + X_1 + X_2 + X_3 + X_4,   f_k = C_k + S_k,   f_(9-k) = C_k - S_k,   k = 1 .. 4.
-template <>
-__device__ __forceinline__ void rot_images<9>(double4_t* acc, int r) {
+template <int S>
+__device__ __forceinline__ void rot_half9(double4_t* acc, int r) {
+    using T = RotTraits<9>;
     constexpr double c1 = 0.76604444311897803520, c2 = 0.17364817766693034885, c4 = -0.93969262078590838405;
     constexpr double s1 = 0.64278760968653932632, s2 = 0.98480775301220805937, s3 = 0.86602540378443864676, s4 = 0.34202014332566873304;
-    const double ca0 = acc[0][r], sb0 = acc[1][r];
-    double ca[4], sa[4], cb[4], sb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        ca[j] = acc[2 + 4 * j][r];
-        sa[j] = acc[3 + 4 * j][r];
-        cb[j] = acc[4 + 4 * j][r];
-        sb[j] = acc[5 + 4 * j][r];
-    }
-#pragma unroll
-    for (int sgn = 0; sgn < 2; ++sgn) {
-        const double x0 = sgn ? ca0 - sb0 : ca0 + sb0;
-        double x[4], y[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            x[j] = sgn ? ca[j] - sb[j] : ca[j] + sb[j];
-            y[j] = sgn ? cb[j] + sa[j] : cb[j] - sa[j];
-        }
-        const double x1 = x[0], x2 = x[1], x3 = x[2], x4 = x[3], y1 = y[0], y2 = y[1], y3 = y[2], y4 = y[3];
-        const double t = (x1 + x2) + x4, x03 = x0 + x3;
-        const double h = fma(-0.5, x3, x0), u = s3 * y3;
-        const double C1 = fma(c1, x1, fma(c2, x2, fma(c4, x4, h)));
-        const double C2 = fma(c2, x1, fma(c4, x2, fma(c1, x4, h)));
-        const double C3 = fma(-0.5, t, x03);
-        const double C4 = fma(c4, x1, fma(c1, x2, fma(c2, x4, h)));
-        const double S1 = fma(s1, y1, fma(s2, y2, fma(s4, y4, u)));
-        const double S2 = fma(s2, y1, fma(s4, y2, fma(-s1, y4, -u)));
-        const double S3 = s3 * ((y1 - y2) + y4);
-        const double S4 = fma(s4, y1, fma(-s1, y2, fma(-s2, y4, u)));
-        acc[9 * sgn + 0][r] = x03 + t;
-        acc[9 * sgn + 1][r] = C1 + S1;
-        acc[9 * sgn + 8][r] = C1 - S1;
-        acc[9 * sgn + 2][r] = C2 + S2;
-        acc[9 * sgn + 7][r] = C2 - S2;
-        acc[9 * sgn + 3][r] = C3 + S3;
-        acc[9 * sgn + 6][r] = C3 - S3;
-        acc[9 * sgn + 4][r] = C4 + S4;
-        acc[9 * sgn + 5][r] = C4 - S4;
-    }
+    const double x0 = acc[T::x_of(0, S)][r];
+    const double x1 = acc[T::x_of(1, S)][r], x2 = acc[T::x_of(2, S)][r], x3 = acc[T::x_of(3, S)][r], x4 = acc[T::x_of(4, S)][r];
+    const double y1 = acc[T::y_of(1, S)][r], y2 = acc[T::y_of(2, S)][r], y3 = acc[T::y_of(3, S)][r], y4 = acc[T::y_of(4, S)][r];
+    const double t = (x1 + x2) + x4, x03 = x0 + x3;
+    const double h = fma(-0.5, x3, x0), u = s3 * y3;
+    const double C1 = fma(c1, x1, fma(c2, x2, fma(c4, x4, h)));
+    const double C2 = fma(c2, x1, fma(c4, x2, fma(c1, x4, h)));
+    const double C3 = fma(-0.5, t, x03);
+    const double C4 = fma(c4, x1, fma(c1, x2, fma(c2, x4, h)));
+    const double S1 = fma(s1, y1, fma(s2, y2, fma(s4, y4, u)));
+    const double S2 = fma(s2, y1, fma(s4, y2, fma(-s1, y4, -u)));
+    const double S3 = s3 * ((y1 - y2) + y4);
+    const double S4 = fma(s4, y1, fma(-s1, y2, fma(-s2, y4, u)));
+    acc[T::img_of(0, S)][r] = x03 + t;
+    acc[T::img_of(1, S)][r] = C1 + S1;
+    acc[T::img_of(8, S)][r] = C1 - S1;
+    acc[T::img_of(2, S)][r] = C2 + S2;
+    acc[T::img_of(7, S)][r] = C2 - S2;
+    acc[T::img_of(3, S)][r] = C3 + S3;
+    acc[T::img_of(6, S)][r] = C3 - S3;
+    acc[T::img_of(4, S)][r] = C4 + S4;
+    acc[T::img_of(5, S)][r] = C4 - S4;
 }
 
-// R = 10, accumulators 0 CA_0, 1 SB_0, 2 CA_5, 3 SB_5, 4 + 4 (r - 1) .. (CA, SA, CB, SB)_r, r = 1 .. 4.  With c1 = cos 36, c2 = cos 72,
+// R = 10, classes 0, 5 (two sums) and 1 .. 4.  With c1 = cos 36, c2 = cos 72,
 // s1 = sin 36, s2 = sin 72 (degrees): the even classes have period 5 in k, the odd ones change sign after 5 steps,
 //   E_0 = X_0 + X_2 + X_4,  E_1,4 = (X_0 + c2 X_2 - c1 X_4) +- (s2 Y_2 + s1 Y_4),  E_2,3 = (X_0 - c1 X_2 + c2 X_4) +- (s1 Y_2 - s2 Y_4)
 //   O_0 = X_1 + X_3 + X_5,  O_1,4 = (s1 Y_1 + s2 Y_3) +- (c1 X_1 - c2 X_3 - X_5),  O_2,3 = (s2 Y_1 - s1 Y_3) +- (c2 X_1 - c1 X_3 + X_5)
 //   f_k = E_k + O_k,  f_(k+5) = E_k - O_k,  k = 0 .. 4.
-template <>
-__device__ __forceinline__ void rot_images<10>(double4_t* acc, int r) {
+template <int S>
+__device__ __forceinline__ void rot_half10(double4_t* acc, int r) {
+    using T = RotTraits<10>;
     constexpr double c1 = 0.80901699437494742410, c2 = 0.30901699437494742410;
     constexpr double s1 = 0.58778525229247312917, s2 = 0.95105651629515357212;
-    const double ca0 = acc[0][r], sb0 = acc[1][r], ca5 = acc[2][r], sb5 = acc[3][r];
-    double ca[4], sa[4], cb[4], sb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        ca[j] = acc[4 + 4 * j][r];
-        sa[j] = acc[5 + 4 * j][r];
-        cb[j] = acc[6 + 4 * j][r];
-        sb[j] = acc[7 + 4 * j][r];
-    }
-#pragma unroll
-    for (int sgn = 0; sgn < 2; ++sgn) {
-        const double x0 = sgn ? ca0 - sb0 : ca0 + sb0, x5 = sgn ? ca5 - sb5 : ca5 + sb5;
-        double x[4], y[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            x[j] = sgn ? ca[j] - sb[j] : ca[j] + sb[j];
-            y[j] = sgn ? cb[j] + sa[j] : cb[j] - sa[j];
-        }
-        const double x1 = x[0], x2 = x[1], x3 = x[2], x4 = x[3], y1 = y[0], y2 = y[1], y3 = y[2], y4 = y[3];
-        const double e0 = (x0 + x2) + x4;
-        const double a1 = fma(c2, x2, fma(-c1, x4, x0)), b1 = fma(s2, y2, s1 * y4);
-        const double a2 = fma(-c1, x2, fma(c2, x4, x0)), b2 = fma(s1, y2, -(s2 * y4));
-        const double e1 = a1 + b1, e4 = a1 - b1, e2 = a2 + b2, e3 = a2 - b2;
-        const double o0 = (x1 + x3) + x5;
-        const double p = fma(c1, x1, fma(-c2, x3, -x5)), q = fma(s1, y1, s2 * y3);
-        const double u = fma(c2, x1, fma(-c1, x3, x5)), v = fma(s2, y1, -(s1 * y3));
-        const double o1 = q + p, o4 = q - p, o2 = v + u, o3 = v - u;
-        acc[10 * sgn + 0][r] = e0 + o0;
-        acc[10 * sgn + 5][r] = e0 - o0;
-        acc[10 * sgn + 1][r] = e1 + o1;
-        acc[10 * sgn + 6][r] = e1 - o1;
-        acc[10 * sgn + 2][r] = e2 + o2;
-        acc[10 * sgn + 7][r] = e2 - o2;
-        acc[10 * sgn + 3][r] = e3 + o3;
-        acc[10 * sgn + 8][r] = e3 - o3;
-        acc[10 * sgn + 4][r] = e4 + o4;
-        acc[10 * sgn + 9][r] = e4 - o4;
-    }
+    const double x0 = acc[T::x_of(0, S)][r], x5 = acc[T::x_of(5, S)][r];
+    const double x1 = acc[T::x_of(1, S)][r], x2 = acc[T::x_of(2, S)][r], x3 = acc[T::x_of(3, S)][r], x4 = acc[T::x_of(4, S)][r];
+    const double y1 = acc[T::y_of(1, S)][r], y2 = acc[T::y_of(2, S)][r], y3 = acc[T::y_of(3, S)][r], y4 = acc[T::y_of(4, S)][r];
+    const double e0 = (x0 + x2) + x4;
+    const double a1 = fma(c2, x2, fma(-c1, x4, x0)), b1 = fma(s2, y2, s1 * y4);
+    const double a2 = fma(-c1, x2, fma(c2, x4, x0)), b2 = fma(s1, y2, -(s2 * y4));
+    const double e1 = a1 + b1, e4 = a1 - b1, e2 = a2 + b2, e3 = a2 - b2;
+    const double o0 = (x1 + x3) + x5;
+    const double p = fma(c1, x1, fma(-c2, x3, -x5)), q = fma(s1, y1, s2 * y3);
+    const double u = fma(c2, x1, fma(-c1, x3, x5)), v = fma(s2, y1, -(s1 * y3));
+    const double o1 = q + p, o4 = q - p, o2 = v + u, o3 = v - u;
+    acc[T::img_of(0, S)][r] = e0 + o0;
+    acc[T::img_of(5, S)][r] = e0 - o0;
+    acc[T::img_of(1, S)][r] = e1 + o1;
+    acc[T::img_of(6, S)][r] = e1 - o1;
+    acc[T::img_of(2, S)][r] = e2 + o2;
+    acc[T::img_of(7, S)][r] = e2 - o2;
+    acc[T::img_of(3, S)][r] = e3 + o3;
+    acc[T::img_of(8, S)][r] = e3 - o3;
+    acc[T::img_of(4, S)][r] = e4 + o4;
+    acc[T::img_of(9, S)][r] = e4 - o4;
+}
+
+template <int R, int S>
+__device__ __forceinline__ void rot_half(double4_t* acc, int r) {
+    static_assert(R == 10 || R == 9 || R == 6 || R == 3, "no butterfly for this rotation count");
+    if constexpr (R == 10) rot_half10<S>(acc, r);
+    else if constexpr (R == 9) rot_half9<S>(acc, r);
+    else if constexpr (R == 6) rot_half6<S>(acc, r);
+    else rot_half3<S>(acc, r);
 }
 
 // Trig stream and fragment registers of one consumer wave; in the persistent kernel they live across tiles.
@@ -352,7 +348,6 @@ __device__ __forceinline__ void rot_phase2(const RotParams& P, const double* As,
                                            int b0, int it) {
     constexpr int PR = 16 * EP;                        // panel rows
     using T = RotTraits<R>;
-    constexpr int kImages = 2 * R;
     const int fr = lane & 15, fk = lane >> 4;
     const int i0 = it * 16, i0n = it * 8;
     const unsigned lane_off = (unsigned)lane * 16u;
@@ -469,44 +464,73 @@ __device__ __forceinline__ void rot_phase2(const RotParams& P, const double* As,
         }
         ROT_STAMP(3 + 2 * min(q, 3));
 
-        // ---- epilogue: the 2 R images of every column, in place
-#pragma unroll
-        for (int r = 0; r < 4; ++r) rot_images<R>(acc, r);      // (unconditional: a run-time switch around an in-place update of the
-                                                                //  accumulator vectors makes hipcc copy every vector, ~60 moves per row)
+        // ---- epilogue: the images of every column, in place.  Where nd % 16 == 8 the last column tile runs on 16 real columns,
+        //      c' = nd - 8 .. nd + 7: the plan's trig stream carries mu_c' = 2 pi / R - mu_(2 nd - 1 - c') in its lanes 8 .. 15, and the descending
+        //      image k + 1 of column c IS the ascending image k of column 2 nd - 1 - c (-mu_c + 2 pi (k + 1) / R = mu_c' + 2 pi k / R).  That
+        //      tile forms and stores its R ascending images only, 16 columns of every row in one piece, and no descending image at all.
+        const bool fold = P.half_fold != 0 && ct == P.nct - 1;           // wave-uniform
         const int b = b0 + rt;
         const bool epoch_ok = b < P.B && !SHG_DBG(P, 1);
         double* const Gb = P.G + (size_t)min(b, P.B - 1) * P.nlat * P.nlon;
-        {
-            // lanes (2 q, 2 q + 1) hold adjacent columns: after the exchange every lane owns two rows x two adjacent columns and
-            // stores 16 bytes.  Byte offset = lane part (row, column inside the tile) + wave-uniform part (image, column tile);
-            // lanes outside the grid carry an offset beyond the buffer and are dropped.
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(Gb, 0, grid_bytes, 0x00020000);
-            const int par = fr & 1, ce = fr & ~1;
-            const int sa = fk + (par ? 8 : 0), sb = sa + 4;
-            const bool col_ok = epoch_ok && ct * 16 + ce < P.nd;
-            const unsigned row_a = col_ok && slot_valid(sa) ? (unsigned)grid_row(sa) * (unsigned)P.nlon * 8u : 0x80000000u;
-            const unsigned row_b = col_ok && slot_valid(sb) ? (unsigned)grid_row(sb) * (unsigned)P.nlon * 8u : 0x80000000u;
-            const unsigned asc = (unsigned)ce * 8u, desc = (unsigned)(14 - ce) * 8u;
+        // lanes (2 q, 2 q + 1) hold adjacent columns: after the exchange every lane owns two rows x two adjacent columns and
+        // stores 16 bytes.  Byte offset = lane part (row, column inside the tile) + wave-uniform part (image, column tile);
+        // lanes outside the grid carry an offset beyond the buffer and are dropped.
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(Gb, 0, grid_bytes, 0x00020000);
+        const int par = fr & 1, ce = fr & ~1;
+        const int sa = fk + (par ? 8 : 0), sb = sa + 4;
+        const bool col_ok = epoch_ok && ct * 16 + ce < (fold ? P.nd + 8 : P.nd);
+        const unsigned row_a = col_ok && slot_valid(sa) ? (unsigned)grid_row(sa) * (unsigned)P.nlon * 8u : 0x80000000u;
+        const unsigned row_b = col_ok && slot_valid(sb) ? (unsigned)grid_row(sb) * (unsigned)P.nlon * 8u : 0x80000000u;
+        // lane part of the store offsets of this unit: row + column inside the tile, ascending (column ce) and descending (14 - ce)
+        const unsigned asc_a = row_a + (unsigned)ce * 8u, asc_b = row_b + (unsigned)ce * 8u;
+        const unsigned desc_a = row_a + (unsigned)(14 - ce) * 8u, desc_b = row_b + (unsigned)(14 - ce) * 8u;
+        // one image of the unit (accumulator vector v): the lane's two rows x two columns at lane part + wave-uniform byte offset
+        auto put_image = [&](const double4_t& v, bool ascending, unsigned lane_a, unsigned lane_b, int soff) {
+            double a_lo, a_hi, b_lo, b_hi;
+            pair_exchange(v[0], v[2], 0xAAAAAAAAAAAAAAAAull, a_lo, a_hi);
+            pair_exchange(v[1], v[3], 0xAAAAAAAAAAAAAAAAull, b_lo, b_hi);
+            const double2_t va = ascending ? (double2_t){a_lo, a_hi} : (double2_t){a_hi, a_lo};
+            const double2_t vb = ascending ? (double2_t){b_lo, b_hi} : (double2_t){b_hi, b_lo};
+            // The wave-uniform part goes into the vector offset, not into the scalar offset operand of the store: with a
+            // REGISTER soffset hipcc assumes that a 16-byte store's data registers may be overwritten by the very next VALU
+            // instruction (the documented exemption of the gfx9 store-data hazard) and schedules one there; on gfx950 that
+            // corrupted the low dword of the stored value in some lanes of some launches.
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, va), rsrc, lane_a + (unsigned)soff, 0, SHG_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, vb), rsrc, lane_b + (unsigned)soff, 0, SHG_STORE_AUX);
+        };
+        // The images of the sign -1 sit behind a switch that only skips: their half of the butterfly works in place on accumulators
+        // of its own and stores them before the switch ends, so no value is live across it in two versions (an in-place update under a
+        // run-time switch whose results outlive the switch makes hipcc copy every vector, ~60 moves per row).
 #pragma unroll
-            for (int t = 0; t < kImages; ++t) {
-                const int k = t < R ? t : t - R;
-                const bool ascending = t < R;
-                // first column of the tile's run: s = +1: (n2 + k nR) mod nlon + 16 ct;  s = -1: (n2 + k nR - nd) mod nlon + nd - 16 ct - 16
-                int w = n2 + k * nR - (ascending ? 0 : P.nd);
-                w = w >= P.nlon ? w - P.nlon : w;
-                const int soff = (ascending ? w + 16 * ct : w + P.nd - 16 * ct - 16) * 8;
-                double a_lo, a_hi, b_lo, b_hi;
-                pair_exchange(acc[t][0], acc[t][2], 0xAAAAAAAAAAAAAAAAull, a_lo, a_hi);
-                pair_exchange(acc[t][1], acc[t][3], 0xAAAAAAAAAAAAAAAAull, b_lo, b_hi);
-                const double2_t va = ascending ? (double2_t){a_lo, a_hi} : (double2_t){a_hi, a_lo};
-                const double2_t vb = ascending ? (double2_t){b_lo, b_hi} : (double2_t){b_hi, b_lo};
-                // The wave-uniform part goes into the vector offset, not into the scalar offset operand of the store: with a
-                // REGISTER soffset hipcc assumes that a 16-byte store's data registers may be overwritten by the very next VALU
-                // instruction (the documented exemption of the gfx9 store-data hazard) and schedules one there; on gfx950 that
-                // corrupted the low dword of the stored value in some lanes of some launches.
-                const unsigned lane_col = (ascending ? asc : desc) + (unsigned)soff;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, va), rsrc, row_a + lane_col, 0, SHG_STORE_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, vb), rsrc, row_b + lane_col, 0, SHG_STORE_AUX);
+        for (int r = 0; r < 4; ++r) rot_split<R>(acc, r);
+        // (the sums of the sign -1 are pinned here: hipcc would otherwise move their part of rot_split behind the switch, where only it
+        // is used, and keep the sums it is formed from alive beside the images that have taken their registers)
+#pragma unroll
+        for (int k = 0; k < R; ++k) asm volatile("" : "+v"(acc[T::img_of(k, 1)]));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rot_half<R, 0>(acc, r);
+        // Ascending image k: the tile's run starts at column (n2 + k nR) mod nlon + 16 ct.  In the folded tile all 16 columns are real.
+        // Even R: the run starts at a multiple of 16 and ends inside the row (whole 128-byte lines).  Odd R: n2 is an odd multiple of
+        // nd = 8 mod 16, the run starts 8 columns into a line and the one that starts at nlon - 8 goes on at column 0: in that image the
+        // lanes of the columns 8 .. 15 take a lane part one row lower (no pair straddles the end of the row, the start is even; a lane
+        // outside the grid stays outside: its offset stays at 2^31 or above).
+        const unsigned row_wrap = R % 2 != 0 && ce >= 8 ? (unsigned)P.nlon * 8u : 0u;
+        int w = n2;
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const bool wraps = R % 2 != 0 && w + 16 * ct + 16 > P.nlon;        // wave-uniform
+            put_image(acc[T::img_of(k, 0)], true, wraps ? asc_a - row_wrap : asc_a, wraps ? asc_b - row_wrap : asc_b, (w + 16 * ct) * 8);
+            w = w + nR >= P.nlon ? w + nR - P.nlon : w + nR;
+        }
+        if (!fold) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) rot_half<R, 1>(acc, r);
+            // descending image k: the run (in descending columns) starts at (n2 + k nR - nd) mod nlon + nd - 16 ct - 16
+            w = n2 - P.nd;
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                put_image(acc[T::img_of(k, 1)], false, desc_a, desc_b, (w + P.nd - 16 * ct - 16) * 8);
+                w = w + nR >= P.nlon ? w + nR - P.nlon : w + nR;
             }
         }
         ROT_STAMP(4 + 2 * min(q, 3));
@@ -783,11 +807,18 @@ __global__ __launch_bounds__(128 * EP) void synthesis_rot_kernel(RotParams P) {
         S.abx = panel[(wave % EP) * 16 + fr + fk * PR];
         S.pf = P.npieces > 1 ? 1 : 0;
         rot_phase2<NS, R>(P, As, panel, S, wave, lane, bt * 4, it);
-        // The prefetched pieces of the stream must have landed before the LDS is released -- but not the stores: the 4 R stores of
-        // the last unit are the youngest operations of the wave (its last LDS-DMA was issued in the last k-step, before them), and
-        // the counter runs in order, so "at most 4 R outstanding" means every DMA is done.  The wave ends with its stores in flight
-        // instead of waiting for HBM to acknowledge them.
-        wait_vmcnt<4 * R>();
+        // The prefetched pieces of the stream must have landed before the LDS is released -- but not the stores: the stores of the
+        // last unit are the youngest operations of the wave (its last LDS-DMA was issued in the last k-step, before them), and the
+        // counter runs in order, so "at most as many outstanding as that unit stored" means every DMA is done.  That is 4 R stores,
+        // or 2 R where the wave's last unit is the folded column tile (waiting for 4 R there would let the LDS go with the prefetched
+        // DMAs still in flight into it, i.e. into the next workgroup's panel).  The wave ends with its stores in flight instead of
+        // waiting for HBM to acknowledge them.  With the fold on every wave waits for 2 R: the waves that end on a whole unit (the
+        // other half of the workgroup; on the headline they have a unit less than those that end on the folded tile) then wait for half of its stores, and
+        // telling the two apart by the wave's last column tile cost the kernels of R = 6 and 3 a stack slot.
+        if (P.half_fold != 0)
+            wait_vmcnt<2 * R>();
+        else
+            wait_vmcnt<4 * R>();
     } else {
         wait_vmcnt<0>();
     }
@@ -896,10 +927,15 @@ int rot_choose(int nlon, const double* lon_h, int N) {
 }
 
 // trig stream [nct][npieces][64][2] (+ one spare piece) of the orders 1 .. level, built on the host like the other cos/sin tables
-// (grates/utilities.py:272-273)
-void rot_trig_stream(int R, int N, int level, int nlon, const double* lon_h, std::vector<double>& tab) {
+// (grates/utilities.py:272-273).  Where nd % 16 == 8 the lanes 8 .. 15 of the last column tile lie beyond the fundamental domain:
+// fill_half = false leaves them zero (shg_rot_level_tables, byte for byte what it always returned), fill_half = true (the plan's device
+// copy) puts the columns c' = nd .. nd + 7 there, whose ascending images are the descending images of the columns 2 nd - 1 - c' (see
+// rot_phase2).  Their angle is derived from the fundamental column, mu_c' = 2 pi / R - mu_(2 nd - 1 - c') in long double, not read from
+// lon_h[nlon / 2 + c']: every output column's argument then stays as close to its own meridian as has_rotation_symmetry demands.
+void rot_trig_stream(int R, int N, int level, int nlon, const double* lon_h, std::vector<double>& tab, bool fill_half) {
     (void)N;
     const int nd = nlon / (2 * R), nct = ceil_div(nd, 16);
+    const long double pi = 3.141592653589793238462643383279502884L;
     int nk[kMaxClasses], cnt[kMaxClasses];
     std::vector<int> order_slot;
     const int nslot = rot_layout(R, level, nk, cnt, &order_slot);
@@ -911,13 +947,19 @@ void rot_trig_stream(int R, int N, int level, int nlon, const double* lon_h, std
         for (int ks = 0; ks < npieces; ++ks)
             for (int l = 0; l < 64; ++l) {
                 const int m = slot_order[4 * ks + (l >> 4)], c = 16 * ct + (l & 15);
-                if (m < 0 || c >= nd) continue;
+                if (m < 0 || (c >= nd && !(fill_half && nd % 16 == 8))) continue;
                 int cls, sg;
                 order_class(R, m, cls, sg);
-                const double arg = (double)m * lon_h[nlon / 2 + c];
                 double* dst = &tab[(((size_t)ct * npieces + ks) * 64 + l) * 2];
-                dst[0] = std::cos(arg);
-                dst[1] = sg * std::sin(arg);
+                if (c < nd) {
+                    const double arg = (double)m * lon_h[nlon / 2 + c];
+                    dst[0] = std::cos(arg);
+                    dst[1] = sg * std::sin(arg);
+                } else {
+                    const long double arg = (long double)m * (2 * pi / R - (long double)lon_h[nlon / 2 + 2 * nd - 1 - c]);
+                    dst[0] = (double)std::cos(arg);
+                    dst[1] = sg * (double)std::sin(arg);
+                }
             }
 }
 
@@ -928,7 +970,7 @@ int build_rot_trig(shg_plan* p, const double* lon_h) {
     std::vector<double> all, tab;
     p->rot_trig_piece.clear();
     for (int level : levels) {
-        rot_trig_stream(p->rotR, p->N, level, p->nlon, lon_h, tab);
+        rot_trig_stream(p->rotR, p->N, level, p->nlon, lon_h, tab, true);
         p->rot_trig_piece.push_back((int)(all.size() / 128));
         all.insert(all.end(), tab.begin(), tab.end());
     }
@@ -1093,6 +1135,7 @@ int synthesis_rot(shg_plan* p, const double* anm, int B, double* grid, hipStream
     P.nh = p->nlat / 2;
     P.nd = p->nlon / (2 * R);
     P.nct = ceil_div(P.nd, 16);
+    P.half_fold = p->half_tile_fold && P.nd % 16 == 8 ? 1 : 0;
     P.nslot = rot_layout(R, p->N, P.cls_nk, P.cls_cnt, nullptr);
     P.npieces = P.nslot / 4;
 #ifdef SHG_EXPERIMENT

@@ -95,7 +95,7 @@ class Plan:
         levels = (ctypes.c_int * max(nblocks.value, 1))()
         _lib.call('shg_plan_order_cutoffs', self._handle, levels, nblocks.value, ctypes.byref(nblocks), ctypes.byref(enabled))
         return {'max_degree': arr[0], 'nlat': arr[1], 'nlon': arr[2], 'fourfold_symmetry': bool(arr[3] & 1), 'north_south_symmetry': bool(arr[3] & 2),
-                'rotation_symmetry': bool(arr[3] & 4), 'epochs_per_pass': arr[4], 'k_slots': arr[5], 'fused': bool(arr[6]), 'path': int(arr[7]) & 0xff, 'rotations': int(arr[7]) >> 8,
+                'rotation_symmetry': bool(arr[3] & 4), 'half_tile_fold': bool(arr[3] & 8), 'epochs_per_pass': arr[4], 'k_slots': arr[5], 'fused': bool(arr[6]), 'path': int(arr[7]) & 0xff, 'rotations': int(arr[7]) >> 8,
                 'order_pruning': bool(enabled.value), 'order_cutoffs': [int(levels[i]) for i in range(nblocks.value)]}
 
     def set_path(self, path):
@@ -114,6 +114,12 @@ class Plan:
         """Rotation-folded kernel only: latitude blocks next to a pole skip the orders that cannot reach them (on by default; off
         for comparisons).  `info()['order_cutoffs']` lists the largest order every block keeps."""
         _lib.call('shg_plan_set_order_pruning', self._handle, 1 if enable else 0)
+
+    def set_half_tile_fold(self, enable):
+        """Rotation-folded kernel only, where the fundamental domain has 8 mod 16 columns: the last column tile runs on 16 real columns
+        and stores its ascending images only (on by default; off for comparisons: all 2 R images, the 8 columns beyond the domain
+        dropped).  `info()['half_tile_fold']` tells whether the kernel folds that tile."""
+        _lib.call('shg_plan_set_half_tile_fold', self._handle, 1 if enable else 0)
 
     def set_rotations(self, R):
         """Rotation count of the rotation-folded kernel: 0 (the plan's own choice), 3, 6, 9 or 10; the meridians must be invariant

@@ -65,9 +65,11 @@ int shg_plan_set_chunk(shg_plan* plan, int epochs_per_pass);
  * parallels when the grid has it and their plain variant otherwise; the variant is not a choice of the caller. */
 int shg_plan_set_path(shg_plan* plan, int path);
 
-/* Kernel 6 only: at most `limit` workgroups run their Legendre stage (in which they do not store) at the same time; limit < 0 = that many
- * sixteenths of the device's CUs, 0 = no limit (the default).  A tuning knob: on MI355X -7 took 1.5-2 % off the d/o-96 / 0.25 degree
- * kernel on some boxes and cost 2-4 % on others.  Waits for the device the first time a limit is set. */
+/* Kernel 6 only: at most `limit` workgroups run their Legendre stage (in which they do not store) at the same time, kept per XCD by
+ * ticket queues; limit < 0 = that many sixteenths of the device's CUs, 0 = no limit.  A plan on which this was never called runs with
+ * the ticket limit of DESIGN.md 4.1: grids of more than one workgroup per CU are limited to 4/16 of the CUs x (Qtot / nlon) / (345 / 1440)
+ * (4/16 on the d/o-96 / 0.25 degree plan: -4.2 % of its step on MI355X), no limit where that reaches the whole device.  Any call, 0
+ * included, replaces that default for good.  Waits for the device whenever a limit > 0 is set (the queues are zeroed). */
 int shg_plan_set_stage_limit(shg_plan* plan, int limit);
 
 /* Rotation count R of kernel 6: the longitude sums are evaluated on nlon / (2 R) columns and the 2 R images of every column are
@@ -92,8 +94,20 @@ int shg_rot_order_cutoffs(int N, int nlat, const double* colat_h, const double* 
 int shg_rot_level_tables(int R, int N, int level, int ns, int nlon, const double* lon_h, int32_t header[24], double* trig,
                          int64_t trig_capacity, int32_t* items, int64_t items_capacity);
 
+/* Kernel 6 only: the half column tile.  Where the fundamental domain has nd = nlon / (2 R) = 8 mod 16 columns (R = 10 and 6 on the 0.25
+ * degree grid, R = 9 on the 0.5 degree grid) the last column tile of 16 has 8 columns.  enable = 1 (the default): that tile runs on the
+ * 16 real columns nd - 8 .. nd + 7 and forms and stores its R ascending images only -- the descending image k + 1 of column c is the
+ * ascending image k of column 2 nd - 1 - c --, half the butterfly and half the stores of that tile, each store a whole 16-column
+ * piece.  enable = 0: that tile forms all 2 R images like every other and the hardware drops the 8 columns beyond nd (for
+ * comparisons).  The plan's own device copy of the trig stream carries cos / sin of m (2 pi / R - mu_(2 nd - 1 - c)) in the lanes 8 .. 15
+ * of that tile's pieces either way; shg_rot_level_tables returns zeros there.  The grids of the two settings differ in the 8 R columns
+ * of the former descending images only, by rounding, and the d/o-96 / 0.25 degree kernel measured 1.9 % faster with the fold on MI355X
+ * (DESIGN.md 4.1).  No effect where nd % 16 == 0.  shg_plan_info: bit 3 of which[3]. */
+int shg_plan_set_half_tile_fold(shg_plan* plan, int enable);
+
 /* Introspection: which[0]=N, [1]=nlat, [2]=nlon, [3]=bit 0: 4-fold longitude symmetry, bit 1: parallels symmetric about the
- * equator, bit 2: the rotation-folded kernel (path 6) applies, [4]=epochs per pass, [5]=K slots of the longitude stage, [6]=1 if synthesis uses the fused kernel, [7]=path | rotation count of kernel 6 << 8. */
+ * equator, bit 2: the rotation-folded kernel (path 6) applies, bit 3: kernel 6 folds its half column tile (shg_plan_set_half_tile_fold is on and nd % 16 == 8),
+ * [4]=epochs per pass, [5]=K slots of the longitude stage, [6]=1 if synthesis uses the fused kernel, [7]=path | rotation count of kernel 6 << 8. */
 int shg_plan_info(const shg_plan* plan, int64_t which[8]);
 
 /* Per-kernel timing with HIP events recorded on the caller's stream around every kernel a plan launches.
