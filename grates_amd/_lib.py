@@ -59,6 +59,7 @@ PROTOTYPES = {
     'shg_covprop_diag_separable_symmetric': [c_plan_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_void_p],
     'shg_epoch_rms': [c_double_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong, c_double_p, ctypes.c_void_p],
     'shg_symmetry_defect': [c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_void_p],
+    'shg_covprop_route': [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int],
     'shg_covprop_points': [ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
     'shg_degree_scale': [c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],
     'shg_orderwise_filter': [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p],

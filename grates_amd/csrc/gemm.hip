@@ -346,8 +346,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams P) {      /
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
             const int p = k0 + b_k + 4 * h, c = n0 + b_col;
-            breg[h].x *= p < c ? 2.0 : (p == c ? 1.0 : 0.0);
-            breg[h].y *= p < c + 1 ? 2.0 : (p == c + 1 ? 1.0 : 0.0);
+            // the entries below the diagonal are replaced by 0, not multiplied with 0: they may hold NaN or infinity.  (Selecting
+            // 2 x / x / 0 outright cost 3.7 % at d/o 60 on a 2 degree grid; this form costs nothing: DESIGN.md 4.2)
+            breg[h].x = (p > c ? 0.0 : breg[h].x) * (p < c ? 2.0 : 1.0);
+            breg[h].y = (p > c + 1 ? 0.0 : breg[h].y) * (p < c + 1 ? 2.0 : 1.0);
         }
     };
 
@@ -776,6 +778,28 @@ extern "C" int shg_dense_filter(const double* W, int Pn, const double* X, int T,
 
 static int covprop_diag_impl(shg_plan* p, const double* cov, int nmin, int lat0, int lat1, double* sigma, void* stream_, bool symmetric);
 
+// The kernel behind shg_covprop_diag / shg_covprop_diag_symmetric for a band of M rows on nlon meridians and a Pn x Pn Sigma
+// whose base address is (aligned) or is not a multiple of 16 bytes.
+// Two kernels: covprop_rows (covprop.hip) keeps row tiles inside one parallel (operand tiles are plain table rows) but
+// pads every parallel to a multiple of 128 meridians; the general kernel generates A element-wise and wastes nothing.
+// The general kernel copies Sigma tiles straight into LDS when the rows of Sigma are 16-byte aligned.  An odd dimension
+// (d/o 180: 32761) or an odd base address gets a copy with rows of even length first: 2 x 8.6 GB of traffic, ~3 ms, against
+// seconds of MFMA work; below ~2 TFLOP of work the copy does not pay and the register path reads the matrix as it is.
+// The symmetric variant always reads Sigma through registers, 8 bytes at a time.
+static int covprop_route(int nlon, int Pn, bool aligned, long long M, bool symmetric) {
+    if (Pn == 0 || M == 0) return SHG_COVPROP_ROUTE_NONE;
+    if (symmetric) return SHG_COVPROP_ROUTE_SYMMETRIC;
+    const int padded = round_up(nlon, 128);
+    if ((padded - nlon) * 25 <= nlon) return SHG_COVPROP_ROUTE_ROWS;      // padding waste <= 4 %
+    if (Pn % 2 == 0 && aligned) return SHG_COVPROP_ROUTE_DIRECT;
+    return (double)M * Pn * Pn > 1e12 ? SHG_COVPROP_ROUTE_PADDED : SHG_COVPROP_ROUTE_REGISTER;
+}
+
+extern "C" int shg_covprop_route(int nlon, int P, int aligned, long long M, int symmetric) {
+    SHG_REQUIRE(nlon >= 1 && P >= 0 && M >= 0 && M < (1LL << 31), "shg_covprop_route: bad size");
+    return covprop_route(nlon, P, aligned != 0, M, symmetric != 0);
+}
+
 extern "C" int shg_covprop_diag(shg_plan* p, const double* cov, int nmin, int lat0, int lat1, double* sigma, void* stream_) {
     return covprop_diag_impl(p, cov, nmin, lat0, lat1, sigma, stream_, false);
 }
@@ -785,7 +809,12 @@ extern "C" int shg_covprop_diag_symmetric(shg_plan* p, const double* cov, int nm
 }
 
 namespace shg {
-// max |S[p][c] - S[c][p]| over 32 x 32 tile pairs (upper tiles compared with their mirror images through LDS)
+// the larger of two non-negative numbers, NaN if either is one (fmax drops a NaN)
+__device__ inline double max_or_nan(double a, double b) { return (a != a || a > b) ? a : b; }
+
+// max |S[p][c] - S[c][p]| over 32 x 32 tile pairs (upper tiles compared with their mirror images through LDS); NaN when a
+// difference is NaN (a NaN on either side, the same infinity on both): fabs clears its sign, and the positive NaN patterns order
+// above infinity in the integer atomicMax
 __global__ __launch_bounds__(256) void symmetry_defect_kernel(int n, const double* __restrict__ S, int ld, double* __restrict__ out) {
     __shared__ double tile[32][33];
     __shared__ double red[256];
@@ -800,16 +829,16 @@ __global__ __launch_bounds__(256) void symmetry_defect_kernel(int n, const doubl
         __syncthreads();
         for (int k = ty; k < 32; k += 8) {
             const int r = bi * 32 + k, c = bj * 32 + tx;
-            if (r < n && c < n) worst = fmax(worst, fabs(S[(size_t)r * ld + c] - tile[tx][k]));
+            if (r < n && c < n) worst = max_or_nan(fabs(S[(size_t)r * ld + c] - tile[tx][k]), worst);
         }
     }
     red[threadIdx.x] = worst;
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + w]);
+        if ((int)threadIdx.x < w) red[threadIdx.x] = max_or_nan(red[threadIdx.x], red[threadIdx.x + w]);
         __syncthreads();
     }
-    if (threadIdx.x == 0 && red[0] > 0.0) atomicMax(reinterpret_cast<unsigned long long*>(out), (unsigned long long)__double_as_longlong(red[0]));
+    if (threadIdx.x == 0 && !(red[0] <= 0.0)) atomicMax(reinterpret_cast<unsigned long long*>(out), (unsigned long long)__double_as_longlong(red[0]));
 }
 }  // namespace shg
 
@@ -864,23 +893,17 @@ static int covprop_diag_impl(shg_plan* p, const double* cov, int nmin, int lat0,
         SHG_HIP(hipMemsetAsync(sigma, 0, M * sizeof(double), stream));
         return SHG_OK;
     }
-    // Two kernels: covprop_rows (covprop.hip) keeps row tiles inside one parallel (operand tiles are plain table rows) but
-    // pads every parallel to a multiple of 128 meridians; the general kernel generates A element-wise and wastes nothing.
-    const int padded = round_up(p->nlon, 128);
-    if (!symmetric && (padded - p->nlon) * 25 <= p->nlon) {   // padding waste <= 4 %
+    const int route = covprop_route(p->nlon, Pn, (uintptr_t)cov % 16 == 0, M, symmetric);
+    if (route == SHG_COVPROP_ROUTE_ROWS) {
         rc = covprop_rows(p, cov, Pn, nmin * nmin, lat0, lat1, p->cov_partial.get(), stream);
         if (rc) return rc;
         hipLaunchKernelGGL(covprop_reduce_kernel, dim3(ceil_div((int)M, 256)), dim3(256), 0, stream, (int)M, ncolblocks, p->cov_partial.get(), sigma);
         SHG_HIP(hipGetLastError());
         return SHG_OK;
     }
-    // The general kernel copies Sigma tiles straight into LDS when the rows of Sigma are 16-byte aligned.  An odd dimension
-    // (d/o 180: 32761) or an odd base address gets a copy with rows of even length first: 2 x 8.6 GB of traffic, ~3 ms, against
-    // seconds of MFMA work; below ~2 TFLOP of work the copy does not pay and the register path reads the matrix as it is.
     const double* sigma_in = cov;
     int ld_in = Pn;
-    const bool aligned = (Pn % 2 == 0) && ((uintptr_t)cov % 16 == 0);
-    if (!symmetric && !aligned && (double)M * Pn * Pn > 1e12) {
+    if (route == SHG_COVPROP_ROUTE_PADDED) {
         const int ld_pad = Pn + (Pn & 1) + ((Pn + (Pn & 1)) % 512 == 0 ? 2 : 0);        // even, not a multiple of 4 KB
         const size_t need_pad = (size_t)Pn * ld_pad;
         if (need_pad > p->cov_pad.size() && p->cov_pad) SHG_HIP(hipStreamSynchronize(stream));

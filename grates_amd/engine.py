@@ -186,12 +186,13 @@ class Plan:
             _lib.call('shg_synthesis', self._handle, _ptr(x), B, _ptr(out), _stream())
         return out[0] if single else out
 
-    def covariance_propagation(self, cov, min_degree, lat0=0, lat1=None, symmetric=False, method='direct'):
-        """cov [P, P] degree-wise -> sigma [(lat1-lat0)*nlon] for the band of parallels [lat0, lat1).
+    def covariance_propagation(self, cov, min_degree, lat0=0, lat1=None, symmetric=False, method='direct', out=None):
+        """cov [P, P] degree-wise -> sigma [(lat1-lat0)*nlon] for the band of parallels [lat0, lat1), written to `out` when given.
 
         symmetric: False (default) multiplies with the full matrix like the reference; True reads only the upper triangle
-        of a symmetric matrix (half the MFMA work); None checks the matrix on the device and takes the shortcut when it is
-        exactly symmetric (the result then differs from the general path by summation order only).
+        of a symmetric matrix (half the MFMA work; the other triangle may hold anything, NaN included); None checks the matrix
+        on the device and takes the shortcut when it is exactly symmetric (the result then differs from the general path by
+        summation order only; a NaN or an infinity on one side of the diagonal counts as not symmetric).
         method: 'direct' forms A Sigma like the reference (2 M P^2 flops on the MFMA units); 'separable' uses the
         factorisation of the synthesis matrix into a latitude and a longitude part (about nlon times fewer flops,
         P^2 + 32 P nlat doubles of workspace), same result up to summation order."""
@@ -201,7 +202,10 @@ class Plan:
         P = (self.max_degree + 1) ** 2 - min_degree ** 2
         if c.dim() != 2 or c.shape[0] != P or c.shape[1] != P:
             raise ValueError('covariance matrix must have shape ({0}, {0}), got {1}'.format(P, tuple(c.shape)))
-        out = torch.empty(((lat1 - lat0) * self.nlon,), dtype=torch.float64, device=self.device)
+        if out is None:
+            out = torch.empty(((lat1 - lat0) * self.nlon,), dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != ((lat1 - lat0) * self.nlon,) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != c.device:
+            raise ValueError('out must be a contiguous fp64 tensor of shape {0} on the plan\'s device'.format(((lat1 - lat0) * self.nlon,)))
         if method not in ('direct', 'separable'):
             raise ValueError("method must be 'direct' or 'separable'")
         with torch.cuda.device(self.device):
@@ -1906,6 +1910,19 @@ def gemm_route(transa, transb, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc
     if which[4] > 0:
         route['rest'] = {'kind': GEMM_ROUTE_KINDS[which[7] & 255], 'slices': (which[7] >> 8) & 255, 'strips': bool(which[7] >> 16 & 1)}
     return route
+
+
+COVPROP_ROUTE_KINDS = ('NONE', 'ROWS', 'DIRECT', 'REGISTER', 'PADDED', 'SYMMETRIC')      # shg_covprop_route_kind
+
+
+def covprop_route(nlon, P, aligned, M, symmetric):
+    """The kernel Plan.covariance_propagation(method='direct') runs for a band of M grid rows on nlon meridians and a P x P matrix
+    whose base address is (aligned) or is not a multiple of 16 bytes: one of COVPROP_ROUTE_KINDS.  Host logic only: works without a GPU."""
+    lib = _lib.load()
+    kind = lib.shg_covprop_route(int(nlon), int(P), int(bool(aligned)), int(M), int(bool(symmetric)))
+    if kind < 0:
+        raise _lib.ShgError('shg_covprop_route', kind, lib.shg_last_error().decode())
+    return COVPROP_ROUTE_KINDS[kind]
 
 
 def gemm_ex_args(A, B, out, transa=False, transb=False):

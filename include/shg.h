@@ -188,6 +188,21 @@ int shg_covprop_diag(shg_plan* plan, const double* cov, int nmin, int lat0, int 
  * max |S[p][c] - S[c][p]| to *defect (device double): 0 means the shortcut reproduces the general result up to summation order. */
 int shg_covprop_diag_symmetric(shg_plan* plan, const double* cov, int nmin, int lat0, int lat1, double* sigma, void* stream);
 int shg_symmetry_defect(const double* S, int n, int ld, double* defect, void* stream);
+/* A NaN on one side of the diagonal makes the defect NaN, an infinity makes it infinite or NaN: never 0.  shg_covprop_diag_symmetric loads the entries
+ * below the diagonal of the 128 x 128 diagonal blocks but discards them unread: they may hold anything, NaN included. */
+
+/* Host-only diagnostic: the kernel that shg_covprop_diag (symmetric 0) or shg_covprop_diag_symmetric (symmetric 1) runs for a band
+ * of M = (lat1 - lat0) * nlon grid rows and a P x P matrix whose base address is (aligned 1) or is not (0) a multiple of 16
+ * bytes.  Makes no HIP call; returns the kind, or SHG_ERR_INVALID.  The thresholds are tuning, not contract. */
+typedef enum {
+    SHG_COVPROP_ROUTE_NONE = 0,       /* P == 0 or an empty band: no product                                            */
+    SHG_COVPROP_ROUTE_ROWS = 1,       /* row-tiled kernel: parallels padded to 128 meridians, at most 4 % of padding    */
+    SHG_COVPROP_ROUTE_DIRECT = 2,     /* general kernel, Sigma tiles copied straight into LDS, 16 bytes at a time       */
+    SHG_COVPROP_ROUTE_REGISTER = 3,   /* general kernel, Sigma through registers, 8 bytes at a time (odd P or base)     */
+    SHG_COVPROP_ROUTE_PADDED = 4,     /* copy of Sigma with even, padded rows, then DIRECT (odd P or base, M P^2 > 1e12) */
+    SHG_COVPROP_ROUTE_SYMMETRIC = 5   /* upper-triangle kernel, Sigma through registers, 8 bytes at a time              */
+} shg_covprop_route_kind;
+int shg_covprop_route(int nlon, int P, int aligned, long long M, int symmetric);
 /* The same result through the separable structure of the synthesis matrix (an extension, see csrc/covsep.hip):
  *   sigma^2(i, j) = t(j)^T B_i t(j),  B_i[s][s'] = sum_{n,n'} PK_n,s(i) Sigma[(n,s)][(n',s')] PK_n',s'(i)
  * 2 nlat P^2 flops instead of 2 nlat nlon P^2 (d/o 180, 0.5 deg: 8e11 instead of 5.6e14); differs from shg_covprop_diag by
